@@ -9,7 +9,13 @@ One "step" = one full training step (forward, three losses, backward, [all-reduc
 VQVAE(1, D=128, K=512) (BASELINE.json configs[1], the reference's `--dim 128 --z-dim 512`, bf16) on a
 synthetic batch of B = 128 clips of 80-mel x 1024 frames per GPU, inputs resident in HBM before the timed
 region.  Weak scaling: B per GPU is fixed, rank r draws its own clips.  Prints ONE JSON line: the bf16
-mode is `value` (configs[1] is quoted in bf16), the fp32 parity mode is timed in the same run (other_mode).
+mode is `value` (configs[1] is quoted in bf16), `ms_per_step` the wall time of one timed step.
+
+A plain run does only that: set up, warm up, time the steps, print the line.  With --full it also measures what the
+headline does not need (roofline, per-kernel tables, the other compute mode as other_mode, the other BASELINE
+configurations as other_configs, the CPU baseline; the --no-* options drop single items of that).  With
+--dump-outputs DIR it writes what the last timed step computed as DIR/<name>.npy (see `step_outputs`); inputs and
+initial weights are seeded, so the same arguments give the same inputs on every run.
 """
 from __future__ import annotations
 
@@ -18,7 +24,9 @@ import json
 import os
 import sys
 import time
+import zlib
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -106,6 +114,39 @@ def write_kernel_tables(tables: dict) -> str:
     return path
 
 
+DUMP_LIMIT = 60_000_000   # bytes of array data in all (the .npy headers come on top): under 64 MB
+
+
+def step_outputs(step, model, losses) -> dict:
+    """What a caller of the timed training step holds after its last step, as host arrays: the three losses (float64), the
+    code index of every latent position (float64, exact), and the model's state after the optimiser step -- parameters,
+    BatchNorm running statistics and counters (floating tensors as float32, integer ones as float64)."""
+    out = {"losses": np.array([float(x.item()) for x in losses], dtype=np.float64),
+           "indices": step.last_indices.detach().reshape(-1).cpu().double().numpy()}
+    for k, v in model.state_dict().items():
+        v = v.detach().cpu()
+        out["state." + k] = (v.float() if v.is_floating_point() and v.dtype != torch.float64 else v.double()).numpy()
+    return out
+
+
+def write_outputs(out_dir: str, arrays: dict, limit: int = DUMP_LIMIT) -> list:
+    """DIR/<name>.npy for every array.  Past `limit` bytes in all, every array larger than an equal share of the limit is
+    replaced by a fixed sample of its flattened elements (positions drawn by a generator seeded with the array's name,
+    kept in ascending order), so two runs with the same arguments dump the same positions."""
+    os.makedirs(out_dir, exist_ok=True)
+    if sum(a.nbytes for a in arrays.values()) > limit:
+        share = limit // len(arrays)
+        for name, a in arrays.items():
+            if a.nbytes > share:
+                pos = np.random.default_rng(zlib.crc32(name.encode())).choice(a.size, share // a.itemsize, replace=False)
+                arrays[name] = a.reshape(-1)[np.sort(pos)]
+    paths = []
+    for name, a in arrays.items():
+        paths.append(os.path.join(out_dir, name + ".npy"))
+        np.save(paths[-1], a)
+    return paths
+
+
 def spawn_ranks(n: int) -> int:
     """`python bench.py --gpus N` without torchrun: start the N ranks ourselves, one fresh process per GPU with torchrun's
     environment contract (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_*).  This parent makes no GPU call before or after (a
@@ -143,12 +184,20 @@ def main():
     ap.add_argument("--dtype", choices=["f32", "bf16"], default="bf16",
                     help="bf16 (default: BASELINE.json configs[1] names bf16): bf16 activations / conv operands with fp32 accumulation, "
                          "statistics, quantiser and optimiser; f32: the parity mode (bit-exact code indices, losses within 1e-5 of "
-                         "the reference).  The mode not chosen is timed too and reported under other_mode.")
+                         "the reference).  With --full the mode not chosen is timed too and reported under other_mode.")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the in-region kernel timer (roofline) and per-kernel "
+                         "tables, the other compute mode, the other BASELINE configurations and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (losses, code indices, model state) "
+                         "as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-second-mode", action="store_true", help="skip the short run of the other compute mode")
     ap.add_argument("--no-kernel-timer", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the short runs of BASELINE configs[3] (K=8192, D=256)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
 
@@ -172,10 +221,11 @@ def main():
             torch.distributed.barrier()
         torch.cuda.synchronize()
 
-    def run_mode(dtype_name, steps, warmup, use_timer, D=D, K=K, B=B, census_steps=0, n_speakers=None):
+    def run_mode(dtype_name, steps, warmup, use_timer, D=D, K=K, B=B, census_steps=0, n_speakers=None, dump=False):
         """Time `steps` training steps of the given compute mode.  Returns dict(value, ms, losses, gather (the dominant
         kernel's HIP-event summary over the timed region), census (per-kernel summary of `census_steps` extra steps taken
-        AFTER the timed region with every entry-point call bracketed by events))."""
+        AFTER the timed region with every entry-point call bracketed by events), outputs (with `dump`: step_outputs of the
+        last timed step, taken before any census step))."""
         torch.manual_seed(1)                       # src/main.py:43,71 -- identical init on every rank
         cdtype = torch.bfloat16 if dtype_name == "bf16" else torch.float32
         model = M.VQVAE(1, D, K, compute_dtype=cdtype, n_speakers=n_speakers).to(dev).train()
@@ -201,7 +251,8 @@ def main():
             torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
             elapsed = float(t.item())
         out = {"value": world * B * T * steps / elapsed, "ms": elapsed / steps * 1e3, "losses": [float(x.item()) for x in losses],
-               "gather": timer.summary().get("gather_gemm_f32") if timer is not None else None, "census": None}
+               "gather": timer.summary().get("gather_gemm_f32") if timer is not None else None, "census": None,
+               "outputs": step_outputs(step, model, losses) if dump else None}
         if census_steps > 0 and rank == 0:
             cen = ops.KernelTimer()
             _lib.CENSUS = cen
@@ -243,13 +294,15 @@ def main():
                          "frac": round(ach / peak, 4) if ach is not None else None})
         return rows
 
-    main_run = run_mode(args.dtype, args.steps, args.warmup, not args.no_kernel_timer, census_steps=0 if args.no_kernel_timer else 3)
+    kernel_timer = args.full and not args.no_kernel_timer
+    main_run = run_mode(args.dtype, args.steps, args.warmup, kernel_timer, census_steps=3 if kernel_timer else 0,
+                        dump=args.dump_outputs is not None and rank == 0)
     value, ms_per_step, s = main_run["value"], main_run["ms"], main_run["gather"]
     tables = {}
     if main_run["census"]:
         tables[f"configs[1] {args.dtype} B={B}"] = kernel_table(main_run["census"], args.dtype, ms_per_step)
     other = None
-    if not args.no_second_mode:
+    if args.full and not args.no_second_mode:
         # the other compute mode, same shapes, a short run: fp32 = parity mode, bf16 = throughput mode
         od = "bf16" if args.dtype == "f32" else "f32"
         o = run_mode(od, max(3, args.steps // 4), 2, not args.no_kernel_timer, census_steps=0 if args.no_kernel_timer else 2)
@@ -260,7 +313,7 @@ def main():
         if o["census"]:
             tables[f"configs[1] {od} B={B}"] = kernel_table(o["census"], od, o["ms"])
     other_configs = None
-    if not args.no_other_configs and world == 1 and (D, K) == (128, 512):
+    if args.full and not args.no_other_configs and world == 1 and (D, K) == (128, 512):
         # the other single-GPU configurations of BASELINE.json, short runs:
         #   configs[2]  speaker-conditioned decoder (7 speakers, hparams.py:84), K = 512, D = 128, same batch as the headline
         #   configs[3]  the large codebook (K = 8192, D = 256), 32 clips (the best of SURVEY.md 8d's {8, 16, 32}: scripts/batch_sweep_c3.sh):
@@ -304,13 +357,15 @@ def main():
                     # the whole step against the same peak: algorithmic FLOP per second / MFMA peak
                     "step_frac": round(value / world * flops_per_frame(D, K) / 1e12 / peak, 4)}
         cpu = None
-        if not args.no_cpu_baseline and world == 1:     # the CPU baseline is taken at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:     # the CPU baseline is taken at N = 1 only
             threads = host_threads()
             v, dt = cpu_baseline(D, K, T, threads)
             cpu = {"value": round(v, 1), "unit": "mel-frames/s", "cores": threads, "kind": "port",
                    "sample": f"oracle train_step, 4 clips x 80x{T}, 1 warm-up + 10 timed steps ({dt * 1e3:.0f} ms/step)"}
         if tables:
             write_kernel_tables(tables)
+        if args.dump_outputs is not None:
+            write_outputs(args.dump_outputs, main_run["outputs"])
         print(build_line(value=value, ms_per_step=ms_per_step, world=world, steps=args.steps, warmup=args.warmup, dtype=args.dtype,
                          D=D, K=K, B=B, T=T, roof=roof, cpu=cpu, other=other, other_configs=other_configs), flush=True)
     if world > 1:

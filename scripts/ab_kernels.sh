@@ -7,7 +7,7 @@ cp $PKG/libnsg.so /tmp/libnsg_base.so
 mkdir -p gpurun_out
 for r in 1 2; do for v in "$@"; do
   if [ "$v" = base ]; then cp /tmp/libnsg_base.so $PKG/libnsg.so; else cp _exp/libnsg_$v.so $PKG/libnsg.so; fi
-  python bench.py --no-cpu-baseline --no-second-mode --no-other-configs 2>/dev/null | python -c "
+  python bench.py --full --no-cpu-baseline --no-second-mode --no-other-configs 2>/dev/null | python -c "
 import json,sys,re
 l=json.loads(sys.stdin.read().strip().splitlines()[-1])
 t=json.load(open('gpurun_out/bench_kernels.json'))

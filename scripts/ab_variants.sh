@@ -7,7 +7,7 @@ cd "$(dirname "$0")/.."
 ROUNDS=$1; shift
 PKG=neural_sound_generation_amd
 cp $PKG/libnsg.so /tmp/libnsg_base.so
-ARGS=${AB_ARGS:---no-cpu-baseline --no-second-mode --no-other-configs}
+ARGS=${AB_ARGS:---full --no-cpu-baseline --no-second-mode --no-other-configs}
 for r in $(seq 1 $ROUNDS); do
   for v in "$@"; do
     if [ "$v" = base ]; then cp /tmp/libnsg_base.so $PKG/libnsg.so; else cp _exp/libnsg_$v.so $PKG/libnsg.so; fi

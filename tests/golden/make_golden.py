@@ -21,6 +21,7 @@ sys.path.insert(0, "/root/reference/src")
 
 import models as ref_models  # noqa: E402
 from vector_quantization import vq as ref_vq, vq_st as ref_vq_st  # noqa: E402
+import fixture_io  # noqa: E402
 import portable_rng  # noqa: E402
 
 torch.set_num_threads(8)
@@ -200,7 +201,7 @@ def make_model_fixture(name, dim, z_dim, shapes, full_grads, steps=1, dp=False):
         out["dp.c0"], out["dp.c1"] = c0.numpy(), c1.numpy()
         out.update(sd_np(m, "dp.sd1."))
         out["dp.losses"] = np.array([[r["loss_recons"].item(), r["loss_vq"].item(), r["loss_commit"].item()] for _, r in recs])
-    np.savez_compressed(os.path.join(HERE, name + ".npz"), **out)
+    fixture_io.save(os.path.join(HERE, name + ".npz"), out)     # in parts when over 1 MiB (model_cfg1)
     print(name, {k: float(v) for k, v in zip(("recons", "vq", "commit"), out["s0.losses"])})
 
 

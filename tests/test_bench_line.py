@@ -54,3 +54,40 @@ def test_kernel_tables_go_to_a_side_file_not_stdout(tmp_path, monkeypatch, capsy
     assert os.path.dirname(path) == str(tmp_path) and json.load(open(path))
     out = capsys.readouterr()
     assert out.out == "" and "patch_gemm 3x3" in out.err
+
+
+def test_dump_sample_is_fixed_and_bounded(tmp_path):
+    import numpy as np
+    rng = np.random.default_rng(0)
+    arrays = {"losses": np.array([1.0, 2.0, 2.0]), "big": rng.standard_normal(50_000).astype(np.float32),
+              "idx": np.arange(30_000, dtype=np.float64), "count": np.array(7.0)}
+    whole = bench.write_outputs(str(tmp_path / "a"), dict(arrays), limit=10 ** 7)
+    for p in whole:
+        a = arrays[os.path.basename(p)[:-4]]
+        assert np.load(p).shape == a.shape and np.array_equal(np.load(p), a)      # 0-d arrays stay 0-d
+    limit = 120_000
+    pa = bench.write_outputs(str(tmp_path / "b"), dict(arrays), limit=limit)
+    pb = bench.write_outputs(str(tmp_path / "c"), dict(arrays), limit=limit)
+    got = {os.path.basename(p)[:-4]: np.load(p) for p in pa}
+    assert sum(a.nbytes for a in got.values()) <= limit
+    assert np.array_equal(got["losses"], arrays["losses"])
+    for name in ("big", "idx"):
+        assert got[name].dtype == arrays[name].dtype and 0 < got[name].size < arrays[name].size
+        assert np.isin(got[name], arrays[name]).all()
+    assert (np.diff(got["idx"]) > 0).all()                       # sampled positions kept in order
+    for p, q in zip(pa, pb):
+        assert np.array_equal(np.load(p), np.load(q))            # the same positions on every run
+
+
+def test_dump_arrays_are_float32_or_float64():
+    import torch
+
+    class Step:
+        last_indices = torch.tensor([[3, 1], [0, 2]])
+
+    model = torch.nn.Sequential(torch.nn.Linear(2, 2).to(torch.bfloat16), torch.nn.BatchNorm1d(2))
+    out = bench.step_outputs(Step(), model, (torch.tensor(0.5), torch.tensor(0.25, dtype=torch.float64), torch.tensor(0.25)))
+    assert out["losses"].dtype.name == "float64" and out["losses"].tolist() == [0.5, 0.25, 0.25]
+    assert out["indices"].dtype.name == "float64" and out["indices"].tolist() == [3, 1, 0, 2]
+    assert out["state.0.weight"].dtype.name == "float32" and out["state.1.num_batches_tracked"].dtype.name == "float64"
+    assert set(out) == {"losses", "indices"} | {"state." + k for k in model.state_dict()}

@@ -18,13 +18,14 @@ from neural_sound_generation_amd import models as M, ops  # noqa: E402
 from neural_sound_generation_amd.optim import FlatAdam  # noqa: E402
 from neural_sound_generation_amd.train import FusedTrainStep, vqvae_loss_terms  # noqa: E402
 from oracle import vqvae_oracle as O  # noqa: E402
+import fixture_io  # noqa: E402
 
 DEV = "cuda:0"
 LOSS_RTOL = 1e-5
 
 
 def golden(golden_dir, name):
-    return np.load(os.path.join(golden_dir, name))
+    return fixture_io.load(os.path.join(golden_dir, name))
 
 
 def build(g, prefix="sd0."):

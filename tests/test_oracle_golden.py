@@ -7,13 +7,14 @@ import pytest
 import torch
 
 from oracle import vqvae_oracle as O
+import fixture_io
 import portable_rng
 
 torch.set_num_threads(min(8, os.cpu_count() or 1))
 
 
 def load(golden_dir, name):
-    return np.load(os.path.join(golden_dir, name))
+    return fixture_io.load(os.path.join(golden_dir, name))
 
 
 def test_vq_robust_and_ties(golden_dir):
