@@ -64,7 +64,11 @@ __global__ __launch_bounds__(256) void gated_bwd_kernel(const float *__restrict_
     }
 }
 
-// One wave per row of K logits.  row_loss[m] = logsumexp - l[target];  dlogits = (softmax - onehot) * gscale (optional).
+// One wave per row of K logits.  With mx = l[a] the row's maximum (a its first index) and s = sum over k != a of
+// exp(l[k] - mx):  row_loss[m] = (mx - l[t]) + log1p(s);  dlogits = (softmax - onehot) * gscale (optional), softmax[k] =
+// exp(l[k] - mx) / (1 + s).  Nothing is rounded at the scale of mx: the textbook (mx + log(sum)) - l[t] loses the loss of a
+// confident row, or of logits that share a large offset, to the rounding of mx + log(sum); and 1 / (1 + s) - 1 at a confident
+// target loses its gradient the same way, so that entry is -s / (1 + s).
 __global__ __launch_bounds__(256) void cross_entropy_kernel(const float *__restrict__ logits, const int64_t *__restrict__ target,
                                                             int64_t M, int K, float gscale, float *__restrict__ row_loss,
                                                             float *__restrict__ dlogits)
@@ -75,19 +79,35 @@ __global__ __launch_bounds__(256) void cross_entropy_kernel(const float *__restr
     for (int64_t m = wave; m < M; m += nw) {
         const float *l = logits + m * K;
         float mx = -INFINITY;
-        for (int k = lane; k < K; k += 64) mx = fmaxf(mx, l[k]);
+        int am = -1;                                   // first index of the maximum (-1: this lane holds no element)
+        for (int k = lane; k < K; k += 64) {
+            const float v = l[k];
+            if (am < 0 || v > mx) { mx = v; am = k; }
+        }
 #pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
-        float se = 0.f;
-        for (int k = lane; k < K; k += 64) se += expf(l[k] - mx);
+        for (int off = 32; off >= 1; off >>= 1) {     // (max, first index) is a total order: every lane ends with the same pair
+            const float ov = __shfl_xor(mx, off, 64);
+            const int oi = __shfl_xor(am, off, 64);
+            if (oi >= 0 && (am < 0 || ov > mx || (ov == mx && oi < am))) { mx = ov; am = oi; }
+        }
+        float s = 0.f;
+        for (int k = lane; k < K; k += 64)
+            if (k != am) s += expf(l[k] - mx);
 #pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) se += __shfl_xor(se, off, 64);   // xor butterfly: the same value, in the same order, on every lane
-        const float lse = mx + logf(se);
+        for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);     // xor butterfly: the same value, in the same order, on every lane
         const int t = (int)target[m];
-        if (lane == 0) row_loss[m] = (t >= 0 && t < K) ? lse - l[t] : 0.f;
+        if (lane == 0) row_loss[m] = (t >= 0 && t < K) ? (mx - l[t]) + log1pf(s) : 0.f;
         if (dlogits) {
-            const float inv = 1.f / se;
-            for (int k = lane; k < K; k += 64) dlogits[m * K + k] = (expf(l[k] - mx) * inv - (k == t ? 1.f : 0.f)) * gscale;
+            const float inv = 1.f / (1.f + s);
+            for (int k = lane; k < K; k += 64) {
+                float g;
+                if (k == am) g = (k == t) ? -s * inv : inv;
+                else {
+                    const float p = expf(l[k] - mx) * inv;
+                    g = (k == t) ? p - 1.f : p;
+                }
+                dlogits[m * K + k] = g * gscale;
+            }
         }
     }
 }
