@@ -510,6 +510,34 @@ NSG_API size_t nsg_cross_entropy_workspace_bytes(int64_t M);
 NSG_API int nsg_cross_entropy(const float *logits, const int64_t *target, int64_t M, int32_t K, float grad_scale,
                               float *loss_out, float *dlogits, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Incremental sampling (GatedPixelCNN.sample in prior.py): the per-row column walk.  For row `row` and each clip b it walks
+ * j = 0 .. W-1 and, per layer l, forms
+ *     out = gate((vh[l][b][j] + horiz_l(columns j-3 .. j-1 of e for l = 0, columns j-1 and j of h_l otherwise)) + cond[l][b]),
+ *     h_{l+1} = resid_l(out) (+ h_l for l >= 1),
+ * then the head  logits = W2 relu(W0 h_L + b0) + b2,  then the code of (b, row, j):
+ *   - teacher-forced (x_in != NULL, u == NULL): x_in[b][row][j];
+ *   - sampling (u != NULL, x_in == NULL): the inverse CDF of softmax(logits) against u[b][row][j] in [0, 1):
+ *     p_k = exp(l_k - max l), S = sum_k p_k; the first k whose inclusive prefix sum exceeds u * S, or, if rounding leaves
+ *     none, the last k with p_k > 0.  (The prefix sums and S come from one fixed-order scan: contiguous chunks of
+ *     ceil(K / 64) codes, chunk totals scanned in chunk order.)
+ * The code goes to codes[b][row][j] (if codes != NULL) and embedding[code] to e_row + b * e_clip_stride + j * dim.
+ * logits (optional) [B][H][W][K] receives the row's logits.
+ * Inputs of the row, produced beforehand by the row pass on the conv kernels: vh [L][B][W][2 dim] = v2h_l(h_vert_l) of the
+ * row (bias included), cond [L][B][2 dim] = the class-embedding rows.  emb [K][dim] is the code embedding.
+ * w: the packed weight blob, fp32, nsg_prior_walk_weight_floats(dim, n_layers, input_dim) floats, Kp = input_dim rounded up
+ * to a multiple of 4, every matrix transposed to [k][n] (input-major):
+ *   layer 0:      horiz [3 dim][2 dim] (taps 0, 1, 2 of horiz_stack: row t * dim + c_in), horiz bias [2 dim],
+ *                 resid [dim][dim], resid bias [dim];
+ *   layer l >= 1: horiz [2 dim][2 dim] (taps 0, 1), horiz bias [2 dim], resid [dim][dim], resid bias [dim];
+ *   head:         W0 [dim][512], b0 [512], W2 [512][Kp] (columns >= input_dim zero), b2 [Kp].
+ * Envelope: dim % 16 == 0, dim <= 128, n_layers >= 1, input_dim <= 1024 (and the LDS of a 4-clip slice within 160 KiB);
+ * outside it the size query returns 0 and the walk NSG_E_UNSUPPORTED.  One workgroup per 4 clips; no workgroup waits on
+ * another; deterministic, and a clip's arithmetic does not depend on the other clips of the batch. */
+NSG_API size_t nsg_prior_walk_weight_floats(int32_t dim, int32_t n_layers, int32_t input_dim);
+NSG_API int nsg_prior_walk(const float *w, const float *emb, const float *cond, const float *vh, const float *u, const int64_t *x_in,
+                           int64_t *codes, float *e_row, int64_t e_clip_stride, float *logits, int32_t B, int32_t H, int32_t W,
+                           int32_t dim, int32_t n_layers, int32_t input_dim, int32_t row, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Mel -> waveform inversion (the epoch loop's audio export)   src/main.py:164-197, src/audio_tacotron.py:99-116,142-153
  * librosa's stft / istft / filters.mel and scipy's lfilter restated; fp32; frame-major spectrograms [B][T][F], F = n_fft/2+1.

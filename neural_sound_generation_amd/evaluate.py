@@ -11,6 +11,8 @@ checkpoint layout, restated from the reference's src/test.py:73-106 and src/main
   * `checkpoint_state` / `save_checkpoint` / `load_checkpoint` -- main.py:61-66,216-220: {'epoch', 'arch',
     'state_dict', 'optimizer'}; state_dict keys are the reference's, the optimiser state is in torch.optim.Adam's
     layout (FlatAdam.state_dict), so checkpoints move both ways between the reference and this package.
+  * `sample_mels(vqvae, prior, label, frames)` -- generation's code -> mel half: codes drawn from the latent prior
+    (GatedPixelCNN.sample) on the VQ-VAE's (20, frames / 4) latent grid, decoded to mels (audio.py goes on to waveforms).
 """
 from __future__ import annotations
 
@@ -101,3 +103,16 @@ def load_checkpoint(filename: str, model, optimizer=None, map_location=None) -> 
     if optimizer is not None and state.get("optimizer") is not None:
         optimizer.load_state_dict(state["optimizer"])
     return state
+
+
+LATENT_ROWS = 20   # the VQ-VAE's latent grid of an 80-band mel: two stride-2 convolutions, 80 / 4 rows
+
+
+@torch.no_grad()
+def sample_mels(vqvae, prior, label: torch.Tensor, frames: int, g=None, generator=None):
+    """Codes (B, 20, frames // 4) sampled from the prior for the class labels (B,), and their decoded mels (B, 1, 80, frames)
+    (vqvae.decode; put the VQ-VAE in eval mode for its running BatchNorm statistics)."""
+    if frames < 4:
+        raise ValueError("sample_mels: frames must be at least 4 (one latent column)")
+    codes = prior.sample(label, shape=(LATENT_ROWS, frames // 4), batch_size=label.shape[0], generator=generator)
+    return codes, vqvae.decode(codes, g)

@@ -920,3 +920,68 @@ def cross_entropy(logits2d, target, want_grad=True, grad_scale=1.0):
     _lib.call("nsg_cross_entropy", _p(logits2d), _p(target), c_int64(M), c_int32(K), c_float(grad_scale), _p(loss), _p(dl), _p(ws),
               c_size_t(nb), _stream())
     return loss, dl
+
+
+# ------------------------------------------------------------------------------------------------
+# latent prior (GatedPixelCNN): incremental sampling, the per-row column walk
+# ------------------------------------------------------------------------------------------------
+def prior_walk_weight_floats(dim, n_layers, input_dim) -> int:
+    """Floats of the walk's packed weight blob (layout: include/nsg.h, nsg_prior_walk); 0 outside the kernel's envelope."""
+    return int(_lib.query("nsg_prior_walk_weight_floats", c_int32(dim), c_int32(n_layers), c_int32(input_dim)))
+
+
+def prior_walk(w, emb, cond, vh, e_row, H, row, u=None, x_in=None, codes=None, logits=None):
+    """Walk row `row` of a (B, H, W) code grid (nsg_prior_walk).  w: packed blob; emb (K, dim); cond (L, B, 2 dim); vh
+    (L, B, 1, W, 2 dim); e_row (B, W, dim), any clip stride, receives the embedding of the row's codes; exactly one of u
+    (B, H, W) fp32 (sampling: codes (B, H, W) int64 is written) and x_in (B, H, W) int64 (teacher-forced); logits
+    (B, H, W, K) optional."""
+    for t, nm in ((w, "w"), (emb, "emb"), (cond, "cond"), (vh, "vh")):
+        _chk(t, nm)
+    K, dim = emb.shape
+    L, B = cond.shape[0], cond.shape[1]
+    W = e_row.shape[1]
+    if tuple(cond.shape) != (L, B, 2 * dim) or tuple(vh.shape) != (L, B, 1, W, 2 * dim):
+        raise _lib.NsgError(f"prior_walk: cond {tuple(cond.shape)} / vh {tuple(vh.shape)} do not match emb {tuple(emb.shape)}")
+    if w.numel() != prior_walk_weight_floats(dim, L, K):
+        raise _lib.NsgError(f"prior_walk: weight blob of {w.numel()} floats, expected {prior_walk_weight_floats(dim, L, K)}")
+    if not e_row.is_cuda or e_row.dtype != torch.float32 or tuple(e_row.shape) != (B, W, dim) or e_row.stride()[1:] != (dim, 1):
+        raise _lib.NsgError(f"prior_walk: e_row must be fp32 (B, W, dim) = {(B, W, dim)} with rows of dim contiguous floats")
+    if (u is None) == (x_in is None):
+        raise _lib.NsgError("prior_walk: exactly one of u (sampling) and x_in (teacher-forced)")
+    grid = (B, H, W)
+    if u is not None and codes is None:
+        raise _lib.NsgError("prior_walk: sampling needs a codes output")
+    for t, nm, dt, shp in ((u, "u", torch.float32, grid), (x_in, "x_in", torch.int64, grid), (codes, "codes", torch.int64, grid),
+                           (logits, "logits", torch.float32, grid + (K,))):
+        if t is not None:
+            _chk(t, nm, dt)
+            if tuple(t.shape) != shp:
+                raise _lib.NsgError(f"prior_walk: {nm} {tuple(t.shape)}, expected {shp}")
+    if not 0 <= row < H:
+        raise _lib.NsgError(f"prior_walk: row {row} outside 0 .. {H - 1}")
+    _lib.call("nsg_prior_walk", _p(w), _p(emb), _p(cond), _p(vh), _p(u), _p(x_in), _p(codes), _p(e_row), c_int64(e_row.stride(0)),
+              _p(logits), c_int32(B), c_int32(H), c_int32(W), c_int32(dim), c_int32(L), c_int32(K), c_int32(row), _stream())
+
+
+def prepared_conv_forward(d: ConvDesc, x, w_fwd, bias, y, flags=0):
+    """nsg_conv_forward on fixed tensors, checked once: returns a no-argument callable that launches it on the current
+    stream (a loop that runs the same layer once per row skips conv_forward's per-call checks and allocations)."""
+    _chk(x, "x", _in_dtype(d)); _chk(y, "y", _out_dtype(d, flags))
+    if tuple(x.shape) != (d.B, d.IH, d.IW, d.C_in) or tuple(y.shape) != (d.B, d.OH, d.OW, d.C_out):
+        raise _lib.NsgError(f"prepared_conv_forward: x {tuple(x.shape)} / y {tuple(y.shape)} do not match descriptor {d.key()}")
+    ws, nb = _conv_ws(d, x.device)
+    keep = (d, x, w_fwd, bias, y, ws)          # the closure owns every buffer whose address it passes
+    args = (byref(d), _p(x), _p(w_fwd), _p(bias), _p(y), c_int32(flags), _p(ws), c_size_t(nb))
+    return lambda: (keep, _lib.call("nsg_conv_forward", *args, _stream()))
+
+
+def prepared_gated_activation(x, cond, y):
+    """nsg_gated_activation_forward on fixed tensors (x (..., 2C), cond (B, 2C), y (..., C)), checked once: a callable."""
+    _chk(x, "x"); _chk(cond, "cond"); _chk(y, "y")
+    C2 = x.shape[-1]
+    M = x.numel() // C2
+    if cond.shape[-1] != C2 or M % cond.shape[0] != 0 or y.numel() != M * (C2 // 2):
+        raise _lib.NsgError(f"prepared_gated_activation: x {tuple(x.shape)}, cond {tuple(cond.shape)}, y {tuple(y.shape)}")
+    keep = (x, cond, y)
+    args = (_p(x), _p(cond), _p(y), c_int64(M), c_int32(C2 // 2), c_int64(M // cond.shape[0]))
+    return lambda: (keep, _lib.call("nsg_gated_activation_forward", *args, _stream()))

@@ -196,6 +196,147 @@ class GatedPixelCNN(nn.Module):
                 x[:, i, j] = probs.multinomial(1).squeeze(-1)
         return x
 
+    # ------------------------------------------------------------------------------------------------
+    # incremental sampling: one row pass (conv kernels) and one column walk (nsg_prior_walk) per row
+    # ------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def sample(self, label, shape=(8, 8), batch_size=64, u=None, generator=None):
+        """Ancestral sampling in raster order with nothing recomputed: int64 codes (batch_size, H, W).  Each code is the
+        inverse CDF of its softmax against u[b, i, j] (include/nsg.h, nsg_prior_walk); u is drawn with torch.rand on the
+        model's device when not given.  The same distribution as `generate`, O(H W) work instead of O((H W)^2)."""
+        H, W = self._grid(shape)
+        B = int(batch_size)
+        label = self._labels(label, B)
+        dev = label.device
+        if u is None:
+            self._check_walk()
+            u = torch.rand((B, H, W), generator=generator, device=dev)
+        elif not isinstance(u, torch.Tensor) or tuple(u.shape) != (B, H, W) or u.dtype != torch.float32:
+            raise ValueError(f"sample: u must be a float32 tensor of shape {(B, H, W)}")
+        codes = torch.empty((B, H, W), dtype=torch.int64, device=dev)
+        self._walk_rows(label, B, H, W, u=u.to(dev).contiguous(), codes=codes)
+        return codes
+
+    @torch.no_grad()
+    def incremental_logits(self, x, label):
+        """Teacher-forced logits (B, H, W, input_dim) NHWC of the codes x (B, H, W) through the sampling schedule: what
+        forward_nhwc computes, one row pass and one column walk per row."""
+        if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.dtype != torch.int64:
+            raise ValueError("incremental_logits: x must be an int64 tensor (B, H, W)")
+        B, H, W = x.shape
+        self._grid((H, W))
+        label = self._labels(label, B)
+        x = x.to(label.device).contiguous()
+        K = self.embedding.num_embeddings
+        if x.numel() and (int(x.min()) < 0 or int(x.max()) >= K):
+            raise ValueError(f"incremental_logits: codes outside [0, {K})")
+        logits = torch.empty((B, H, W, K), dtype=torch.float32, device=x.device)
+        self._walk_rows(label, B, H, W, x_in=x, logits=logits)
+        return logits
+
+    def walk_supported(self) -> bool:
+        """Whether sample / incremental_logits run for this module's widths (generate serves every width)."""
+        oc = self.output_conv
+        return oc[0].out_channels == 512 and ops.prior_walk_weight_floats(self.dim, len(self.layers), self.embedding.num_embeddings) > 0
+
+    def _check_walk(self):
+        if not self.walk_supported():
+            raise NotImplementedError(f"GatedPixelCNN(input_dim={self.embedding.num_embeddings}, dim={self.dim}, n_layers={len(self.layers)}): "
+                                      "outside the incremental sampler's envelope (dim % 16 == 0, dim <= 128, input_dim <= 1024); "
+                                      "use generate()")
+
+    @staticmethod
+    def _grid(shape):
+        if len(shape) != 2 or int(shape[0]) < 1 or int(shape[1]) < 1:
+            raise ValueError(f"the code grid {tuple(shape)} must be (H, W) with H, W >= 1")
+        return int(shape[0]), int(shape[1])
+
+    def _labels(self, label, B):
+        if B < 1:
+            raise ValueError("batch_size must be at least 1")
+        if not isinstance(label, torch.Tensor) or tuple(label.shape) != (B,) or label.dtype != torch.int64:
+            raise ValueError(f"label must be an int64 tensor of shape ({B},)")
+        n_classes = self.layers[0].class_cond_embedding.num_embeddings
+        label = label.to(next(self.parameters()).device).contiguous()
+        if int(label.min()) < 0 or int(label.max()) >= n_classes:
+            raise ValueError(f"label values outside [0, {n_classes})")
+        return label
+
+    def _walk_blob(self, K):
+        """The walk's packed weights (include/nsg.h, nsg_prior_walk): every matrix transposed to input-major."""
+        parts = []
+        for i, layer in enumerate(self.layers):
+            taps = 3 if i == 0 else 2                                 # layer 0's fourth tap (column j) is masked
+            hw = layer.horiz_stack.weight.detach()[:, :, 0, :taps]    # (2 dim, dim, taps)
+            parts += [hw.permute(2, 1, 0).reshape(-1), layer.horiz_stack.bias.detach(),
+                      layer.horiz_resid.weight.detach()[:, :, 0, 0].t().reshape(-1), layer.horiz_resid.bias.detach()]
+        w0, w2 = self.output_conv[0], self.output_conv[2]
+        Kp = (K + 3) // 4 * 4
+        w2t = torch.zeros(512, Kp, dtype=torch.float32, device=w2.weight.device)
+        w2t[:, :K] = w2.weight.detach()[:, :, 0, 0].t()
+        b2 = torch.zeros(Kp, dtype=torch.float32, device=w2.weight.device)
+        b2[:K] = w2.bias.detach()
+        parts += [w0.weight.detach()[:, :, 0, 0].t().reshape(-1), w0.bias.detach(), w2t.reshape(-1), b2]
+        return torch.cat([p.reshape(-1).float() for p in parts]).contiguous()
+
+    def _walk_rows(self, label, B, H, W, u=None, codes=None, x_in=None, logits=None, times=None):
+        """Row i: the row pass (vertical stacks, their gates and the v2h 1x1s of every layer, all W columns, on the conv
+        kernels), then the column walk.  Layer 0 reads rows i-3 .. i of e (row i is masked: zeros until the walk writes it),
+        the others rows i-1, i of their vertical input; rows above the grid are zero, as the conv's padding is.
+        times: optional dict that collects the row passes' and walks' GPU milliseconds (scripts/prior_sample_timing.py)."""
+        self._check_walk()
+        self.layers[0].make_causal()
+        dim, L, K = self.dim, len(self.layers), self.embedding.num_embeddings
+        dev = label.device
+        blob = self._walk_blob(K)
+        emb = self.embedding.weight.detach().contiguous()
+        cond = torch.stack([ops.gather_rows(layer.class_cond_embedding.weight.detach().contiguous(), label) for layer in self.layers])
+        d0 = ops.conv_desc(B, 4, W, dim, 2 * dim, (4, 7), 1, (0, 3), out_hw=(1, W))
+        dv = ops.conv_desc(B, 2, W, dim, 2 * dim, (2, 3), 1, (0, 1), out_hw=(1, W))
+        d11 = ops.conv_desc(B, 1, W, 2 * dim, 2 * dim, 1, 1, 0, out_hw=(1, W))
+        # Layer l >= 1 keeps rows i-1, i of its vertical input in a 2-row strip, row i in slot i % 2: on even rows the slots
+        # are in reverse order, which the same kernel with its two rows swapped reads in place (no shift copy).
+        vw = [layer.vert_stack.weight.detach().contiguous() for layer in self.layers]
+        jobs = [(d0, vw[0], True, False)] + [(dv, w, True, False) for w in vw[1:]] + [(dv, w.flip(2).contiguous(), True, False) for w in vw[1:]]
+        jobs += [(d11, layer.vert_to_horiz.weight.detach().contiguous(), True, False) for layer in self.layers]
+        packed = [wf for wf, _ in ops.pack_weights_batch(jobs)]
+        vert_w, vert_w_flip, v2h_w = packed[:L], [None] + packed[L:2 * L - 1], packed[2 * L - 1:]
+        e_grid = torch.zeros((B, H + 3, W, dim), dtype=torch.float32, device=dev)   # e with 3 zero rows above the grid
+        e_strip = torch.empty((B, 4, W, dim), dtype=torch.float32, device=dev)
+        strips = torch.zeros((L, B, 2, W, dim), dtype=torch.float32, device=dev)     # slot i % 2: row i of layer l's vertical input
+        h_vert = torch.empty((L, B, 1, W, 2 * dim), dtype=torch.float32, device=dev)
+        v = torch.empty((B, 1, W, dim), dtype=torch.float32, device=dev)
+        vh = torch.empty((L, B, 1, W, 2 * dim), dtype=torch.float32, device=dev)
+        vert, v2h, gate = [], [], []
+        for l, layer in enumerate(self.layers):
+            vb = layer.vert_stack.bias.detach()
+            if l == 0:
+                vert.append((ops.prepared_conv_forward(d0, e_strip, vert_w[0], vb, h_vert[0]),) * 2)
+            else:
+                vert.append((ops.prepared_conv_forward(dv, strips[l], vert_w_flip[l], vb, h_vert[l]),     # even rows
+                             ops.prepared_conv_forward(dv, strips[l], vert_w[l], vb, h_vert[l])))         # odd rows
+            v2h.append(ops.prepared_conv_forward(d11, h_vert[l], v2h_w[l], layer.vert_to_horiz.bias.detach(), vh[l]))
+            gate.append(ops.prepared_gated_activation(h_vert[l], cond[l], v) if l + 1 < L else None)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if times is not None else None
+        for i in range(H):
+            if ev:
+                ev[0].record()
+            e_strip.copy_(e_grid[:, i:i + 4])
+            for l in range(L):
+                vert[l][i % 2]()
+                if gate[l] is not None:
+                    gate[l]()
+                    strips[l + 1, :, i % 2].copy_(v[:, 0])
+                v2h[l]()
+            if ev:
+                ev[1].record()
+            ops.prior_walk(blob, emb, cond, vh, e_grid[:, i + 3], H, i, u=u, x_in=x_in, codes=codes, logits=logits)
+            if ev:
+                ev[2].record()
+                ev[2].synchronize()
+                times["row_pass_ms"] = times.get("row_pass_ms", 0.0) + ev[0].elapsed_time(ev[1])
+                times["walk_ms"] = times.get("walk_ms", 0.0) + ev[1].elapsed_time(ev[2])
+
 
 def _weights_init_quiet(m):
     """models.weights_init (src/models.py:25-32) without the reference's "Skipping initialization of ..." print for the

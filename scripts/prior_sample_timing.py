@@ -1,0 +1,43 @@
+"""Timing of the latent prior's incremental sampler (GatedPixelCNN.sample) at production width, GatedPixelCNN(512, 64, 15):
+64 clips x 20 x 256 codes, with the row passes' and column walks' GPU time reported separately; and sample against the
+naive `generate` (a full forward per position) at 64 x 20 x 32.  Prints one JSON line per measurement."""
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+from neural_sound_generation_amd.prior import GatedPixelCNN  # noqa: E402
+
+dev = "cuda:0"
+torch.manual_seed(1)
+m = GatedPixelCNN(512, 64, 15, 10).to(dev)
+B = 64
+label = torch.randint(0, 10, (B,), device=dev)
+
+
+def wall(fn, n):
+    fn()
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    for _ in range(n):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t) / n
+
+
+for H, W in ((20, 256), (20, 32)):
+    u = torch.rand(B, H, W, device=dev)
+    dt = wall(lambda: m.sample(label, shape=(H, W), batch_size=B, u=u), 3)
+    times = {}
+    with torch.no_grad():                       # the two phases, one synchronised row at a time
+        m._walk_rows(label, B, H, W, u=u, codes=torch.empty(B, H, W, dtype=torch.int64, device=dev), times=times)
+    rec = {"what": "sample", "B": B, "H": H, "W": W, "s": round(dt, 4),
+           "row_pass_ms_per_row": round(times["row_pass_ms"] / H, 3), "walk_ms_per_row": round(times["walk_ms"] / H, 3),
+           "walk_us_per_position": round(times["walk_ms"] * 1e3 / (H * W), 2)}
+    print(json.dumps(rec), flush=True)
+    if W == 32:
+        torch.manual_seed(0)
+        g = wall(lambda: m.generate(label, shape=(H, W), batch_size=B), 1)
+        print(json.dumps({"what": "generate", "B": B, "H": H, "W": W, "s": round(g, 3), "speedup_sample": round(g / dt, 1)}), flush=True)
