@@ -517,9 +517,10 @@ NSG_API int nsg_cross_entropy(const float *logits, const int64_t *target, int64_
  * then the head  logits = W2 relu(W0 h_L + b0) + b2,  then the code of (b, row, j):
  *   - teacher-forced (x_in != NULL, u == NULL): x_in[b][row][j];
  *   - sampling (u != NULL, x_in == NULL): the inverse CDF of softmax(logits) against u[b][row][j] in [0, 1):
- *     p_k = exp(l_k - max l), S = sum_k p_k; the first k whose inclusive prefix sum exceeds u * S, or, if rounding leaves
- *     none, the last k with p_k > 0.  (The prefix sums and S come from one fixed-order scan: contiguous chunks of
- *     ceil(K / 64) codes, chunk totals scanned in chunk order.)
+ *     p_k = exp(l_k - max l) in fp32, S = sum_k p_k; the first k with p_k > 0 whose inclusive prefix sum exceeds u * S, or,
+ *     if rounding leaves none, the last k with p_k > 0.  A code with p_k == 0 is never returned.  (The prefix sums and S
+ *     come from one fixed-order scan: contiguous chunks of ceil(K / 64) codes, chunk totals scanned in chunk order, each
+ *     chunk's prefix sums continuing from the scan of the chunks before it.)
  * The code goes to codes[b][row][j] (if codes != NULL) and embedding[code] to e_row + b * e_clip_stride + j * dim.
  * logits (optional) [B][H][W][K] receives the row's logits.
  * Inputs of the row, produced beforehand by the row pass on the conv kernels: vh [L][B][W][2 dim] = v2h_l(h_vert_l) of the

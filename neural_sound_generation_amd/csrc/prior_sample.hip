@@ -214,13 +214,19 @@ __global__ __launch_bounds__(THREADS) void prior_walk_kernel(WalkArgs a)
                 }
                 const float S_ = __shfl(incl, 63, 64);
                 const float target = a.u[pos] * S_;
-                float run = incl - tot;
+                // A lane's running sum starts at the scan of the lanes before it, but its end can differ from that scan's next
+                // value by a few ulps.  A target in such a gap is passed at once by the next lane: only a code with p > 0 may
+                // take it, so a code the distribution excludes is never returned.
+                const float before = __shfl_up(incl, 1, 64);
+                float run = lane == 0 ? 0.f : before;
                 int first = K, lastpos = -1;
                 for (int k = k0; k < k1; ++k) {
                     const float p = expf(l[k] - mx);
                     run += p;
-                    if (first == K && run > target) first = k;
-                    if (p > 0.f) lastpos = k;
+                    if (p > 0.f) {
+                        if (first == K && run > target) first = k;
+                        lastpos = k;
+                    }
                 }
 #pragma unroll
                 for (int off = 32; off >= 1; off >>= 1) {

@@ -113,3 +113,43 @@ def test_loader_refuses_a_library_of_another_abi_version(monkeypatch):
     monkeypatch.setattr(_lib, "NSG_VERSION", lib.nsg_version() + 1)
     with pytest.raises(_lib.NsgError, match="ABI version"):
         _lib._bind(ctypes.CDLL(_lib.LIB_PATH))
+
+
+def test_prior_walk_size_query_and_argument_checks():
+    """nsg_prior_walk_weight_floats is the size of GatedPixelCNN._walk_blob inside the walk's envelope and 0 outside it;
+    nsg_prior_walk refuses each bad argument, and a shape outside the envelope, with dummy pointers before any launch."""
+    from neural_sound_generation_amd.prior import GatedPixelCNN
+    from tests.test_gpu_prior_walk_envelope import DEEPEST, WIDTHS, deepest_layers
+    lib = _lib.load()
+    for K, dim, L in WIDTHS:
+        L = deepest_layers(K, dim) if L is DEEPEST else L
+        assert lib.nsg_prior_walk_weight_floats(dim, L, K) == GatedPixelCNN(K, dim, L)._walk_blob(K).numel(), (K, dim, L)
+    outside = [(8, 2, 64), (20, 2, 64), (136, 2, 64), (0, 2, 64), (-16, 2, 64), (16, 0, 64), (16, -1, 64), (16, 2, 0),
+               (16, 2, -1), (16, 2, 1025), (128, deepest_layers(1024, 128) + 1, 1024), (64, deepest_layers(512, 64) + 1, 512)]
+    for dim, L, K in outside:
+        assert lib.nsg_prior_walk_weight_floats(dim, L, K) == 0, (dim, L, K)
+
+    ok, odd = 0x10000, 0x10004      # never dereferenced: every call below fails its checks before the launch
+    B, H, W, dim = 5, 4, 37, 16
+    good = dict(w=ok, emb=ok, cond=ok, vh=ok, u=ok, x_in=0, codes=ok, e_row=ok, e_clip_stride=W * dim, logits=0,
+                B=B, H=H, W=W, dim=dim, n_layers=2, input_dim=64, row=0)
+
+    def walk(**change):
+        a = dict(good, **change)
+        p = [ctypes.c_void_p(a[k]) for k in ("w", "emb", "cond", "vh", "u", "x_in", "codes", "e_row")]
+        return lib.nsg_prior_walk(*p, a["e_clip_stride"], ctypes.c_void_p(a["logits"]), a["B"], a["H"], a["W"], a["dim"],
+                                  a["n_layers"], a["input_dim"], a["row"], None)
+
+    invalid = [dict(w=0), dict(emb=0), dict(cond=0), dict(vh=0), dict(e_row=0),
+               dict(x_in=ok), dict(u=0), dict(codes=0),                              # both u and x_in, neither, no codes
+               dict(B=0), dict(H=0), dict(W=0), dict(row=-1), dict(row=H),
+               dict(e_clip_stride=W * dim - 4), dict(e_clip_stride=W * dim + 2),
+               dict(w=odd), dict(emb=odd), dict(cond=odd), dict(vh=odd), dict(e_row=odd)]
+    for change in invalid:
+        assert walk(**change) == -1, change
+        assert b"nsg_prior_walk" in lib.nsg_last_error_string()
+    unsupported = [dict(dim=8), dict(dim=20), dict(dim=136), dict(n_layers=0), dict(input_dim=0), dict(input_dim=1025),
+                   dict(dim=128, n_layers=deepest_layers(1024, 128) + 1, input_dim=1024, e_clip_stride=W * 128)]
+    for change in unsupported:
+        assert walk(**change) == -2, change
+        assert b"outside the envelope" in lib.nsg_last_error_string()

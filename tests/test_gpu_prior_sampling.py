@@ -56,9 +56,12 @@ def _inverse_cdf(l64, u):
     return y, pre, S[..., 0]
 
 
-def _agree_up_to_near_ties(x, y, pre, S, u, tol=1e-4):
-    """Per clip: y == x everywhere, or at the first raster-order mismatch u * S lies within tol * S of a prefix boundary
+def _agree_up_to_near_ties(x, y, pre, S, u, l64, tol=1e-4):
+    """Every sampled code x has a positive fp64 probability under its logits l64, one that fp32 can hold (p >= 2^-149).
+    Per clip: y == x everywhere, or at the first raster-order mismatch u * S lies within tol * S of a prefix boundary
     between the two codes.  Returns the number of clips that needed the near-tie allowance."""
+    p = torch.exp(l64 - l64.amax(dim=-1, keepdim=True)).gather(-1, x[..., None])[..., 0]
+    assert bool((p >= 2.0 ** -149).all()), f"{int((p < 2.0 ** -149).sum())} sampled codes have zero probability"
     B = x.shape[0]
     near = 0
     for b in range(B):
@@ -120,8 +123,9 @@ def test_sample_is_the_inverse_cdf_of_its_logits(which, golden_dir):
     x = model.sample(label.to(DEV), shape=(H, W), batch_size=B, u=u.to(DEV))
     assert tuple(x.shape) == (B, H, W) and x.dtype == torch.int64
     st = {k: v.clone() for k, v in model.state_dict().items()}
-    y, pre, S = _inverse_cdf(_fp64_logits(st, x, label, n_layers), u)
-    near = _agree_up_to_near_ties(x.cpu(), y, pre, S, u)
+    l64 = _fp64_logits(st, x, label, n_layers)
+    y, pre, S = _inverse_cdf(l64, u)
+    near = _agree_up_to_near_ties(x.cpu(), y, pre, S, u, l64)
     assert near <= 3, f"{near} of {B} clips needed the near-tie allowance"
 
 
@@ -142,7 +146,7 @@ def test_sample_equals_a_naive_ancestral_loop(golden_dir):
     l64 = _fp64_logits(st, got, label, n_layers)
     y, pre, S = _inverse_cdf(l64, u)
     # the sampler's codes agree with the loop's up to near-ties
-    near = _agree_up_to_near_ties(got, x, pre, S, u)
+    near = _agree_up_to_near_ties(got, x, pre, S, u, l64)
     assert near <= 1
 
 
