@@ -539,6 +539,30 @@ NSG_API int nsg_prior_walk(const float *w, const float *emb, const float *cond, 
                            int64_t *codes, float *e_row, int64_t e_clip_stride, float *logits, int32_t B, int32_t H, int32_t W,
                            int32_t dim, int32_t n_layers, int32_t input_dim, int32_t row, void *stream);
 
+/* The same walk with a controlled pick: temperature, top-k and top-p truncation, and kept (primed) codes.  u and codes are
+ * required; x_in and keep ([B][H][W], one byte per position) are given together or both NULL.  The rule, for one position
+ * with fp32 logits l_k (k < K), mx = max l, temperature T > 0, top_k >= 0 (0 = off) and 0 < top_p <= 1 (1 = off):
+ *   1. p_k = expf((l_k - mx) * inv_t) with inv_t = 1.0f / T computed once in fp32 by the launcher (T == 1: the product is
+ *      exact and p_k has nsg_prior_walk's bits).  The live codes are those with p_k > 0.
+ *   2. top-k, if 1 <= top_k < the number of live codes: t = the top_k-th largest LOGIT of the live codes, counted with
+ *      multiplicity, and A = {k live : l_k >= t} (codes tied at t are all kept); otherwise A = the live codes.
+ *   3. top-p, if top_p < 1: S_A = sum_{k in A} p_k; v = the largest value among {p_k : k in A} with
+ *      sum_{k in A, p_k >= v} p_k >= top_p * S_A; N = {k in A : p_k >= v} -- the smallest set of most probable codes that
+ *      reaches the mass, ties kept (if rounding left no such v, N = A).  With top_p == 1 the step is skipped, N = A.
+ *   4. the pick is nsg_prior_walk's over N in index order: the first k in N whose inclusive prefix sum over N exceeds
+ *      u * S_N, or else the last k in N.  A code outside N is never returned.
+ *   5. where keep[b][row][j] != 0 the code is x_in[b][row][j] (clamped to [0, input_dim)) and u is not consulted.
+ * Every sum is in a fixed order that depends only on K (the scan of step 4 is nsg_prior_walk's; the masses of step 3 add each
+ * chunk of ceil(K / 64) codes in index order, then the 64 chunk totals in a fixed tree).  With T == 1, top_k == 0, top_p == 1
+ * and nothing kept the codes are nsg_prior_walk's, bit for bit.  Kept codes are not conditioned on by the positions before
+ * them in raster order: each sampled code is drawn from the conditional given everything BEFORE it, kept or sampled.
+ * Same envelope, alignment and extent checks as nsg_prior_walk; NSG_E_INVALID for a temperature that is not finite and > 0
+ * (or whose fp32 reciprocal is not finite), top_k < 0, or top_p outside (0, 1]. */
+NSG_API int nsg_prior_walk_ctl(const float *w, const float *emb, const float *cond, const float *vh, const float *u,
+                               const int64_t *x_in, const uint8_t *keep, int64_t *codes, float *e_row, int64_t e_clip_stride,
+                               float *logits, int32_t B, int32_t H, int32_t W, int32_t dim, int32_t n_layers, int32_t input_dim,
+                               int32_t row, float temperature, int32_t top_k, float top_p, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Mel -> waveform inversion (the epoch loop's audio export)   src/main.py:164-197, src/audio_tacotron.py:99-116,142-153
  * librosa's stft / istft / filters.mel and scipy's lfilter restated; fp32; frame-major spectrograms [B][T][F], F = n_fft/2+1.

@@ -114,6 +114,8 @@ _SIGS = {
     "nsg_cross_entropy": (None, [_P, _P, c_int64, c_int32, c_float, _P, _P, _P, c_size_t, _P]),
     "nsg_prior_walk_weight_floats": (c_size_t, [c_int32, c_int32, c_int32]),
     "nsg_prior_walk": (None, [_P, _P, _P, _P, _P, _P, _P, _P, c_int64, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P]),
+    "nsg_prior_walk_ctl": (None, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                  c_float, c_int32, c_float, _P]),
     "nsg_audio_mel_to_linear": (None, [_P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_float, c_float, _P]),
     "nsg_audio_griffin_lim_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
     "nsg_audio_griffin_lim": (None, [_P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, _P, c_size_t, _P]),

@@ -13,6 +13,7 @@
 // order: a clip's arithmetic is the same in any batch, and the result is deterministic.  fp32 throughout.
 #include "nsg_common.h"
 #include <math.h>
+#include <type_traits>
 
 namespace {
 
@@ -21,6 +22,7 @@ constexpr int THREADS = 1024;
 constexpr int SMAX = 8;        // k-slices per output at most (the slices' partials are summed serially)
 constexpr int HEAD = 512;      // output_conv's hidden width (fixed by the module)
 constexpr int RED = 4096;      // per-clip partial-sum slots: S * N <= THREADS * 4 for every product (see matvec_partial)
+constexpr int CKMAX = 16;      // codes per lane of the pick at most: ceil(1024 / 64)
 
 struct WalkArgs {
     const float *w;          // packed weights (layout: nsg_prior_walk_weight_floats in include/nsg.h)
@@ -34,6 +36,13 @@ struct WalkArgs {
     int64_t e_clip_stride;
     float *logits;           // [B][H][W][K] or null
     int B, H, W, dim, L, K, Kp, row;
+};
+
+struct WalkCtlArgs : WalkArgs {   // nsg_prior_walk_ctl: u and codes are set; x_in and keep come together
+    const uint8_t *keep;     // [B][H][W] or null: where non-zero the code is x_in's
+    float inv_t;             // 1 / temperature
+    int top_k;               // 0 = off
+    float top_p;             // 1 = off
 };
 
 // Partial sums of y[c][n] for n < N (N % 4 == 0), k < Kd, into red[(s * NC + c) * N + n], s = the thread's k-slice
@@ -92,7 +101,139 @@ __device__ __forceinline__ float reduce_out(const float *red, int S, int N, int 
     return v + bias;
 }
 
-__global__ __launch_bounds__(THREADS) void prior_walk_kernel(WalkArgs a)
+// fp32 as an unsigned key of the same order (finite values and infinities)
+__device__ __forceinline__ uint32_t order_key(float f)
+{
+    uint32_t b = __float_as_uint(f);
+    if (b == 0x80000000u) b = 0;                 // -0 orders as +0, as the comparison of the values has it
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+// The sum over the wave of per-lane counts n <= CKMAX < 32: one ballot per bit of n, no cross-lane data movement
+__device__ __forceinline__ int wave_count(int n)
+{
+    int s = 0;
+#pragma unroll
+    for (int b = 0; b < 5; ++b) s += __popcll(__ballot((n >> b) & 1)) << b;
+    return s;
+}
+
+// The sum of the 64 lanes' values (every lane active) in a fixed order, the same bits in every lane: within rows of 16 lanes by
+// DPP (pairs, quads, row_shr:4, row_shr:8 leave the row's sum in its lane 15), then row_bcast:15 and row_bcast:31 carry the
+// rows' sums into lane 63, which is read back.  No LDS traffic: a few cycles per step where a __shfl costs an LDS round trip.
+template <int CTRL>
+__device__ __forceinline__ float dpp_add(float v)
+{
+    // lanes the pattern gives no source add 0 (old = 0, bound_ctrl off): they do not lie on lane 63's path
+    return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
+}
+
+__device__ __forceinline__ float wave_sum(float v)
+{
+    v = dpp_add<0xb1>(v);     // quad_perm:[1,0,3,2]
+    v = dpp_add<0x4e>(v);     // quad_perm:[2,3,0,1]
+    v = dpp_add<0x114>(v);    // row_shr:4
+    v = dpp_add<0x118>(v);    // row_shr:8
+    v = dpp_add<0x142>(v);    // row_bcast:15
+    v = dpp_add<0x143>(v);    // row_bcast:31
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
+}
+
+// The pick of nsg_prior_walk_ctl (include/nsg.h) by one wave: the lane holds its chunk of ceil(K / 64) consecutive codes in
+// registers as q[r] = p_k inside the kept set and 0 outside it, then runs the plain walk's scan over q.  Both thresholds are
+// the largest key whose monotone statistic (a count of logits >= t, a mass of p >= v) reaches its goal, built bit by bit
+// from the top with one wave reduction per bit.  With temperature 1 and both filters off q is the plain walk's p, bit for bit.
+// CK: the register chunk, >= ceil(K / 64) (8 serves K <= 512 at half the per-lane work of 16; the arithmetic is the same).
+// Not inlined: the walk's products already take 124 of the 128 VGPRs a 1024-thread workgroup allows, and with the pick's
+// register arrays inlined the allocator spilled some 800 VGPRs to scratch; as a call it gets registers of its own (98).
+template <int CK>
+__device__ __noinline__ int pick_ctl(const float *l, int K, int lane, float u, float inv_t, int top_k, float top_p)
+{
+    const int ck = (K + 63) / 64;
+    const int k0 = lane * ck, k1 = min(K, k0 + ck);
+    float mx = -INFINITY;
+    for (int k = k0; k < k1; ++k) mx = fmaxf(mx, l[k]);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
+    float q[CK];
+    int nlive = 0;
+#pragma unroll
+    for (int r = 0; r < CK; ++r) {
+        q[r] = 0.f;
+        if (k0 + r < k1) q[r] = expf((l[k0 + r] - mx) * inv_t);
+        nlive += q[r] > 0.f;
+    }
+    if (top_k >= 1 && top_k < wave_count(nlive)) {   // t = the top_k-th largest logit of the live codes; ties at t are kept
+        uint32_t key[CK];
+#pragma unroll
+        for (int r = 0; r < CK; ++r) {
+            key[r] = 0u;                     // no logit has key 0
+            if (q[r] > 0.f) key[r] = order_key(l[k0 + r]);
+        }
+        uint32_t t = 0;
+#pragma unroll 1
+        for (int bit = 31; bit >= 0; --bit) {
+            const uint32_t cand = t | (1u << bit);
+            int n = 0;
+#pragma unroll
+            for (int r = 0; r < CK; ++r) n += key[r] >= cand;
+            if (wave_count(n) >= top_k) t = cand;
+        }
+#pragma unroll
+        for (int r = 0; r < CK; ++r)
+            if (key[r] < t) q[r] = 0.f;
+    }
+    if (top_p < 1.f) {                           // v = the largest kept p whose mass of p >= v reaches top_p * S_A
+        float m = 0.f;
+#pragma unroll
+        for (int r = 0; r < CK; ++r) m += q[r];
+        const float goal = top_p * wave_sum(m);
+        uint32_t t = 0;                          // q >= 0: its bits order as the values do
+#pragma unroll 1
+        for (int bit = 30; bit >= 0; --bit) {
+            const uint32_t cand = t | (1u << bit);
+            m = 0.f;
+#pragma unroll
+            for (int r = 0; r < CK; ++r) m += __float_as_uint(q[r]) >= cand ? q[r] : 0.f;
+            if (wave_sum(m) >= goal) t = cand;
+        }
+#pragma unroll
+        for (int r = 0; r < CK; ++r)
+            if (__float_as_uint(q[r]) < t) q[r] = 0.f;
+    }
+    // the plain walk's scan and pick (prior_walk_kernel, step 5) over q
+    float tot = 0.f;
+#pragma unroll
+    for (int r = 0; r < CK; ++r) tot += q[r];
+    float incl = tot;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const float o = __shfl_up(incl, off, 64);
+        if (lane >= off) incl = o + incl;
+    }
+    const float target = u * __shfl(incl, 63, 64);
+    const float before = __shfl_up(incl, 1, 64);
+    float run = lane == 0 ? 0.f : before;
+    int first = K, lastpos = -1;
+#pragma unroll
+    for (int r = 0; r < CK; ++r) {
+        run += q[r];
+        if (q[r] > 0.f) {
+            if (first == K && run > target) first = k0 + r;
+            lastpos = k0 + r;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        first = min(first, __shfl_xor(first, off, 64));
+        lastpos = max(lastpos, __shfl_xor(lastpos, off, 64));
+    }
+    return first < K ? first : lastpos;
+}
+
+// CTL: the instantiation of nsg_prior_walk_ctl (temperature, top-k, top-p, kept codes); the plain one is nsg_prior_walk's.
+template <bool CTL>
+__global__ __launch_bounds__(THREADS) void prior_walk_kernel(std::conditional_t<CTL, WalkCtlArgs, WalkArgs> a)
 {
     extern __shared__ float lds[];
     const int dim = a.dim, D2 = 2 * dim, L = a.L, Kp = a.Kp;
@@ -194,7 +335,11 @@ __global__ __launch_bounds__(THREADS) void prior_walk_kernel(WalkArgs a)
             const int c = wave, b = b0 + c;
             const size_t pos = ((size_t)b * a.H + i) * a.W + j;
             int code;
-            if (a.x_in) {
+            if constexpr (CTL) {
+                if (a.keep && a.keep[pos]) code = (int)a.x_in[pos];
+                else if (a.K <= 64 * 8) code = pick_ctl<8>(lg + c * Kp, a.K, lane, a.u[pos], a.inv_t, a.top_k, a.top_p);
+                else code = pick_ctl<CKMAX>(lg + c * Kp, a.K, lane, a.u[pos], a.inv_t, a.top_k, a.top_p);
+            } else if (a.x_in) {
                 code = (int)a.x_in[pos];
             } else {
                 const float *l = lg + c * Kp;
@@ -280,30 +425,66 @@ size_t nsg_prior_walk_weight_floats(int32_t dim, int32_t n_layers, int32_t input
     return layer0 + (size_t)(n_layers - 1) * layerN + (size_t)dim * HEAD + HEAD + HEAD * Kp + Kp;
 }
 
+// The checks nsg_prior_walk and nsg_prior_walk_ctl share (fn: the entry point's name for the error string)
+static int walk_checks(const char *fn, const float *w, const float *emb, const float *cond, const float *vh, const float *e_row,
+                       int64_t e_clip_stride, int32_t B, int32_t H, int32_t W, int32_t dim, int32_t n_layers, int32_t input_dim, int32_t row)
+{
+    NSG_REQUIRE(w && emb && cond && vh && e_row, NSG_E_INVALID, "%s: null pointer", fn);
+    NSG_REQUIRE(B > 0 && H > 0 && W > 0 && row >= 0 && row < H, NSG_E_INVALID, "%s: bad extents (B, H, W > 0, 0 <= row < H)", fn);
+    NSG_REQUIRE(walk_supported(dim, n_layers, input_dim), NSG_E_UNSUPPORTED,
+                "%s: dim=%d n_layers=%d input_dim=%d outside the envelope (dim %% 16 == 0, dim <= 128, n_layers >= 1, "
+                "input_dim <= 1024, LDS <= 160 KiB)", fn, dim, n_layers, input_dim);
+    NSG_REQUIRE(e_clip_stride >= (int64_t)W * dim && e_clip_stride % 4 == 0, NSG_E_INVALID, "%s: bad e_clip_stride", fn);
+    NSG_REQUIRE(nsg_aligned16(w) && nsg_aligned16(emb) && nsg_aligned16(cond) && nsg_aligned16(vh) && nsg_aligned16(e_row), NSG_E_INVALID,
+                "%s: pointers must be 16-byte aligned", fn);
+    return NSG_OK;
+}
+
+static void walk_fill(WalkArgs &a, const float *w, const float *emb, const float *cond, const float *vh, const float *u, const int64_t *x_in,
+                      int64_t *codes, float *e_row, int64_t e_clip_stride, float *logits, int32_t B, int32_t H, int32_t W, int32_t dim,
+                      int32_t n_layers, int32_t input_dim, int32_t row)
+{
+    a.w = w; a.emb = emb; a.cond = cond; a.vh = vh; a.u = u; a.x_in = x_in; a.codes = codes;
+    a.e_row = e_row; a.e_clip_stride = e_clip_stride; a.logits = logits;
+    a.B = B; a.H = H; a.W = W; a.dim = dim; a.L = n_layers; a.K = input_dim; a.Kp = (input_dim + 3) / 4 * 4; a.row = row;
+}
+
 int nsg_prior_walk(const float *w, const float *emb, const float *cond, const float *vh, const float *u, const int64_t *x_in,
                    int64_t *codes, float *e_row, int64_t e_clip_stride, float *logits, int32_t B, int32_t H, int32_t W, int32_t dim,
                    int32_t n_layers, int32_t input_dim, int32_t row, void *stream)
 {
-    NSG_REQUIRE(w && emb && cond && vh && e_row, NSG_E_INVALID, "nsg_prior_walk: null pointer");
     NSG_REQUIRE((u != nullptr) != (x_in != nullptr), NSG_E_INVALID, "nsg_prior_walk: exactly one of u (sampling) and x_in (teacher-forced)");
     NSG_REQUIRE(x_in || codes, NSG_E_INVALID, "nsg_prior_walk: sampling needs a codes output");
-    NSG_REQUIRE(B > 0 && H > 0 && W > 0 && row >= 0 && row < H, NSG_E_INVALID, "nsg_prior_walk: bad extents (B, H, W > 0, 0 <= row < H)");
-    NSG_REQUIRE(walk_supported(dim, n_layers, input_dim), NSG_E_UNSUPPORTED,
-                "nsg_prior_walk: dim=%d n_layers=%d input_dim=%d outside the envelope (dim %% 16 == 0, dim <= 128, n_layers >= 1, "
-                "input_dim <= 1024, LDS <= 160 KiB)", dim, n_layers, input_dim);
-    NSG_REQUIRE(e_clip_stride >= (int64_t)W * dim && e_clip_stride % 4 == 0, NSG_E_INVALID, "nsg_prior_walk: bad e_clip_stride");
-    NSG_REQUIRE(nsg_aligned16(w) && nsg_aligned16(emb) && nsg_aligned16(cond) && nsg_aligned16(vh) && nsg_aligned16(e_row), NSG_E_INVALID,
-                "nsg_prior_walk: pointers must be 16-byte aligned");
-    const int Kp = (input_dim + 3) / 4 * 4;
-    const size_t lds = walk_lds_bytes(dim, n_layers, Kp);
+    if (const int rc = walk_checks("nsg_prior_walk", w, emb, cond, vh, e_row, e_clip_stride, B, H, W, dim, n_layers, input_dim, row)) return rc;
     static LdsOptIn once;
-    if (const int rc = nsg_lds_opt_in(once, {reinterpret_cast<const void *>(&prior_walk_kernel)}, LDS_MAX, "nsg_prior_walk")) return rc;
+    if (const int rc = nsg_lds_opt_in(once, {reinterpret_cast<const void *>(&prior_walk_kernel<false>)}, LDS_MAX, "nsg_prior_walk")) return rc;
     WalkArgs a;
-    a.w = w; a.emb = emb; a.cond = cond; a.vh = vh; a.u = u; a.x_in = x_in; a.codes = codes;
-    a.e_row = e_row; a.e_clip_stride = e_clip_stride; a.logits = logits;
-    a.B = B; a.H = H; a.W = W; a.dim = dim; a.L = n_layers; a.K = input_dim; a.Kp = Kp; a.row = row;
-    hipLaunchKernelGGL(prior_walk_kernel, dim3((unsigned)nsg_cdiv(B, NC)), dim3(THREADS), lds, (hipStream_t)stream, a);
+    walk_fill(a, w, emb, cond, vh, u, x_in, codes, e_row, e_clip_stride, logits, B, H, W, dim, n_layers, input_dim, row);
+    hipLaunchKernelGGL(prior_walk_kernel<false>, dim3((unsigned)nsg_cdiv(B, NC)), dim3(THREADS), walk_lds_bytes(dim, n_layers, a.Kp),
+                       (hipStream_t)stream, a);
     return nsg_check_launch("prior_walk_kernel");
+}
+
+int nsg_prior_walk_ctl(const float *w, const float *emb, const float *cond, const float *vh, const float *u, const int64_t *x_in,
+                       const uint8_t *keep, int64_t *codes, float *e_row, int64_t e_clip_stride, float *logits, int32_t B, int32_t H,
+                       int32_t W, int32_t dim, int32_t n_layers, int32_t input_dim, int32_t row, float temperature, int32_t top_k,
+                       float top_p, void *stream)
+{
+    NSG_REQUIRE(u && codes, NSG_E_INVALID, "nsg_prior_walk_ctl: u and codes are required");
+    NSG_REQUIRE((x_in != nullptr) == (keep != nullptr), NSG_E_INVALID, "nsg_prior_walk_ctl: x_in and keep come together");
+    NSG_REQUIRE(isfinite(temperature) && temperature > 0.f && isfinite(1.0f / temperature), NSG_E_INVALID,
+                "nsg_prior_walk_ctl: temperature must be finite and > 0, and so must 1 / temperature in fp32");
+    NSG_REQUIRE(top_k >= 0, NSG_E_INVALID, "nsg_prior_walk_ctl: top_k=%d must be >= 0 (0 = off)", top_k);
+    NSG_REQUIRE(top_p > 0.f && top_p <= 1.f, NSG_E_INVALID, "nsg_prior_walk_ctl: top_p must be in (0, 1] (1 = off)");
+    if (const int rc = walk_checks("nsg_prior_walk_ctl", w, emb, cond, vh, e_row, e_clip_stride, B, H, W, dim, n_layers, input_dim, row)) return rc;
+    static LdsOptIn once;
+    if (const int rc = nsg_lds_opt_in(once, {reinterpret_cast<const void *>(&prior_walk_kernel<true>)}, LDS_MAX, "nsg_prior_walk_ctl")) return rc;
+    WalkCtlArgs a;
+    walk_fill(a, w, emb, cond, vh, u, x_in, codes, e_row, e_clip_stride, logits, B, H, W, dim, n_layers, input_dim, row);
+    a.keep = keep; a.inv_t = 1.0f / temperature; a.top_k = top_k; a.top_p = top_p;
+    hipLaunchKernelGGL(prior_walk_kernel<true>, dim3((unsigned)nsg_cdiv(B, NC)), dim3(THREADS), walk_lds_bytes(dim, n_layers, a.Kp),
+                       (hipStream_t)stream, a);
+    return nsg_check_launch("prior_walk_ctl_kernel");
 }
 
 }  // extern "C"

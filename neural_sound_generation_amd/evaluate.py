@@ -13,6 +13,8 @@ checkpoint layout, restated from the reference's src/test.py:73-106 and src/main
     layout (FlatAdam.state_dict), so checkpoints move both ways between the reference and this package.
   * `sample_mels(vqvae, prior, label, frames)` -- generation's code -> mel half: codes drawn from the latent prior
     (GatedPixelCNN.sample) on the VQ-VAE's (20, frames / 4) latent grid, decoded to mels (audio.py goes on to waveforms).
+  * `continue_mels(vqvae, prior, mel, label, keep_frames, frames)` -- the same with the first keep_frames of a given mel held:
+    encode, keep the leading latent columns, sample the rest (GatedPixelCNN.continue_codes), decode.
 """
 from __future__ import annotations
 
@@ -109,10 +111,27 @@ LATENT_ROWS = 20   # the VQ-VAE's latent grid of an 80-band mel: two stride-2 co
 
 
 @torch.no_grad()
-def sample_mels(vqvae, prior, label: torch.Tensor, frames: int, g=None, generator=None):
+def sample_mels(vqvae, prior, label: torch.Tensor, frames: int, g=None, generator=None, **controls):
     """Codes (B, 20, frames // 4) sampled from the prior for the class labels (B,), and their decoded mels (B, 1, 80, frames)
-    (vqvae.decode; put the VQ-VAE in eval mode for its running BatchNorm statistics)."""
+    (vqvae.decode; put the VQ-VAE in eval mode for its running BatchNorm statistics).  controls: GatedPixelCNN.sample's
+    temperature, top_k and top_p."""
     if frames < 4:
         raise ValueError("sample_mels: frames must be at least 4 (one latent column)")
-    codes = prior.sample(label, shape=(LATENT_ROWS, frames // 4), batch_size=label.shape[0], generator=generator)
+    codes = prior.sample(label, shape=(LATENT_ROWS, frames // 4), batch_size=label.shape[0], generator=generator, **controls)
+    return codes, vqvae.decode(codes, g)
+
+
+@torch.no_grad()
+def continue_mels(vqvae, prior, mel: torch.Tensor, label: torch.Tensor, keep_frames: int, frames: int, g=None, generator=None, **controls):
+    """Continue mels in time: mel (B, 1, 80, T) is encoded to its codes, the first keep_frames // 4 latent columns are kept
+    and the prior samples the grid out to frames // 4 columns (GatedPixelCNN.continue_codes, which says what the sampled codes
+    are conditioned on; controls: temperature, top_k, top_p), then the grid is decoded.  Returns codes (B, 20, frames // 4)
+    and mels (B, 1, 80, frames)."""
+    if frames < 4:
+        raise ValueError("continue_mels: frames must be at least 4 (one latent column)")
+    known = vqvae.encode(mel)
+    w0 = int(keep_frames) // 4
+    if keep_frames < 0 or w0 > known.shape[-1] or w0 > frames // 4:
+        raise ValueError(f"continue_mels: keep_frames = {keep_frames} must be within the mel's {4 * known.shape[-1]} frames and frames = {frames}")
+    codes = prior.continue_codes(known[:, :, :w0].contiguous(), label, frames // 4, generator=generator, **controls)
     return codes, vqvae.decode(codes, g)

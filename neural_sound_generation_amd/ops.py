@@ -6,6 +6,7 @@ All activations are fp32 NHWC; see include/nsg.h.
 from __future__ import annotations
 
 import ctypes
+import math
 from ctypes import byref, c_float, c_int32, c_int64, c_size_t, c_void_p
 
 import torch
@@ -930,37 +931,68 @@ def prior_walk_weight_floats(dim, n_layers, input_dim) -> int:
     return int(_lib.query("nsg_prior_walk_weight_floats", c_int32(dim), c_int32(n_layers), c_int32(input_dim)))
 
 
-def prior_walk(w, emb, cond, vh, e_row, H, row, u=None, x_in=None, codes=None, logits=None):
-    """Walk row `row` of a (B, H, W) code grid (nsg_prior_walk).  w: packed blob; emb (K, dim); cond (L, B, 2 dim); vh
-    (L, B, 1, W, 2 dim); e_row (B, W, dim), any clip stride, receives the embedding of the row's codes; exactly one of u
-    (B, H, W) fp32 (sampling: codes (B, H, W) int64 is written) and x_in (B, H, W) int64 (teacher-forced); logits
-    (B, H, W, K) optional."""
+def _prior_walk_extents(fn, w, emb, cond, vh, e_row, H, row, tensors):
+    """The checks prior_walk and prior_walk_ctl share; tensors: (tensor or None, name, dtype, trailing shape after (B, H, W)).
+    Returns (B, W, dim, L, K)."""
     for t, nm in ((w, "w"), (emb, "emb"), (cond, "cond"), (vh, "vh")):
         _chk(t, nm)
     K, dim = emb.shape
     L, B = cond.shape[0], cond.shape[1]
     W = e_row.shape[1]
     if tuple(cond.shape) != (L, B, 2 * dim) or tuple(vh.shape) != (L, B, 1, W, 2 * dim):
-        raise _lib.NsgError(f"prior_walk: cond {tuple(cond.shape)} / vh {tuple(vh.shape)} do not match emb {tuple(emb.shape)}")
+        raise _lib.NsgError(f"{fn}: cond {tuple(cond.shape)} / vh {tuple(vh.shape)} do not match emb {tuple(emb.shape)}")
     if w.numel() != prior_walk_weight_floats(dim, L, K):
-        raise _lib.NsgError(f"prior_walk: weight blob of {w.numel()} floats, expected {prior_walk_weight_floats(dim, L, K)}")
+        raise _lib.NsgError(f"{fn}: weight blob of {w.numel()} floats, expected {prior_walk_weight_floats(dim, L, K)}")
     if not e_row.is_cuda or e_row.dtype != torch.float32 or tuple(e_row.shape) != (B, W, dim) or e_row.stride()[1:] != (dim, 1):
-        raise _lib.NsgError(f"prior_walk: e_row must be fp32 (B, W, dim) = {(B, W, dim)} with rows of dim contiguous floats")
-    if (u is None) == (x_in is None):
-        raise _lib.NsgError("prior_walk: exactly one of u (sampling) and x_in (teacher-forced)")
-    grid = (B, H, W)
-    if u is not None and codes is None:
-        raise _lib.NsgError("prior_walk: sampling needs a codes output")
-    for t, nm, dt, shp in ((u, "u", torch.float32, grid), (x_in, "x_in", torch.int64, grid), (codes, "codes", torch.int64, grid),
-                           (logits, "logits", torch.float32, grid + (K,))):
+        raise _lib.NsgError(f"{fn}: e_row must be fp32 (B, W, dim) = {(B, W, dim)} with rows of dim contiguous floats")
+    for t, nm, dt, tail in tensors:
         if t is not None:
             _chk(t, nm, dt)
-            if tuple(t.shape) != shp:
-                raise _lib.NsgError(f"prior_walk: {nm} {tuple(t.shape)}, expected {shp}")
+            if tuple(t.shape) != (B, H, W) + tail:
+                raise _lib.NsgError(f"{fn}: {nm} {tuple(t.shape)}, expected {(B, H, W) + tail}")
     if not 0 <= row < H:
-        raise _lib.NsgError(f"prior_walk: row {row} outside 0 .. {H - 1}")
+        raise _lib.NsgError(f"{fn}: row {row} outside 0 .. {H - 1}")
+    return B, W, dim, L, K
+
+
+def prior_walk(w, emb, cond, vh, e_row, H, row, u=None, x_in=None, codes=None, logits=None):
+    """Walk row `row` of a (B, H, W) code grid (nsg_prior_walk).  w: packed blob; emb (K, dim); cond (L, B, 2 dim); vh
+    (L, B, 1, W, 2 dim); e_row (B, W, dim), any clip stride, receives the embedding of the row's codes; exactly one of u
+    (B, H, W) fp32 (sampling: codes (B, H, W) int64 is written) and x_in (B, H, W) int64 (teacher-forced); logits
+    (B, H, W, K) optional."""
+    if (u is None) == (x_in is None):
+        raise _lib.NsgError("prior_walk: exactly one of u (sampling) and x_in (teacher-forced)")
+    if u is not None and codes is None:
+        raise _lib.NsgError("prior_walk: sampling needs a codes output")
+    K = emb.shape[0]
+    B, W, dim, L, K = _prior_walk_extents("prior_walk", w, emb, cond, vh, e_row, H, row, (
+        (u, "u", torch.float32, ()), (x_in, "x_in", torch.int64, ()), (codes, "codes", torch.int64, ()), (logits, "logits", torch.float32, (K,))))
     _lib.call("nsg_prior_walk", _p(w), _p(emb), _p(cond), _p(vh), _p(u), _p(x_in), _p(codes), _p(e_row), c_int64(e_row.stride(0)),
               _p(logits), c_int32(B), c_int32(H), c_int32(W), c_int32(dim), c_int32(L), c_int32(K), c_int32(row), _stream())
+
+
+def prior_walk_ctl(w, emb, cond, vh, e_row, H, row, u, codes, x_in=None, keep=None, logits=None, temperature=1.0, top_k=0, top_p=1.0):
+    """prior_walk's sampling mode with a controlled pick (nsg_prior_walk_ctl; the rule is in include/nsg.h): temperature > 0,
+    top_k >= 0 (0 = off), 0 < top_p <= 1 (1 = off), and kept codes: where keep (B, H, W) bool or uint8 is non-zero the code
+    is x_in's (B, H, W) int64 and u is not consulted.  x_in and keep come together.  u (B, H, W) fp32 and codes (B, H, W)
+    int64 are required; logits (B, H, W, K) optional."""
+    if u is None or codes is None:
+        raise _lib.NsgError("prior_walk_ctl: u and codes are required")
+    if (x_in is None) != (keep is None):
+        raise _lib.NsgError("prior_walk_ctl: x_in and keep come together")
+    if keep is not None and keep.dtype not in (torch.bool, torch.uint8):
+        raise _lib.NsgError(f"prior_walk_ctl: keep must be bool or uint8, got {keep.dtype}")
+    temperature, top_p = float(temperature), float(top_p)
+    if not (math.isfinite(temperature) and temperature > 0 and 0 < top_p <= 1) or int(top_k) != top_k or top_k < 0:
+        raise _lib.NsgError(f"prior_walk_ctl: temperature {temperature} (finite, > 0), top_k {top_k} (integer >= 0) or top_p {top_p} "
+                            "(in (0, 1]) out of range")
+    K = emb.shape[0]
+    B, W, dim, L, K = _prior_walk_extents("prior_walk_ctl", w, emb, cond, vh, e_row, H, row, (
+        (u, "u", torch.float32, ()), (x_in, "x_in", torch.int64, ()), (keep, "keep", None, ()), (codes, "codes", torch.int64, ()),
+        (logits, "logits", torch.float32, (K,))))
+    _lib.call("nsg_prior_walk_ctl", _p(w), _p(emb), _p(cond), _p(vh), _p(u), _p(x_in), _p(keep), _p(codes), _p(e_row),
+              c_int64(e_row.stride(0)), _p(logits), c_int32(B), c_int32(H), c_int32(W), c_int32(dim), c_int32(L), c_int32(K), c_int32(row),
+              c_float(temperature), c_int32(min(int(top_k), 2 ** 31 - 1)), c_float(top_p), _stream())
 
 
 def prepared_conv_forward(d: ConvDesc, x, w_fwd, bias, y, flags=0):

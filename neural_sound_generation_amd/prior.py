@@ -23,6 +23,9 @@ torch.zeros, models.py:325-341).
 """
 from __future__ import annotations
 
+import math
+import numbers
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -200,22 +203,87 @@ class GatedPixelCNN(nn.Module):
     # incremental sampling: one row pass (conv kernels) and one column walk (nsg_prior_walk) per row
     # ------------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def sample(self, label, shape=(8, 8), batch_size=64, u=None, generator=None):
+    def sample(self, label, shape=(8, 8), batch_size=64, u=None, generator=None, *, temperature=1.0, top_k=0, top_p=1.0,
+               given=None, keep=None):
         """Ancestral sampling in raster order with nothing recomputed: int64 codes (batch_size, H, W).  Each code is the
         inverse CDF of its softmax against u[b, i, j] (include/nsg.h, nsg_prior_walk); u is drawn with torch.rand on the
-        model's device when not given.  The same distribution as `generate`, O(H W) work instead of O((H W)^2)."""
+        model's device when not given.  The same distribution as `generate`, O(H W) work instead of O((H W)^2).
+
+        Controls of the pick (include/nsg.h, nsg_prior_walk_ctl, states the exact rule): temperature > 0 divides the logits;
+        top_k >= 1 keeps the top_k largest logits (ties kept; 0 or >= input_dim: off); top_p < 1 keeps the smallest set of
+        most probable codes whose mass reaches top_p (ties kept; 1: off).  With all three off and nothing given this is the
+        plain walk, and its results do not move.
+
+        Priming: given int64 (B, H, W) and keep bool (B, H, W) come together; where keep is set the result holds given's code
+        and only the other positions are sampled.  This is not posterior inference: each sampled code is drawn from the
+        prior's conditional given everything BEFORE it in raster order, kept or sampled, and kept codes later in raster order
+        do not influence it.  Keeping whole leading rows is exact conditional sampling; keeping the first columns of every
+        row is the usual "hold the known, sample the rest"."""
         H, W = self._grid(shape)
         B = int(batch_size)
         label = self._labels(label, B)
         dev = label.device
+        ctl = self._controls(temperature, top_k, top_p)
+        if (given is None) != (keep is None):
+            raise ValueError("sample: given and keep come together")
+        if given is not None:
+            if not isinstance(given, torch.Tensor) or tuple(given.shape) != (B, H, W) or given.dtype != torch.int64:
+                raise ValueError(f"sample: given must be an int64 tensor of shape {(B, H, W)}")
+            if not isinstance(keep, torch.Tensor) or tuple(keep.shape) != (B, H, W) or keep.dtype != torch.bool:
+                raise ValueError(f"sample: keep must be a bool tensor of shape {(B, H, W)}")
+            given, keep = given.to(dev).contiguous(), keep.to(dev).contiguous()
+            kept = given[keep]
+            K = self.embedding.num_embeddings
+            if kept.numel() and (int(kept.min()) < 0 or int(kept.max()) >= K):
+                raise ValueError(f"sample: kept codes outside [0, {K})")
         if u is None:
             self._check_walk()
             u = torch.rand((B, H, W), generator=generator, device=dev)
         elif not isinstance(u, torch.Tensor) or tuple(u.shape) != (B, H, W) or u.dtype != torch.float32:
             raise ValueError(f"sample: u must be a float32 tensor of shape {(B, H, W)}")
         codes = torch.empty((B, H, W), dtype=torch.int64, device=dev)
-        self._walk_rows(label, B, H, W, u=u.to(dev).contiguous(), codes=codes)
+        if ctl is None and given is None:
+            self._walk_rows(label, B, H, W, u=u.to(dev).contiguous(), codes=codes)
+        else:
+            self._walk_rows(label, B, H, W, u=u.to(dev).contiguous(), codes=codes, x_in=given, keep=keep, ctl=ctl or (1.0, 0, 1.0))
         return codes
+
+    @torch.no_grad()
+    def continue_codes(self, prefix, label, width, **controls):
+        """Continue a grid of codes in time: prefix int64 (B, H, W0) with W0 <= width -> int64 (B, H, width) whose columns
+        < W0 are the prefix and whose other columns are sampled (`sample` with the first W0 columns of every row kept;
+        controls: sample's u, generator, temperature, top_k, top_p).  Not posterior inference: a sampled code is conditioned
+        on what precedes it in raster order -- the rows above, prefix and continuation, and its own row to its left -- and
+        not on the prefix columns of the rows below it."""
+        if not isinstance(prefix, torch.Tensor) or prefix.dim() != 3 or prefix.dtype != torch.int64:
+            raise ValueError("continue_codes: prefix must be an int64 tensor (B, H, W0)")
+        B, H, W0 = prefix.shape
+        width = int(width)
+        if W0 > width:
+            raise ValueError(f"continue_codes: the prefix has {W0} columns, more than width = {width}")
+        given = torch.zeros((B, H, width), dtype=torch.int64, device=prefix.device)
+        given[:, :, :W0] = prefix
+        keep = torch.zeros((B, H, width), dtype=torch.bool, device=prefix.device)
+        keep[:, :, :W0] = True
+        return self.sample(label, shape=(H, width), batch_size=B, given=given, keep=keep, **controls)
+
+    def _controls(self, temperature, top_k, top_p):
+        """Validates the pick's controls; None when all three are off (the plain walk), else (temperature, top_k, top_p)."""
+        K = self.embedding.num_embeddings
+        for v, nm in ((temperature, "temperature"), (top_p, "top_p")):
+            if isinstance(v, bool) or not isinstance(v, numbers.Real):
+                raise ValueError(f"sample: {nm} must be a number")
+        if isinstance(top_k, bool) or not isinstance(top_k, numbers.Integral) or top_k < 0:
+            raise ValueError("sample: top_k must be an integer >= 0 (0: off)")
+        inv_t = torch.tensor(1.0, dtype=torch.float32) / torch.tensor(float(temperature), dtype=torch.float32)
+        if not (math.isfinite(temperature) and temperature > 0 and bool(torch.isfinite(inv_t))):
+            raise ValueError("sample: temperature must be finite and > 0 (and so must its fp32 reciprocal)")
+        if not 0 < top_p <= 1:
+            raise ValueError("sample: top_p must be in (0, 1] (1: off)")
+        top_k = 0 if top_k >= K else int(top_k)
+        if float(temperature) == 1.0 and top_k == 0 and float(top_p) == 1.0:
+            return None
+        return float(temperature), top_k, float(top_p)
 
     @torch.no_grad()
     def incremental_logits(self, x, label):
@@ -279,11 +347,13 @@ class GatedPixelCNN(nn.Module):
         parts += [w0.weight.detach()[:, :, 0, 0].t().reshape(-1), w0.bias.detach(), w2t.reshape(-1), b2]
         return torch.cat([p.reshape(-1).float() for p in parts]).contiguous()
 
-    def _walk_rows(self, label, B, H, W, u=None, codes=None, x_in=None, logits=None, times=None):
+    def _walk_rows(self, label, B, H, W, u=None, codes=None, x_in=None, logits=None, times=None, ctl=None, keep=None):
         """Row i: the row pass (vertical stacks, their gates and the v2h 1x1s of every layer, all W columns, on the conv
         kernels), then the column walk.  Layer 0 reads rows i-3 .. i of e (row i is masked: zeros until the walk writes it),
         the others rows i-1, i of their vertical input; rows above the grid are zero, as the conv's padding is.
-        times: optional dict that collects the row passes' and walks' GPU milliseconds (scripts/prior_sample_timing.py)."""
+        times: optional dict that collects the row passes' and walks' GPU milliseconds (scripts/prior_sample_timing.py).
+        ctl: None for the plain walk (nsg_prior_walk), or (temperature, top_k, top_p) for the controlled one
+        (nsg_prior_walk_ctl), which also takes keep (B, H, W) with x_in as the kept codes."""
         self._check_walk()
         self.layers[0].make_causal()
         dim, L, K = self.dim, len(self.layers), self.embedding.num_embeddings
@@ -330,7 +400,11 @@ class GatedPixelCNN(nn.Module):
                 v2h[l]()
             if ev:
                 ev[1].record()
-            ops.prior_walk(blob, emb, cond, vh, e_grid[:, i + 3], H, i, u=u, x_in=x_in, codes=codes, logits=logits)
+            if ctl is None:
+                ops.prior_walk(blob, emb, cond, vh, e_grid[:, i + 3], H, i, u=u, x_in=x_in, codes=codes, logits=logits)
+            else:
+                ops.prior_walk_ctl(blob, emb, cond, vh, e_grid[:, i + 3], H, i, u, codes, x_in=x_in, keep=keep, logits=logits,
+                                   temperature=ctl[0], top_k=ctl[1], top_p=ctl[2])
             if ev:
                 ev[2].record()
                 ev[2].synchronize()

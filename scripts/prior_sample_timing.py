@@ -1,6 +1,7 @@
 """Timing of the latent prior's incremental sampler (GatedPixelCNN.sample) at production width, GatedPixelCNN(512, 64, 15):
-64 clips x 20 x 256 codes, with the row passes' and column walks' GPU time reported separately; and sample against the
-naive `generate` (a full forward per position) at 64 x 20 x 32.  Prints one JSON line per measurement."""
+64 clips x 20 x 256 codes, with the row passes' and column walks' GPU time reported separately; the same draw with the
+pick's controls on (temperature 0.8, top_k 64, top_p 0.95: nsg_prior_walk_ctl); and sample against the naive `generate` (a
+full forward per position) at 64 x 20 x 32.  Prints one JSON line per measurement."""
 import json
 import os
 import sys
@@ -27,16 +28,27 @@ def wall(fn, n):
     return (time.perf_counter() - t) / n
 
 
-for H, W in ((20, 256), (20, 32)):
-    u = torch.rand(B, H, W, device=dev)
-    dt = wall(lambda: m.sample(label, shape=(H, W), batch_size=B, u=u), 3)
+CONTROLS = dict(temperature=0.8, top_k=64, top_p=0.95)
+
+
+def measure(what, H, W, u, controls):
+    dt = wall(lambda: m.sample(label, shape=(H, W), batch_size=B, u=u, **controls), 3)
     times = {}
     with torch.no_grad():                       # the two phases, one synchronised row at a time
-        m._walk_rows(label, B, H, W, u=u, codes=torch.empty(B, H, W, dtype=torch.int64, device=dev), times=times)
-    rec = {"what": "sample", "B": B, "H": H, "W": W, "s": round(dt, 4),
+        m._walk_rows(label, B, H, W, u=u, codes=torch.empty(B, H, W, dtype=torch.int64, device=dev), times=times,
+                     ctl=tuple(controls.values()) if controls else None)
+    rec = {"what": what, "B": B, "H": H, "W": W, "s": round(dt, 4),
            "row_pass_ms_per_row": round(times["row_pass_ms"] / H, 3), "walk_ms_per_row": round(times["walk_ms"] / H, 3),
            "walk_us_per_position": round(times["walk_ms"] * 1e3 / (H * W), 2)}
-    print(json.dumps(rec), flush=True)
+    print(json.dumps(dict(rec, **controls)), flush=True)
+    return dt
+
+
+for H, W in ((20, 256), (20, 32)):
+    u = torch.rand(B, H, W, device=dev)
+    dt = measure("sample", H, W, u, {})
+    if W == 256:
+        measure("sample_controls", H, W, u, CONTROLS)
     if W == 32:
         torch.manual_seed(0)
         g = wall(lambda: m.generate(label, shape=(H, W), batch_size=B), 1)
