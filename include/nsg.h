@@ -587,6 +587,33 @@ NSG_API int nsg_audio_stft(const float *y, float *X, int32_t B, int32_t L, int32
  * |k| < 1.  Chunked with a discarded warm-up of ceil(log 1e-9 / log |k|) samples: chunks are independent to below fp32 rounding. */
 NSG_API int nsg_audio_inv_preemphasis(const float *x, float *y, int32_t B, int32_t L, float k, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Waveform -> mel (the front end)   src/audio_tacotron.py:23-26,70-78,154-158,196-200,221-234 with hparams_tacotron.py
+ * (use_lws=False, preemphasize, signal_normalization, allow_clipping_in_normalization, symmetric_mels=False).
+ * ------------------------------------------------------------------------------------------- */
+
+/* p[n] = x[n] - k * x[n-1], p[0] = x[0] per clip (scipy.signal.lfilter([1, -k], [1], x)); x, p [B][L], out of place. */
+NSG_API int nsg_audio_preemphasis(const float *x, float *y, int32_t B, int32_t L, float k, void *stream);
+
+/* One pass from samples to the normalised mel spectrogram, per clip b of len_b = lengths[b] samples (lengths NULL: all L):
+ *     p[n]   = x[n] - k x[n-1],  p[0] = x[0]
+ *     X[t]   = rfft(hann_periodic * reflect_pad(p[0:len_b], n_fft/2)[t hop : t hop + n_fft])          (librosa.stft)
+ *     m[j,t] = sum_f basis[j][f] |X[t][f]|                                  over f in [bands[j][0], bands[j][1]] only
+ *     S      = 20 log10(max(10^(min_level_db/20), m)) - ref_level_db
+ *     out    = clip(max_abs (S - min_level_db) / (-min_level_db), 0, max_abs)
+ * for t < T_b = 1 + len_b / hop; frames T_b <= t < T = 1 + L / hop are written as zeros.  A clip's result does not depend on
+ * B, L or its position in the batch (bit for bit).  The spectrum never leaves the workgroup: only n_mels floats per frame
+ * are stored.  wav [B][L] zero-padded; basis [n_mels][F] dense, F = n_fft/2 + 1, device; bands [n_mels][2] HOST memory: the
+ * first and last bin of each row's non-zero run (first > last: an empty row, which yields the floor), read and checked
+ * before the launch.  out [B][n_mels][T] (frame_major 0) or [B][T][n_mels] (frame_major 1).
+ * n_fft in {512, 1024, 2048}, hop > 0, n_mels <= 128, L > n_fft/2, B * T < 2^31.
+ * PRECONDITION the entry point cannot check (lengths is device memory): n_fft/2 < lengths[b] <= L for every b; the caller
+ * checks it on the host copy it built lengths from.  (The kernel clamps lengths[b] into [1, L], so no read leaves wav.) */
+NSG_API int nsg_audio_melspectrogram(const float *wav, const int32_t *lengths, const float *basis, const int32_t *bands,
+                                     float *out, int32_t B, int32_t L, int32_t n_fft, int32_t hop, int32_t n_mels,
+                                     float preemphasis, float min_level_db, float ref_level_db, float max_abs_value,
+                                     int32_t frame_major, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

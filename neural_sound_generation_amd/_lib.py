@@ -121,6 +121,9 @@ _SIGS = {
     "nsg_audio_griffin_lim": (None, [_P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, _P, c_size_t, _P]),
     "nsg_audio_stft": (None, [_P, _P, c_int32, c_int32, c_int32, c_int32, _P]),
     "nsg_audio_inv_preemphasis": (None, [_P, _P, c_int32, c_int32, c_float, _P]),
+    "nsg_audio_preemphasis": (None, [_P, _P, c_int32, c_int32, c_float, _P]),
+    "nsg_audio_melspectrogram": (None, [_P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_float, c_float,
+                                        c_int32, _P]),
     "nsg_debug_dot": (None, [_P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P]),
 }
 # entry points declared in include/nsg.h: exactly the product library's exports (tests/test_abi.py checks both directions)

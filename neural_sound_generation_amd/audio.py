@@ -9,6 +9,14 @@ filterbank and its pseudo-inverse are constants built once on the host with nump
 scale, area normalisation).  hparams are the reference's (src/hparams_tacotron.py:77-117: use_lws=False, power 1.5,
 60 iterations, pre-emphasis 0.97, min_level_db -100, ref_level_db 20, fmin 125, fmax 7600, clipped [0, 1] normalisation).
 
+The opposite direction, wav -> mel, is the reference's preprocessing (audio_tacotron.py:70-78 melspectrogram, :23-26 preemphasis):
+
+    melspectrogram(wav, sample_rate, fft_size, hop_size, n_mels) -> (n_mels, T) normalised to [0, 1]  (same signature)
+
+one kernel from samples to the normalised mel (pre-emphasis at the reflect-mapped index, Hann, FFT, |X| in LDS, the
+filterbank as a band matrix, dB, normalise, clip; ragged batches, two layouts).  load_wav reads PCM files with scipy; it
+does not resample (the reference does, through librosa).
+
 parity unpinned: librosa is absent (here, on the GPU box, and from the reference's own tree), and no file of the reference
 holds a waveform; tests compare with the numpy restatement in oracle/audio_oracle.py (same initial phases) and check the
 transform identities (istft(stft(y)) == y, the spectral error falls over the iterations).
@@ -16,7 +24,7 @@ transform identities (istft(stft(y)) == y, the spectral error falls over the ite
 from __future__ import annotations
 
 import functools
-from ctypes import c_float, c_int32, c_size_t
+from ctypes import c_float, c_int32, c_size_t, c_void_p
 
 import numpy as np
 import torch
@@ -100,6 +108,80 @@ def stft(y: torch.Tensor, fft_size=1024, hop_size=256) -> torch.Tensor:
     return torch.view_as_complex(X)
 
 
+@functools.lru_cache(maxsize=8)
+def _mel_bands(sample_rate, fft_size, n_mels):
+    """(n_mels, 2) int32: first and last non-zero bin of each filterbank row (first > last for an empty row).  Each Slaney
+    triangle is non-zero on one contiguous run of bins; anything else is refused, since the kernel sums the run only."""
+    basis = mel_basis(sample_rate, fft_size, n_mels)
+    bands = np.empty((n_mels, 2), dtype=np.int32)
+    for i in range(n_mels):
+        nz = np.flatnonzero(basis[i])
+        bands[i] = (nz[0], nz[-1]) if len(nz) else (1, 0)
+        if len(nz) and len(nz) != nz[-1] - nz[0] + 1:
+            raise ValueError(f"mel filter {i} of ({sample_rate}, {fft_size}, {n_mels}) is not one contiguous run of bins")
+    return bands
+
+
+@functools.lru_cache(maxsize=8)
+def _mel_basis_on(sample_rate, fft_size, n_mels, device):
+    return torch.from_numpy(mel_basis(sample_rate, fft_size, n_mels)).to(device)
+
+
+def preemphasis(y: torch.Tensor, k=PREEMPHASIS) -> torch.Tensor:
+    """audio_tacotron.py:23-26: p[n] = y[n] - k y[n-1], p[0] = y[0], per row of y (B, L)."""
+    _chk(y, "y")
+    B, L = y.shape
+    out = torch.empty_like(y)
+    _lib.call("nsg_audio_preemphasis", _p(y), _p(out), c_int32(B), c_int32(L), c_float(k), _stream())
+    return out
+
+
+LAYOUTS = {"mel_major": 0, "frame_major": 1}
+
+
+def melspectrogram(wav, sample_rate=22050, fft_size=1024, hop_size=256, n_mels=80, lengths=None, layout="mel_major", device="cuda:0"):
+    """audio_tacotron.py:70-78 with hparams_tacotron.py's settings.  wav: a 1-D numpy waveform as in the reference (returns a
+    float32 numpy (n_mels, T), T = 1 + len // hop_size), or a float32 GPU tensor (B, L) of zero-padded clips (returns a GPU
+    tensor).  lengths (B,) integers: clip b has lengths[b] samples, is reflect-padded at its own end, and its frames past
+    1 + lengths[b] // hop_size are zeros; a clip's mel is bit for bit what it is alone.  layout: "mel_major" (B, n_mels, T),
+    what VQVAE and mel_to_linear take, or "frame_major" (B, T, n_mels), the on-disk orientation.  Every argument is
+    checked before anything is launched."""
+    if layout not in LAYOUTS:
+        raise ValueError(f"melspectrogram: layout must be one of {sorted(LAYOUTS)}, got {layout!r}")
+    if fft_size not in (512, 1024, 2048) or hop_size <= 0 or n_mels <= 0:
+        raise ValueError(f"melspectrogram: fft_size must be 512, 1024 or 2048 and hop_size, n_mels positive (got {fft_size}, {hop_size}, {n_mels})")
+    as_numpy = isinstance(wav, np.ndarray)
+    if as_numpy:
+        if wav.ndim != 1 or not np.issubdtype(wav.dtype, np.floating):
+            raise TypeError(f"melspectrogram: a numpy waveform must be 1-D floating point, got {wav.dtype} {wav.shape}")
+        B, L = 1, len(wav)
+    else:
+        if not torch.is_tensor(wav) or wav.dim() != 2 or wav.dtype != torch.float32:
+            raise TypeError("melspectrogram: expected a 1-D numpy waveform or a float32 tensor (B, L)")
+        B, L = wav.shape
+    if L <= fft_size // 2:
+        raise ValueError(f"melspectrogram: {L} samples; reflect padding needs more than fft_size / 2 = {fft_size // 2}")
+    lens = None
+    if lengths is not None:
+        host = lengths.detach().cpu().numpy() if torch.is_tensor(lengths) else np.asarray(lengths)
+        if host.shape != (B,) or not np.issubdtype(host.dtype, np.integer):
+            raise ValueError(f"melspectrogram: lengths must be {B} integers, got {host.dtype} {host.shape}")
+        if host.max() > L or host.min() <= fft_size // 2:
+            raise ValueError(f"melspectrogram: every length must be in ({fft_size // 2}, {L}], got {int(host.min())} .. {int(host.max())}")
+        lens = np.ascontiguousarray(host, dtype=np.int32)
+    bands = _mel_bands(sample_rate, fft_size, n_mels)
+    y = torch.from_numpy(np.ascontiguousarray(wav, dtype=np.float32)[None]).to(device) if as_numpy else wav
+    _chk(y, "wav")
+    T = 1 + L // hop_size
+    basis = _mel_basis_on(sample_rate, fft_size, n_mels, y.device)
+    lens_d = torch.from_numpy(lens).to(y.device) if lens is not None else None
+    out = torch.empty((B, T, n_mels) if LAYOUTS[layout] else (B, n_mels, T), dtype=torch.float32, device=y.device)
+    _lib.call("nsg_audio_melspectrogram", _p(y), _p(lens_d), _p(basis), c_void_p(bands.ctypes.data), _p(out), c_int32(B), c_int32(L),
+              c_int32(fft_size), c_int32(hop_size), c_int32(n_mels), c_float(PREEMPHASIS), c_float(MIN_LEVEL_DB), c_float(REF_LEVEL_DB),
+              c_float(MAX_ABS_VALUE), c_int32(LAYOUTS[layout]), _stream())
+    return out[0].cpu().numpy() if as_numpy else out
+
+
 def inv_preemphasis(y: torch.Tensor, k=PREEMPHASIS) -> torch.Tensor:
     _chk(y, "y")
     B, L = y.shape
@@ -130,3 +212,24 @@ def save_wav(wav, path, sample_rate=22050):
     wav = np.asarray(wav, dtype=np.float32)
     wav = wav * (32767 / max(0.01, float(np.max(np.abs(wav)))))
     wavfile.write(path, sample_rate, wav.astype(np.int16))
+
+
+def load_wav(path, sample_rate=22050) -> np.ndarray:
+    """audio_tacotron.py:12-13 without the resampling: the samples of a PCM file as float32 in [-1, 1) (int16 / int32 / uint8
+    scaled by their range, float as stored), the first channel of a multi-channel file.  The reference resamples to
+    sample_rate through librosa; here a file at another rate is an error."""
+    from scipy.io import wavfile
+    sr, data = wavfile.read(path)
+    if sr != sample_rate:
+        raise ValueError(f"{path}: sample rate {sr}, expected {sample_rate} (resampling is not implemented: convert the file first)")
+    if data.ndim > 1:
+        data = data[:, 0]
+    if data.dtype == np.int16:
+        return data.astype(np.float32) / 32768.0
+    if data.dtype == np.int32:
+        return (data.astype(np.float64) / 2147483648.0).astype(np.float32)
+    if data.dtype == np.uint8:
+        return (data.astype(np.float32) - 128.0) / 128.0
+    if np.issubdtype(data.dtype, np.floating):
+        return np.ascontiguousarray(data, dtype=np.float32)
+    raise ValueError(f"{path}: unsupported sample format {data.dtype}")

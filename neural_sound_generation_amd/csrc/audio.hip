@@ -8,6 +8,8 @@
 //   * istft: Hermitian extension -> inverse FFT -> x window -> frame buffer; overlap-add as a gather (deterministic)
 //     divided by the window's sum of squares, centre-trimmed;
 //   * inverse pre-emphasis y[n] = x[n] + k y[n-1]: chunked, each chunk re-running a discarded warm-up (k^W < 1e-9).
+// The opposite direction (audio_tacotron.py:23-26,70-78), wav -> normalised mel, is one kernel on the same FFT: pre-emphasis at the
+// reflect-mapped index, Hann, two frames per complex FFT, |X| in LDS, the filterbank as a band matrix, dB, normalise, clip.
 // fp32 throughout (complex as float2).  These are LDS- / HBM-bound kernels; nothing here touches the matrix pipe.
 #include "nsg_common.h"
 #include <math.h>
@@ -183,6 +185,87 @@ __global__ void inv_preemphasis_kernel(const float *__restrict__ x, float *__res
     }
 }
 
+// Per-row non-zero run [first, last] of the mel filterbank (a band matrix: each Slaney triangle covers one contiguous run of
+// bins), passed by value: the launcher has checked the indices on the host, and no upload precedes the launch.
+constexpr int MEL_MAX_ROWS = 128;
+struct MelBands { int16_t first[MEL_MAX_ROWS], last[MEL_MAX_ROWS]; };
+static_assert(2 * MEL_MAX_ROWS == 256, "melspectrogram_kernel: one thread per (frame of the pair, mel row)");
+
+// wav -> normalised mel in one pass (audio_tacotron.py:70-78 with hparams_tacotron.py's settings): pre-emphasis evaluated at the
+// reflect-mapped index, x periodic Hann, FFT, |X| kept in LDS, band product, dB, normalise, clip.  Only n_mels floats per frame
+// reach HBM.  A workgroup owns frames 2q and 2q+1 of one clip and transforms them as the real and the imaginary part of ONE
+// complex FFT (z = x0 + i x1; X0[f] = (Z[f] + conj Z[N-f]) / 2, X1[f] = (Z[f] - conj Z[N-f]) / 2i): half the FFTs, twiddle tables and
+// barriers per frame.  Frame 2q+1 is zeros when the clip ends at 2q.  A frame's arithmetic depends on the clip's samples, its
+// length and t alone (the partner is the clip's own neighbour), never on B, L or b.
+template <int LOG2N>
+__global__ __launch_bounds__(256) void melspectrogram_kernel(const float *__restrict__ wav, const int32_t *__restrict__ lengths,
+                                                             const float *__restrict__ basis, const MelBands bands, float *__restrict__ out,
+                                                             int T, int pairs, int hop, int L, int n_mels, float k, float min_amp, float min_db,
+                                                             float ref_db, float max_abs, int frame_major)
+{
+    constexpr int N = 1 << LOG2N, F = N / 2 + 1;
+    __shared__ v2f b0[N], b1[N], tw[N / 2];
+    __shared__ float mag[2][F];
+    const int tid = threadIdx.x;
+    const int b = (int)(blockIdx.x / (unsigned)pairs), t0 = 2 * (int)(blockIdx.x - (unsigned)b * pairs);
+    int len = lengths ? lengths[b] : L;
+    len = len < 1 ? 1 : (len > L ? L : len);                  // (the caller checked N/2 < len <= L on its host copy)
+    const int Tb = 1 + len / hop;                             // the clip's own frame count
+    float *ob = out + (size_t)b * n_mels * T;
+    const size_t m_stride = frame_major ? 1 : (size_t)T, t_stride = frame_major ? (size_t)n_mels : 1;
+    const int j = tid >> 7, m = tid & (MEL_MAX_ROWS - 1);     // the output this thread owns: frame t0 + j, mel row m
+    const bool owns = m < n_mels && t0 + j < T;
+    if (t0 >= Tb) {                                           // past the clip's end: the collate's padding value
+        if (owns) ob[(t0 + j) * t_stride + m * m_stride] = 0.f;
+        return;
+    }
+    fill_twiddles<LOG2N>(tw, tid);
+    const float *x = wav + (size_t)b * L;
+    const bool two = t0 + 1 < Tb;
+    for (int n = tid; n < N; n += 256) {
+        const float w = 0.5f - 0.5f * cospif(2.0f * (float)n / (float)N);
+        float p[2] = {0.f, 0.f};
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            if (q == 1 && !two) break;
+            int idx = (t0 + q) * hop + n - N / 2;
+            if (idx < 0) idx = -idx;                          // np.pad(mode="reflect") of the pre-emphasised clip
+            if (idx >= len) idx = 2 * (len - 1) - idx;
+            idx = idx < 0 ? 0 : (idx >= len ? len - 1 : idx);
+            p[q] = idx > 0 ? x[idx] - k * x[idx - 1] : x[0];
+        }
+        b0[n] = v2f{p[0] * w, p[1] * w};
+    }
+    v2f *r = fft_lds<LOG2N>(b0, b1, tw, tid, false);
+    for (int f = tid; f < F; f += 256) {
+        const v2f Z = r[f], C = r[(N - f) & (N - 1)];
+        const float ar = Z.x + C.x, ai = Z.y - C.y;           // 2 X0[f]
+        const float br = Z.y + C.y, bi = Z.x - C.x;           // 2 i X1[f] up to sign: the same modulus
+        mag[0][f] = 0.5f * sqrtf(ar * ar + ai * ai);
+        mag[1][f] = 0.5f * sqrtf(br * br + bi * bi);
+    }
+    __syncthreads();
+    if (!owns) return;
+    float v = 0.f;
+    if (j == 0 || two) {
+        const float *row = basis + (size_t)m * F;
+        const float *mg = mag[j];
+        const int f1 = bands.last[m];
+        float acc = 0.f;
+        for (int f = bands.first[m]; f <= f1; ++f) acc = fmaf(row[f], mg[f], acc);
+        const float S = 20.f * log10f(fmaxf(min_amp, acc)) - ref_db;
+        v = fminf(fmaxf(max_abs * ((S - min_db) / (-min_db)), 0.f), max_abs);
+    }
+    ob[(t0 + j) * t_stride + m * m_stride] = v;
+}
+
+// p[n] = x[n] - k x[n-1], p[0] = x[0] per clip (scipy.signal.lfilter([1, -k], [1], x)); out of place.
+__global__ void preemphasis_kernel(const float *__restrict__ x, float *__restrict__ y, int64_t total, int L, float k)
+{
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x)
+        y[i] = i % L ? x[i] - k * x[i - 1] : x[i];
+}
+
 inline int ew_blocks(int64_t n) { const int64_t b = nsg_cdiv(n, 256); return (int)(b > 4096 ? 4096 : (b < 1 ? 1 : b)); }
 inline int log2_of(int n) { int l = 0; while ((1 << l) < n) ++l; return (1 << l) == n ? l : -1; }
 
@@ -270,6 +353,48 @@ int nsg_audio_inv_preemphasis(const float *x, float *y, int32_t B, int32_t L, fl
     const int64_t threads = (int64_t)B * nsg_cdiv(L, PRE_CHUNK);
     hipLaunchKernelGGL(inv_preemphasis_kernel, dim3((unsigned)nsg_cdiv(threads, 64)), dim3(64), 0, (hipStream_t)stream, x, y, B, L, k, warm);
     return nsg_check_launch("inv_preemphasis_kernel");
+}
+
+int nsg_audio_preemphasis(const float *x, float *y, int32_t B, int32_t L, float k, void *stream)
+{
+    NSG_REQUIRE(x && y && x != y && B > 0 && L > 0, NSG_E_INVALID, "nsg_audio_preemphasis: bad argument (out of place)");
+    const int64_t total = (int64_t)B * L;
+    hipLaunchKernelGGL(preemphasis_kernel, dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, x, y, total, L, k);
+    return nsg_check_launch("preemphasis_kernel");
+}
+
+int nsg_audio_melspectrogram(const float *wav, const int32_t *lengths, const float *basis, const int32_t *bands, float *out, int32_t B, int32_t L,
+                             int32_t n_fft, int32_t hop, int32_t n_mels, float preemphasis, float min_level_db, float ref_level_db,
+                             float max_abs_value, int32_t frame_major, void *stream)
+{
+    NSG_REQUIRE(wav && basis && bands && out && B > 0 && L > 0 && hop > 0 && n_mels > 0, NSG_E_INVALID, "nsg_audio_melspectrogram: bad argument");
+    NSG_REQUIRE(max_abs_value > 0.f && min_level_db < 0.f && (frame_major == 0 || frame_major == 1), NSG_E_INVALID,
+                "nsg_audio_melspectrogram: bad argument (max_abs_value > 0, min_level_db < 0, frame_major 0 or 1)");
+    const int lg = log2_of(n_fft);
+    NSG_REQUIRE(lg >= 9 && lg <= 11, NSG_E_UNSUPPORTED, "nsg_audio_melspectrogram: n_fft must be 512, 1024 or 2048");
+    NSG_REQUIRE(n_mels <= MEL_MAX_ROWS, NSG_E_UNSUPPORTED, "nsg_audio_melspectrogram: at most 128 mel bins");
+    NSG_REQUIRE(L > n_fft / 2, NSG_E_UNSUPPORTED, "nsg_audio_melspectrogram: reflect padding needs more than n_fft/2 samples");
+    const int T = 1 + L / hop, F = n_fft / 2 + 1;
+    NSG_REQUIRE((int64_t)B * T < 0x7fffffff, NSG_E_UNSUPPORTED, "nsg_audio_melspectrogram: too many frames (B * T >= 2^31)");
+    MelBands mb;
+    for (int m = 0; m < n_mels; ++m) {
+        const int32_t f0 = bands[2 * m], f1 = bands[2 * m + 1];
+        NSG_REQUIRE(f0 >= 0 && f0 < F && f1 >= 0 && f1 < F, NSG_E_INVALID, "nsg_audio_melspectrogram: band index outside [0, n_fft/2]");
+        mb.first[m] = (int16_t)f0;
+        mb.last[m] = (int16_t)f1;
+    }
+    for (int m = n_mels; m < MEL_MAX_ROWS; ++m) { mb.first[m] = 1; mb.last[m] = 0; }
+    const float min_amp = (float)pow(10.0, (double)min_level_db / 20.0);
+    hipStream_t s = (hipStream_t)stream;
+    const int pairs = (T + 1) / 2;                 // a workgroup owns two frames of a clip
+    const unsigned nwg = (unsigned)(B * pairs);
+#define NSG_MEL_LAUNCH(LG) hipLaunchKernelGGL((melspectrogram_kernel<LG>), dim3(nwg), dim3(256), 0, s, wav, lengths, basis, mb, out, T, pairs, hop, L, n_mels, \
+                                              preemphasis, min_amp, min_level_db, ref_level_db, max_abs_value, frame_major)
+    if (lg == 9)       NSG_MEL_LAUNCH(9);
+    else if (lg == 10) NSG_MEL_LAUNCH(10);
+    else               NSG_MEL_LAUNCH(11);
+#undef NSG_MEL_LAUNCH
+    return nsg_check_launch("melspectrogram_kernel");
 }
 
 }  // extern "C"

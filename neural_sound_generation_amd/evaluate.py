@@ -15,6 +15,8 @@ checkpoint layout, restated from the reference's src/test.py:73-106 and src/main
     (GatedPixelCNN.sample) on the VQ-VAE's (20, frames / 4) latent grid, decoded to mels (audio.py goes on to waveforms).
   * `continue_mels(vqvae, prior, mel, label, keep_frames, frames)` -- the same with the first keep_frames of a given mel held:
     encode, keep the leading latent columns, sample the rest (GatedPixelCNN.continue_codes), decode.
+  * `continue_audio(vqvae, prior, wav, label, keep_frames, frames)` -- wav in, wav out: audio.melspectrogram, continue_mels,
+    audio.inv_mel_spectrogram.
 """
 from __future__ import annotations
 
@@ -135,3 +137,17 @@ def continue_mels(vqvae, prior, mel: torch.Tensor, label: torch.Tensor, keep_fra
         raise ValueError(f"continue_mels: keep_frames = {keep_frames} must be within the mel's {4 * known.shape[-1]} frames and frames = {frames}")
     codes = prior.continue_codes(known[:, :, :w0].contiguous(), label, frames // 4, generator=generator, **controls)
     return codes, vqvae.decode(codes, g)
+
+
+@torch.no_grad()
+def continue_audio(vqvae, prior, wav: torch.Tensor, label: torch.Tensor, keep_frames: int, frames: int, g=None, generator=None,
+                   sample_rate=22050, fft_size=1024, hop_size=256, angles0=None, **controls):
+    """Continue recordings in time: wav (B, L) float32 on the GPU -> its mel (audio.melspectrogram, 1 + L // hop_size frames)
+    -> continue_mels (the first keep_frames held, the grid sampled out to frames) -> waveform (audio.inv_mel_spectrogram;
+    angles0 (B, frames, 1 + fft_size / 2) fixes Griffin-Lim's initial phases).  Returns codes (B, 20, frames // 4), mels
+    (B, 1, 80, frames) and waveforms (B, hop_size * (frames - 1))."""
+    from . import audio
+    mel = audio.melspectrogram(wav, sample_rate, fft_size, hop_size, 80)
+    codes, out = continue_mels(vqvae, prior, mel.unsqueeze(1), label, keep_frames, frames, g=g, generator=generator, **controls)
+    y = audio.inv_mel_spectrogram(out.squeeze(1), sample_rate, fft_size, hop_size, 80, angles0=angles0)
+    return codes, out, y
