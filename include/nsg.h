@@ -510,6 +510,49 @@ NSG_API size_t nsg_cross_entropy_workspace_bytes(int64_t M);
 NSG_API int nsg_cross_entropy(const float *logits, const int64_t *target, int64_t M, int32_t K, float grad_scale,
                               float *loss_out, float *dlogits, void *workspace, size_t workspace_bytes, void *stream);
 
+/* The training step's forms of the gate (prior_train.py).
+ *
+ * Gate of a sum: y = gate((a + b) + cond) for two summands a, b [M][2C], the fp32 additions in exactly that order, so that y
+ * equals nsg_add(a, b) followed by nsg_gated_activation_forward bit for bit while the [M][2C] sum is never stored.  The
+ * backward writes the one dx [M][2C] that both summands share (d/da = d/db = d/d(a + b)), equal bit for bit to
+ * nsg_gated_activation_backward on the materialised sum.
+ *
+ * Column sums: with dcond != NULL the backward also writes dcond [B][2C], B = M / rows_per_clip: dcond[b][c] = sum over the
+ * rows of clip b of dx[m][c], the gradient of cond (what nsg_clip_colsum(dx) returns, up to the rounding of another summation
+ * order), formed while dx is written.  Deterministic: every thread sums its rows in double in a fixed order, the threads of a
+ * block and then the blocks of a clip are added in a fixed order, no atomics.  M must be a whole number of clips, C <= 1024;
+ * the workspace (nsg_gated_colsum_workspace_bytes, 16-byte aligned) is needed only with dcond.  cond may be NULL with dcond set
+ * (rows_per_clip still says where the clips end).  nsg_gated_activation_backward_colsum is the plain gate's backward with the
+ * column sums (dcond required); nsg_gated_activation_backward stays as it is.
+ * All pointers 16-byte aligned, C % 4 == 0. */
+NSG_API int nsg_gated_activation_sum_forward(const float *a, const float *b, const float *cond, float *y, int64_t M,
+                                             int32_t C, int64_t rows_per_clip, void *stream);
+NSG_API size_t nsg_gated_colsum_workspace_bytes(int64_t M, int32_t C, int64_t rows_per_clip);
+NSG_API int nsg_gated_activation_sum_backward(const float *a, const float *b, const float *cond, const float *dy, float *dx,
+                                              float *dcond, int64_t M, int32_t C, int64_t rows_per_clip, void *workspace,
+                                              size_t workspace_bytes, void *stream);
+NSG_API int nsg_gated_activation_backward_colsum(const float *x, const float *cond, const float *dy, float *dx, float *dcond,
+                                                 int64_t M, int32_t C, int64_t rows_per_clip, void *workspace,
+                                                 size_t workspace_bytes, void *stream);
+
+/* nsg_cross_entropy over the valid rows only, with per-clip sums: rows [M][K], M = B * rows_per_clip, row m belongs to clip
+ * m / rows_per_clip.  A row whose target is NEGATIVE is ignored (the padded positions of a zero-padded batch).  A target >= K
+ * violates the precondition; such a row is treated as ignored too, never read out of range.  With row_loss[m] the loss of a
+ * valid row (the formula of nsg_cross_entropy) and n_valid the number of valid rows, counted on the device:
+ *   loss_out[0]   = (sum of row_loss over the valid rows) / n_valid;
+ *   dlogits       = (softmax - onehot) * grad_scale / n_valid on valid rows, exact zeros on ignored rows   (or NULL);
+ *   clip_nll[b]   = sum of row_loss over the valid rows of clip b, fp32                                    (or NULL);
+ *   clip_count[b] = number of valid rows of clip b, int64                                                  (or NULL).
+ * n_valid == 0 gives loss 0 and an all-zero gradient.  (F.cross_entropy with ignore_index returns NaN there; a training loop
+ * has to survive a batch whose clips are all too short, so this does not.)  Nothing synchronises with the host.
+ * Deterministic, fixed-order reductions; clip_nll[b] is formed from clip b's own rows only, so it does not depend on the other
+ * clips of the batch.  With nothing ignored, loss_out and dlogits equal nsg_cross_entropy's bit for bit (the same row kernel,
+ * the same summation order, the same 1 / M).  The workspace must be 16-byte aligned. */
+NSG_API size_t nsg_cross_entropy_masked_workspace_bytes(int64_t M, int64_t rows_per_clip);
+NSG_API int nsg_cross_entropy_masked(const float *logits, const int64_t *target, int64_t M, int32_t K, int64_t rows_per_clip,
+                                     float grad_scale, float *loss_out, float *dlogits, float *clip_nll, int64_t *clip_count,
+                                     void *workspace, size_t workspace_bytes, void *stream);
+
 /* Incremental sampling (GatedPixelCNN.sample in prior.py): the per-row column walk.  For row `row` and each clip b it walks
  * j = 0 .. W-1 and, per layer l, forms
  *     out = gate((vh[l][b][j] + horiz_l(columns j-3 .. j-1 of e for l = 0, columns j-1 and j of h_l otherwise)) + cond[l][b]),

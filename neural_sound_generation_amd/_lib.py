@@ -112,6 +112,12 @@ _SIGS = {
     "nsg_gated_activation_backward": (None, [_P, _P, _P, _P, c_int64, c_int32, c_int64, _P]),
     "nsg_cross_entropy_workspace_bytes": (c_size_t, [c_int64]),
     "nsg_cross_entropy": (None, [_P, _P, c_int64, c_int32, c_float, _P, _P, _P, c_size_t, _P]),
+    "nsg_gated_activation_sum_forward": (None, [_P, _P, _P, _P, c_int64, c_int32, c_int64, _P]),
+    "nsg_gated_colsum_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int64]),
+    "nsg_gated_activation_sum_backward": (None, [_P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int64, _P, c_size_t, _P]),
+    "nsg_gated_activation_backward_colsum": (None, [_P, _P, _P, _P, _P, c_int64, c_int32, c_int64, _P, c_size_t, _P]),
+    "nsg_cross_entropy_masked_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "nsg_cross_entropy_masked": (None, [_P, _P, c_int64, c_int32, c_int64, c_float, _P, _P, _P, _P, _P, c_size_t, _P]),
     "nsg_prior_walk_weight_floats": (c_size_t, [c_int32, c_int32, c_int32]),
     "nsg_prior_walk": (None, [_P, _P, _P, _P, _P, _P, _P, _P, c_int64, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P]),
     "nsg_prior_walk_ctl": (None, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,

@@ -12,7 +12,8 @@ import numpy as np
 import torch
 
 from . import audio as nsg_audio
-from .evaluate import checkpoint_state, save_checkpoint, test_vqvae
+from .evaluate import checkpoint_state, sample_mels, save_checkpoint, test_prior, test_vqvae
+from .prior_train import PriorTrainStep, train_prior
 from .train import train_vqvae
 
 SAMPLING_RATE, FFT_SIZE, HOP_SIZE, N_MELS = 22050, 1024, 256, 80      # src/main.py:167-170
@@ -45,4 +46,34 @@ def run_epoch(args, model, optimizer, train_loader, test_loader, device, epoch, 
             out["wav"] = os.path.join(sample_dir, 'audio_recon' + stem + '_fftsize_' + str(FFT_SIZE) + '_hopsize_' + str(HOP_SIZE) + '.wav')
             nsg_audio.save_wav(signal, out["wav"], SAMPLING_RATE)
     out["checkpoint"] = save_checkpoint(args, checkpoint_state(epoch, args.model, model, optimizer), filename=checkpoint_path)
+    return out
+
+
+def run_prior_epoch(args, vqvae, prior, step_or_optimizer, train_loader, test_loader, device, epoch, checkpoint_path=None,
+                    sample_label=None, sample_frames=64, generator=None):
+    """Stage two's epoch: train_prior -> test_prior -> checkpoint ({'epoch', 'arch': 'pixelcnn', 'state_dict', 'optimizer'}, the
+    layout of run_epoch's; evaluate.load_checkpoint into the prior and the step's optimiser resumes bit-identically) -> with
+    sample_label (B,) int64: evaluate.sample_mels of those classes, sample_frames frames each, saved as a .npy of mels
+    (B, 80, sample_frames).  step_or_optimizer: a PriorTrainStep or a torch optimiser (train_prior).  The VQ-VAE is only read.
+    Returns a dict with the numbers and the files written."""
+    train_loss = train_prior(args, vqvae, prior, step_or_optimizer, train_loader, device, epoch)
+    nats = test_prior(args, vqvae, prior, test_loader, device, epoch)
+    out = {"train_loss": train_loss, "test_nats_per_code": nats, "test_bits_per_code": nats / float(np.log(2.0))}
+    optimizer = step_or_optimizer.opt if isinstance(step_or_optimizer, PriorTrainStep) else step_or_optimizer
+    if checkpoint_path is None:
+        checkpoint_path = './models/pixelcnn/checkpoint_{}_{}_{}.pth.tar'.format(args.dataset, args.dim, args.z_dim)
+    out["checkpoint"] = save_checkpoint(args, checkpoint_state(epoch, 'pixelcnn', prior, optimizer), filename=checkpoint_path)
+    if sample_label is not None:
+        sample_dir = os.path.join(args.sampledir, format(args.dataset))
+        os.makedirs(sample_dir, exist_ok=True)
+        stem = '_pixelcnn_data_' + str(args.dataset) + '_dim_' + str(args.dim) + '_z_dim_' + str(args.z_dim) + '_epoch_' + str(epoch)
+        was_training = vqvae.training
+        vqvae.eval()
+        try:
+            codes, mels = sample_mels(vqvae, prior, sample_label.to(device), sample_frames, generator=generator)
+        finally:
+            vqvae.train(was_training)
+        out["sample_codes"] = codes
+        out["samples"] = os.path.join(sample_dir, 'prior_samples' + stem + '.npy')
+        np.save(out["samples"], mels.squeeze(1).float().cpu().numpy(), allow_pickle=False)
     return out

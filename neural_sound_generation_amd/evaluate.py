@@ -13,6 +13,9 @@ checkpoint layout, restated from the reference's src/test.py:73-106 and src/main
     layout (FlatAdam.state_dict), so checkpoints move both ways between the reference and this package.
   * `sample_mels(vqvae, prior, label, frames)` -- generation's code -> mel half: codes drawn from the latent prior
     (GatedPixelCNN.sample) on the VQ-VAE's (20, frames / 4) latent grid, decoded to mels (audio.py goes on to waveforms).
+  * `codes_from_mels(vqvae, c, input_lengths)` -- stage two's input: a padded mel batch -> its codes and the number of valid
+    latent columns of each clip; `test_prior(args, vqvae, prior, test_loader, device, epoch)` -- the prior's test figure, nats
+    per code over the whole loader, weighted by codes (prior_train.py has the training side).
   * `continue_mels(vqvae, prior, mel, label, keep_frames, frames)` -- the same with the first keep_frames of a given mel held:
     encode, keep the leading latent columns, sample the rest (GatedPixelCNN.continue_codes), decode.
   * `continue_audio(vqvae, prior, wav, label, keep_frames, frames)` -- wav in, wav out: audio.melspectrogram, continue_mels,
@@ -121,6 +124,62 @@ def sample_mels(vqvae, prior, label: torch.Tensor, frames: int, g=None, generato
         raise ValueError("sample_mels: frames must be at least 4 (one latent column)")
     codes = prior.sample(label, shape=(LATENT_ROWS, frames // 4), batch_size=label.shape[0], generator=generator, **controls)
     return codes, vqvae.decode(codes, g)
+
+
+@torch.no_grad()
+def codes_from_mels(vqvae, c: torch.Tensor, input_lengths: torch.Tensor, hop_size: int = 256):
+    """c (B, 1, 80, T) (or (B, 80, T)) mels on the GPU, zero-padded to the batch's longest clip, T a multiple of 4;
+    input_lengths (B,) int64 audio samples per clip (what the loaders yield) -> (codes (B, 20, T // 4) int64 on c's device,
+    lengths (B,) int64 on input_lengths' device): lengths = (input_lengths // hop_size) // 4, clipped to the grid's width, is the
+    number of latent columns that come from the clip itself.  The VQ-VAE runs in eval mode (its mode is restored) and is not
+    changed.  The codes under the padding are whatever the VQ-VAE makes of zero mel; they are left out of the prior's loss
+    (GatedPixelCNN.loss(..., lengths)) but still lie in the causal context of valid positions of later rows -- the vertical
+    stacks reach +-3 columns in layer 0 and +-1 per later layer -- so a clip's likelihood depends slightly on how far its
+    batch was padded.  That is the loader's padding showing through; nothing here hides it."""
+    if c.dim() == 3:
+        c = c.unsqueeze(1)
+    if c.dim() != 4 or c.shape[1] != 1:
+        raise ValueError("codes_from_mels: c must be (B, 1, 80, T) or (B, 80, T)")
+    B = c.shape[0]
+    if not isinstance(input_lengths, torch.Tensor) or tuple(input_lengths.shape) != (B,) or input_lengths.dtype != torch.int64:
+        raise ValueError(f"codes_from_mels: input_lengths must be an int64 tensor of shape ({B},)")
+    was_training = vqvae.training
+    vqvae.eval()
+    try:
+        codes = vqvae.encode(c).contiguous()
+    finally:
+        vqvae.train(was_training)
+    return codes, latent_lengths(input_lengths, codes.shape[-1], hop_size)
+
+
+def latent_lengths(input_lengths: torch.Tensor, width: int, hop_size: int = 256) -> torch.Tensor:
+    """(input_lengths // hop_size) // 4 clipped to [0, width]: frames per clip -> valid latent columns (two stride-2 convs)."""
+    if int(hop_size) < 1:
+        raise ValueError("hop_size must be positive")
+    return ((input_lengths // int(hop_size)) // 4).clamp(0, int(width))
+
+
+def test_prior(args, vqvae, prior, test_loader, device, epoch):
+    """The prior's test figure: nats per code = sum of the clips' negative log-likelihoods / number of valid codes, over the
+    whole loader (weighted by codes, not a mean of batch means); printed also as bits per code."""
+    from .prior_train import prior_labels
+    nll = torch.zeros((), dtype=torch.float64, device=device)
+    count = torch.zeros((), dtype=torch.int64, device=device)
+    n = 0
+    for x, y, c, g, input_lengths in test_loader:
+        c = c.to(device).unsqueeze(1)
+        codes, lengths = codes_from_mels(vqvae, c, input_lengths)
+        clip_nll, clip_count = prior.nll(codes, prior_labels(prior, g, len(c)), lengths)
+        nll += clip_nll.double().sum()
+        count += clip_count.sum()
+        n += 1
+    if n == 0:
+        raise ValueError("test_prior: empty loader")
+    if int(count) == 0:
+        raise ValueError("test_prior: no clip of the loader is long enough for one latent column")
+    nats = float(nll / count)
+    print('====> Prior test set: {:.4f} nats per code ({:.4f} bits)'.format(nats, nats / float(np.log(2.0))))
+    return nats
 
 
 @torch.no_grad()

@@ -258,11 +258,14 @@ def increment_counters(counters):
     _lib.call("nsg_increment_counters", ctypes.cast(arr, c_void_p), c_int32(n), _stream())
 
 
-def gather_rows(codebook, idx):
+def gather_rows(codebook, idx, out=None):
     """codebook (K,D), idx (...) int64 -> (..., D)"""
     _chk(codebook, "codebook"); _chk(idx, "idx", torch.int64)
     K, D = codebook.shape
-    out = torch.empty(*idx.shape, D, dtype=torch.float32, device=codebook.device)
+    if out is None:
+        out = torch.empty(*idx.shape, D, dtype=torch.float32, device=codebook.device)
+    elif _chk(out, "out").numel() != idx.numel() * D:
+        raise _lib.NsgError(f"gather_rows: out {tuple(out.shape)} does not hold {idx.numel()} rows of {D}")
     _lib.call("nsg_gather_rows", _p(codebook), _p(idx), c_int64(idx.numel()), c_int32(D), c_int32(K), _p(out), _stream())
     return out
 
@@ -884,12 +887,12 @@ def adam_step(p, g, m, v, step, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, grad_
 # ------------------------------------------------------------------------------------------------
 # latent prior (GatedPixelCNN): element-wise pieces
 # ------------------------------------------------------------------------------------------------
-def gated_activation(x, cond=None):
+def gated_activation(x, cond=None, out=None):
     """x (..., 2C) NHWC rows, cond (B, 2C) or None -> tanh(a) * sigmoid(b) of the channel halves, (..., C)."""
     _chk(x, "x")
     C2 = x.shape[-1]
     M = x.numel() // C2
-    y = torch.empty(*x.shape[:-1], C2 // 2, dtype=torch.float32, device=x.device)
+    y = _gate_out(out, x.shape[:-1] + (C2 // 2,), x.device, "gated_activation: out")
     rpc = 1
     if cond is not None:
         _chk(cond, "cond")
@@ -910,6 +913,75 @@ def gated_activation_backward(x, cond, dy):
     return dx
 
 
+def _gate_out(out, shape, device, name):
+    if out is None:
+        return torch.empty(tuple(shape), dtype=torch.float32, device=device)
+    if tuple(_chk(out, name).shape) != tuple(shape):
+        raise _lib.NsgError(f"{name} has shape {tuple(out.shape)}, expected {tuple(shape)}")
+    return out
+
+
+def _gate_extents(fn, x, cond, dy=None, x2=None, n_clips=None):
+    """Checks shared by the gate wrappers -> (M, C, rows_per_clip, B); B from cond, else n_clips, else None."""
+    _chk(x, "x")
+    C2 = x.shape[-1]
+    M = x.numel() // C2
+    if x2 is not None and _chk(x2, "b").shape != x.shape:
+        raise _lib.NsgError(f"{fn}: the summands {tuple(x.shape)} and {tuple(x2.shape)} differ in shape")
+    if dy is not None and (_chk(dy, "dy").numel() != M * (C2 // 2) or dy.shape[-1] != C2 // 2):
+        raise _lib.NsgError(f"{fn}: dy {tuple(dy.shape)} does not match x {tuple(x.shape)}")
+    B = None
+    if cond is not None:
+        _chk(cond, "cond")
+        if cond.dim() != 2 or cond.shape[-1] != C2 or M % cond.shape[0] != 0:
+            raise _lib.NsgError(f"{fn}: cond {tuple(cond.shape)} does not match x {tuple(x.shape)}")
+        B = cond.shape[0]
+    if n_clips is not None:
+        if (B is not None and B != n_clips) or n_clips < 1 or M % n_clips != 0:
+            raise _lib.NsgError(f"{fn}: {n_clips} clips do not match x {tuple(x.shape)} / cond")
+        B = n_clips
+    return M, C2 // 2, (M // B if B else 1), B
+
+
+def gated_activation_sum(a, b, cond=None, out=None):
+    """gate((a + b) + cond) of two summands (..., 2C): what gated_activation(add(a, b), cond) returns, bit for bit, without the
+    sum in memory (nsg_gated_activation_sum_forward)."""
+    M, C, rpc, _ = _gate_extents("gated_activation_sum", a, cond, x2=b)
+    y = _gate_out(out, a.shape[:-1] + (C,), a.device, "gated_activation_sum: out")
+    _lib.tag("gated_activation_sum", 0, 4.0 * M * C * 5)
+    _lib.call("nsg_gated_activation_sum_forward", _p(a), _p(b), _p(cond), _p(y), c_int64(M), c_int32(C), c_int64(rpc), _stream())
+    return y
+
+
+def _gate_backward(fn, entry, x, x2, cond, dy, out, dcond, want_dcond, n_clips):
+    M, C, rpc, B = _gate_extents(fn, x, cond, dy=dy, x2=x2, n_clips=n_clips)
+    dx = _gate_out(out, x.shape, x.device, fn + ": out")
+    ws, nb = None, 0
+    if want_dcond or dcond is not None:
+        if B is None:
+            raise _lib.NsgError(f"{fn}: the column sums need cond or n_clips")
+        dcond = _gate_out(dcond, (B, 2 * C), x.device, fn + ": dcond")
+        nb = _lib.query("nsg_gated_colsum_workspace_bytes", c_int64(M), c_int32(C), c_int64(rpc))
+        if nb == 0:
+            raise _lib.NsgError(f"{fn}: the column sums take C % 4 == 0, C <= 1024 (C = {C})")
+        ws = WS.get(nb, x.device)
+    _lib.tag(fn, 0, 4.0 * M * C * (5 + (2 if x2 is not None else 0)))
+    head = (_p(x), _p(x2)) if x2 is not None else (_p(x),)
+    _lib.call(entry, *head, _p(cond), _p(dy), _p(dx), _p(dcond), c_int64(M), c_int32(C), c_int64(rpc), _p(ws), c_size_t(nb), _stream())
+    return dx, dcond
+
+
+def gated_activation_sum_backward(a, b, cond, dy, out=None, dcond=None, want_dcond=False, n_clips=None):
+    """Backward of gated_activation_sum -> (dx, dcond): dx (..., 2C) is the gradient of both summands; dcond (B, 2C), the
+    per-clip column sums of dx, when want_dcond or a dcond buffer is given (else None).  n_clips: B when there is no cond."""
+    return _gate_backward("gated_activation_sum_backward", "nsg_gated_activation_sum_backward", a, b, cond, dy, out, dcond, want_dcond, n_clips)
+
+
+def gated_activation_backward_colsum(x, cond, dy, out=None, dcond=None, n_clips=None):
+    """gated_activation_backward with the per-clip column sums of dx formed in the same pass -> (dx, dcond (B, 2C))."""
+    return _gate_backward("gated_activation_backward_colsum", "nsg_gated_activation_backward_colsum", x, None, cond, dy, out, dcond, True, n_clips)
+
+
 def cross_entropy(logits2d, target, want_grad=True, grad_scale=1.0):
     """mean cross-entropy of rows (M, K) against int64 targets (M,) -> (loss[1], dlogits or None)."""
     _chk(logits2d, "logits"); _chk(target, "target", torch.int64)
@@ -921,6 +993,29 @@ def cross_entropy(logits2d, target, want_grad=True, grad_scale=1.0):
     _lib.call("nsg_cross_entropy", _p(logits2d), _p(target), c_int64(M), c_int32(K), c_float(grad_scale), _p(loss), _p(dl), _p(ws),
               c_size_t(nb), _stream())
     return loss, dl
+
+
+def cross_entropy_masked(logits2d, target, rows_per_clip, want_grad=True, grad_scale=1.0, want_clip=False, out=None):
+    """Mean cross-entropy over the rows whose target is >= 0 (nsg_cross_entropy_masked): rows (M, K), int64 targets (M,),
+    M = B * rows_per_clip -> (loss[1], dlogits or None, clip_nll (B,) fp32 or None, clip_count (B,) int64 or None).  Nothing
+    valid: loss 0, zero gradient.  out: optional (M, K) destination of the gradient."""
+    _chk(logits2d, "logits"); _chk(target, "target", torch.int64)
+    M, K = logits2d.shape
+    rows_per_clip = int(rows_per_clip)
+    if target.numel() != M or rows_per_clip < 1 or M % rows_per_clip != 0:
+        raise _lib.NsgError(f"cross_entropy_masked: {M} rows, {target.numel()} targets, clips of {rows_per_clip} rows")
+    B = M // rows_per_clip
+    dev = logits2d.device
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    dl = _gate_out(out, (M, K), dev, "cross_entropy_masked: out") if (want_grad or out is not None) else None
+    nll = torch.empty(B, dtype=torch.float32, device=dev) if want_clip else None
+    cnt = torch.empty(B, dtype=torch.int64, device=dev) if want_clip else None
+    nb = _lib.query("nsg_cross_entropy_masked_workspace_bytes", c_int64(M), c_int64(rows_per_clip))
+    ws = WS.get(nb, dev)
+    _lib.tag("cross_entropy_masked", 0, 4.0 * M * K * (2 if dl is not None else 1))
+    _lib.call("nsg_cross_entropy_masked", _p(logits2d), _p(target), c_int64(M), c_int32(K), c_int64(rows_per_clip), c_float(grad_scale),
+              _p(loss), _p(dl), _p(nll), _p(cnt), _p(ws), c_size_t(nb), _stream())
+    return loss, dl, nll, cnt
 
 
 # ------------------------------------------------------------------------------------------------

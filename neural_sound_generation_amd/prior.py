@@ -105,6 +105,29 @@ class _CrossEntropy(Function):
         return dl * g, None
 
 
+class _CrossEntropyMasked(Function):
+    """Mean cross-entropy over the rows whose target is >= 0 (nsg_cross_entropy_masked); clips of rows_per_clip rows."""
+
+    @staticmethod
+    def forward(ctx, logits2d, target, rows_per_clip):
+        loss, dl, _, _ = ops.cross_entropy_masked(logits2d.contiguous(), target.contiguous(), rows_per_clip, want_grad=True)
+        ctx.save_for_backward(dl)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        (dl,) = ctx.saved_tensors
+        return dl * g, None, None
+
+
+def masked_targets(x, lengths):
+    """x int64 (B, H, W), lengths int64 (B,) = valid columns per clip -> the loss targets (B, H, W): x where the column is
+    < lengths[b], -1 (ignored) elsewhere.  Built on x's device, no host synchronisation."""
+    W = x.shape[-1]
+    valid = torch.arange(W, device=x.device)[None, None, :] < lengths.to(x.device)[:, None, None]
+    return torch.where(valid, x, torch.full_like(x, -1))
+
+
 def _conv(x_nhwc, conv: nn.Conv2d, relu_out: bool = False):
     """The module's own (possibly rectangular) kernel and padding, output cropped to the input extent."""
     return _Conv.apply(x_nhwc, conv.weight, conv.bias, tuple(conv.padding), relu_out)
@@ -182,10 +205,45 @@ class GatedPixelCNN(nn.Module):
     def forward(self, x, label):
         return Fn.to_nchw_view(self.forward_nhwc(x, label))
 
-    def loss(self, x, label):
-        """Mean cross-entropy of the prior's logits against the codes themselves (each code from its causal context)."""
+    def loss(self, x, label, lengths=None):
+        """Mean cross-entropy of the prior's logits against the codes themselves (each code from its causal context).
+        lengths int64 (B,): valid latent columns per clip, 0 <= lengths[b] <= W; the positions [b, :, lengths[b]:] (the padding
+        of a zero-padded batch) are left out of the mean.  No valid position at all gives 0 (not NaN).  The codes under the
+        padding still lie in the causal context of valid positions of later rows: nothing is masked on the input side."""
+        if lengths is None:
+            logits = self.forward_nhwc(x, label)
+            return _CrossEntropy.apply(logits.view(-1, logits.shape[-1]), x.reshape(-1))
+        x, label, lengths = self.check_batch(x, label, lengths)
         logits = self.forward_nhwc(x, label)
-        return _CrossEntropy.apply(logits.view(-1, logits.shape[-1]), x.reshape(-1))
+        return _CrossEntropyMasked.apply(logits.view(-1, logits.shape[-1]), masked_targets(x, lengths).reshape(-1), x.shape[1] * x.shape[2])
+
+    @torch.no_grad()
+    def nll(self, x, label, lengths=None):
+        """Each clip's summed negative log-likelihood in nats over its valid positions, and their number:
+        (nll (B,) fp32, count (B,) int64).  lengths as in `loss` (None: every position is valid)."""
+        x, label, lengths = self.check_batch(x, label, lengths)
+        logits = self.forward_nhwc(x, label)
+        target = x if lengths is None else masked_targets(x, lengths)
+        _, _, nll, count = ops.cross_entropy_masked(logits.view(-1, logits.shape[-1]), target.reshape(-1).contiguous(), x.shape[1] * x.shape[2],
+                                                    want_grad=False, want_clip=True)
+        return nll, count
+
+    def check_batch(self, x, label, lengths=None):
+        """Validates a training batch (ValueError) and returns it on the model's device: codes int64 (B, H, W), label int64 (B,)
+        in [0, n_classes), lengths None or int64 (B,) in [0, W].  The value checks read the tensors where they are: free for
+        host tensors (what a loader yields), one synchronisation for device tensors."""
+        if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.dtype != torch.int64:
+            raise ValueError("codes must be an int64 tensor (B, H, W)")
+        B, H, W = x.shape
+        self._grid((H, W))
+        label = self._labels(label, B)
+        if lengths is not None:
+            if not isinstance(lengths, torch.Tensor) or tuple(lengths.shape) != (B,) or lengths.dtype != torch.int64:
+                raise ValueError(f"lengths must be an int64 tensor of shape ({B},)")
+            if int(lengths.min()) < 0 or int(lengths.max()) > W:
+                raise ValueError(f"lengths outside [0, {W}]")
+            lengths = lengths.to(label.device).contiguous()
+        return x.to(label.device).contiguous(), label, lengths
 
     @torch.no_grad()
     def generate(self, label, shape=(8, 8), batch_size=64):
