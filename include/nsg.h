@@ -123,6 +123,21 @@ NSG_API int nsg_vq_forward_bf16x3_cond(const float *x, const float *e, int64_t N
                                        const float *clip_rows, int64_t rows_per_clip, void *workspace, size_t workspace_bytes,
                                        void *stream);
 
+/* Rows given as their SOURCES instead of as fp32 values (the *_bnres entry points below): the encoder's last ResBlock ends in
+ * BatchNorm + skip connection (src/models.py:154-158), so every element of its output z_e is
+ *     z[n][c] = ((h[n][c] - mean[c]) * (invstd[c] * gamma[c]) + beta[c]) + r[n][c]
+ * with h (the BatchNorm's input) and r (the block's ReLU'd input) bf16 [N][D] and the four vectors fp32 [D].  The three
+ * consumers of z_e in the bf16 training step -- the search, the loss / encoder gradient and the per-code sums -- form this
+ * expression while they load their rows, exactly as nsg_bn_apply(h, ..., residual = r) spells it for an fp32 output (same order
+ * of operations, no contraction), so each returns bit for bit what its fp32-row form returns on nsg_bn_apply's result: the
+ * fp32 copy of z_e (a pass that reads 2 x N*D*2 bytes and writes N*D*4, then read three times) is never made. */
+
+/* nsg_vq_forward_bf16x3_cond on such rows (no dmin_out: the distances' |x|^2 pass would need the rows).  h, r 16-byte aligned. */
+NSG_API int nsg_vq_forward_bf16x3_bnres(const void *h, const void *r, const float *mean, const float *invstd, const float *gamma,
+                                        const float *beta, const float *e, int64_t N, int32_t D, int32_t K, int64_t *idx_out,
+                                        float *codes_out, void *codes_bf16_out, int32_t bf16_relu, const float *clip_rows,
+                                        int64_t rows_per_clip, void *workspace, size_t workspace_bytes, void *stream);
+
 /* out[r] = torch.sum(v[r]**2) with ATen's CPU summation order (vector_quantization.py:12-13). */
 NSG_API int nsg_rowsumsq(const float *v, int64_t rows, int32_t D, float *out, void *stream);
 
@@ -150,6 +165,12 @@ NSG_API int nsg_index_add_rows_bf16x2(const int64_t *idx, const float *g, int64_
 NSG_API size_t nsg_index_add_sorted_workspace_bytes(int64_t N, int32_t D, int32_t K);
 NSG_API int nsg_index_add_rows_sorted(const int64_t *idx, const float *g, int64_t N, int32_t D, int32_t K, float *out,
                                       float *counts_out, void *workspace, size_t workspace_bytes, void *stream);
+
+/* The same on rows given as their sources (see nsg_vq_forward_bf16x3_bnres): every lane adds the values the fp32 rows would
+ * hold, in the same order.  D a power of two, 4 <= D <= 256.  Same workspace. */
+NSG_API int nsg_index_add_rows_sorted_bnres(const int64_t *idx, const void *h, const void *r, const float *mean, const float *invstd,
+                                            const float *gamma, const float *beta, int64_t N, int32_t D, int32_t K, float *out,
+                                            float *counts_out, void *workspace, size_t workspace_bytes, void *stream);
 
 /* out[i][:] = e[idx[i]][:] for i < N.  Replaces torch.index_select(codebook, 0, indices)
  * (vector_quantization.py:40-41, src/models.py:137) and self.codebook.embedding(latents)
@@ -465,6 +486,13 @@ NSG_API int nsg_vq_losses_indexed_bn(const float *z, const float *codebook, cons
                                      float dz_scale, const void *dz_add, float *loss_out, void *dz, int32_t grad_dtype,
                                      const void *bn_x, const float *bn_mean, const float *bn_invstd, float *bn_dgamma,
                                      float *bn_dbeta, void *workspace, size_t workspace_bytes, void *stream);
+/* nsg_vq_losses_indexed_bn with z given as its sources (see nsg_vq_forward_bf16x3_bnres): z IS the output of that BatchNorm plus
+ * the skip connection, so bn_x = h (read once for both uses), bn_mean = mean, bn_invstd = invstd.  bf16 gradients (dz, dz_add);
+ * D a multiple of 8 up to 1024; workspace nsg_vq_losses_indexed_bn_workspace_bytes. */
+NSG_API int nsg_vq_losses_indexed_bnres(const void *h, const void *r, const float *mean, const float *invstd, const float *gamma,
+                                        const float *beta, const float *codebook, const int64_t *idx, int64_t N, int32_t D, int32_t K,
+                                        float dz_scale, const void *dz_add, float *loss_out, void *dz, float *bn_dgamma,
+                                        float *bn_dbeta, void *workspace, size_t workspace_bytes, void *stream);
 
 /* torch.optim.Adam step (src/main.py:124 defaults, no weight decay, no amsgrad) over one flat
  * fp32 buffer.  g is multiplied by grad_scale first (1/world_size after a sum all-reduce).

@@ -43,6 +43,7 @@ _SIGS = {
     "nsg_vq_bf16x3_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32]),
     "nsg_vq_forward_bf16x3": (None, [_P, _P, c_int64, c_int32, c_int32, _P, _P, _P, _P, c_int32, _P, c_size_t, _P]),
     "nsg_vq_forward_bf16x3_cond": (None, [_P, _P, c_int64, c_int32, c_int32, _P, _P, _P, _P, c_int32, _P, c_int64, _P, c_size_t, _P]),
+    "nsg_vq_forward_bf16x3_bnres": (None, [_P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, _P, _P, _P, c_int32, _P, c_int64, _P, c_size_t, _P]),
     "nsg_debug_vq_forward_valu": (None, [_P, _P, c_int64, c_int32, c_int32, _P, _P, _P, _P, c_size_t, _P]),
     "nsg_rowsumsq": (None, [_P, c_int64, c_int32, _P, _P]),
     "nsg_index_add_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32]),
@@ -50,6 +51,7 @@ _SIGS = {
     "nsg_index_add_rows_bf16x2": (None, [_P, _P, c_int64, c_int32, c_int32, _P, _P, _P, c_size_t, _P]),
     "nsg_index_add_sorted_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32]),
     "nsg_index_add_rows_sorted": (None, [_P, _P, c_int64, c_int32, c_int32, _P, _P, _P, c_size_t, _P]),
+    "nsg_index_add_rows_sorted_bnres": (None, [_P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, _P, _P, _P, c_size_t, _P]),
     "nsg_gather_rows": (None, [_P, _P, c_int64, c_int32, c_int32, _P, _P]),
     "nsg_vq_ema_update": (None, [_P, _P, _P, _P, _P, c_int32, c_int32, c_float, c_float, _P, _P]),
     "nsg_codebook_grad_from_sums": (None, [_P, _P, _P, c_int32, c_int32, c_float, _P, _P]),
@@ -106,6 +108,7 @@ _SIGS = {
     "nsg_vq_losses_indexed_bn_supported": (c_int32, [c_int32]),
     "nsg_vq_losses_indexed_bn_workspace_bytes": (c_size_t, [c_int64, c_int32]),
     "nsg_vq_losses_indexed_bn": (None, [_P, _P, _P, c_int64, c_int32, c_int32, c_float, _P, _P, _P, c_int32, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "nsg_vq_losses_indexed_bnres": (None, [_P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, c_float, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
     "nsg_vq_losses": (None, [_P, _P, c_int64, c_float, c_float, _P, _P, _P, _P, c_int32, _P, c_size_t, _P]),
     "nsg_adam_step": (None, [_P, _P, _P, _P, c_int64, c_float, c_float, c_float, c_float, c_int32, c_float, _P]),
     "nsg_gated_activation_forward": (None, [_P, _P, _P, c_int64, c_int32, c_int64, _P]),

@@ -223,8 +223,10 @@ template <> __device__ __forceinline__ float round_as<bf16_t>(float v) { return 
 // sums of that BatchNorm's backward -- bn_partial[slab][2][D] = (sum dz, sum dz * xhat) of the values AS STORED -- are formed
 // while dz is written, with bn_bwd_partial_kernel's expressions in its order: for bf16 gradients (8 channels per thread there
 // too) the finished sums equal those of the separate pass over (bn_x, dz) bit for bit.
-template <typename TG, bool BN>
-__global__ __launch_bounds__(256) void vq_losses_indexed_kernel(const float *__restrict__ z, const float *__restrict__ e,
+// BNRES (with BN and bf16 gradients): z is not read as fp32 but formed from its sources (BnResRows, nsg_common.h) -- it IS the
+// output of that BatchNorm plus the skip connection, so bn_x is the sources' h (loaded once) and bn_mean / bn_invstd are theirs.
+template <typename TG, bool BN, bool BNRES = false>
+__global__ __launch_bounds__(256) void vq_losses_indexed_kernel(const typename RowArg<BNRES>::T z, const float *__restrict__ e,
                                                                 const int64_t *__restrict__ idx, int64_t N, int D, int K, float zscale,
                                                                 const TG *__restrict__ dz_add, TG *__restrict__ dz, double *partial,
                                                                 int slab_rows, const TG *__restrict__ bn_x,
@@ -241,12 +243,49 @@ __global__ __launch_bounds__(256) void vq_losses_indexed_kernel(const float *__r
     float s1[8], s2[8], mu[8], is[8];
 #pragma unroll
     for (int c = 0; c < 8; ++c) { s1[c] = 0.f; s2[c] = 0.f; mu[c] = BN ? bn_mean[d8 + c] : 0.f; is[c] = BN ? bn_invstd[d8 + c] : 0.f; }
+    // BNRES: the four constants per channel -- mean, sc = invstd * gamma, beta, invstd -- wait in LDS (the sums' reduction buffer,
+    // idle until the rows are done) and are read per row, four channels at a time: held in registers beside the sums they would
+    // cost the kernel two of its seven waves per SIMD (86 registers against 72)
+    __shared__ float red[BN ? 2 * 256 * 8 : 1];
+    if constexpr (BNRES) {
+        if (rg == 0) {
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+                red[d8 + c] = mu[c];
+                red[D + d8 + c] = is[c] * z.gamma[d8 + c];
+                red[2 * D + d8 + c] = z.beta[d8 + c];
+                red[3 * D + d8 + c] = is[c];
+            }
+        }
+        __syncthreads();
+    }
     for (int64_t row = r0 + rg; row < r1 && rg < rgroups; row += rgroups) {
         const int64_t i = row * D8 + cg;
         int64_t k = idx[row];
         k = k < 0 ? 0 : (k >= K ? K - 1 : k);                 // (validated indices; clamped so a bad one cannot fault)
-        float zv[8], qv[8], g[8];
-        ldw<float, 8>(z + i * 8, zv);
+        float zv[8], qv[8], g[8], xv[8];
+        if constexpr (BNRES) {
+            float rv[8];
+            ldw<bf16_t, 8>(z.h + i * 8, xv);
+            ldw<bf16_t, 8>(z.r + i * 8, rv);
+            int lo = d8;
+            asm volatile("" : "+v"(lo));          // (an offset the compiler cannot prove loop-invariant: the reads stay in the loop)
+#pragma unroll
+            for (int c4 = 0; c4 < 8; c4 += 4) {
+                float m[4], sc[4], be[4];
+                ldw<float, 4>(red + lo + c4, m);
+                ldw<float, 4>(red + D + lo + c4, sc);
+                ldw<float, 4>(red + 2 * D + lo + c4, be);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    xv[c4 + c] -= m[c];            // h - mean: the BatchNorm backward sum below starts from it too
+                    zv[c4 + c] = nsg_bn_res_centered(xv[c4 + c], rv[c4 + c], sc[c], be[c]);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        } else {
+            ldw<float, 8>(z + i * 8, zv);
+        }
         ldw<float, 8>(e + (size_t)k * D + d8, qv);
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
@@ -263,20 +302,24 @@ __global__ __launch_bounds__(256) void vq_losses_indexed_kernel(const float *__r
             }
             stw<TG, 8>(dz + i * 8, g);
             if constexpr (BN) {
-                float xv[8];
-                ldw<TG, 8>(bn_x + i * 8, xv);
+                if constexpr (!BNRES) ldw<TG, 8>(bn_x + i * 8, xv);
+                float isl[8];
+                if constexpr (BNRES) {
+                    int lo = d8;
+                    asm volatile("" : "+v"(lo));
+                    ldw<float, 8>(red + 3 * D + lo, isl);
+                }
 #pragma unroll
                 for (int c = 0; c < 8; ++c) {
                     const float gs = round_as<TG>(g[c]);
                     s1[c] += gs;
-                    s2[c] += gs * ((xv[c] - mu[c]) * is[c]);
+                    s2[c] += gs * (BNRES ? xv[c] * isl[c] : (xv[c] - mu[c]) * is[c]);
                 }
             }
         }
     }
     block_sum_store(acc, partial);
     if constexpr (BN) {
-        __shared__ float red[2 * 256 * 8];
         __syncthreads();
 #pragma unroll
         for (int c = 0; c < 8; ++c)
@@ -631,6 +674,34 @@ int nsg_vq_losses_indexed_bn(const float *z, const float *codebook, const int64_
                            rows, (const float *)bn_x, bn_mean, bn_invstd, bnp);
     hipLaunchKernelGGL(final_mean_kernel, dim3(1), dim3(64), 0, s, partial, nb, (double)n, loss_out);
     int rc = nsg_check_launch("vq_losses_indexed_bn");
+    if (rc) return rc;
+    return nsg_launch_bn_bwd_final(bnp, nb, D, bn_dgamma, bn_dbeta, s);
+}
+
+int nsg_vq_losses_indexed_bnres(const void *h, const void *r, const float *mean, const float *invstd, const float *gamma, const float *beta,
+                                const float *codebook, const int64_t *idx, int64_t N, int32_t D, int32_t K, float dz_scale, const void *dz_add,
+                                float *loss_out, void *dz, float *bn_dgamma, float *bn_dbeta, void *workspace, size_t workspace_bytes,
+                                void *stream)
+{
+    NSG_REQUIRE(h && r && mean && invstd && gamma && beta && codebook && idx && loss_out && dz && bn_dgamma && bn_dbeta && N > 0 && K > 0,
+                NSG_E_INVALID, "nsg_vq_losses_indexed_bnres: bad argument");
+    // (the kernel keeps four constants per channel in its 4096-float reduction buffer)
+    NSG_REQUIRE(D >= 8 && D % 8 == 0 && D <= 1024, NSG_E_UNSUPPORTED, "nsg_vq_losses_indexed_bnres: D=%d must be a multiple of 8 up to 1024", D);
+    NSG_REQUIRE(nsg_aligned16(h) && nsg_aligned16(r) && nsg_aligned16(codebook) && nsg_aligned16(dz) && (!dz_add || nsg_aligned16(dz_add)), NSG_E_INVALID,
+                "nsg_vq_losses_indexed_bnres: pointers must be 16-byte aligned");
+    const int64_t n = N * D;
+    NSG_REQUIRE(workspace && workspace_bytes >= nsg_vq_losses_indexed_bn_workspace_bytes(N, D), NSG_E_WORKSPACE, "nsg_vq_losses_indexed_bnres: workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    double *partial = reinterpret_cast<double *>(workspace);
+    float *bnp = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + nsg_align_up(nsg_reduce_workspace_bytes(n), 256));
+    const float zs = dz_scale * 2.0f / (float)n;
+    int nb, rows;
+    nsg_bn_slab_geom(N, &nb, &rows);
+    const BnResRows src = {reinterpret_cast<const bf16_t *>(h), reinterpret_cast<const bf16_t *>(r), mean, invstd, gamma, beta};
+    hipLaunchKernelGGL((vq_losses_indexed_kernel<bf16_t, true, true>), dim3(nb), dim3(256), 0, s, src, codebook, idx, N, D, K, zs, (const bf16_t *)dz_add, (bf16_t *)dz,
+                       partial, rows, src.h, mean, invstd, bnp);
+    hipLaunchKernelGGL(final_mean_kernel, dim3(1), dim3(64), 0, s, partial, nb, (double)n, loss_out);
+    int rc = nsg_check_launch("vq_losses_indexed_bnres");
     if (rc) return rc;
     return nsg_launch_bn_bwd_final(bnp, nb, D, bn_dgamma, bn_dbeta, s);
 }

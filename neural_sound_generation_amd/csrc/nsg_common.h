@@ -64,6 +64,36 @@ template <> struct Elem<bf16_t> {
     static __device__ __forceinline__ void put(bf16_t *p, float v) { *p = nsg_f2bf(v); }
 };
 
+// ---- rows given as their sources: a ResBlock's closing BatchNorm + skip connection, formed where the rows are loaded ---------
+//   z[row][c] = ((h[row][c] - mean[c]) * (invstd[c] * gamma[c]) + beta[c]) + r[row][c]
+// h (the BatchNorm's input) and r (the block's ReLU'd input) are bf16 [N][D], the four vectors fp32 [D].  The expression is
+// bn_apply_kernel's (bn.hip), in its order (sc = invstd * gamma first); the library is built with -ffp-contract=off, so every
+// kernel that spells it through nsg_bn_res() forms the bits bn_apply_kernel would have stored as fp32.
+struct BnResRows {
+    const bf16_t *h, *r;
+    const float *mean, *invstd, *gamma, *beta;
+};
+__device__ __forceinline__ float nsg_bn_res_centered(float t, float r, float sc, float be) { return (t * sc + be) + r; }   // t = h - mean
+__device__ __forceinline__ float nsg_bn_res(float h, float r, float mu, float sc, float be) { return nsg_bn_res_centered(h - mu, r, sc, be); }
+// kernel-argument type of a row operand: the fp32 rows themselves, or their sources
+template <bool BNRES> struct RowArg { typedef const float *T; };
+template <> struct RowArg<true> { typedef BnResRows T; };
+// a lane's W per-channel constants of such rows, channels c .. c + W - 1 (c + W <= D), and W of its elements at p = row * D + c
+template <int W>
+struct BnResLane {
+    float mu[W], sc[W], be[W];
+    __device__ __forceinline__ void init(const BnResRows &s, int c)
+    {
+#pragma unroll
+        for (int e = 0; e < W; ++e) { mu[e] = s.mean[c + e]; sc[e] = s.invstd[c + e] * s.gamma[c + e]; be[e] = s.beta[c + e]; }
+    }
+    __device__ __forceinline__ void apply(const float *hv, const float *rv, float *z) const
+    {
+#pragma unroll
+        for (int e = 0; e < W; ++e) z[e] = nsg_bn_res(hv[e], rv[e], mu[e], sc[e], be[e]);
+    }
+};
+
 // Fixed-order sum of n floats p[0], p[stride], p[2*stride], ... : the loads are issued 16 at a time (the
 // finalize kernels are otherwise a chain of dependent global-load latencies), the adds stay in index order.
 template <typename ACC>

@@ -170,9 +170,20 @@ __global__ __launch_bounds__(64) void seg_place_kernel(const int64_t *__restrict
     }
 }
 
+// four bf16 elements (8 bytes) as floats
+__device__ __forceinline__ void ld_bf16x4(const bf16_t *p, float *o)
+{
+    const uint2 u = *reinterpret_cast<const uint2 *>(p);
+    o[0] = nsg_bitsf(u.x << 16); o[1] = nsg_bitsf(u.x & 0xffff0000u);
+    o[2] = nsg_bitsf(u.y << 16); o[3] = nsg_bitsf(u.y & 0xffff0000u);
+}
+
 // one wave per chunk: rows perm[p0 .. p1) of code k summed in position order.  D = 4 * 64 * RPL... a lane owns one 16-byte piece
 // of a row; a wave-wide load covers 1024 / (4 D) rows; lanes that own the same piece of different rows are combined in lane order.
-__global__ __launch_bounds__(256) void seg_sum_kernel(const float *__restrict__ g, const int *__restrict__ perm, const int *__restrict__ total,
+// BNRES: the rows are formed from their sources where they are loaded (BnResRows, nsg_common.h): the same lane owns the same
+// four channels and adds the same values in the same order, so the sums are those of the fp32 rows bn_apply would have stored.
+template <bool BNRES>
+__global__ __launch_bounds__(256) void seg_sum_kernel(const typename RowArg<BNRES>::T g, const int *__restrict__ perm, const int *__restrict__ total,
                                                      const int *__restrict__ base, const int *__restrict__ chunkbase, int K, int D,
                                                      float *__restrict__ partial)
 {
@@ -195,13 +206,26 @@ __global__ __launch_bounds__(256) void seg_sum_kernel(const float *__restrict__ 
     if (ppr <= 64) {
         const int sub = lane / ppr, pc = lane - sub * ppr;
         const bool act = sub < rpi;
+        BnResLane<BNRES ? 4 : 1> gc;
+        if constexpr (BNRES) gc.init(g, pc * 4);
+        auto ldrow = [&](int row) -> v4f {
+            if constexpr (BNRES) {
+                float hv[4], rv[4], z[4];
+                ld_bf16x4(g.h + (size_t)row * D + pc * 4, hv);
+                ld_bf16x4(g.r + (size_t)row * D + pc * 4, rv);
+                gc.apply(hv, rv, z);
+                return v4f{z[0], z[1], z[2], z[3]};
+            } else {
+                return *reinterpret_cast<const v4f *>(g + (size_t)row * D + pc * 4);
+            }
+        };
         int p = p0;
         for (; p + 4 * rpi <= p1; p += 4 * rpi) {       // four loads in flight, added in position order
             v4f v[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int row = act ? perm[p + u * rpi + sub] : 0;
-                v[u] = *reinterpret_cast<const v4f *>(g + (size_t)row * D + pc * 4);
+                v[u] = ldrow(row);
             }
             if (act) {
 #pragma unroll
@@ -209,7 +233,7 @@ __global__ __launch_bounds__(256) void seg_sum_kernel(const float *__restrict__ 
             }
         }
         for (; p < p1; p += rpi) {
-            if (act && p + sub < p1) acc += *reinterpret_cast<const v4f *>(g + (size_t)perm[p + sub] * D + pc * 4);
+            if (act && p + sub < p1) acc += ldrow(perm[p + sub]);
         }
         // combine the rpi sub-rows of each piece in sub order, then the four waves in wave order, through LDS
         __shared__ v4f red[256];
@@ -224,7 +248,7 @@ __global__ __launch_bounds__(256) void seg_sum_kernel(const float *__restrict__ 
             }
             *reinterpret_cast<v4f *>(partial + (size_t)chunk * D + threadIdx.x * 4) = s;
         }
-    } else {
+    } else if constexpr (!BNRES) {
         for (int pc = threadIdx.x; pc < ppr; pc += 256) {        // wide rows: a thread walks its pieces over the whole chunk
             v4f s = {0.f, 0.f, 0.f, 0.f};
             for (int p = base[k] + j * SEG_CH; p < pend; ++p) s += *reinterpret_cast<const v4f *>(g + (size_t)perm[p] * D + pc * 4);
@@ -269,23 +293,11 @@ __global__ __launch_bounds__(256) void seg_final_kernel(const float *__restrict_
     }
 }
 
-}  // namespace
-
-extern "C" {
-
-size_t nsg_index_add_sorted_workspace_bytes(int64_t N, int32_t D, int32_t K)
+// the six launches behind the entry points' argument checks
+template <bool BNRES>
+int seg_sums(const int64_t *idx, const typename RowArg<BNRES>::T g, int64_t N, int32_t D, int32_t K, float *out, float *counts_out, void *workspace,
+             size_t workspace_bytes, void *stream)
 {
-    if (N <= 0 || D <= 0 || K <= 0) return 0;
-    return seg_layout(N, D, K).bytes;
-}
-
-int nsg_index_add_rows_sorted(const int64_t *idx, const float *g, int64_t N, int32_t D, int32_t K, float *out, float *counts_out,
-                              void *workspace, size_t workspace_bytes, void *stream)
-{
-    NSG_REQUIRE(idx && g && out && N > 0 && D > 0 && K > 0, NSG_E_INVALID, "nsg_index_add_rows_sorted: bad argument");
-    NSG_REQUIRE(D % 4 == 0 && nsg_aligned16(g) && nsg_aligned16(out), NSG_E_UNSUPPORTED, "nsg_index_add_rows_sorted: D %% 4 == 0 and 16-byte aligned tensors");
-    NSG_REQUIRE(N < 0x7fffffffll && K <= 8192 && 64 % (D / 4 > 64 ? 64 : D / 4) == 0, NSG_E_UNSUPPORTED,
-                "nsg_index_add_rows_sorted: N < 2^31, K <= 8192, D a power of two up to 256 (or a multiple of 256)");
     const SegLayout L = seg_layout(N, D, K);
     NSG_REQUIRE(workspace && workspace_bytes >= L.bytes, NSG_E_WORKSPACE, "nsg_index_add_rows_sorted: workspace too small");
     char *ws = reinterpret_cast<char *>(workspace);
@@ -303,9 +315,43 @@ int nsg_index_add_rows_sorted(const int64_t *idx, const float *g, int64_t N, int
         if (rc != NSG_OK) return rc;
     }
     hipLaunchKernelGGL(seg_place_kernel, dim3(L.nb), dim3(64), (size_t)K * 12, s, idx, N, K, blockcnt, base, perm);
-    hipLaunchKernelGGL(seg_sum_kernel, dim3((unsigned)L.maxchunks), dim3(256), 0, s, g, perm, total, base, chunkbase, K, D, partial);
+    hipLaunchKernelGGL(seg_sum_kernel<BNRES>, dim3((unsigned)L.maxchunks), dim3(256), 0, s, g, perm, total, base, chunkbase, K, D, partial);
     hipLaunchKernelGGL(seg_final_kernel, dim3((unsigned)K), dim3(256), 0, s, partial, chunkbase, K, D, out);
     return nsg_check_launch("index_add_rows_sorted");
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t nsg_index_add_sorted_workspace_bytes(int64_t N, int32_t D, int32_t K)
+{
+    if (N <= 0 || D <= 0 || K <= 0) return 0;
+    return seg_layout(N, D, K).bytes;
+}
+
+int nsg_index_add_rows_sorted(const int64_t *idx, const float *g, int64_t N, int32_t D, int32_t K, float *out, float *counts_out,
+                              void *workspace, size_t workspace_bytes, void *stream)
+{
+    NSG_REQUIRE(idx && g && out && N > 0 && D > 0 && K > 0, NSG_E_INVALID, "nsg_index_add_rows_sorted: bad argument");
+    NSG_REQUIRE(D % 4 == 0 && nsg_aligned16(g) && nsg_aligned16(out), NSG_E_UNSUPPORTED, "nsg_index_add_rows_sorted: D %% 4 == 0 and 16-byte aligned tensors");
+    NSG_REQUIRE(N < 0x7fffffffll && K <= 8192 && 64 % (D / 4 > 64 ? 64 : D / 4) == 0, NSG_E_UNSUPPORTED,
+                "nsg_index_add_rows_sorted: N < 2^31, K <= 8192, D a power of two up to 256 (or a multiple of 256)");
+    return seg_sums<false>(idx, g, N, D, K, out, counts_out, workspace, workspace_bytes, stream);
+}
+
+int nsg_index_add_rows_sorted_bnres(const int64_t *idx, const void *h, const void *r, const float *mean, const float *invstd, const float *gamma,
+                                    const float *beta, int64_t N, int32_t D, int32_t K, float *out, float *counts_out, void *workspace,
+                                    size_t workspace_bytes, void *stream)
+{
+    NSG_REQUIRE(idx && h && r && mean && invstd && gamma && beta && out && N > 0 && D > 0 && K > 0, NSG_E_INVALID,
+                "nsg_index_add_rows_sorted_bnres: bad argument");
+    NSG_REQUIRE(D % 4 == 0 && nsg_aligned16(h) && nsg_aligned16(r) && nsg_aligned16(out), NSG_E_UNSUPPORTED,
+                "nsg_index_add_rows_sorted_bnres: D %% 4 == 0 and 16-byte aligned tensors");
+    NSG_REQUIRE(N < 0x7fffffffll && K <= 8192 && D <= 256 && 64 % (D / 4) == 0, NSG_E_UNSUPPORTED,
+                "nsg_index_add_rows_sorted_bnres: N < 2^31, K <= 8192, D a power of two up to 256");
+    const BnResRows src = {reinterpret_cast<const bf16_t *>(h), reinterpret_cast<const bf16_t *>(r), mean, invstd, gamma, beta};
+    return seg_sums<true>(idx, src, N, D, K, out, counts_out, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

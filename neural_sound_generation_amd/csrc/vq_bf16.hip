@@ -44,8 +44,10 @@ __device__ __forceinline__ void split8(const v4f a, const v4f b, bf16x8 &hi, bf1
 // HAS_X2 = false: no |x|^2 term (it changes no argmin; only the reported distances need it): 16 registers fewer, which at
 // D = 128 is the difference between two and three blocks per CU (the kernel alternates between an HBM phase -- its rows in, the
 // picked codes out -- and an MFMA phase, and only other blocks on the CU overlap the two)
-template <int NKS, bool HAS_X2>   // k-steps of 16 channels: DP = 16 * NKS >= D
-__global__ __launch_bounds__(256) void vq_forward_bf16x3_kernel(const float *__restrict__ x, const bf16_t *__restrict__ ehi,
+// BNRES: the rows are not read as fp32 but formed from their sources while the A fragments are built (BnResRows, nsg_common.h:
+// the encoder's closing BatchNorm + skip connection -- the same values bn_apply would have stored, so the same search)
+template <int NKS, bool HAS_X2, bool BNRES>   // k-steps of 16 channels: DP = 16 * NKS >= D
+__global__ __launch_bounds__(256) void vq_forward_bf16x3_kernel(const typename RowArg<BNRES>::T x, const bf16_t *__restrict__ ehi,
                                                                 const bf16_t *__restrict__ elo, const float *__restrict__ e,
                                                                 const float *__restrict__ x2, const float *__restrict__ c2,
                                                                 int64_t N, int D, int K, int64_t *__restrict__ idx_out,
@@ -76,8 +78,19 @@ __global__ __launch_bounds__(256) void vq_forward_bf16x3_kernel(const float *__r
             const int d0 = 16 * s + 8 * h;
             v4f a = {0.f, 0.f, 0.f, 0.f}, b = {0.f, 0.f, 0.f, 0.f};
             if (row < N && d0 < D) {               // D % 8 == 0: the 8 channels are all inside the row
-                a = *reinterpret_cast<const v4f *>(x + row * D + d0);
-                b = *reinterpret_cast<const v4f *>(x + row * D + d0 + 4);
+                if constexpr (BNRES) {             // one k-step at a time: its 8 channels' constants die with it
+                    float hv[8], rv[8], z[8];
+                    ldw<bf16_t, 8>(x.h + row * D + d0, hv);
+                    ldw<bf16_t, 8>(x.r + row * D + d0, rv);
+                    BnResLane<8> c;
+                    c.init(x, d0);
+                    c.apply(hv, rv, z);
+                    a = v4f{z[0], z[1], z[2], z[3]};
+                    b = v4f{z[4], z[5], z[6], z[7]};
+                } else {
+                    a = *reinterpret_cast<const v4f *>(x + row * D + d0);
+                    b = *reinterpret_cast<const v4f *>(x + row * D + d0 + 4);
+                }
             }
             split8(a, b, ahi[s], alo[s]);
         }
@@ -208,8 +221,8 @@ __global__ __launch_bounds__(256) void vq_forward_bf16x3_kernel(const float *__r
     }
 }
 
-template <int NKS>
-int launch(const float *x, const bf16_t *ehi, const bf16_t *elo, const float *e, const float *x2, const float *c2, int64_t N, int D,
+template <int NKS, bool BNRES>
+int launch(const typename RowArg<BNRES>::T x, const bf16_t *ehi, const bf16_t *elo, const float *e, const float *x2, const float *c2, int64_t N, int D,
            int K, int64_t *idx, float *codes, float *dmin, bf16_t *codes_lp, int lp_relu, const float *clip_rows, int64_t rows_per_clip,
            hipStream_t s)
 {
@@ -219,17 +232,71 @@ int launch(const float *x, const bf16_t *ehi, const bf16_t *elo, const float *e,
     if (nb > 0x7fffffff) return nsg_fail(NSG_E_UNSUPPORTED, "vq_forward_bf16x3: too many rows");
     static LdsOptIn once;
     if (lds > 65536 - 1024) {
-        const int rc = nsg_lds_opt_in(once, {reinterpret_cast<const void *>(&vq_forward_bf16x3_kernel<NKS, true>),
-                                             reinterpret_cast<const void *>(&vq_forward_bf16x3_kernel<NKS, false>)}, lds, "vq_forward_bf16x3");
+        int rc;
+        if constexpr (BNRES) {     // rows from their sources come without distances: only the HAS_X2 = false kernel exists
+            rc = nsg_lds_opt_in(once, {reinterpret_cast<const void *>(&vq_forward_bf16x3_kernel<NKS, false, true>)}, lds, "vq_forward_bf16x3");
+        } else {
+            rc = nsg_lds_opt_in(once, {reinterpret_cast<const void *>(&vq_forward_bf16x3_kernel<NKS, true, false>),
+                                       reinterpret_cast<const void *>(&vq_forward_bf16x3_kernel<NKS, false, false>)}, lds, "vq_forward_bf16x3");
+        }
         if (rc != NSG_OK) return rc;
     }
-    if (x2) hipLaunchKernelGGL((vq_forward_bf16x3_kernel<NKS, true>), dim3((unsigned)nb), dim3(256), lds, s, x, ehi, elo, e, x2, c2, N, D, K, idx, codes, dmin, codes_lp, lp_relu, clip_rows, rows_per_clip);
-    else    hipLaunchKernelGGL((vq_forward_bf16x3_kernel<NKS, false>), dim3((unsigned)nb), dim3(256), lds, s, x, ehi, elo, e, x2, c2, N, D, K, idx, codes, dmin, codes_lp, lp_relu, clip_rows, rows_per_clip);
+    if constexpr (!BNRES) {
+        if (x2) {
+            hipLaunchKernelGGL((vq_forward_bf16x3_kernel<NKS, true, false>), dim3((unsigned)nb), dim3(256), lds, s, x, ehi, elo, e, x2, c2, N, D, K, idx, codes, dmin, codes_lp, lp_relu, clip_rows, rows_per_clip);
+            return nsg_check_launch("vq_forward_bf16x3_kernel");
+        }
+    }
+    hipLaunchKernelGGL((vq_forward_bf16x3_kernel<NKS, false, BNRES>), dim3((unsigned)nb), dim3(256), lds, s, x, ehi, elo, e, x2, c2, N, D, K, idx, codes, dmin, codes_lp, lp_relu, clip_rows, rows_per_clip);
     return nsg_check_launch("vq_forward_bf16x3_kernel");
 }
 
 inline int dp_of(int D) { return D <= 16 ? 16 : D <= 32 ? 32 : D <= 64 ? 64 : D <= 128 ? 128 : 256; }
 inline size_t split_bytes(int D, int K) { return nsg_align_up((size_t)nsg_cdiv(K, 32) * 32 * dp_of(D) * sizeof(bf16_t), 256); }
+
+// the entry points behind the null checks of their row operand (xf: the fp32 rows again, for the distances' |x|^2 pass)
+template <bool BNRES>
+int search(const typename RowArg<BNRES>::T x, const float *xf, bool rows_aligned, const float *e, int64_t N, int32_t D, int32_t K, int64_t *idx_out, float *codes_out,
+           float *dmin_out, void *codes_bf16_out, int32_t bf16_relu, const float *clip_rows, int64_t rows_per_clip, void *workspace,
+           size_t workspace_bytes, void *stream)
+{
+    NSG_REQUIRE(!clip_rows || (codes_bf16_out && rows_per_clip > 0 && nsg_aligned16(clip_rows)), NSG_E_INVALID,
+                "nsg_vq_forward_bf16x3_cond: clip_rows needs codes_bf16_out, rows_per_clip > 0 and 16-byte alignment");
+    NSG_REQUIRE(D <= 256 && D % 8 == 0, NSG_E_UNSUPPORTED, "nsg_vq_forward_bf16x3: D=%d must be a multiple of 8, at most 256", D);
+    NSG_REQUIRE(rows_aligned && nsg_aligned16(e) && (!codes_out || nsg_aligned16(codes_out)) && (!codes_bf16_out || nsg_aligned16(codes_bf16_out)),
+                NSG_E_INVALID, "nsg_vq_forward_bf16x3: pointers must be 16-byte aligned");
+    bf16_t *lp = reinterpret_cast<bf16_t *>(codes_bf16_out);
+    if (N == 0) return NSG_OK;
+    NSG_REQUIRE(workspace && workspace_bytes >= nsg_vq_bf16x3_workspace_bytes(N, D, K), NSG_E_WORKSPACE,
+                "nsg_vq_forward_bf16x3: workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    char *ws = reinterpret_cast<char *>(workspace);
+    float *x2 = reinterpret_cast<float *>(ws);
+    float *c2 = reinterpret_cast<float *>(ws + nsg_align_up((size_t)N * sizeof(float), 256));
+    bf16_t *ehi = reinterpret_cast<bf16_t *>(ws + nsg_vq_workspace_bytes(N, D, K));
+    bf16_t *elo = reinterpret_cast<bf16_t *>(ws + nsg_vq_workspace_bytes(N, D, K) + split_bytes(D, K));
+    // |x|^2 is constant along a row: it only matters for the reported distances.  Without dmin_out it is neither computed
+    // (a pass over x) nor added (the sum c2 + x2 would round the small code norms away)
+    int rc = NSG_OK;
+    if (dmin_out) rc = nsg_rowsumsq(xf, N, D, x2, stream);
+    else x2 = nullptr;
+    if (rc) return rc;
+    rc = nsg_rowsumsq(e, K, D, c2, stream);
+    if (rc) return rc;
+    const int DP = dp_of(D), Kp = (int)nsg_cdiv(K, 32) * 32;
+    const int64_t tot = (int64_t)Kp * DP;
+    hipLaunchKernelGGL(split_bf16_kernel, dim3((unsigned)(nsg_cdiv(tot, 256) > 1024 ? 1024 : nsg_cdiv(tot, 256))), dim3(256), 0, s, e, K, D,
+                       Kp, DP, ehi, elo);
+    rc = nsg_check_launch("split_bf16_kernel");
+    if (rc) return rc;
+    switch (DP) {
+    case 16:  return launch<1, BNRES>(x, ehi, elo, e, x2, c2, N, D, K, idx_out, codes_out, dmin_out, lp, bf16_relu, clip_rows, rows_per_clip, s);
+    case 32:  return launch<2, BNRES>(x, ehi, elo, e, x2, c2, N, D, K, idx_out, codes_out, dmin_out, lp, bf16_relu, clip_rows, rows_per_clip, s);
+    case 64:  return launch<4, BNRES>(x, ehi, elo, e, x2, c2, N, D, K, idx_out, codes_out, dmin_out, lp, bf16_relu, clip_rows, rows_per_clip, s);
+    case 128: return launch<8, BNRES>(x, ehi, elo, e, x2, c2, N, D, K, idx_out, codes_out, dmin_out, lp, bf16_relu, clip_rows, rows_per_clip, s);
+    default:  return launch<16, BNRES>(x, ehi, elo, e, x2, c2, N, D, K, idx_out, codes_out, dmin_out, lp, bf16_relu, clip_rows, rows_per_clip, s);
+    }
+}
 
 }  // namespace
 
@@ -253,42 +320,20 @@ int nsg_vq_forward_bf16x3_cond(const float *x, const float *e, int64_t N, int32_
                                void *workspace, size_t workspace_bytes, void *stream)
 {
     NSG_REQUIRE(x && e && idx_out && N >= 0 && D > 0 && K > 0, NSG_E_INVALID, "nsg_vq_forward_bf16x3: bad argument");
-    NSG_REQUIRE(!clip_rows || (codes_bf16_out && rows_per_clip > 0 && nsg_aligned16(clip_rows)), NSG_E_INVALID,
-                "nsg_vq_forward_bf16x3_cond: clip_rows needs codes_bf16_out, rows_per_clip > 0 and 16-byte alignment");
-    NSG_REQUIRE(D <= 256 && D % 8 == 0, NSG_E_UNSUPPORTED, "nsg_vq_forward_bf16x3: D=%d must be a multiple of 8, at most 256", D);
-    NSG_REQUIRE(nsg_aligned16(x) && nsg_aligned16(e) && (!codes_out || nsg_aligned16(codes_out)) && (!codes_bf16_out || nsg_aligned16(codes_bf16_out)),
-                NSG_E_INVALID, "nsg_vq_forward_bf16x3: pointers must be 16-byte aligned");
-    bf16_t *lp = reinterpret_cast<bf16_t *>(codes_bf16_out);
-    if (N == 0) return NSG_OK;
-    NSG_REQUIRE(workspace && workspace_bytes >= nsg_vq_bf16x3_workspace_bytes(N, D, K), NSG_E_WORKSPACE,
-                "nsg_vq_forward_bf16x3: workspace too small");
-    hipStream_t s = (hipStream_t)stream;
-    char *ws = reinterpret_cast<char *>(workspace);
-    float *x2 = reinterpret_cast<float *>(ws);
-    float *c2 = reinterpret_cast<float *>(ws + nsg_align_up((size_t)N * sizeof(float), 256));
-    bf16_t *ehi = reinterpret_cast<bf16_t *>(ws + nsg_vq_workspace_bytes(N, D, K));
-    bf16_t *elo = reinterpret_cast<bf16_t *>(ws + nsg_vq_workspace_bytes(N, D, K) + split_bytes(D, K));
-    // |x|^2 is constant along a row: it only matters for the reported distances.  Without dmin_out it is neither computed
-    // (a pass over x) nor added (the sum c2 + x2 would round the small code norms away)
-    int rc = NSG_OK;
-    if (dmin_out) rc = nsg_rowsumsq(x, N, D, x2, stream);
-    else x2 = nullptr;
-    if (rc) return rc;
-    rc = nsg_rowsumsq(e, K, D, c2, stream);
-    if (rc) return rc;
-    const int DP = dp_of(D), Kp = (int)nsg_cdiv(K, 32) * 32;
-    const int64_t tot = (int64_t)Kp * DP;
-    hipLaunchKernelGGL(split_bf16_kernel, dim3((unsigned)(nsg_cdiv(tot, 256) > 1024 ? 1024 : nsg_cdiv(tot, 256))), dim3(256), 0, s, e, K, D,
-                       Kp, DP, ehi, elo);
-    rc = nsg_check_launch("split_bf16_kernel");
-    if (rc) return rc;
-    switch (DP) {
-    case 16:  return launch<1>(x, ehi, elo, e, x2, c2, N, D, K, idx_out, codes_out, dmin_out, lp, bf16_relu, clip_rows, rows_per_clip, s);
-    case 32:  return launch<2>(x, ehi, elo, e, x2, c2, N, D, K, idx_out, codes_out, dmin_out, lp, bf16_relu, clip_rows, rows_per_clip, s);
-    case 64:  return launch<4>(x, ehi, elo, e, x2, c2, N, D, K, idx_out, codes_out, dmin_out, lp, bf16_relu, clip_rows, rows_per_clip, s);
-    case 128: return launch<8>(x, ehi, elo, e, x2, c2, N, D, K, idx_out, codes_out, dmin_out, lp, bf16_relu, clip_rows, rows_per_clip, s);
-    default:  return launch<16>(x, ehi, elo, e, x2, c2, N, D, K, idx_out, codes_out, dmin_out, lp, bf16_relu, clip_rows, rows_per_clip, s);
-    }
+    return search<false>(x, x, nsg_aligned16(x), e, N, D, K, idx_out, codes_out, dmin_out, codes_bf16_out, bf16_relu, clip_rows, rows_per_clip, workspace,
+                         workspace_bytes, stream);
+}
+
+int nsg_vq_forward_bf16x3_bnres(const void *h, const void *r, const float *mean, const float *invstd, const float *gamma, const float *beta,
+                                const float *e, int64_t N, int32_t D, int32_t K, int64_t *idx_out, float *codes_out, void *codes_bf16_out,
+                                int32_t bf16_relu, const float *clip_rows, int64_t rows_per_clip, void *workspace, size_t workspace_bytes,
+                                void *stream)
+{
+    NSG_REQUIRE(h && r && mean && invstd && gamma && beta && e && idx_out && N >= 0 && D > 0 && K > 0, NSG_E_INVALID,
+                "nsg_vq_forward_bf16x3_bnres: bad argument");
+    const BnResRows src = {reinterpret_cast<const bf16_t *>(h), reinterpret_cast<const bf16_t *>(r), mean, invstd, gamma, beta};
+    return search<true>(src, nullptr, nsg_aligned16(h) && nsg_aligned16(r), e, N, D, K, idx_out, codes_out, nullptr, codes_bf16_out, bf16_relu, clip_rows, rows_per_clip, workspace,
+                        workspace_bytes, stream);
 }
 
 }  // extern "C"

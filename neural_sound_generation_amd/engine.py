@@ -13,7 +13,7 @@ Parameter bundles are plain tuples of tensors in the reference's state_dict orde
 from __future__ import annotations
 
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -154,14 +154,17 @@ def _bn_forward(h, bn: BNParams, training: bool):
 # ------------------------------------------------------------------------------------------------
 # ResBlock   y = relu(x) + BN(conv1x1(relu(BN(conv3x3(relu(x))))))      (src/models.py:145-158)
 # ------------------------------------------------------------------------------------------------
-def resblock_forward(r, P: ResBlockParams, training: bool, out_dtype=None, relu_out=False, packs=None):
+def resblock_forward(r, P: ResBlockParams, training: bool, out_dtype=None, relu_out=False, packs=None, defer_bn2=False):
     """r = relu(x) NHWC of the compute dtype, ALREADY ReLU'd by its producer: the reference's block starts
     with an in-place ReLU that overwrites its input (models.py:149), so nothing ever needs the un-ReLU'd
     tensor and the backward mask (x > 0) equals (r > 0).  Applying that ReLU where the tensor is written
     removes all ReLU work from the GEMM operand staging.
     out_dtype: storage type of the output (default: r's) -- the encoder's last block writes fp32 for the
     quantiser.  relu_out: store relu(y) because the consumer is again a ResBlock / the decoder's ReLU.
-    packs: ((w_fwd, w_dgrad) of conv1, of conv2) when the caller packed the weights already (pack_all)."""
+    packs: ((w_fwd, w_dgrad) of conv1, of conv2) when the caller packed the weights already (pack_all).
+    defer_bn2: do not run the closing BatchNorm + skip pass: y is None and the consumers form it from its sources (resblock_bn2
+    on the saved state) while they load it.  Honoured only where those pieces exist in bf16 (the fused 1x1 path, no output ReLU);
+    otherwise y is returned as usual."""
     B, H, W, D = r.shape
     d1 = ops.conv_desc(B, H, W, D, D, 3, 1, 1, dtype=r.dtype)
     d2 = ops.conv_desc(B, H, W, D, D, 1, 1, 0, dtype=r.dtype)
@@ -179,30 +182,52 @@ def resblock_forward(r, P: ResBlockParams, training: bool, out_dtype=None, relu_
     else:
         a1 = ops.bn_apply(h1, m1, i1, P.bn1.weight, P.bn1.bias, relu=True)
         h2, m2, i2 = _conv_bn(d2, a1, wf2, P.conv2, P.bn2, training)
-    y = ops.bn_apply(h2, m2, i2, P.bn2.weight, P.bn2.bias, relu=False, residual=r, relu_residual=False, out_dtype=out_dtype,
-                     relu_out=relu_out)
+    if defer_bn2 and a1 is None and not relu_out and h2.dtype == torch.bfloat16 and r.dtype == torch.bfloat16:
+        y = None
+    else:
+        y = ops.bn_apply(h2, m2, i2, P.bn2.weight, P.bn2.bias, relu=False, residual=r, relu_residual=False, out_dtype=out_dtype,
+                         relu_out=relu_out)
     saved = (r, h1, a1, h2, m1, i1, m2, i2, d1, d2, wd1, wd2)
     return y, saved
 
 
-def resblock_bn2(saved):
-    """(h2, mean, invstd) of a ResBlock's closing BatchNorm from its saved forward state, for a producer of the block's incoming
-    gradient that forms that BatchNorm's backward sums itself (ops.vq_losses_indexed(bn=)) and passes them on as bn2_sums= --
-    or None when the block's backward would not take them (it ran the separate operators: their BatchNorm backward is one call)."""
+class ClosingBN(NamedTuple):
+    """A ResBlock's closing BatchNorm and skip connection: y = ((h - mean) * invstd * gamma + beta) + residual."""
+    h: torch.Tensor
+    mean: torch.Tensor
+    invstd: torch.Tensor
+    gamma: torch.Tensor
+    beta: torch.Tensor
+    residual: torch.Tensor
+
+
+def resblock_bn2(saved, P: ResBlockParams):
+    """The closing BatchNorm of a ResBlock from its saved forward state and parameters, for a producer of the block's incoming
+    gradient that forms that BatchNorm's backward sums itself (ops.vq_losses_indexed(bn=)) and passes them on as bn2_sums=, and for
+    consumers of the block's output that form it from these pieces (resblock_forward(defer_bn2=True)) -- or None when the block's
+    backward would not take the sums (it ran the separate operators: their BatchNorm backward is one call)."""
     r, h1, a1, h2, m1, i1, m2, i2 = saved[:8]
-    return (h2, m2, i2) if a1 is None else None
+    return ClosingBN(h2, m2, i2, P.bn2.weight, P.bn2.bias, r) if a1 is None else None
 
 
-def encoder_closing_bn(saved):
+def encoder_closing_bn(saved, P: EncoderParams):
     """resblock_bn2 of the encoder's last ResBlock (the BatchNorm whose output is z_e), from encoder_forward's saved state."""
-    return resblock_bn2(saved[9])
+    return resblock_bn2(saved[9], P.res5)
+
+
+def _into(slot, value):
+    """value, held by slot (a preallocated gradient view): slot itself when value already is that memory, else a copy into it."""
+    if slot is None or (value.data_ptr() == slot.data_ptr() and value.shape == slot.shape):
+        return value
+    slot.copy_(value)
+    return slot
 
 
 def resblock_backward(dy, saved, P: ResBlockParams, need_dx: bool = True, gout=None, bn2_sums=None):
     """Returns (dx, grads) with grads in the order conv1.w, conv1.b, bn1.w, bn1.b, conv2.w, conv2.b, bn2.w, bn2.b.
     gout: optional list of 8 preallocated tensors (e.g. views of a flat gradient bucket) to write into.
-    bn2_sums: (dgamma, dbeta) of the closing BatchNorm when whoever produced dy has formed them already (written into gout[6],
-    gout[7] if gout is given)."""
+    bn2_sums: (dgamma, dbeta) of the closing BatchNorm when whoever produced dy has formed them already; with gout they end up in
+    gout[6], gout[7] (no copy when the producer wrote there, as FusedTrainStep does)."""
     x, h1, a1, h2, m1, i1, m2, i2, d1, d2, wd1, wd2 = saved
     o = gout if gout is not None else [None] * 8
     D = h2.shape[-1]
@@ -213,6 +238,8 @@ def resblock_backward(dy, saved, P: ResBlockParams, need_dx: bool = True, gout=N
     if a1 is None:      # flat-GEMM 1x1: bn2's sums, then its apply + the conv's data gradient in one pass, the weight gradient from h1
         if bn2_sums is not None:
             dg2, db2n = bn2_sums
+            if gout is not None:       # the caller's gradient slots hold them: already (the producer wrote there) or by a copy
+                dg2, db2n = _into(o[6], dg2), _into(o[7], db2n)
         else:
             dg2, db2n = ops.bn_backward_sums(h2, dy, m2, i2, P.bn2.weight, dgamma=o[6], dbeta=o[7])
         if FUSED_1X1_BWD and ops.bn_backward_conv1x1_dgrad_wgrad_supported(h2.dtype, D):     # data + weight gradient in one pass, dh2 never stored
@@ -241,9 +268,11 @@ def resblock_backward(dy, saved, P: ResBlockParams, need_dx: bool = True, gout=N
 # ------------------------------------------------------------------------------------------------
 # Encoder   (src/models.py:164-171)
 # ------------------------------------------------------------------------------------------------
-def encoder_forward(x, P: EncoderParams, training: bool, dtype=torch.float32, packs=None):
+def encoder_forward(x, P: EncoderParams, training: bool, dtype=torch.float32, packs=None, defer_closing_bn=False):
     """x fp32 NHWC (B, H, W, 1) -> z_e fp32 NHWC (B, H/4, W/4, D).  dtype: storage type of the activations in
-    between (fp32 = parity mode, bf16 = throughput mode); the quantiser input z_e is fp32 in both."""
+    between (fp32 = parity mode, bf16 = throughput mode); the quantiser input z_e is fp32 in both.
+    defer_closing_bn: leave the last ResBlock's closing BatchNorm + skip pass to z_e's consumers (resblock_forward(defer_bn2=)):
+    z_e is then None and encoder_closing_bn(saved, P) names its sources; where the block cannot defer, z_e comes back as usual."""
     B, H, W, _ = x.shape
     D = P.conv0.weight.shape[0]
     d0 = ops.conv_desc(B, H, W, 1, D, 4, 2, 1, dtype=dtype)
@@ -268,7 +297,7 @@ def encoder_forward(x, P: EncoderParams, training: bool, dtype=torch.float32, pa
     wf3, wd3 = pk["conv3"] if packs is not None else ops.pack_weights(d3, P.conv3.weight)
     e3 = ops.conv_forward(d3, a0, wf3, P.conv3.bias, flags=NSG_RELU_OUT)     # stored ReLU'd: its only consumer is a ResBlock
     r4, s4 = resblock_forward(e3, P.res4, training, relu_out=True, packs=pk.get("res4"))
-    ze, s5 = resblock_forward(r4, P.res5, training, out_dtype=torch.float32, packs=pk.get("res5"))
+    ze, s5 = resblock_forward(r4, P.res5, training, out_dtype=torch.float32, packs=pk.get("res5"), defer_bn2=defer_closing_bn)
     saved = (x, h0, a0, m0, i0, d0, d3, wd3, s4, s5, mom0)
     return ze, saved
 

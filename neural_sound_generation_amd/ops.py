@@ -8,6 +8,7 @@ from __future__ import annotations
 import ctypes
 import math
 from ctypes import byref, c_float, c_int32, c_int64, c_size_t, c_void_p
+from typing import NamedTuple
 
 import torch
 
@@ -135,6 +136,44 @@ def _gemm_flops(d: "ConvDesc") -> float:
 # ------------------------------------------------------------------------------------------------
 # vector quantiser
 # ------------------------------------------------------------------------------------------------
+class BnResRows(NamedTuple):
+    """(N, D) rows given as their sources: z = bn_apply(h, mean, invstd, gamma, beta, residual=r, out_dtype=float32) WITHOUT
+    that pass -- h, r bf16 (N, D), the four vectors fp32 (D,).  vq_forward (impl="bf16x3"), vq_losses_indexed and
+    index_add_rows (impl="sorted") take one in place of the fp32 rows and return bit for bit what they return on them
+    (include/nsg.h, the *_bnres entry points)."""
+    h: torch.Tensor
+    r: torch.Tensor
+    mean: torch.Tensor
+    invstd: torch.Tensor
+    gamma: torch.Tensor
+    beta: torch.Tensor
+
+    @property
+    def shape(self):
+        return self.h.shape
+
+    @property
+    def device(self):
+        return self.h.device
+
+    def check(self, who):
+        _chk(self.h, who + ": h", torch.bfloat16); _chk(self.r, who + ": r", torch.bfloat16)
+        if self.h.dim() != 2 or self.r.shape != self.h.shape:
+            raise _lib.NsgError(f"{who}: h and r must be (N, D) tensors of one shape")
+        for v, name in ((self.mean, "mean"), (self.invstd, "invstd"), (self.gamma, "gamma"), (self.beta, "beta")):
+            if _chk(v, f"{who}: {name}").numel() != self.h.shape[1]:
+                raise _lib.NsgError(f"{who}: {name} must hold one value per column")
+        return self
+
+    def pointers(self):
+        return tuple(_p(v) for v in self)
+
+
+def bnres_rows_supported(D) -> bool:
+    """Row widths all three consumers of a BnResRows take (the search stops at D = 256; the segment sum wants a power of two)."""
+    return 8 <= D <= 256 and D & (D - 1) == 0
+
+
 def vq_forward(x2d, codebook, want_codes=True, want_dist=False, impl="mfma", codes_bf16=None, clip_rows=None):
     """x2d (N,D), codebook (K,D) -> idx (N,) int64 [, codes (N,D)] [, dmin (N,)]
     impl: "mfma" = the bit-exact fp32 search (parity mode); "valu" = its vector-ALU cross-check; "bf16x3" = the bf16
@@ -142,7 +181,14 @@ def vq_forward(x2d, codebook, want_codes=True, want_dist=False, impl="mfma", cod
     codes_bf16 ("plain" | "relu", bf16x3 only): also return the code rows as a bf16 (N,D) tensor (ReLU'd: the decoder's
     input after its leading ReLU) as a 4th result.  clip_rows (B, D) fp32 (with codes_bf16): a per-clip conditioning row added
     to every bf16 code row of that clip before the ReLU (N = B * rows per clip; the speaker-conditioned decoder)."""
-    _chk(x2d, "x"); _chk(codebook, "codebook")
+    bnres = isinstance(x2d, BnResRows)
+    if bnres:
+        x2d.check("vq_forward")
+        if impl != "bf16x3" or want_codes or want_dist or not bnres_rows_supported(x2d.shape[1]):
+            raise _lib.NsgError("vq_forward: rows given as their sources need impl='bf16x3', no fp32 codes or distances, D a power of two <= 256")
+    else:
+        _chk(x2d, "x")
+    _chk(codebook, "codebook")
     if clip_rows is not None:
         _chk(clip_rows, "clip_rows")
         if impl != "bf16x3" or not codes_bf16 or clip_rows.shape[1] != x2d.shape[1] or x2d.shape[0] % clip_rows.shape[0] != 0:
@@ -152,7 +198,7 @@ def vq_forward(x2d, codebook, want_codes=True, want_dist=False, impl="mfma", cod
     if D != D2:
         raise _lib.NsgError(f"vq_forward: input rows have {D} columns, codebook has {D2}")
     idx = torch.empty(N, dtype=torch.int64, device=x2d.device)
-    codes = torch.empty_like(x2d) if want_codes else None
+    codes = torch.empty_like(x2d) if want_codes else None           # (never with BnResRows)
     dmin = torch.empty(N, dtype=torch.float32, device=x2d.device) if want_dist else None
     if N > 0:
         wsfn = "nsg_vq_bf16x3_workspace_bytes" if impl == "bf16x3" else "nsg_vq_workspace_bytes"
@@ -162,7 +208,11 @@ def vq_forward(x2d, codebook, want_codes=True, want_dist=False, impl="mfma", cod
         if impl == "bf16x3":
             lp = torch.empty(N, D, dtype=torch.bfloat16, device=x2d.device) if codes_bf16 else None
             _lib.tag("vq_forward_bf16x3 (search + gather)", 2.0 * N * K * D)
-            if clip_rows is not None:
+            if bnres:
+                _lib.call("nsg_vq_forward_bf16x3_bnres", *x2d.pointers(), _p(codebook), c_int64(N), c_int32(D), c_int32(K), _p(idx), _p(None),
+                          _p(lp), c_int32(1 if codes_bf16 == "relu" else 0), _p(clip_rows),
+                          c_int64(N // clip_rows.shape[0] if clip_rows is not None else 0), _p(ws), c_size_t(nb), _stream())
+            elif clip_rows is not None:
                 _lib.call("nsg_vq_forward_bf16x3_cond", _p(x2d), _p(codebook), c_int64(N), c_int32(D), c_int32(K), _p(idx), _p(codes), _p(dmin),
                           _p(lp), c_int32(1 if codes_bf16 == "relu" else 0), _p(clip_rows), c_int64(N // clip_rows.shape[0]), _p(ws),
                           c_size_t(nb), _stream())
@@ -200,7 +250,14 @@ def index_add_rows(idx, g2d, K, want_counts=False, impl="f32", out=None, counts=
     moved; the training step's default), "f32" (one-hot GEMM on the fp32 matrix pipe, exact products) or "bf16x2" (one-hot GEMM
     on the bf16 pipe: rows split into bf16 hi + lo, relative error of a sum ~2^-17).
     out (K, D) / counts (K,): optional preallocated fp32 destinations (e.g. views of a communication buffer)."""
-    _chk(idx, "idx", torch.int64); _chk(g2d, "g")
+    _chk(idx, "idx", torch.int64)
+    bnres = isinstance(g2d, BnResRows)
+    if bnres:
+        g2d.check("index_add_rows")
+        if impl != "sorted" or not bnres_rows_supported(g2d.shape[1]) or not index_add_sorted_supported(g2d.shape[0], g2d.shape[1], K):
+            raise _lib.NsgError("index_add_rows: rows given as their sources need impl='sorted' and a shape it takes (D a power of two <= 256)")
+    else:
+        _chk(g2d, "g")
     N, D = g2d.shape
     if out is None:
         out = torch.empty(K, D, dtype=torch.float32, device=g2d.device)
@@ -222,7 +279,11 @@ def index_add_rows(idx, g2d, K, want_counts=False, impl="f32", out=None, counts=
             return (out, counts) if want_counts else out
         nb = _lib.query("nsg_index_add_sorted_workspace_bytes", c_int64(N), c_int32(D), c_int32(K))
         ws = WS.get(nb, g2d.device)
-        _lib.tag("index_add_rows (sorted segment sum)", 0, 4.0 * N * D + 8.0 * N)
+        _lib.tag("index_add_rows (sorted segment sum)", 0, 4.0 * N * D + 8.0 * N)     # (two bf16 sources = the fp32 rows' bytes)
+        if bnres:
+            _lib.call("nsg_index_add_rows_sorted_bnres", _p(idx), *g2d.pointers(), c_int64(N), c_int32(D), c_int32(K), _p(out), _p(counts), _p(ws),
+                      c_size_t(nb), _stream())
+            return (out, counts) if want_counts else out
         _lib.call("nsg_index_add_rows_sorted", _p(idx), _p(g2d), c_int64(N), c_int32(D), c_int32(K), _p(out), _p(counts), _p(ws), c_size_t(nb),
                   _stream())
         return (out, counts) if want_counts else out
@@ -850,9 +911,12 @@ def vq_losses_indexed(z2d, codebook, idx, dz_scale=1.0, dz_add=None, want_dz=Tru
     """vq_losses with q = codebook[idx] read from the codebook itself: returns (loss, dz).  z2d (N, D) fp32.
     bn = (x, mean, invstd): dz is the incoming gradient of a BatchNorm with input x (N, D) of grad_dtype; returns
     (loss, dz, dgamma, dbeta) with that BatchNorm's backward sums (= bn_backward_sums(x, dz, ...)) formed while dz is written."""
-    _chk(z2d, "z"); _chk(codebook, "codebook"); _chk(idx, "idx", torch.int64)
+    _chk(codebook, "codebook"); _chk(idx, "idx", torch.int64)
     if dz_add is not None:
         _chk(dz_add, "dz_add", grad_dtype)
+    if isinstance(z2d, BnResRows):
+        return _vq_losses_indexed_bnres(z2d.check("vq_losses_indexed"), codebook, idx, dz_scale, dz_add, want_dz, grad_dtype, bn, dgamma, dbeta)
+    _chk(z2d, "z")
     N, D = z2d.shape
     loss = torch.empty(1, dtype=torch.float32, device=z2d.device)
     dz = torch.empty(z2d.shape, dtype=grad_dtype, device=z2d.device) if want_dz else None
@@ -876,6 +940,27 @@ def vq_losses_indexed(z2d, codebook, idx, dz_scale=1.0, dz_add=None, want_dz=Tru
     _lib.call("nsg_vq_losses_indexed", _p(z2d), _p(codebook), _p(idx), c_int64(N), c_int32(D), c_int32(codebook.shape[0]), c_float(dz_scale),
               _p(dz_add), _p(loss), _p(dz), c_int32(nsg_dtype(grad_dtype)), _p(ws), c_size_t(nb), _stream())
     return loss, dz
+
+
+def _vq_losses_indexed_bnres(z, codebook, idx, dz_scale, dz_add, want_dz, grad_dtype, bn, dgamma, dbeta):
+    """vq_losses_indexed on rows given as their sources: they ARE the output of the BatchNorm whose backward sums bn= asks for,
+    so bn must be that BatchNorm, (z.h, z.mean, z.invstd); z.h is then read once for both uses.  Returns (loss, dz, dgamma, dbeta)."""
+    N, D = z.shape
+    if bn is None or not want_dz or grad_dtype != torch.bfloat16 or not bnres_rows_supported(D):
+        raise _lib.NsgError("vq_losses_indexed: rows given as their sources need bn=, want_dz, bf16 gradients and D a power of two <= 256")
+    if bn[0].data_ptr() != z.h.data_ptr() or bn[1].data_ptr() != z.mean.data_ptr() or bn[2].data_ptr() != z.invstd.data_ptr():
+        raise _lib.NsgError("vq_losses_indexed: bn= must be the BatchNorm the rows' sources name (h, mean, invstd)")
+    loss = torch.empty(1, dtype=torch.float32, device=z.device)
+    dz = torch.empty(z.shape, dtype=grad_dtype, device=z.device)
+    dgamma = dgamma if dgamma is not None else torch.empty(D, dtype=torch.float32, device=z.device)
+    dbeta = dbeta if dbeta is not None else torch.empty(D, dtype=torch.float32, device=z.device)
+    nb = _lib.query("nsg_vq_losses_indexed_bn_workspace_bytes", c_int64(N), c_int32(D))
+    ws = WS.get(nb, z.device)
+    # h, r and dz_add in, dz out (bf16), the indices; the codebook rows come from cache
+    _lib.tag("vq_losses_indexed", 0, 2.0 * N * D * 2 + 8.0 * N + dz.numel() * _es(dz) * (2 if dz_add is not None else 1))
+    _lib.call("nsg_vq_losses_indexed_bnres", *z.pointers(), _p(codebook), _p(idx), c_int64(N), c_int32(D), c_int32(codebook.shape[0]),
+              c_float(dz_scale), _p(dz_add), _p(loss), _p(dz), _p(dgamma), _p(dbeta), _p(ws), c_size_t(nb), _stream())
+    return loss, dz, dgamma, dbeta
 
 
 def adam_step(p, g, m, v, step, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0):

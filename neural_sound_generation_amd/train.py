@@ -26,6 +26,10 @@ from .optim import FlatAdam
 
 # The bf16 step without an fp32 z_q (see _forward_backward); NSG_LEAN_VQ=0 keeps the materialised form.
 LEAN_VQ = os.environ.get("NSG_LEAN_VQ", "1") == "1"
+# ... and without an fp32 z_e either: the encoder's closing BatchNorm + skip pass is not run, its three consumers (search, loss /
+# encoder gradient, per-code sums) form z_e from its bf16 sources while they load it -- the same bits, 0.84 GB less traffic per
+# step at the bench's shape.  NSG_ZE_FROM_SOURCES=0 keeps the materialised form.
+ZE_FROM_SOURCES = os.environ.get("NSG_ZE_FROM_SOURCES", "1") == "1"
 
 class FusedTrainStep:
     def __init__(self, model, lr: float = 1e-3, beta: float = 1.0, betas=(0.9, 0.999), eps: float = 1e-8,
@@ -93,20 +97,29 @@ class FusedTrainStep:
 
     def _forward_backward(self, x, g, B, H, T):
         enc_packs, dec_packs = engine.pack_all(self.encP, self.decP, B, H, T, self.dtype)
-        ze, es = engine.encoder_forward(x, self.encP, True, dtype=self.dtype, packs=enc_packs)
-        D = ze.shape[-1]
-        K = self.codebook.shape[0]
+        K, D = self.codebook.shape
         search = getattr(self.model.codebook, "search_impl", "mfma")
         # bf16 mode: z_q is never materialised in fp32 -- the search writes the decoder's (ReLU'd, bf16) input itself, with the
         # clip's speaker row added when the decoder is speaker-conditioned; the losses read codebook[idx], the codebook gradient
         # comes from per-code sums of z_e
         lean = LEAN_VQ and search == "bf16x3" and self.dtype == torch.bfloat16 and D % 8 == 0
+        # ... and z_e itself only as its sources, where all of its consumers take them (the encoder may still decline: ze is then a tensor)
+        defer = (lean and ZE_FROM_SOURCES and self.force_indices is None and self.scatter_impl == "sorted" and ops.bnres_rows_supported(D)
+                 and ops.index_add_sorted_supported(x.numel(), D, K) and ops.vq_losses_indexed_bn_supported(D))
+        ze, es = engine.encoder_forward(x, self.encP, True, dtype=self.dtype, packs=enc_packs, defer_closing_bn=defer)
+        if ze is None:
+            bn2 = engine.encoder_closing_bn(es, self.encP)
+            ze_shape = bn2.h.shape
+            ze_rows = ops.BnResRows(bn2.h.view(-1, D), bn2.residual.view(-1, D), bn2.mean, bn2.invstd, bn2.gamma, bn2.beta)
+        else:
+            ze_shape, ze_rows = ze.shape, ze.view(-1, D)
+        ze_numel = ze_rows.shape[0] * D
         spk_rows = None
         if self.spk is not None and g is not None:
             g = g.view(-1).to(torch.int64).contiguous()
             spk_rows = ops.gather_rows(self.spk.weight.detach(), g)          # (B, D) fp32
         if self.force_indices is not None:
-            idx = self.force_indices.view(-1).to(device=ze.device, dtype=torch.int64).contiguous()
+            idx = self.force_indices.view(-1).to(device=ze.device, dtype=torch.int64).contiguous()     # (ze is a tensor here: defer is off)
             if idx.numel() != ze.numel() // D:
                 raise ValueError("force_indices must hold one code index per latent row")
             zq = ops.gather_rows(self.codebook.detach(), idx).view_as(ze)
@@ -115,10 +128,10 @@ class FusedTrainStep:
                 zdec = ops.add_per_clip(zq, spk_rows) if spk_rows is not None else zq
                 zdec, zq = ops.convert(zdec, self.dtype, relu=True), None
         elif lean:
-            idx, _, _, zdec = ops.vq_forward(ze.view(-1, D), self.codebook.detach(), want_codes=False, impl=search, codes_bf16="relu",
+            idx, _, _, zdec = ops.vq_forward(ze_rows, self.codebook.detach(), want_codes=False, impl=search, codes_bf16="relu",
                                              clip_rows=spk_rows)
             zq = None
-            zdec = zdec.view(ze.shape)
+            zdec = zdec.view(ze_shape)
         else:
             idx, zq, _ = ops.vq_forward(ze.view(-1, D), self.codebook.detach(), want_codes=True, impl=search)
             zq = zq.view_as(ze)
@@ -141,27 +154,26 @@ class FusedTrainStep:
             else:
                 self.g_spk.zero_()
         if self.ema:    # per-code counts and sums of the assigned encoder rows straight into the communication buffer's tail
-            ops.index_add_rows(idx, ze.view(-1, D), K, impl=self.scatter_impl, out=self.ema_s, counts=self.ema_n)
+            ops.index_add_rows(idx, ze_rows, K, impl=self.scatter_impl, out=self.ema_s, counts=self.ema_n)
         self._reduce_back_part()        # decoder, speaker table, EMA statistics: final from here on (no-op on one rank / in a graph)
         # loss_vq = mse(z_q, sg(z_e)) -> codebook; loss_commit = mse(z_e, sg(z_q)) -> encoder,
         # plus the straight-through gradient from the decoder               (train.py:131-134)
         bn2_sums = None
         if lean:
             # dz is the incoming gradient of the encoder's closing BatchNorm: its backward sums are formed while dz is written
-            bn2 = engine.encoder_closing_bn(es)
-            if bn2 is not None and bn2[0].dtype == self.dtype and ops.vq_losses_indexed_bn_supported(D):
-                h2, m2, i2 = bn2
-                loss_vq, dz, dg, db = ops.vq_losses_indexed(ze.view(-1, D), self.codebook.detach(), idx, dz_scale=self.beta, dz_add=dzq.view(-1, D),
-                                                            grad_dtype=self.dtype, bn=(h2.view(-1, D), m2, i2), dgamma=self.g_enc[20],
-                                                            dbeta=self.g_enc[21])
+            bn2 = engine.encoder_closing_bn(es, self.encP)
+            if bn2 is not None and bn2.h.dtype == self.dtype and ops.vq_losses_indexed_bn_supported(D):
+                loss_vq, dz, dg, db = ops.vq_losses_indexed(ze_rows, self.codebook.detach(), idx, dz_scale=self.beta, dz_add=dzq.view(-1, D),
+                                                            grad_dtype=self.dtype, bn=(bn2.h.view(-1, D), bn2.mean, bn2.invstd),
+                                                            dgamma=self.g_enc[20], dbeta=self.g_enc[21])
                 bn2_sums = (dg, db)
             else:
-                loss_vq, dz = ops.vq_losses_indexed(ze.view(-1, D), self.codebook.detach(), idx, dz_scale=self.beta, dz_add=dzq.view(-1, D),
+                loss_vq, dz = ops.vq_losses_indexed(ze_rows, self.codebook.detach(), idx, dz_scale=self.beta, dz_add=dzq.view(-1, D),
                                                     grad_dtype=self.dtype)
-            dz = dz.view(ze.shape)
+            dz = dz.view(ze_shape)
             if not self.ema:    # d loss_vq / d e_k = 2/numel * sum over the rows assigned to k of (e_k - z) = 2/numel * (n_k e_k - s_k)
-                s, n = ops.index_add_rows(idx, ze.view(-1, D), K, want_counts=True, impl=self.scatter_impl)
-                ops.codebook_grad_from_sums(self.codebook.detach(), n, s, 2.0 / ze.numel(), out=self.g_code)
+                s, n = ops.index_add_rows(idx, ze_rows, K, want_counts=True, impl=self.scatter_impl)
+                ops.codebook_grad_from_sums(self.codebook.detach(), n, s, 2.0 / ze_numel, out=self.g_code)
         elif self.ema:
             # EMA codebook (extension): no codebook gradient; per-code counts and sums of the assigned
             # encoder rows are the statistics every rank contributes (summed over ranks in step())
