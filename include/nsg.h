@@ -38,7 +38,7 @@ extern "C" {
 #define NSG_API
 #endif
 
-#define NSG_VERSION 102 /* bumped on ANY change of an existing entry point's signature; _lib.py refuses a library of another version */
+#define NSG_VERSION 103 /* bumped on ANY change of an existing entry point's signature; _lib.py refuses a library of another version */
 
 enum {
     NSG_OK = 0,
@@ -191,6 +191,38 @@ NSG_API int nsg_codebook_grad_from_sums(const float *e, const float *n, const fl
  * scratch: one device float (holds sum(ema_n) between the two kernels). */
 NSG_API int nsg_vq_ema_update(float *e, float *ema_n, float *ema_s, const float *n, const float *s, int32_t K,
                               int32_t D, float decay, float eps, float *scratch, void *stream);
+
+/* Codebook usage statistics and dead-code revival (extension, not in the reference: its plain nearest-neighbour codebook at the
+ * U(-1/K, 1/K) initialisation keeps a handful of live codes).  Integer atomics only: every result is independent of arrival order.
+ *
+ * nsg_code_usage: batch_counts[k] (int32 [K], overwritten) = number of rows with idx == k, rows whose index lies outside [0, K)
+ * ignored (as nsg_index_add_rows_sorted ignores them); window[k] (int32 [K]) += batch_counts[k]; stats (two doubles):
+ *   stats[0] = the batch's perplexity exp(-sum_k p_k ln p_k), p_k = batch_counts[k] / sum(batch_counts), accumulated in fp64 in a
+ *              fixed order (0 when no index lies in range);   stats[1] = the number of codes with batch_counts > 0.
+ * 1 <= N < 2^31, K >= 1 (K <= 8192: per-block LDS bins, one global atomic per block and non-zero bin; larger K: global atomics).
+ * No workspace: batch_counts is cleared by an asynchronous memset on the stream. */
+NSG_API int nsg_code_usage(const int64_t *idx, int64_t N, int32_t K, int32_t *batch_counts, int32_t *window, double *stats, void *stream);
+
+/* Re-seed the dead codes from rows of the current encoder output z [N][D] (fp32 rows, or their sources: the _bnres form, see
+ * nsg_vq_forward_bf16x3_bnres; each row is formed exactly as nsg_bn_apply(..., residual = r) forms it for an fp32 output).
+ *   - code k is DEAD when window[k] < min_count, or when revive_all != 0;  j(k) = the number of dead codes with an index below k;
+ *   - slot[k] (int32 [K], out) = j(k) for a dead code, -1 for a live one;
+ *   - a dead code takes codebook[k][:] = z[(base_row + j(k) * stride) mod N][:], a bit-for-bit copy (64-bit index arithmetic);
+ *     where given (pairs, each nullable): adam_m[k][:] = adam_v[k][:] = 0 (the optimiser's moments of that row, [K][D]);
+ *     ema_count[k] = 1 and ema_sum[k][:] = the same row (the EMA codebook's statistics);
+ *   - live rows of every array are not written at all;   afterwards window is all zero;
+ *   - stats (two int64): stats[0] = the number of revived codes, stats[1] += it (a running total the caller zeroes once).
+ * The rows chosen for different dead codes are pairwise distinct while stride is coprime to N (the caller's duty) and there are
+ * at most N dead codes; beyond that rows repeat.
+ * NSG_E_INVALID: a null required pointer, N < 1 or >= 2^31, K < 1, stride < 1 or >= 2^31, base_row outside [0, N), half a pair;
+ * NSG_E_UNSUPPORTED: D % 4 != 0 (the _bnres form: D not a power of two in 8 ... 256), tensors not 16-byte aligned. */
+NSG_API int nsg_vq_revive(const float *z, int64_t N, int32_t D, float *codebook, int32_t K, int32_t *window, int32_t min_count,
+                          int64_t base_row, int64_t stride, float *adam_m, float *adam_v, float *ema_count, float *ema_sum,
+                          int32_t *slot, int64_t *stats, int32_t revive_all, void *stream);
+NSG_API int nsg_vq_revive_bnres(const void *h, const void *r, const float *mean, const float *invstd, const float *gamma,
+                                const float *beta, int64_t N, int32_t D, float *codebook, int32_t K, int32_t *window,
+                                int32_t min_count, int64_t base_row, int64_t stride, float *adam_m, float *adam_v, float *ema_count,
+                                float *ema_sum, int32_t *slot, int64_t *stats, int32_t revive_all, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Convolutions                                            src/models.py:150,153,165,168,179,182

@@ -18,7 +18,7 @@ NSG_OUT_F32 = 8
 NSG_RELU_OUT = 16
 NSG_F32 = 0
 NSG_BF16 = 1
-NSG_VERSION = 102      # include/nsg.h NSG_VERSION this binding was written against (bumped on ANY signature change)
+NSG_VERSION = 103      # include/nsg.h NSG_VERSION this binding was written against (bumped on ANY signature change)
 
 
 class ConvDesc(Structure):
@@ -54,6 +54,10 @@ _SIGS = {
     "nsg_index_add_rows_sorted_bnres": (None, [_P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, _P, _P, _P, c_size_t, _P]),
     "nsg_gather_rows": (None, [_P, _P, c_int64, c_int32, c_int32, _P, _P]),
     "nsg_vq_ema_update": (None, [_P, _P, _P, _P, _P, c_int32, c_int32, c_float, c_float, _P, _P]),
+    "nsg_code_usage": (None, [_P, c_int64, c_int32, _P, _P, _P, _P]),
+    "nsg_vq_revive": (None, [_P, c_int64, c_int32, _P, c_int32, _P, c_int32, c_int64, c_int64, _P, _P, _P, _P, _P, _P, c_int32, _P]),
+    "nsg_vq_revive_bnres": (None, [_P, _P, _P, _P, _P, _P, c_int64, c_int32, _P, c_int32, _P, c_int32, c_int64, c_int64, _P, _P, _P, _P, _P, _P,
+                                   c_int32, _P]),
     "nsg_codebook_grad_from_sums": (None, [_P, _P, _P, c_int32, c_int32, c_float, _P, _P]),
     "nsg_increment_counters": (None, [_P, c_int32, _P]),
     "nsg_packed_weight_floats": (c_size_t, [_D]),

@@ -20,6 +20,7 @@ checkpoint layout, restated from the reference's src/test.py:73-106 and src/main
     encode, keep the leading latent columns, sample the rest (GatedPixelCNN.continue_codes), decode.
   * `continue_audio(vqvae, prior, wav, label, keep_frames, frames)` -- wav in, wav out: audio.melspectrogram, continue_mels,
     audio.inv_mel_spectrogram.
+  * `codebook_usage(model, loader, device)` -- how much of the codebook a dataset uses: per-code counts and their perplexity.
 """
 from __future__ import annotations
 
@@ -69,6 +70,33 @@ def test_vqvae(args, model, test_loader, device, epoch):
     loss_recons, loss_vq = float(loss_recons / n), float(loss_vq / n)
     print('====> Test set loss: {:.4f}'.format(loss_recons + loss_vq))
     return loss_recons, loss_vq
+
+
+@torch.no_grad()
+def codebook_usage(model, loader, device):
+    """Per-code usage of `model`'s codebook over a dataset: `loader` yields (x, y, c, g, input_lengths) with c (B, 80, T) mels, as
+    for test_vqvae.  Returns (counts (K,) int64 on `device`: latent positions assigned to each code; perplexity: exp of the
+    entropy of counts / counts.sum(), a float).  Built from model.encode (eval mode; the model's mode is restored) and
+    ops.code_usage, whose int32 window is folded into the int64 counts after every batch."""
+    K = model.codebook.embedding.weight.shape[0]
+    counts = torch.zeros(K, dtype=torch.int64, device=device)
+    window = torch.zeros(K, dtype=torch.int32, device=device)
+    was_training = model.training
+    model.eval()
+    try:
+        for x, y, c, g, input_lengths in loader:
+            idx = model.encode(c.to(device).unsqueeze(1))
+            ops.code_usage(idx.reshape(-1).contiguous(), K, window)
+            counts += window
+            window.zero_()
+    finally:
+        model.train(was_training)
+    total = counts.sum()
+    if int(total) == 0:
+        raise ValueError("codebook_usage: empty loader")
+    p = counts.double() / total
+    nz = p > 0
+    return counts, float(torch.exp(-(p[nz] * p[nz].log()).sum()))
 
 
 __test__ = False  # (not a pytest module even though a function is named test_*)

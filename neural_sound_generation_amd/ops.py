@@ -306,6 +306,67 @@ def codebook_grad_from_sums(codebook, n, s, scale, out):
     return out
 
 
+def code_usage(idx, K, window, stats=None, batch_counts=None):
+    """Histogram of a batch's code indices (any shape, int64; indices outside [0, K) are ignored) -> (batch_counts (K,) int32,
+    stats (2,) float64 = [the batch's perplexity, the number of codes in the batch]); window (K,) int32 += batch_counts.
+    Nothing synchronises: the two tensors are device results."""
+    _chk(idx, "idx", torch.int64); _chk(window, "window", torch.int32)
+    K = int(K)
+    if window.shape != (K,):
+        raise _lib.NsgError(f"code_usage: window has shape {tuple(window.shape)}, expected {(K,)}")
+    if batch_counts is None:
+        batch_counts = torch.empty(K, dtype=torch.int32, device=idx.device)
+    elif _chk(batch_counts, "batch_counts", torch.int32).shape != (K,):
+        raise _lib.NsgError(f"code_usage: batch_counts has shape {tuple(batch_counts.shape)}, expected {(K,)}")
+    if stats is None:
+        stats = torch.empty(2, dtype=torch.float64, device=idx.device)
+    elif _chk(stats, "stats", torch.float64).numel() != 2:
+        raise _lib.NsgError("code_usage: stats must hold two float64 values")
+    _lib.tag("code_usage (histogram + perplexity)", 0, 8.0 * idx.numel())
+    _lib.call("nsg_code_usage", _p(idx), c_int64(idx.numel()), c_int32(K), _p(batch_counts), _p(window), _p(stats), _stream())
+    return batch_counts, stats
+
+
+def vq_revive(rows, codebook, window, min_count=1, base_row=0, stride=1, adam_m=None, adam_v=None, ema_count=None, ema_sum=None,
+              slot=None, stats=None, revive_all=False):
+    """Re-seed the dead codes of `codebook` (K, D) from `rows`, the current encoder output: (N, D) fp32 rows or a BnResRows.
+    Code k is dead when window[k] < min_count (or revive_all); the j-th dead code, in index order, takes row
+    (base_row + j * stride) mod N bit for bit; adam_m / adam_v (K, D) rows of dead codes are zeroed, ema_count (K,) / ema_sum
+    (K, D) set to 1 / the row; live rows are not written; window is cleared (include/nsg.h, nsg_vq_revive).
+    Returns (slot (K,) int32: j for a dead code, -1 for a live one; stats (2,) int64: [revived now, running total])."""
+    bnres = isinstance(rows, BnResRows)
+    if bnres:
+        rows.check("vq_revive")
+    else:
+        _chk(rows, "rows")
+        if rows.dim() != 2:
+            raise _lib.NsgError("vq_revive: rows must be an (N, D) tensor")
+    _chk(codebook, "codebook"); _chk(window, "window", torch.int32)
+    N, D = rows.shape
+    K = codebook.shape[0]
+    if codebook.dim() != 2 or codebook.shape[1] != D or window.shape != (K,):
+        raise _lib.NsgError(f"vq_revive: rows have {D} columns; codebook {tuple(codebook.shape)} and window {tuple(window.shape)} must be (K, {D}) and (K,)")
+    for t, name, shape in ((adam_m, "adam_m", (K, D)), (adam_v, "adam_v", (K, D)), (ema_sum, "ema_sum", (K, D)), (ema_count, "ema_count", (K,))):
+        if t is not None and _chk(t, "vq_revive: " + name).shape != shape:
+            raise _lib.NsgError(f"vq_revive: {name} has shape {tuple(t.shape)}, expected {shape}")
+    if slot is None:
+        slot = torch.empty(K, dtype=torch.int32, device=codebook.device)
+    elif _chk(slot, "slot", torch.int32).shape != (K,):
+        raise _lib.NsgError(f"vq_revive: slot has shape {tuple(slot.shape)}, expected {(K,)}")
+    if stats is None:
+        stats = torch.zeros(2, dtype=torch.int64, device=codebook.device)
+    elif _chk(stats, "stats", torch.int64).numel() != 2:
+        raise _lib.NsgError("vq_revive: stats must hold two int64 values")
+    tail = (c_int64(N), c_int32(D), _p(codebook), c_int32(K), _p(window), c_int32(int(min_count)), c_int64(int(base_row)), c_int64(int(stride)),
+            _p(adam_m), _p(adam_v), _p(ema_count), _p(ema_sum), _p(slot), _p(stats), c_int32(1 if revive_all else 0), _stream())
+    _lib.tag("vq_revive (dead-code re-seed)", 0, 8.0 * K * D)
+    if bnres:
+        _lib.call("nsg_vq_revive_bnres", *rows.pointers(), *tail)
+    else:
+        _lib.call("nsg_vq_revive", _p(rows), *tail)
+    return slot, stats
+
+
 def increment_counters(counters):
     """counters: int64 GPU scalars (BatchNorm2d.num_batches_tracked), each += 1, one launch."""
     n = len(counters)

@@ -33,7 +33,12 @@ ZE_FROM_SOURCES = os.environ.get("NSG_ZE_FROM_SOURCES", "1") == "1"
 
 class FusedTrainStep:
     def __init__(self, model, lr: float = 1e-3, beta: float = 1.0, betas=(0.9, 0.999), eps: float = 1e-8,
-                 process_group=None, optimizer: FlatAdam | None = None):
+                 process_group=None, optimizer: FlatAdam | None = None, revive_every: int = 0, revive_min_count: int = 1,
+                 revive_seed: int = 0, codebook_init: str | None = None):
+        """revive_every = R > 0 (extension, off by default): every step ends with the codebook usage kernel on its indices, every
+        R-th step re-seeds the codes used fewer than revive_min_count times since the last revival from that step's z_e
+        (codebook.CodebookReviver; revive_seed seeds its row choice).  codebook_init = "data": the first step ends by
+        initialising the whole codebook from its z_e.  With both off the step launches and holds nothing new."""
         self.model = model
         self.beta = float(beta)
         self.group = process_group
@@ -81,6 +86,16 @@ class FusedTrainStep:
         # test hook: (N,) int64 code indices to use INSTEAD of the search's (the search still runs and is ignored).  Lets a test
         # compare this mode's backward with another evaluation's on the SAME codes (tests/test_gpu_model.py, bf16 fidelity).
         self.force_indices = None
+        self.reviver = None
+        if revive_every or codebook_init is not None:
+            from .codebook import CodebookReviver
+            self.reviver = CodebookReviver(model.codebook, every=revive_every, min_count=revive_min_count, seed=revive_seed,
+                                           init=codebook_init, process_group=process_group)
+        # z_e of the step in flight (rows, or their sources with the BatchNorm's gamma / beta as they were BEFORE the optimiser
+        # step): kept only on a step that ends with a revival -- the host knows before the forward pass -- and in a captured
+        # graph, whose replays cannot choose (the graph keeps them alive with its other buffers)
+        self._keep_rows = False
+        self._kept_rows = None
 
     @torch.no_grad()
     def forward_backward(self, c: torch.Tensor, g: torch.Tensor | None = None):
@@ -114,6 +129,8 @@ class FusedTrainStep:
         else:
             ze_shape, ze_rows = ze.shape, ze.view(-1, D)
         ze_numel = ze_rows.shape[0] * D
+        if self._keep_rows:
+            self._kept_rows = ze_rows._replace(gamma=ze_rows.gamma.clone(), beta=ze_rows.beta.clone()) if ze is None else ze_rows
         spk_rows = None
         if self.spk is not None and g is not None:
             g = g.view(-1).to(torch.int64).contiguous()
@@ -223,9 +240,14 @@ class FusedTrainStep:
         torch.cuda.current_stream(c.device).wait_stream(self._graph_stream)
         torch.cuda.synchronize()
         self._graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self._graph, stream=self._graph_stream):
-            self._graph_losses = self.forward_backward(self._static_c, self._static_g)
-            ws_after = ops.WS.current(c.device)
+        self._keep_rows = self.reviver is not None
+        try:
+            with torch.cuda.graph(self._graph, stream=self._graph_stream):
+                self._graph_losses = self.forward_backward(self._static_c, self._static_g)
+                ws_after = ops.WS.current(c.device)
+        finally:
+            self._keep_rows = False
+        self._graph_rows, self._kept_rows = self._kept_rows, None     # every replay refills them
         if ws is None or ws_after is not ws:
             self._graph = None
             raise RuntimeError("FusedTrainStep.capture: the workspace grew during capture (warm-up steps must see the captured shapes)")
@@ -241,14 +263,17 @@ class FusedTrainStep:
 
     @torch.no_grad()
     def step(self, c: torch.Tensor, g: torch.Tensor | None = None):
+        revive = self.reviver is not None and self.reviver.next_step_revives()
         if getattr(self, "_graph", None) is not None and c.shape == self._static_c.shape and (g is None) == (self._static_g is None):
             losses = self._replay(c, g)
+            rows = self._graph_rows if revive else None
         else:
-            self._stepping = True
+            self._stepping, self._keep_rows = True, revive
             try:
                 losses = self.forward_backward(c, g)
             finally:
-                self._stepping = False
+                self._stepping = self._keep_rows = False
+            rows, self._kept_rows = self._kept_rows, None
         if self.world > 1:
             # the gradient bucket and behind it (EMA mode) the per-code counts and sums: the back part is already in flight
             # (_reduce_back_part), the front part (encoder, codebook) goes now; a replayed graph holds no collective: one for all
@@ -256,7 +281,17 @@ class FusedTrainStep:
         self.opt.step(grad_scale=1.0 / self.world)
         if self.ema:
             self.apply_ema()
+        if self.reviver is not None:
+            # outside the captured graph, like Adam and the collectives; data parallel: the gradients' all-reduce is joined above
+            self.reviver.end_step(self.last_indices, rows, self.opt)
         return losses
+
+    def codebook_stats(self) -> dict:
+        """CodebookReviver.stats() of this step's reviver: perplexity and codes in use of the last batch, codes revived by the last
+        revival and in total.  Synchronises with the device."""
+        if self.reviver is None:
+            raise RuntimeError("FusedTrainStep.codebook_stats: built without revive_every / codebook_init")
+        return self.reviver.stats()
 
     @torch.no_grad()
     def apply_ema(self, n: torch.Tensor | None = None, s: torch.Tensor | None = None):
