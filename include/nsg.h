@@ -678,12 +678,14 @@ NSG_API int nsg_audio_mel_to_linear(const float *mel, const float *inv_basis, fl
                                     void *stream);
 
 /* Griffin-Lim (audio_tacotron.py:142-153): y [B][hop*(T-1)] from magnitudes S [B][T][F]; u [B][T][F] are the uniform
- * [0,1) numbers behind the random initial phases exp(2 pi i u).  n_fft in {512, 1024, 2048}, hop divides n_fft. */
+ * [0,1) numbers behind the random initial phases exp(2 pi i u).  n_fft in {512, 1024, 2048}, hop divides n_fft, T >= 2 and
+ * hop*(T-1) >= 2: every such grid is reflect-padded as np.pad(mode="reflect") does, however short it is against n_fft/2. */
 NSG_API size_t nsg_audio_griffin_lim_workspace_bytes(int32_t B, int32_t T, int32_t n_fft);
 NSG_API int nsg_audio_griffin_lim(const float *S, const float *u, float *y, int32_t B, int32_t T, int32_t n_fft, int32_t hop,
                                   int32_t iters, void *workspace, size_t workspace_bytes, void *stream);
 
-/* X [B][1 + L/hop][F] complex (interleaved re, im) = librosa.stft(y[b], n_fft, hop): centred, reflect-padded, periodic Hann. */
+/* X [B][1 + L/hop][F] complex (interleaved re, im) = librosa.stft(y[b], n_fft, hop): centred, reflect-padded, periodic Hann.
+ * n_fft in {512, 1024, 2048}, L > n_fft/2 (as librosa requires), any hop > 0, B * (1 + L/hop) < 2^31. */
 NSG_API int nsg_audio_stft(const float *y, float *X, int32_t B, int32_t L, int32_t n_fft, int32_t hop, void *stream);
 
 /* y[n] = x[n] + k * y[n-1] per clip (scipy.signal.lfilter([1], [1, -k], x); audio_tacotron.py:28-31), out of place,

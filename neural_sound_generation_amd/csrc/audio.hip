@@ -47,6 +47,13 @@ __device__ v2f *fft_lds(v2f *buf0, v2f *buf1, const v2f *tw, int tid, bool inver
     return in;
 }
 
+// Periodic Hann window 0.5 - 0.5 cos(2 pi n / N) as sin^2(pi n / N): no cancellation at the window's ends, where the cosine form
+// is wrong by eps / w (8e-4 of w at n = 1, N = 512).  Griffin-Lim needs the accurate form: overlap-add divides by the sum of
+// w^2, and with hop == N that sum is one term, so the quotient w / w^2 carries the window's relative error into y, and the
+// next STFT multiplies those same samples (y = frame / w there) by w again.  (melspectrogram_kernel keeps the cosine form:
+// it only multiplies by w, where the error is 3e-8 of the window's peak, and its outputs are pinned bit for bit.)
+__device__ __forceinline__ float hann_sin2(int n, int N) { const float s = sinpif((float)n / (float)N); return s * s; }
+
 template <int LOG2N>
 __device__ __forceinline__ void fill_twiddles(v2f *tw, int tid)
 {
@@ -106,10 +113,7 @@ __global__ __launch_bounds__(256) void istft_frames_kernel(const v2f *__restrict
     }
     v2f *r = fft_lds<LOG2N>(b0, b1, tw, tid, true);
     float *dst = frames + fr * N;
-    for (int n = tid; n < N; n += 256) {
-        const float w = 0.5f - 0.5f * cospif(2.0f * (float)n / (float)N);
-        dst[n] = r[n].x * (1.0f / (float)N) * w;
-    }
+    for (int n = tid; n < N; n += 256) dst[n] = r[n].x * (1.0f / (float)N) * hann_sin2(n, N);
 }
 
 // y[b][i] = (sum over frames covering sample i + N/2 of frames[b][t][i + N/2 - t hop]) / (sum of hann^2 over the same frames)
@@ -126,7 +130,7 @@ __global__ __launch_bounds__(256) void overlap_add_kernel(const float *__restric
         float acc = 0.f, wss = 0.f;
         for (int t = t0; t <= t1; ++t) {
             const int k = n - t * hop;
-            const float w = 0.5f - 0.5f * cospif(2.0f * (float)k / (float)N);
+            const float w = hann_sin2(k, N);
             acc += frames[((size_t)b * T + t) * N + k];
             wss += w * w;
         }
@@ -135,6 +139,8 @@ __global__ __launch_bounds__(256) void overlap_add_kernel(const float *__restric
 }
 
 // one frame per workgroup: X = rfft(hann * reflect-padded frame of y);  spec[b][t][f] = S[b][t][f] * X[f] / |X[f]|
+// The padded index is numpy's reflect map for every L >= 2, however short the signal is against N/2 (Griffin-Lim's grid is
+// hop (T - 1) samples, a quarter of N/2 at T = 2 and hop = N/8).  L = 1 has no reflection (period 0): both launchers refuse it.
 template <int LOG2N>
 __global__ __launch_bounds__(256) void stft_phase_kernel(const float *__restrict__ y, const float *__restrict__ S, v2f *__restrict__ spec,
                                                          int T, int hop, int L, int F, int want_raw)
@@ -146,13 +152,12 @@ __global__ __launch_bounds__(256) void stft_phase_kernel(const float *__restrict
     const int b = (int)(fr / T), t = (int)(fr - (size_t)b * T);
     fill_twiddles<LOG2N>(tw, tid);
     const float *yb = y + (size_t)b * L;
+    const int period = 2 * (L - 1);
     for (int n = tid; n < N; n += 256) {
-        int idx = t * hop + n - N / 2;
-        if (idx < 0) idx = -idx;                              // np.pad(mode="reflect")
-        if (idx >= L) idx = 2 * (L - 1) - idx;
-        idx = idx < 0 ? 0 : (idx >= L ? L - 1 : idx);         // (signals shorter than N/2: clamp)
-        const float w = 0.5f - 0.5f * cospif(2.0f * (float)n / (float)N);
-        b0[n] = v2f{yb[idx] * w, 0.f};
+        int idx = (t * hop + n - N / 2) % period;             // np.pad(mode="reflect"): the reflection has period 2 (L - 1) and
+        if (idx < 0) idx += period;                           // folds as often as the padding needs (a grid shorter than N/2
+        if (idx >= L) idx = period - idx;                     // folds more than once); the launchers guarantee L >= 2
+        b0[n] = v2f{yb[idx] * hann_sin2(n, N), 0.f};
     }
     v2f *r = fft_lds<LOG2N>(b0, b1, tw, tid, false);
     for (int f = tid; f < F; f += 256) {
@@ -228,6 +233,9 @@ __global__ __launch_bounds__(256) void melspectrogram_kernel(const float *__rest
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             if (q == 1 && !two) break;
+            // Precondition len > N/2 (checked by the launcher for L and by the caller for lengths[]): the padding is N/2 on each
+            // side, so one fold is the exact reflect map and the clamp below is never taken.  Shorter clips would need the
+            // periodic map of stft_phase_kernel.
             int idx = (t0 + q) * hop + n - N / 2;
             if (idx < 0) idx = -idx;                          // np.pad(mode="reflect") of the pre-emphasised clip
             if (idx >= len) idx = 2 * (len - 1) - idx;
@@ -298,6 +306,8 @@ int nsg_audio_griffin_lim(const float *S, const float *u, float *y, int32_t B, i
     const int lg = log2_of(n_fft);
     NSG_REQUIRE(lg >= 9 && lg <= 11, NSG_E_UNSUPPORTED, "nsg_audio_griffin_lim: n_fft must be 512, 1024 or 2048");
     NSG_REQUIRE(n_fft % hop == 0, NSG_E_UNSUPPORTED, "nsg_audio_griffin_lim: hop must divide n_fft");
+    NSG_REQUIRE((int64_t)hop * (T - 1) < 0x7fffffff, NSG_E_UNSUPPORTED, "nsg_audio_griffin_lim: too many samples (hop * (T - 1) >= 2^31)");
+    NSG_REQUIRE((int64_t)hop * (T - 1) >= 2, NSG_E_UNSUPPORTED, "nsg_audio_griffin_lim: hop * (T - 1) must be at least 2 samples (a one-sample grid has no reflect padding)");
     NSG_REQUIRE(workspace && workspace_bytes >= nsg_audio_griffin_lim_workspace_bytes(B, T, n_fft), NSG_E_WORKSPACE, "nsg_audio_griffin_lim: workspace too small");
     NSG_REQUIRE((int64_t)B * T < 0x7fffffff, NSG_E_UNSUPPORTED, "nsg_audio_griffin_lim: too many frames");
     hipStream_t s = (hipStream_t)stream;
@@ -333,6 +343,7 @@ int nsg_audio_stft(const float *y, float *X, int32_t B, int32_t L, int32_t n_fft
     NSG_REQUIRE(L > n_fft / 2, NSG_E_UNSUPPORTED, "nsg_audio_stft: reflect padding needs more than n_fft/2 samples");
     const int T = 1 + L / hop, F = n_fft / 2 + 1;
     hipStream_t s = (hipStream_t)stream;
+    NSG_REQUIRE((int64_t)B * T < 0x7fffffff, NSG_E_UNSUPPORTED, "nsg_audio_stft: too many frames (B * T >= 2^31)");
     const unsigned nfr = (unsigned)(B * T);
     v2f *spec = reinterpret_cast<v2f *>(X);
     if (lg == 9)       hipLaunchKernelGGL((stft_phase_kernel<9>), dim3(nfr), dim3(256), 0, s, y, nullptr, spec, T, hop, L, F, 1);
