@@ -719,6 +719,46 @@ NSG_API int nsg_audio_melspectrogram(const float *wav, const int32_t *lengths, c
                                      float preemphasis, float min_level_db, float ref_level_db, float max_abs_value,
                                      int32_t frame_major, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Before the front end: resampling and silence trimming   src/audio_tacotron.py:12-13 (librosa.core.load(path, sr=...)),
+ * src/cmu_arctic.py:72 (librosa.effects.trim(wav, top_db=20)).  parity unpinned: librosa and resampy are absent.
+ * ------------------------------------------------------------------------------------------- */
+
+/* Band-limited resampling by the rational factor up / down = P / Q (in lowest terms), per clip b of len_b = lengths[b]
+ * samples (lengths NULL: all L_in):
+ *     y[m] = sum_n x[n] * s h(s (m Q - n P) / P),   s = min(1, P / Q),  x zero outside [0, len_b)
+ *     h(u) = rolloff sinc(rolloff u) I0(beta sqrt(1 - (u / Z)^2)) / I0(beta)  for |u| < Z, else 0;  sinc(v) = sin(pi v) / (pi v)
+ * a Kaiser-windowed sinc with Z zero crossings a side, evaluated per polyphase phase phi = (m Q) mod P exactly -- no
+ * interpolation in a filter table.  The caller supplies the coefficients, W = half_width = ceil(Z / s), 2 W taps a phase:
+ *     c[phi][j] = s h(s (phi / P + W - 1 - j))   multiplies   x[floor(m Q / P) - W + 1 + j],   j = 0 .. 2 W - 1
+ * stored tap-major with the phases in the order consecutive outputs meet them:  table[j][k] = c[(k Q) mod P][j], k = m mod P,
+ * [2 W][P] floats on the device (consecutive lanes read consecutive floats).  An output is one fp32 fmaf chain over j
+ * increasing, from 0: a clip's samples depend on its own samples and length alone, never on B, L_in, its row or the tiling
+ * (bit for bit).  wav [B][L_in] zero-padded; out [B][L_out], L_out = ceil(L_in P / Q); clip b has ceil(len_b P / Q) samples
+ * (its last one included: librosa would zero-pad it when floor != ceil), the rest of its row is written as zeros.
+ * Index arithmetic in 64 bits.  NSG_E_INVALID: a null pointer, a non-positive size, up / down not in lowest terms;
+ * NSG_E_UNSUPPORTED: P * 2 W > 2^20 floats, L_out >= 2^31, B * ceil(L_out / 256) >= 2^31, or a tile's input span
+ * (255 Q / P + 2 W + 1 floats) above 64 KiB of LDS.  lengths[b] is clamped into [0, L_in], so no read leaves wav. */
+NSG_API int nsg_audio_resample(const float *wav, const int32_t *lengths, const float *table, float *out, int32_t B, int32_t L_in,
+                               int32_t up, int32_t down, int32_t half_width, void *stream);
+
+/* librosa.effects.trim(y, top_db, ref=np.max, frame_length, hop_length) restated, per clip b of len_b = lengths[b] samples
+ * (lengths NULL: all L):
+ *     p      = reflect_pad(y[0:len_b], frame_length / 2),   T_b = 1 + len_b / hop
+ *     mse[t] = mean(p[t hop : t hop + frame_length]^2),   ref = max_t mse[t]
+ *     frame t is non-silent iff 10 log10(max(1e-10, mse[t])) - 10 log10(max(1e-10, ref)) > -top_db
+ *     bounds[b] = (first hop, min(len_b, (last + 1) hop)) over the non-silent frames, (0, 0) if there is none
+ * A frame's energy is summed in a fixed order of its own samples (64 strided partial sums, then a fixed butterfly); the
+ * per-clip maximum and the first / last search are exact, so a clip's bounds do not depend on the batch.  wav [B][L]
+ * zero-padded; bounds [B][2] int32; workspace: nsg_audio_trim_workspace_bytes(B, L, hop) bytes (the frame energies).
+ * NSG_E_INVALID: a null pointer, a non-positive size, top_db not > 0; NSG_E_UNSUPPORTED: frame_length odd or outside
+ * [2, 8192], L <= frame_length / 2, too many frames.  PRECONDITION the entry point cannot check (lengths is device memory):
+ * frame_length / 2 < lengths[b] <= L; the caller checks it on its host copy (the kernels clamp into [1, L]). */
+NSG_API size_t nsg_audio_trim_workspace_bytes(int32_t B, int32_t L, int32_t hop);
+NSG_API int nsg_audio_trim_bounds(const float *wav, const int32_t *lengths, int32_t *bounds, int32_t B, int32_t L,
+                                  int32_t frame_length, int32_t hop, float top_db, void *workspace, size_t workspace_bytes,
+                                  void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -137,6 +137,9 @@ _SIGS = {
     "nsg_audio_preemphasis": (None, [_P, _P, c_int32, c_int32, c_float, _P]),
     "nsg_audio_melspectrogram": (None, [_P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_float, c_float,
                                         c_int32, _P]),
+    "nsg_audio_resample": (None, [_P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, _P]),
+    "nsg_audio_trim_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
+    "nsg_audio_trim_bounds": (None, [_P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_float, _P, c_size_t, _P]),
     "nsg_debug_dot": (None, [_P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P]),
 }
 # entry points declared in include/nsg.h: exactly the product library's exports (tests/test_abi.py checks both directions)

@@ -14,8 +14,17 @@ The opposite direction, wav -> mel, is the reference's preprocessing (audio_taco
     melspectrogram(wav, sample_rate, fft_size, hop_size, n_mels) -> (n_mels, T) normalised to [0, 1]  (same signature)
 
 one kernel from samples to the normalised mel (pre-emphasis at the reflect-mapped index, Hann, FFT, |X| in LDS, the
-filterbank as a band matrix, dB, normalise, clip; ragged batches, two layouts).  load_wav reads PCM files with scipy; it
-does not resample (the reference does, through librosa).
+filterbank as a band matrix, dB, normalise, clip; ragged batches, two layouts).
+
+What the reference's multi-speaker preprocessing does to a recording before that (cmu_arctic.py:59-72):
+
+    resample(wav, orig_sr, target_sr)    librosa.core.load(path, sr=22050)'s resampling (audio_tacotron.py:12-13)
+    trim_silence(wav, top_db=20)         librosa.effects.trim(wav, top_db=20) -> (trimmed, (start, end))
+
+resample is a band-limited Kaiser-windowed sinc interpolator in resampy's kaiser_best style, evaluated exactly per polyphase
+phase from a table built in fp64 on the host (csrc/resample.hip; it makes no claim to reproduce resampy's table
+interpolation); trim_silence restates librosa's frame energies and threshold.  read_wav reads PCM files with scipy at their
+own rate; load_wav refuses a file at another rate unless resample=True, which sends it through the kernel.
 
 parity unpinned: librosa is absent (here, on the GPU box, and from the reference's own tree), and no file of the reference
 holds a waveform; tests compare with the numpy restatement in oracle/audio_oracle.py (same initial phases) and check the
@@ -24,6 +33,7 @@ transform identities (istft(stft(y)) == y, the spectral error falls over the ite
 from __future__ import annotations
 
 import functools
+import math
 from ctypes import c_float, c_int32, c_size_t, c_void_p
 
 import numpy as np
@@ -214,22 +224,172 @@ def save_wav(wav, path, sample_rate=22050):
     wavfile.write(path, sample_rate, wav.astype(np.int16))
 
 
-def load_wav(path, sample_rate=22050) -> np.ndarray:
-    """audio_tacotron.py:12-13 without the resampling: the samples of a PCM file as float32 in [-1, 1) (int16 / int32 / uint8
-    scaled by their range, float as stored), the first channel of a multi-channel file.  The reference resamples to
-    sample_rate through librosa; here a file at another rate is an error."""
+def read_wav(path):
+    """(sample rate, samples): the samples of a PCM file as float32 in [-1, 1) (int16 / int32 / uint8 scaled by their range,
+    float as stored), the first channel of a multi-channel file, at the file's own rate."""
     from scipy.io import wavfile
     sr, data = wavfile.read(path)
-    if sr != sample_rate:
-        raise ValueError(f"{path}: sample rate {sr}, expected {sample_rate} (resampling is not implemented: convert the file first)")
     if data.ndim > 1:
         data = data[:, 0]
     if data.dtype == np.int16:
-        return data.astype(np.float32) / 32768.0
+        return sr, data.astype(np.float32) / 32768.0
     if data.dtype == np.int32:
-        return (data.astype(np.float64) / 2147483648.0).astype(np.float32)
+        return sr, (data.astype(np.float64) / 2147483648.0).astype(np.float32)
     if data.dtype == np.uint8:
-        return (data.astype(np.float32) - 128.0) / 128.0
+        return sr, (data.astype(np.float32) - 128.0) / 128.0
     if np.issubdtype(data.dtype, np.floating):
-        return np.ascontiguousarray(data, dtype=np.float32)
+        return sr, np.ascontiguousarray(data, dtype=np.float32)
     raise ValueError(f"{path}: unsupported sample format {data.dtype}")
+
+
+# The resampler's filter: Z zero crossings a side, roll-off and Kaiser beta.  These are resampy's kaiser_best parameters as
+# recalled; resampy is not here to check them, so they are this project's constants, not a parity claim.
+RESAMPLE_ZEROS, RESAMPLE_ROLLOFF, RESAMPLE_BETA = 64, 0.9475937167399596, 14.769656459379492
+RESAMPLE_MAX_TABLE = 1 << 20          # floats: ratios whose polyphase table is larger are refused
+
+
+def resample_filter(u):
+    """h(u) = rolloff sinc(rolloff u) I0(beta sqrt(1 - (u/Z)^2)) / I0(beta) for |u| < Z, else 0 (float64)."""
+    u = np.asarray(u, dtype=np.float64)
+    r2 = (u / RESAMPLE_ZEROS) ** 2
+    inside = r2 < 1.0
+    window = np.i0(RESAMPLE_BETA * np.sqrt(np.where(inside, 1.0 - r2, 0.0))) / np.i0(RESAMPLE_BETA)
+    return np.where(inside, RESAMPLE_ROLLOFF * np.sinc(RESAMPLE_ROLLOFF * u) * window, 0.0)
+
+
+def resample_ratio(orig_sr, target_sr):
+    """(P, Q) = (target_sr, orig_sr) / gcd: P outputs for every Q inputs."""
+    for nm, v in (("orig_sr", orig_sr), ("target_sr", target_sr)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v <= 0:
+            raise ValueError(f"resample: {nm} must be a positive integer, got {v!r}")
+    g = math.gcd(int(orig_sr), int(target_sr))
+    return int(target_sr) // g, int(orig_sr) // g
+
+
+@functools.lru_cache(maxsize=16)
+def resample_table(P: int, Q: int) -> np.ndarray:
+    """The polyphase coefficients of the ratio P / Q, (P, 2W) float32, W = ceil(Z / s), s = min(1, P / Q): tap j of phase
+    phi = (m Q) mod P multiplies x[floor(m Q / P) - W + 1 + j] by c[phi][j] = s h(s (phi / P + W - 1 - j)).  Evaluated in float64
+    and rounded once.  16000 -> 22050 is 441 x 128; 48000 -> 22050 is 147 x 280."""
+    if P <= 0 or Q <= 0 or math.gcd(P, Q) != 1:
+        raise ValueError(f"resample_table: {P} / {Q} must be positive and in lowest terms")
+    Z = RESAMPLE_ZEROS
+    W = Z if P >= Q else -(-Z * Q // P)
+    if P * 2 * W > RESAMPLE_MAX_TABLE:
+        raise ValueError(f"resample: the ratio {P} / {Q} needs a table of {P} x {2 * W} = {P * 2 * W} coefficients, more than "
+                         f"{RESAMPLE_MAX_TABLE}; resample in two steps or pick rates with a larger common divisor")
+    s = min(1.0, P / Q)
+    c = s * resample_filter(s * (np.arange(P)[:, None] / P + (W - 1 - np.arange(2 * W))[None, :]))
+    c = c.astype(np.float32)
+    c.setflags(write=False)
+    return c
+
+
+@functools.lru_cache(maxsize=16)
+def _resample_table_on(P, Q, device):
+    """The kernel's layout of resample_table: tap-major, the phases in the order consecutive outputs meet them
+    (column k = m mod P holds phase (k Q) mod P), so the lanes of a wave read consecutive floats."""
+    c = resample_table(P, Q)
+    return torch.from_numpy(np.ascontiguousarray(c[(np.arange(P) * Q) % P].T)).to(device)
+
+
+def _clip_batch(fn, wav, lengths, shortest):
+    """Shared argument checks of resample / trim_silence: (as_numpy, B, L, int32 host lengths or None)."""
+    as_numpy = isinstance(wav, np.ndarray)
+    if as_numpy:
+        if wav.ndim != 1 or not np.issubdtype(wav.dtype, np.floating):
+            raise TypeError(f"{fn}: a numpy waveform must be 1-D floating point, got {wav.dtype} {wav.shape}")
+        if lengths is not None:
+            raise ValueError(f"{fn}: lengths goes with a batch tensor, not with a numpy waveform")
+        B, L = 1, len(wav)
+    else:
+        if not torch.is_tensor(wav) or wav.dim() != 2 or wav.dtype != torch.float32:
+            raise TypeError(f"{fn}: expected a 1-D numpy waveform or a float32 tensor (B, L)")
+        B, L = wav.shape
+    if B < 1 or L < shortest:
+        raise ValueError(f"{fn}: {B} clip(s) of {L} samples; need at least one clip of at least {shortest} samples")
+    lens = None
+    if lengths is not None:
+        host = lengths.detach().cpu().numpy() if torch.is_tensor(lengths) else np.asarray(lengths)
+        if host.shape != (B,) or not np.issubdtype(host.dtype, np.integer):
+            raise ValueError(f"{fn}: lengths must be {B} integers, got {host.dtype} {host.shape}")
+        if host.max() > L or host.min() < shortest:
+            raise ValueError(f"{fn}: every length must be in [{shortest}, {L}], got {int(host.min())} .. {int(host.max())}")
+        lens = np.ascontiguousarray(host, dtype=np.int32)
+    return as_numpy, B, L, lens
+
+
+def resample(wav, orig_sr, target_sr, lengths=None, device="cuda:0"):
+    """Band-limited resampling from orig_sr to target_sr, what librosa.core.load(path, sr=target_sr) does to a file at another
+    rate (audio_tacotron.py:12-13), as a Kaiser-windowed sinc interpolator in resampy's kaiser_best style evaluated exactly per
+    polyphase phase: with (P, Q) = resample_ratio(orig_sr, target_sr), s = min(1, P / Q) and h = resample_filter,
+
+        y[m] = sum_n x[n] s h(s (m Q - n P) / P),   m < ceil(len P / Q),   x zero outside the clip.
+
+    The last sample m = ceil(len P / Q) - 1 is evaluated like every other; librosa fixes the length to ceil too but would
+    zero-pad that sample where resampy returned floor(len P / Q) of them.  wav: a 1-D numpy waveform (returns a float32
+    numpy waveform), or a float32 GPU tensor (B, L) of zero-padded clips with optional lengths (B,) integers (returns
+    (tensor (B, ceil(L P / Q)), out_lengths), out_lengths the int32 numpy array ceil(lengths P / Q); the rest of a row is
+    zeros).  A clip's samples are bit for bit what they are alone.  orig_sr == target_sr returns the input unchanged.
+    Every argument is checked before anything is launched."""
+    P, Q = resample_ratio(orig_sr, target_sr)
+    as_numpy, B, L, lens = _clip_batch("resample", wav, lengths, 1)
+    if P == Q:
+        return wav if as_numpy else (wav, lens if lens is not None else np.full(B, L, dtype=np.int32))
+    W = resample_table(P, Q).shape[1] // 2
+    L_out = -(-L * P // Q)
+    if L_out >= 2 ** 31:
+        raise ValueError(f"resample: {L} samples at {P} / {Q} give {L_out} samples, 2^31 or more")
+    y = torch.from_numpy(np.ascontiguousarray(wav, dtype=np.float32)[None]).to(device) if as_numpy else wav
+    _chk(y, "wav")
+    table = _resample_table_on(P, Q, str(y.device))
+    lens_d = torch.from_numpy(lens).to(y.device) if lens is not None else None
+    out = torch.empty(B, L_out, dtype=torch.float32, device=y.device)
+    _lib.call("nsg_audio_resample", _p(y), _p(lens_d), _p(table), _p(out), c_int32(B), c_int32(L), c_int32(P), c_int32(Q), c_int32(W), _stream())
+    if as_numpy:
+        return out[0].cpu().numpy()
+    src = lens.astype(np.int64) if lens is not None else np.full(B, L, dtype=np.int64)
+    return out, (-(-src * P // Q)).astype(np.int32)
+
+
+_resample = resample          # load_wav's flag has the function's name
+
+
+def trim_silence(wav, top_db=20.0, frame_length=2048, hop_length=512, lengths=None, device="cuda:0"):
+    """librosa.effects.trim(y, top_db, ref=np.max, frame_length, hop_length) (cmu_arctic.py:72 calls it with top_db=20): the
+    mean square of centred, reflect-padded frames, the loudest frame as the reference, and the span from the first to the last
+    frame less than top_db below it: start = first * hop_length, end = min(len, (last + 1) * hop_length).  wav: a 1-D numpy
+    waveform (returns (wav[start:end], (start, end)) as librosa does), or a float32 GPU tensor (B, L) of zero-padded clips
+    with optional lengths (returns an int32 (B, 2) GPU tensor of (start, end); a clip's bounds do not depend on the batch).
+    frame_length even in [2, 8192], hop_length >= 1, top_db > 0, every clip longer than frame_length / 2.  Every argument is
+    checked before anything is launched."""
+    if isinstance(frame_length, bool) or not isinstance(frame_length, (int, np.integer)) or frame_length % 2 or not 2 <= frame_length <= 8192:
+        raise ValueError(f"trim_silence: frame_length must be an even integer in [2, 8192], got {frame_length!r}")
+    if isinstance(hop_length, bool) or not isinstance(hop_length, (int, np.integer)) or hop_length < 1:
+        raise ValueError(f"trim_silence: hop_length must be a positive integer, got {hop_length!r}")
+    if not top_db > 0:
+        raise ValueError(f"trim_silence: top_db must be positive, got {top_db!r}")
+    as_numpy, B, L, lens = _clip_batch("trim_silence", wav, lengths, frame_length // 2 + 1)
+    y = torch.from_numpy(np.ascontiguousarray(wav, dtype=np.float32)[None]).to(device) if as_numpy else wav
+    _chk(y, "wav")
+    lens_d = torch.from_numpy(lens).to(y.device) if lens is not None else None
+    bounds = torch.empty(B, 2, dtype=torch.int32, device=y.device)
+    nb = _lib.query("nsg_audio_trim_workspace_bytes", c_int32(B), c_int32(L), c_int32(hop_length))
+    ws = WS.get(nb, y.device)
+    _lib.call("nsg_audio_trim_bounds", _p(y), _p(lens_d), _p(bounds), c_int32(B), c_int32(L), c_int32(frame_length), c_int32(hop_length),
+              c_float(top_db), _p(ws), c_size_t(nb), _stream())
+    if not as_numpy:
+        return bounds
+    start, end = (int(v) for v in bounds[0].cpu().numpy())
+    return wav[start:end], (start, end)
+
+
+def load_wav(path, sample_rate=22050, resample=False, device="cuda:0") -> np.ndarray:
+    """audio_tacotron.py:12-13: the samples of a PCM file (read_wav) at sample_rate.  The reference resamples a file at another
+    rate through librosa; here that is an error unless resample=True, which resamples it with `resample` on `device`."""
+    sr, wav = read_wav(path)
+    if sr != sample_rate:
+        if not resample:
+            raise ValueError(f"{path}: sample rate {sr}, expected {sample_rate} (pass resample=True to resample it)")
+        wav = _resample(wav, sr, sample_rate, device=device)
+    return wav

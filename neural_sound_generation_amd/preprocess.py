@@ -8,8 +8,15 @@ batches); the audio zero-padded by lws_pad_lr and cut to N * hop_size samples --
 would while it frames the mel with librosa; that mismatch is kept, it defines `timesteps`; `<name>-audio-%05d.npy`,
 `<name>-mel-%05d.npy`, and one `train.txt` line `audio|mel|timesteps|text[|speaker]`.
 
-Not restated: resampling (a file at another rate is an error), silence trimming, the mu-law input types, a process pool
-and the CLI.  parity unpinned, as for the rest of audio.py: tests hold the files to an fp64 restatement of the formulas.
+Recordings at another rate, and silent ends (src/cmu_arctic.py:55-128, the multi-speaker writer): process_utterances(...,
+resample=True, trim_top_db=20) reads each file at its own rate, resamples and trims on the device in ragged batches
+(audio.resample, audio.trim_silence) and then runs the same rescale -> mel -> pad flow, in the reference's order: load and
+resample, trim, rescale, mel.  build_from_path_cmu_arctic walks `cmu_us_<speaker>_arctic/wav/*.wav` and writes the speaker
+id as the fifth field.  Both options are off by default, and then nothing differs from the LJSpeech path.
+
+Not restated: the mu-law input types, the jsut / librivox walkers, the dead `.lab` branch of cmu_arctic.py (`and False`), a
+process pool and the CLI.  parity unpinned, as for the rest of audio.py: tests hold the files to an fp64 restatement of the
+formulas.
 """
 from __future__ import annotations
 
@@ -41,27 +48,82 @@ def lws_pad_lr(x, fsize, fshift):
     return pad, pad + r
 
 
+TRIM_FRAME_LENGTH, TRIM_HOP_LENGTH = 2048, 512     # librosa.effects.trim's defaults, which cmu_arctic.py:72 leaves alone
+# nnmnkwii.datasets.cmu_arctic.available_speakers as recalled (cmu_arctic.py:22); nnmnkwii is not here to check the list or
+# its order, which fixes the speaker ids.
+CMU_ARCTIC_SPEAKERS = ("awb", "bdl", "clb", "jmk", "ksp", "rms", "slt")
+
+
+def _rescaled(label, wav, fft_size):
+    if wav.ndim != 1 or len(wav) <= fft_size // 2:
+        raise ValueError(f"{label}: {wav.shape} samples; need a 1-D clip longer than fft_size / 2 = {fft_size // 2}")
+    peak = float(np.abs(wav).max())
+    if not peak > 0.0 or not np.isfinite(peak):
+        raise ValueError(f"{label}: an all-zero (or non-finite) clip cannot be rescaled")
+    return (wav / peak * RESCALING_MAX).astype(np.float32)
+
+
+def _resample_and_trim(wavs, rates, labels, sample_rate, trim_top_db, batch_clips, device):
+    """The clips of `wavs` (each at its own rates[i]) at sample_rate, cut to audio.trim_silence's bounds when trim_top_db is
+    set: grouped by rate, sorted by length, on the device in ragged batches of batch_clips, and back on the host.  The kernels
+    give a clip what they give it alone, so the result does not depend on batch_clips."""
+    shortest = TRIM_FRAME_LENGTH // 2 + 1 if trim_top_db is not None else 1
+    for label, wav, sr in zip(labels, wavs, rates):
+        P, Q = audio.resample_ratio(sr, sample_rate)
+        if wav.ndim != 1 or -(-len(wav) * P // Q) < shortest:
+            raise ValueError(f"{label}: {wav.shape} samples at {sr} Hz; need a 1-D clip of at least {shortest} samples at {sample_rate} Hz")
+    out = [None] * len(wavs)
+    for sr in sorted(set(rates)):
+        order = sorted((i for i in range(len(wavs)) if rates[i] == sr), key=lambda i: len(wavs[i]))
+        for s in range(0, len(order), batch_clips):
+            idx = order[s:s + batch_clips]
+            lens = np.array([len(wavs[i]) for i in idx], dtype=np.int32)
+            batch = np.zeros((len(idx), int(lens.max())), dtype=np.float32)
+            for r, i in enumerate(idx):
+                batch[r, :lens[r]] = wavs[i]
+            y, lens = audio.resample(torch.from_numpy(batch).to(device), sr, sample_rate, lengths=lens)
+            bounds = np.stack([np.zeros_like(lens), lens], axis=1)
+            if trim_top_db is not None:
+                bounds = audio.trim_silence(y, trim_top_db, TRIM_FRAME_LENGTH, TRIM_HOP_LENGTH, lengths=lens).cpu().numpy()
+            y = y.cpu().numpy()
+            for r, i in enumerate(idx):
+                out[i] = np.ascontiguousarray(y[r, bounds[r, 0]:bounds[r, 1]])
+    return out
+
+
 def process_utterances(wavs, texts, out_dir, name="ljspeech", start_index=1, speaker_ids=None, sample_rate=22050, fft_size=1024,
-                       hop_size=256, n_mels=80, batch_clips=64, device="cuda:0"):
+                       hop_size=256, n_mels=80, batch_clips=64, device="cuda:0", resample=False, trim_top_db=None):
     """ljspeech._process_utterance over a list.  wavs: paths of PCM files (audio.load_wav) or 1-D float arrays; texts: one
     string each; speaker_ids: optional integers, appended as a fifth field.  Utterance i is written as
     `<name>-audio-%05d.npy` / `<name>-mel-%05d.npy` with number start_index + i.  Returns the metadata tuples
-    (audio_filename, mel_filename, timesteps, text[, speaker]) in the order given.  The files do not depend on batch_clips."""
+    (audio_filename, mel_filename, timesteps, text[, speaker]) in the order given.  The files do not depend on batch_clips.
+    resample=True: a file at another rate is resampled to sample_rate instead of refused (arrays are taken to be at
+    sample_rate).  trim_top_db: cut each clip to audio.trim_silence(clip, trim_top_db)'s span before the rescale, as
+    cmu_arctic._process_utterance does with 20.  With both off (the default) every step is the LJSpeech path's."""
     if len(texts) != len(wavs) or (speaker_ids is not None and len(speaker_ids) != len(wavs)):
         raise ValueError("process_utterances: wavs, texts and speaker_ids must have one entry per utterance")
     if batch_clips < 1:
         raise ValueError("process_utterances: batch_clips must be at least 1")
+    if trim_top_db is not None and not trim_top_db > 0:
+        raise ValueError(f"process_utterances: trim_top_db must be positive or None, got {trim_top_db!r}")
     os.makedirs(out_dir, exist_ok=True)
-    clips = []
+    prepare = bool(resample) or trim_top_db is not None
+    clips, rates, labels = [], [], []
     for i, w in enumerate(wavs):
-        label = str(w) if isinstance(w, (str, os.PathLike)) else f"utterance {i}"
-        wav = audio.load_wav(w, sample_rate) if isinstance(w, (str, os.PathLike)) else np.asarray(w, dtype=np.float32)
-        if wav.ndim != 1 or len(wav) <= fft_size // 2:
-            raise ValueError(f"{label}: {wav.shape} samples; need a 1-D clip longer than fft_size / 2 = {fft_size // 2}")
-        peak = float(np.abs(wav).max())
-        if not peak > 0.0 or not np.isfinite(peak):
-            raise ValueError(f"{label}: an all-zero (or non-finite) clip cannot be rescaled")
-        clips.append((wav / peak * RESCALING_MAX).astype(np.float32))
+        is_path = isinstance(w, (str, os.PathLike))
+        label = str(w) if is_path else f"utterance {i}"
+        if is_path and prepare:
+            sr, wav = audio.read_wav(w)
+            if sr != sample_rate and not resample:
+                raise ValueError(f"{label}: sample rate {sr}, expected {sample_rate} (pass resample=True to resample it)")
+        else:
+            sr, wav = sample_rate, (audio.load_wav(w, sample_rate) if is_path else np.asarray(w, dtype=np.float32))
+        clips.append(wav if prepare else _rescaled(label, wav, fft_size))
+        rates.append(sr)
+        labels.append(label)
+    if prepare:
+        clips = [_rescaled(label, wav, fft_size)
+                 for label, wav in zip(labels, _resample_and_trim(clips, rates, labels, sample_rate, trim_top_db, batch_clips, device))]
     metadata = [None] * len(clips)
     order = sorted(range(len(clips)), key=lambda i: len(clips[i]))
     for s in range(0, len(order), batch_clips):
@@ -106,5 +168,25 @@ def build_from_path(in_dir, out_dir, sample_rate=22050, fft_size=1024, hop_size=
             wavs.append(join(in_dir, "wavs", "%s.wav" % parts[0]))
             texts.append(parts[2])
     metadata = process_utterances(wavs, texts, out_dir, "ljspeech", 1, None, sample_rate, fft_size, hop_size, n_mels, batch_clips, device)
+    write_metadata(metadata, out_dir)
+    return metadata
+
+
+def build_from_path_cmu_arctic(in_dir, out_dir, speakers=CMU_ARCTIC_SPEAKERS, trim_top_db=20.0, sample_rate=22050, fft_size=1024,
+                               hop_size=256, n_mels=80, batch_clips=64, device="cuda:0"):
+    """cmu_arctic.py:18-32: the CMU Arctic layout -- `cmu_us_<speaker>_arctic/wav/*.wav` under in_dir (16 kHz recordings,
+    resampled to sample_rate), the speakers in the order given, each one's files sorted; the speaker id is the index in
+    `speakers`, the text "N/A", the numbering runs from 1 over all speakers.  Each clip is trimmed with trim_top_db (None: not
+    at all).  Writes the .npy files and train.txt (fifth field: the speaker id) into out_dir and returns the metadata."""
+    wavs, ids = [], []
+    for sid, speaker in enumerate(speakers):
+        d = join(in_dir, "cmu_us_%s_arctic" % speaker, "wav")
+        if not os.path.isdir(d):
+            raise FileNotFoundError(f"build_from_path_cmu_arctic: speaker {speaker!r} has no directory {d}")
+        files = sorted(f for f in os.listdir(d) if f.endswith(".wav"))
+        wavs += [join(d, f) for f in files]
+        ids += [sid] * len(files)
+    metadata = process_utterances(wavs, ["N/A"] * len(wavs), out_dir, "cmu_arctic", 1, ids, sample_rate, fft_size, hop_size, n_mels,
+                                  batch_clips, device, resample=True, trim_top_db=trim_top_db)
     write_metadata(metadata, out_dir)
     return metadata
