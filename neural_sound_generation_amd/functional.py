@@ -65,7 +65,7 @@ class EncoderFn(Function):
             raise RuntimeError("backward through the encoder in eval() mode is not implemented")
         ctx.saved_tensors                      # version check of the parameters (see _run_forward)
         grads = engine.encoder_backward(to_nhwc(dz), ctx.saved, ctx.bundle)
-        return (None, None, None, None) + tuple(grads)
+        return (None, None, None, None) + tuple(engine.encoder_grad_list(grads))
 
 
 class DecoderFn(Function):
@@ -81,7 +81,7 @@ class DecoderFn(Function):
         dz, grads = engine.decoder_backward(to_nhwc(dxt), ctx.saved, ctx.bundle, need_dz=ctx.needs_input_grad[0])
         if dz is not None:
             dz = to_nchw_view(ops.convert(dz, torch.float32))
-        return (dz, None, None, None) + tuple(grads)
+        return (dz, None, None, None) + tuple(engine.decoder_grad_list(grads))
 
 
 class ResBlockFn(Function):
@@ -97,7 +97,7 @@ class ResBlockFn(Function):
         dx, grads = engine.resblock_backward(ops.convert(to_nhwc(dy), ctx.dtype), ctx.saved, ctx.bundle, need_dx=ctx.needs_input_grad[0])
         if dx is not None:
             dx = to_nchw_view(ops.convert(dx, torch.float32))
-        return (dx, None, None, None) + tuple(grads)
+        return (dx, None, None, None) + tuple(engine.resblock_grad_list(grads))
 
 
 def encoder_apply(x, bundle, training, dtype=torch.float32):

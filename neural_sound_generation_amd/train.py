@@ -31,6 +31,20 @@ LEAN_VQ = os.environ.get("NSG_LEAN_VQ", "1") == "1"
 # step at the bench's shape.  NSG_ZE_FROM_SOURCES=0 keeps the materialised form.
 ZE_FROM_SOURCES = os.environ.get("NSG_ZE_FROM_SOURCES", "1") == "1"
 
+
+def comm_split(opt: FlatAdam, front, back) -> int:
+    """Where a data-parallel step may cut opt's communication buffer in two, in floats from its start: `back` (gradient views that
+    are final early: decoder, speaker table) is then all-reduced while `front` (encoder, codebook) is still being written.  The
+    split is the lowest start of a back view, so no back view lies in front of it; it stands only if every front view ends at or
+    before it, and is 0 -- one collective at the end -- otherwise.  (A tail reserved with opt.reserve_tail lies behind opt.total,
+    so behind any split.)"""
+    lo = opt.flat_grad.data_ptr()
+    split = min((t.data_ptr() - lo) // 4 for t in back)
+    if 0 < split < opt.total and all((t.data_ptr() - lo) // 4 + t.numel() <= split for t in front):
+        return split
+    return 0
+
+
 class FusedTrainStep:
     def __init__(self, model, lr: float = 1e-3, beta: float = 1.0, betas=(0.9, 0.999), eps: float = 1e-8,
                  process_group=None, optimizer: FlatAdam | None = None, revive_every: int = 0, revive_min_count: int = 1,
@@ -68,8 +82,9 @@ class FusedTrainStep:
         self.encP = engine.encoder_params(model.encoder)
         self.decP = engine.decoder_params(model.decoder)
         self.codebook = model.codebook.embedding.weight
-        self.g_enc = self.opt.grads_for(engine.encoder_param_list(self.encP))
-        self.g_dec = self.opt.grads_for(engine.decoder_param_list(self.decP))
+        g_enc = self.opt.grads_for(engine.encoder_param_list(self.encP))
+        g_dec = self.opt.grads_for(engine.decoder_param_list(self.decP))
+        self.g_enc, self.g_dec = engine.encoder_grads(g_enc), engine.decoder_grads(g_dec)
         self.g_code = None if self.ema else self.opt.grads_for([self.codebook])[0]
         self.spk = getattr(model, "speaker_embedding", None)
         self.g_spk = self.opt.grads_for([self.spk.weight])[0] if self.spk is not None else None
@@ -77,10 +92,9 @@ class FusedTrainStep:
         # from the decoder's first gradient on is final when the decoder's backward has been enqueued, BEFORE the encoder's
         # backward starts, so that part is all-reduced on the collective's own stream beside the encoder backward and only the
         # front part waits for the end of the step (two collectives, the first one hidden).
-        lo = self.opt.flat_grad.data_ptr()
-        self._comm_split = (self.g_dec[0].data_ptr() - lo) // 4
-        if not (0 < self._comm_split < self.opt.flat_grad.numel()) or any(t.data_ptr() < self.g_dec[0].data_ptr() for t in self.g_dec):
-            self._comm_split = 0          # (unexpected parameter order: one collective at the end, as before)
+        # (An optimiser with another parameter order: comm_split is 0, one collective at the end.)
+        self._comm_split = comm_split(self.opt, front=g_enc + ([] if self.g_code is None else [self.g_code]),
+                                      back=g_dec + ([] if self.g_spk is None else [self.g_spk]))
         self._reduce = None               # nsg_dist.TwoPartAllReduce over the communication buffer (made on first use: reserve_tail may still grow it)
         self._stepping = False            # collectives only from step(): forward_backward() alone never communicates
         # test hook: (N,) int64 code indices to use INSTEAD of the search's (the search still runs and is ignored).  Lets a test
@@ -122,12 +136,12 @@ class FusedTrainStep:
         defer = (lean and ZE_FROM_SOURCES and self.force_indices is None and self.scatter_impl == "sorted" and ops.bnres_rows_supported(D)
                  and ops.index_add_sorted_supported(x.numel(), D, K) and ops.vq_losses_indexed_bn_supported(D))
         ze, es = engine.encoder_forward(x, self.encP, True, dtype=self.dtype, packs=enc_packs, defer_closing_bn=defer)
-        if ze is None:
-            bn2 = engine.encoder_closing_bn(es, self.encP)
-            ze_shape = bn2.h.shape
-            ze_rows = ops.BnResRows(bn2.h.view(-1, D), bn2.residual.view(-1, D), bn2.mean, bn2.invstd, bn2.gamma, bn2.beta)
-        else:
-            ze_shape, ze_rows = ze.shape, ze.view(-1, D)
+        # the encoder's closing BatchNorm as rows given by their sources (ops.BnResRows), or None where the block ran the separate
+        # operators: z_e itself where the forward deferred it, and -- deferred or not -- what the loss pass needs for bn= further
+        # down (fetched once, here: these are views, nothing is launched)
+        bn2 = engine.encoder_closing_bn(es, self.encP) if lean else None
+        ze_rows = bn2 if ze is None else ze.view(-1, D)
+        ze_shape = es.ze_shape
         ze_numel = ze_rows.shape[0] * D
         if self._keep_rows:
             self._kept_rows = ze_rows._replace(gamma=ze_rows.gamma.clone(), beta=ze_rows.beta.clone()) if ze is None else ze_rows
@@ -157,10 +171,10 @@ class FusedTrainStep:
             zdec = ops.add_per_clip(zq, spk_rows, out_dtype=self.dtype)
         # loss_recons = mse(zero-pad(x_tilde), c) and d/dx_tilde             (train.py:118-129)
         xt, ds = engine.decoder_forward(zdec, self.decP, True, dtype=self.dtype, packs=dec_packs, zq_is_relu=lean, mse_target=x,
-                                        mse_dbias=self.g_dec[21])
-        if isinstance(xt, tuple):       # the fused output layer formed the loss and the gradient at the Tanh's input with the image
-            loss_recons, dpre = xt
-            dzq, _ = engine.decoder_backward(dpre, ds, self.decP, need_dz=True, dxt_is_pre_tanh=True, gout=self.g_dec)
+                                        mse_dbias=self.g_dec.convt6.bias)
+        if isinstance(xt, engine.FusedLoss):    # the fused output layer formed the loss and the gradient at the Tanh's input with the image
+            loss_recons = xt.loss
+            dzq, _ = engine.decoder_backward(xt.dpre, ds, self.decP, need_dz=True, dxt_is_pre_tanh=True, gout=self.g_dec)
         else:
             loss_recons, dxt = ops.mse_padded(xt, x, B * H, xt.shape[2], T)
             dzq, _ = engine.decoder_backward(dxt, ds, self.decP, need_dz=True, gout=self.g_dec)
@@ -178,11 +192,10 @@ class FusedTrainStep:
         bn2_sums = None
         if lean:
             # dz is the incoming gradient of the encoder's closing BatchNorm: its backward sums are formed while dz is written
-            bn2 = engine.encoder_closing_bn(es, self.encP)
             if bn2 is not None and bn2.h.dtype == self.dtype and ops.vq_losses_indexed_bn_supported(D):
                 loss_vq, dz, dg, db = ops.vq_losses_indexed(ze_rows, self.codebook.detach(), idx, dz_scale=self.beta, dz_add=dzq.view(-1, D),
-                                                            grad_dtype=self.dtype, bn=(bn2.h.view(-1, D), bn2.mean, bn2.invstd),
-                                                            dgamma=self.g_enc[20], dbeta=self.g_enc[21])
+                                                            grad_dtype=self.dtype, bn=(bn2.h, bn2.mean, bn2.invstd),
+                                                            dgamma=self.g_enc.res5.bn2.weight, dbeta=self.g_enc.res5.bn2.bias)
                 bn2_sums = (dg, db)
             else:
                 loss_vq, dz = ops.vq_losses_indexed(ze_rows, self.codebook.detach(), idx, dz_scale=self.beta, dz_add=dzq.view(-1, D),

@@ -6,10 +6,11 @@ import numpy as np
 import pytest
 import torch
 
-from neural_sound_generation_amd import models as M, ops
+from neural_sound_generation_amd import engine, models as M, ops
 from neural_sound_generation_amd._lib import NsgError
 from neural_sound_generation_amd.distributed import shard_batch
 from neural_sound_generation_amd.optim import FlatAdam
+from neural_sound_generation_amd.train import comm_split
 from neural_sound_generation_amd.vector_quantization import vq, vq_st
 from oracle import vqvae_oracle as O
 import fixture_io
@@ -80,6 +81,82 @@ def test_flat_adam_bucket_layout():
     assert float(opt.flat_grad.abs().sum()) == 0.0 and all(p.grad is not None for p in m.parameters())
     views = opt.grads_for([m.codebook.embedding.weight])
     assert views[0].data_ptr() == m.codebook.embedding.weight.grad.data_ptr()
+
+
+def test_stack_order_is_the_state_dicts():
+    """engine.*_LAYERS, the one statement of each stack's parameter order: its names are the state_dict's, its lists the modules'."""
+    m = M.VQVAE(1, 16, 32)
+    encP, decP = engine.encoder_params(m.encoder), engine.decoder_params(m.decoder)
+    for got, want in ((engine.encoder_param_list(encP), m.encoder.parameters()), (engine.decoder_param_list(decP), m.decoder.parameters()),
+                      (engine.resblock_param_list(decP.res1), m.decoder[1].parameters())):
+        want = list(want)
+        assert len(got) == len(want) and all(a is b for a, b in zip(got, want))
+    buffers = ("running_mean", "running_var", "num_batches_tracked")
+    keys = [k for k, _ in O.state_keys(16, 32) if not k.endswith(buffers)]
+    assert [k[len("encoder."):] for k in keys if k.startswith("encoder.")] == engine.param_names(engine.ENCODER_LAYERS)
+    assert [k[len("decoder."):] for k in keys if k.startswith("decoder.")] == engine.param_names(engine.DECODER_LAYERS)
+    assert [k[len("decoder.1."):] for k in keys if k.startswith("decoder.1.")] == engine.param_names(engine.RESBLOCK_LAYERS)
+
+
+def test_named_gradient_slots_are_the_state_dict_positions():
+    t = [torch.tensor(i) for i in range(22)]
+    res = lambda g: [g.conv1.weight, g.conv1.bias, g.bn1.weight, g.bn1.bias, g.conv2.weight, g.conv2.bias, g.bn2.weight, g.bn2.bias]
+    same = lambda got, want: len(got) == len(want) and all(a is b for a, b in zip(got, want))
+    e = engine.encoder_grads(t)
+    assert e.res5.bn2.weight is t[20] and e.res5.bn2.bias is t[21]
+    assert same(res(e.res4), t[6:14]) and same(res(e.res5), t[14:22])
+    assert e.conv3.weight is t[4] and e.conv3.bias is t[5]
+    assert same([e.conv0.weight, e.conv0.bias, e.bn0.weight, e.bn0.bias], t[0:4])
+    assert same(engine.encoder_grad_list(e), t) and same(engine.resblock_grad_list(e.res4), t[6:14])
+    d = engine.decoder_grads(t)
+    assert d.convt3.weight is t[16] and d.convt3.bias is t[17]
+    assert d.bn4.weight is t[18] and d.bn4.bias is t[19]
+    assert d.convt6.weight is t[20] and d.convt6.bias is t[21]
+    assert same(res(d.res0), t[0:8]) and same(res(d.res1), t[8:16])
+    assert same(engine.decoder_grad_list(d), t)
+    with pytest.raises(ValueError):
+        engine.encoder_grads(t[:21])
+    assert all(g is None for g in engine.decoder_grad_list(engine.DecoderGrads()))       # no destinations: every slot empty
+
+
+def _split_case(model, params=None, tail=0):
+    """comm_split for FlatAdam(params) as FusedTrainStep asks for it, and the optimiser."""
+    opt = FlatAdam(model.parameters() if params is None else params)
+    if tail:
+        opt.reserve_tail(tail)
+    code = [] if model.codebook.ema_decay is not None else [model.codebook.embedding.weight]
+    spk = [model.speaker_embedding.weight] if getattr(model, "speaker_embedding", None) is not None else []
+    front = opt.grads_for(engine.encoder_param_list(engine.encoder_params(model.encoder)) + code)
+    back = opt.grads_for(engine.decoder_param_list(engine.decoder_params(model.decoder)) + spk)
+    return comm_split(opt, front, back), opt
+
+
+def test_comm_split_is_the_decoders_first_offset_or_zero():
+    def first_decoder_offset(model, opt):
+        first = next(model.decoder.parameters())
+        return next(off for p, off in zip(opt._params, opt.offsets) if p is first)
+
+    m = M.VQVAE(1, 16, 32)
+    split, opt = _split_case(m)
+    assert split > 0 and split == first_decoder_offset(m, opt)
+    assert split == opt.offsets[len(list(m.encoder.parameters())) + 1]          # [encoder | codebook | decoder]
+
+    ms = M.VQVAE(1, 16, 32, n_speakers=7)
+    split, opt = _split_case(ms)
+    assert split > 0 and split == first_decoder_offset(ms, opt)
+    spk_off = next(off for p, off in zip(opt._params, opt.offsets) if p is ms.speaker_embedding.weight)
+    assert spk_off >= split                                                       # the speaker table lies behind the split
+
+    me = M.VQVAE(1, 16, 32, ema_decay=0.99)
+    plain, _ = _split_case(M.VQVAE(1, 16, 32, ema_decay=0.99))
+    split, opt = _split_case(me, tail=64 + 32 * 16)
+    assert split > 0 and split == plain == first_decoder_offset(me, opt)          # the reserved tail changes nothing
+
+    # another parameter order: one collective at the end
+    for order in ("dec enc code", "dec code enc", "enc dec code"):              # decoder before encoder; codebook after the decoder
+        m2 = M.VQVAE(1, 16, 32)
+        part = dict(enc=list(m2.encoder.parameters()), dec=list(m2.decoder.parameters()), code=[m2.codebook.embedding.weight])
+        assert _split_case(m2, [p for name in order.split() for p in part[name]])[0] == 0
 
 
 def test_conv_geometry_helpers():
