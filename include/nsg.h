@@ -38,7 +38,7 @@ extern "C" {
 #define NSG_API
 #endif
 
-#define NSG_VERSION 103 /* bumped on ANY change of an existing entry point's signature; _lib.py refuses a library of another version */
+#define NSG_VERSION 103 /* bumped HERE on ANY change of an existing entry point's signature; _lib.py binds from this header and refuses a library of another version */
 
 enum {
     NSG_OK = 0,

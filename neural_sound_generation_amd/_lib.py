@@ -7,158 +7,106 @@ from __future__ import annotations
 
 import ctypes
 import os
+import re
 from ctypes import POINTER, Structure, c_char_p, c_float, c_int32, c_int64, c_size_t, c_void_p
+
+from .build import INCLUDE
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "libnsg.so")
-
-NSG_RELU_IN = 1
-NSG_TANH_OUT = 2
-NSG_OUT_F32 = 8
-NSG_RELU_OUT = 16
-NSG_F32 = 0
-NSG_BF16 = 1
-NSG_VERSION = 103      # include/nsg.h NSG_VERSION this binding was written against (bumped on ANY signature change)
-
-
-class ConvDesc(Structure):
-    """struct nsg_conv_desc (include/nsg.h)."""
-    _fields_ = [("B", c_int32), ("IH", c_int32), ("IW", c_int32), ("C_in", c_int32),
-                ("OH", c_int32), ("OW", c_int32), ("C_out", c_int32),
-                ("k", c_int32), ("stride", c_int32), ("pad", c_int32), ("transposed", c_int32), ("dtype", c_int32),
-                ("k_w", c_int32), ("pad_w", c_int32)]
-
-    def key(self):
-        return tuple(getattr(self, f) for f, _ in self._fields_)
-
-
-_P = c_void_p
-_D = POINTER(ConvDesc)
-# name -> (restype, argtypes); restype None means "int status, checked"
-_SIGS = {
-    "nsg_version": (c_int32, []),
-    "nsg_last_error_string": (c_char_p, []),
-    "nsg_vq_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32]),
-    "nsg_vq_forward": (None, [_P, _P, c_int64, c_int32, c_int32, _P, _P, _P, _P, c_size_t, _P]),
-    "nsg_vq_bf16x3_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32]),
-    "nsg_vq_forward_bf16x3": (None, [_P, _P, c_int64, c_int32, c_int32, _P, _P, _P, _P, c_int32, _P, c_size_t, _P]),
-    "nsg_vq_forward_bf16x3_cond": (None, [_P, _P, c_int64, c_int32, c_int32, _P, _P, _P, _P, c_int32, _P, c_int64, _P, c_size_t, _P]),
-    "nsg_vq_forward_bf16x3_bnres": (None, [_P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, _P, _P, _P, c_int32, _P, c_int64, _P, c_size_t, _P]),
-    "nsg_debug_vq_forward_valu": (None, [_P, _P, c_int64, c_int32, c_int32, _P, _P, _P, _P, c_size_t, _P]),
-    "nsg_rowsumsq": (None, [_P, c_int64, c_int32, _P, _P]),
-    "nsg_index_add_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32]),
-    "nsg_index_add_rows": (None, [_P, _P, c_int64, c_int32, c_int32, _P, _P, _P, c_size_t, _P]),
-    "nsg_index_add_rows_bf16x2": (None, [_P, _P, c_int64, c_int32, c_int32, _P, _P, _P, c_size_t, _P]),
-    "nsg_index_add_sorted_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32]),
-    "nsg_index_add_rows_sorted": (None, [_P, _P, c_int64, c_int32, c_int32, _P, _P, _P, c_size_t, _P]),
-    "nsg_index_add_rows_sorted_bnres": (None, [_P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, _P, _P, _P, c_size_t, _P]),
-    "nsg_gather_rows": (None, [_P, _P, c_int64, c_int32, c_int32, _P, _P]),
-    "nsg_vq_ema_update": (None, [_P, _P, _P, _P, _P, c_int32, c_int32, c_float, c_float, _P, _P]),
-    "nsg_code_usage": (None, [_P, c_int64, c_int32, _P, _P, _P, _P]),
-    "nsg_vq_revive": (None, [_P, c_int64, c_int32, _P, c_int32, _P, c_int32, c_int64, c_int64, _P, _P, _P, _P, _P, _P, c_int32, _P]),
-    "nsg_vq_revive_bnres": (None, [_P, _P, _P, _P, _P, _P, c_int64, c_int32, _P, c_int32, _P, c_int32, c_int64, c_int64, _P, _P, _P, _P, _P, _P,
-                                   c_int32, _P]),
-    "nsg_codebook_grad_from_sums": (None, [_P, _P, _P, c_int32, c_int32, c_float, _P, _P]),
-    "nsg_increment_counters": (None, [_P, c_int32, _P]),
-    "nsg_packed_weight_floats": (c_size_t, [_D]),
-    "nsg_pack_conv_weights": (None, [_D, _P, _P, _P, _P]),
-    "nsg_pack_conv_weights_batch": (None, [c_int32, _P, _P, _P, _P, _P]),
-    "nsg_conv_workspace_bytes": (c_size_t, [_D]),
-    "nsg_conv_forward": (None, [_D, _P, _P, _P, _P, c_int32, _P, c_size_t, _P]),
-    "nsg_conv_forward_bnstats": (None, [_D, _P, _P, _P, _P, c_int32, c_float, c_float, _P, _P, _P, _P, _P, c_size_t, _P]),
-    "nsg_conv_dgrad": (None, [_D, _P, _P, _P, c_int32, _P, c_size_t, _P]),
-    "nsg_conv_dgrad_relu_add": (None, [_D, _P, _P, _P, _P, _P, c_int32, _P, c_size_t, _P]),
-    "nsg_conv_wgrad": (None, [_D, _P, _P, _P, _P, c_int32, _P, c_size_t, _P]),
-    "nsg_bn_workspace_bytes": (c_size_t, [c_int64, c_int32]),
-    "nsg_bn_stats": (None, [_P, c_int64, c_int32, c_int32, c_float, c_float, _P, _P, _P, _P, _P, c_size_t, _P]),
-    "nsg_bn_eval_stats": (None, [_P, _P, c_int32, c_float, _P, _P, _P]),
-    "nsg_bn_apply": (None, [_P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, _P]),
-    "nsg_bn_backward": (None, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, _P, c_size_t, _P]),
-    "nsg_c1conv_bn_workspace_bytes": (c_size_t, [c_int32]),
-    "nsg_c1conv_bn_relu_forward": (None, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_float, c_float, c_int32, _P, c_int32, c_int32, c_int32, c_int32,
-                                          c_int32, _P, c_size_t, _P, _P]),
-    "nsg_c1conv_bn_relu_backward": (None, [_P, _P, _P, _P, _P, _P, _P, _P, c_int32, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P,
-                                           c_size_t, _P, _P]),
-    "nsg_bn_relu_c1convt_supported": (c_int32, [c_int32, c_int32]),
-    "nsg_bn_relu_c1convt_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
-    "nsg_bn_relu_c1convt_forward": (None, [_P, c_int32, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, _P, c_size_t, _P]),
-    "nsg_bn_relu_c1convt_forward_mse": (None, [_P, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, c_int32, c_float, _P, _P, _P, c_int32, c_int32, c_int32,
-                                               c_int32, _P, c_size_t, _P]),
-    "nsg_bn_relu_c1convt_backward": (None, [_P, c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P,
-                                            c_size_t, _P]),
-    "nsg_bn_relu_conv1x1_supported": (c_int32, [c_int32, c_int32]),
-    "nsg_bn_relu_conv1x1_workspace_bytes": (c_size_t, [c_int64, c_int32]),
-    "nsg_bn_relu_conv1x1_forward": (None, [_P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, _P, c_size_t, _P]),
-    "nsg_bn_relu_conv1x1_forward_bnstats": (None, [_P, _P, _P, _P, _P, _P, _P, _P, c_float, c_float, _P, _P, _P, _P, c_int64, c_int32, c_int32, _P,
-                                                   c_size_t, _P]),
-    "nsg_bn_relu_conv1x1_wgrad": (None, [_P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, _P, c_size_t, _P]),
-    "nsg_bn_backward_conv1x1_dgrad": (None, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, _P,
-                                             c_size_t, _P]),
-    "nsg_bn_backward_conv1x1_dgrad_wgrad_supported": (c_int32, [c_int32, c_int32]),
-    "nsg_bn_backward_conv1x1_dgrad_wgrad_workspace_bytes": (c_size_t, [c_int64, c_int32]),
-    "nsg_bn_backward_conv1x1_dgrad_wgrad": (None, [_P] * 18 + [c_int64, c_int32, c_int32, _P, c_size_t, _P]),
-    "nsg_bn_backward_apply": (None, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, _P, c_size_t, _P]),
-    "nsg_bn_backward_sums": (None, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, _P, c_size_t, _P]),
-    "nsg_relu_backward_add": (None, [_P, _P, _P, _P, c_int64, c_int32, _P]),
-    "nsg_convert": (None, [_P, c_int32, _P, c_int32, c_int64, c_int32, _P]),
-    "nsg_tanh_backward": (None, [_P, _P, _P, c_int64, _P]),
-    "nsg_add": (None, [_P, _P, _P, c_int64, _P]),
-    "nsg_add_per_clip": (None, [_P, _P, _P, c_int32, c_int64, c_int32, c_int32, _P]),
-    "nsg_clip_colsum_workspace_bytes": (c_size_t, [c_int32, c_int32]),
-    "nsg_clip_colsum": (None, [_P, c_int32, c_int32, c_int64, c_int32, _P, _P, c_size_t, _P]),
-    "nsg_reduce_workspace_bytes": (c_size_t, [c_int64]),
-    "nsg_mse_padded": (None, [_P, _P, c_int64, c_int32, c_int32, c_float, _P, _P, _P, c_size_t, _P]),
-    "nsg_vq_losses_indexed": (None, [_P, _P, _P, c_int64, c_int32, c_int32, c_float, _P, _P, _P, c_int32, _P, c_size_t, _P]),
-    "nsg_vq_losses_indexed_bn_supported": (c_int32, [c_int32]),
-    "nsg_vq_losses_indexed_bn_workspace_bytes": (c_size_t, [c_int64, c_int32]),
-    "nsg_vq_losses_indexed_bn": (None, [_P, _P, _P, c_int64, c_int32, c_int32, c_float, _P, _P, _P, c_int32, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
-    "nsg_vq_losses_indexed_bnres": (None, [_P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, c_float, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
-    "nsg_vq_losses": (None, [_P, _P, c_int64, c_float, c_float, _P, _P, _P, _P, c_int32, _P, c_size_t, _P]),
-    "nsg_adam_step": (None, [_P, _P, _P, _P, c_int64, c_float, c_float, c_float, c_float, c_int32, c_float, _P]),
-    "nsg_gated_activation_forward": (None, [_P, _P, _P, c_int64, c_int32, c_int64, _P]),
-    "nsg_gated_activation_backward": (None, [_P, _P, _P, _P, c_int64, c_int32, c_int64, _P]),
-    "nsg_cross_entropy_workspace_bytes": (c_size_t, [c_int64]),
-    "nsg_cross_entropy": (None, [_P, _P, c_int64, c_int32, c_float, _P, _P, _P, c_size_t, _P]),
-    "nsg_gated_activation_sum_forward": (None, [_P, _P, _P, _P, c_int64, c_int32, c_int64, _P]),
-    "nsg_gated_colsum_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int64]),
-    "nsg_gated_activation_sum_backward": (None, [_P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int64, _P, c_size_t, _P]),
-    "nsg_gated_activation_backward_colsum": (None, [_P, _P, _P, _P, _P, c_int64, c_int32, c_int64, _P, c_size_t, _P]),
-    "nsg_cross_entropy_masked_workspace_bytes": (c_size_t, [c_int64, c_int64]),
-    "nsg_cross_entropy_masked": (None, [_P, _P, c_int64, c_int32, c_int64, c_float, _P, _P, _P, _P, _P, c_size_t, _P]),
-    "nsg_prior_walk_weight_floats": (c_size_t, [c_int32, c_int32, c_int32]),
-    "nsg_prior_walk": (None, [_P, _P, _P, _P, _P, _P, _P, _P, c_int64, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P]),
-    "nsg_prior_walk_ctl": (None, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
-                                  c_float, c_int32, c_float, _P]),
-    "nsg_audio_mel_to_linear": (None, [_P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_float, c_float, _P]),
-    "nsg_audio_griffin_lim_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
-    "nsg_audio_griffin_lim": (None, [_P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, _P, c_size_t, _P]),
-    "nsg_audio_stft": (None, [_P, _P, c_int32, c_int32, c_int32, c_int32, _P]),
-    "nsg_audio_inv_preemphasis": (None, [_P, _P, c_int32, c_int32, c_float, _P]),
-    "nsg_audio_preemphasis": (None, [_P, _P, c_int32, c_int32, c_float, _P]),
-    "nsg_audio_melspectrogram": (None, [_P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_float, c_float, c_float,
-                                        c_int32, _P]),
-    "nsg_audio_resample": (None, [_P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, _P]),
-    "nsg_audio_trim_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
-    "nsg_audio_trim_bounds": (None, [_P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_float, _P, c_size_t, _P]),
-    "nsg_debug_dot": (None, [_P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P]),
-}
-# entry points declared in include/nsg.h: exactly the product library's exports (tests/test_abi.py checks both directions)
-HEADER_SYMBOLS = list(_SIGS)
-
-_lib = None
+HEADER_PATH = os.path.join(INCLUDE, "nsg.h")
 
 
 class NsgError(RuntimeError):
     pass
 
 
+class ConvDesc(Structure):
+    """struct nsg_conv_desc; its _fields_ are the header's, filled in below."""
+
+    def key(self):
+        return tuple(getattr(self, f) for f, _ in self._fields_)
+
+
+_SCALARS = {"int": c_int32, "int32_t": c_int32, "int64_t": c_int64, "size_t": c_size_t, "float": c_float}
+_PROTO = re.compile(r"NSG_API\s+([\w\s\*]+?)\b(nsg_\w+)\s*\(([^()]*)\)\s*;")
+
+
+def _ctype(decl, proto, ret=False):
+    """ctypes type of one parameter declaration of `proto`, or (ret) of its return type.  Nothing is defaulted."""
+    words = re.findall(r"\w+|\*", decl)
+    if "*" in words:
+        if ret:
+            if words == ["const", "char", "*"]:
+                return c_char_p
+        else:
+            return POINTER(ConvDesc) if "nsg_conv_desc" in words else c_void_p
+    else:
+        words = [w for w in words if w != "const"]
+        typ = " ".join(words if ret or len(words) == 1 else words[:-1])     # a parameter's last word is its name
+        if typ in _SCALARS:
+            return _SCALARS[typ]
+    raise NsgError(f"include/nsg.h: no ctypes mapping for '{decl.strip()}' in: {proto}")
+
+
+def parse_header(text):
+    """The ABI as header text states it -> (signatures: name -> (restype, argtypes), every NSG_API prototype in order;
+    constants: name -> int, the integer #defines and enumerators; the field names of struct nsg_conv_desc, in order)."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)      # the header's prose quotes function names
+    consts = {m[1]: int(m[2]) for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(NSG_\w+)[ \t]+(-?\d+)[ \t]*$", text, re.M)}
+    for body in re.findall(r"\benum\s*\w*\s*\{([^}]*)\}", text):
+        for item in filter(str.strip, body.split(",")):
+            m = re.fullmatch(r"\s*(\w+)\s*=\s*(-?\d+)\s*", item)
+            if not m:
+                raise NsgError(f"include/nsg.h: enumerator without an explicit integer value: '{item.strip()}'")
+            consts[m[1]] = int(m[2])
+    fields = []
+    m = re.search(r"\bstruct\s+nsg_conv_desc\s*\{([^}]*)\}", text)
+    for stmt in filter(str.strip, m[1].split(";")) if m else ():
+        typ, _, names = stmt.strip().partition(" ")
+        if typ != "int32_t":
+            raise NsgError(f"include/nsg.h: struct nsg_conv_desc holds int32_t fields only, got '{stmt.strip()}'")
+        fields += [n.strip() for n in names.split(",")]
+    sigs = {}
+    body = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)             # (#define NSG_API ... is not a prototype)
+    for at in re.finditer(r"\bNSG_API\b", body):
+        m = _PROTO.match(body, at.start())
+        if not m:
+            raise NsgError("include/nsg.h: cannot parse the prototype: " + " ".join(body[at.start():].split(";")[0].split()))
+        proto = " ".join(m[0].split())
+        params = [] if m[3].strip() == "void" else m[3].split(",")
+        sigs[m[2]] = (_ctype(m[1], proto, ret=True), [_ctype(a, proto) for a in params])
+    return sigs, consts, fields
+
+
+def _header():
+    try:
+        with open(HEADER_PATH) as f:
+            return parse_header(f.read())
+    except OSError as e:
+        raise NsgError(f"{HEADER_PATH}: cannot read the ABI header ({e})")
+
+
+# name -> (restype, argtypes) of every entry point include/nsg.h declares: exactly the product library's exports
+_SIGS, _CONSTS, _fields = _header()
+if not _fields:
+    raise NsgError(f"{HEADER_PATH}: struct nsg_conv_desc not found")
+ConvDesc._fields_ = [(f, c_int32) for f in _fields]
+HEADER_SYMBOLS = list(_SIGS)
+NSG_VERSION = _CONSTS["NSG_VERSION"]      # bumped in the header on ANY signature change; a library of another version is refused
+NSG_RELU_IN, NSG_TANH_OUT, NSG_OUT_F32, NSG_RELU_OUT, NSG_F32, NSG_BF16, NSG_C1_MOMENTS = (_CONSTS[n] for n in (
+    "NSG_RELU_IN", "NSG_TANH_OUT", "NSG_OUT_F32", "NSG_RELU_OUT", "NSG_F32", "NSG_BF16", "NSG_C1_MOMENTS"))
+
+_lib = None
+
+
 def _bind(lib):
     for name, (res, args) in _SIGS.items():
         fn = getattr(lib, name)
         fn.argtypes = args
-        fn.restype = c_int32 if res is None else res
+        fn.restype = res
     if lib.nsg_version() != NSG_VERSION:
-        raise NsgError(f"the HIP library reports ABI version {lib.nsg_version()}, this package binds version {NSG_VERSION}: rebuild it "
+        raise NsgError(f"the HIP library reports ABI version {lib.nsg_version()}, include/nsg.h declares version {NSG_VERSION}: rebuild it "
                        "(python -m neural_sound_generation_amd.build --force)")
     return lib
 

@@ -34,13 +34,13 @@ from __future__ import annotations
 
 import functools
 import math
-from ctypes import c_float, c_int32, c_size_t, c_void_p
+from ctypes import c_void_p
 
 import numpy as np
 import torch
 
 from . import _lib
-from .ops import WS, _chk, _p, _stream
+from .ops import _chk, _p, _stream, _ws
 
 MIN_LEVEL_DB, REF_LEVEL_DB, MAX_ABS_VALUE = -100.0, 20.0, 1.0     # hparams_tacotron.py:99,110,111
 POWER, GRIFFIN_LIM_ITERS, PREEMPHASIS = 1.5, 60, 0.97            # :116,117,107
@@ -89,8 +89,7 @@ def mel_to_linear(mel: torch.Tensor, sample_rate=22050, fft_size=1024, n_mels=80
     F = fft_size // 2 + 1
     inv = torch.from_numpy(_inv_mel_basis(sample_rate, fft_size, n_mels)).to(mel.device)
     S = torch.empty(B, T, F, dtype=torch.float32, device=mel.device)
-    _lib.call("nsg_audio_mel_to_linear", _p(mel), _p(inv), _p(S), c_int32(B), c_int32(M), c_int32(T), c_int32(F), c_float(MIN_LEVEL_DB),
-              c_float(REF_LEVEL_DB), c_float(MAX_ABS_VALUE), c_float(power), _stream())
+    _lib.call("nsg_audio_mel_to_linear", _p(mel), _p(inv), _p(S), B, M, T, F, MIN_LEVEL_DB, REF_LEVEL_DB, MAX_ABS_VALUE, power, _stream())
     return S
 
 
@@ -102,10 +101,8 @@ def griffin_lim(S: torch.Tensor, fft_size=1024, hop_size=256, iters=GRIFFIN_LIM_
         raise _lib.NsgError(f"griffin_lim: S has {F} bins, fft_size {fft_size} needs {fft_size // 2 + 1}")
     u = torch.rand(B, T, F, device=S.device) if angles0 is None else _chk(angles0.contiguous(), "angles0")
     y = torch.empty(B, hop_size * (T - 1), dtype=torch.float32, device=S.device)
-    nb = _lib.query("nsg_audio_griffin_lim_workspace_bytes", c_int32(B), c_int32(T), c_int32(fft_size))
-    ws = WS.get(nb, S.device)
-    _lib.call("nsg_audio_griffin_lim", _p(S), _p(u), _p(y), c_int32(B), c_int32(T), c_int32(fft_size), c_int32(hop_size), c_int32(iters),
-              _p(ws), c_size_t(nb), _stream())
+    ws, nb = _ws(S.device, "nsg_audio_griffin_lim_workspace_bytes", B, T, fft_size)
+    _lib.call("nsg_audio_griffin_lim", _p(S), _p(u), _p(y), B, T, fft_size, hop_size, iters, _p(ws), nb, _stream())
     return y
 
 
@@ -114,7 +111,7 @@ def stft(y: torch.Tensor, fft_size=1024, hop_size=256) -> torch.Tensor:
     _chk(y, "y")
     B, L = y.shape
     X = torch.empty(B, 1 + L // hop_size, fft_size // 2 + 1, 2, dtype=torch.float32, device=y.device)
-    _lib.call("nsg_audio_stft", _p(y), _p(X), c_int32(B), c_int32(L), c_int32(fft_size), c_int32(hop_size), _stream())
+    _lib.call("nsg_audio_stft", _p(y), _p(X), B, L, fft_size, hop_size, _stream())
     return torch.view_as_complex(X)
 
 
@@ -142,7 +139,7 @@ def preemphasis(y: torch.Tensor, k=PREEMPHASIS) -> torch.Tensor:
     _chk(y, "y")
     B, L = y.shape
     out = torch.empty_like(y)
-    _lib.call("nsg_audio_preemphasis", _p(y), _p(out), c_int32(B), c_int32(L), c_float(k), _stream())
+    _lib.call("nsg_audio_preemphasis", _p(y), _p(out), B, L, k, _stream())
     return out
 
 
@@ -186,9 +183,8 @@ def melspectrogram(wav, sample_rate=22050, fft_size=1024, hop_size=256, n_mels=8
     basis = _mel_basis_on(sample_rate, fft_size, n_mels, y.device)
     lens_d = torch.from_numpy(lens).to(y.device) if lens is not None else None
     out = torch.empty((B, T, n_mels) if LAYOUTS[layout] else (B, n_mels, T), dtype=torch.float32, device=y.device)
-    _lib.call("nsg_audio_melspectrogram", _p(y), _p(lens_d), _p(basis), c_void_p(bands.ctypes.data), _p(out), c_int32(B), c_int32(L),
-              c_int32(fft_size), c_int32(hop_size), c_int32(n_mels), c_float(PREEMPHASIS), c_float(MIN_LEVEL_DB), c_float(REF_LEVEL_DB),
-              c_float(MAX_ABS_VALUE), c_int32(LAYOUTS[layout]), _stream())
+    _lib.call("nsg_audio_melspectrogram", _p(y), _p(lens_d), _p(basis), c_void_p(bands.ctypes.data), _p(out), B, L, fft_size, hop_size, n_mels,
+              PREEMPHASIS, MIN_LEVEL_DB, REF_LEVEL_DB, MAX_ABS_VALUE, LAYOUTS[layout], _stream())
     return out[0].cpu().numpy() if as_numpy else out
 
 
@@ -196,7 +192,7 @@ def inv_preemphasis(y: torch.Tensor, k=PREEMPHASIS) -> torch.Tensor:
     _chk(y, "y")
     B, L = y.shape
     out = torch.empty_like(y)
-    _lib.call("nsg_audio_inv_preemphasis", _p(y), _p(out), c_int32(B), c_int32(L), c_float(k), _stream())
+    _lib.call("nsg_audio_inv_preemphasis", _p(y), _p(out), B, L, k, _stream())
     return out
 
 
@@ -345,7 +341,7 @@ def resample(wav, orig_sr, target_sr, lengths=None, device="cuda:0"):
     table = _resample_table_on(P, Q, str(y.device))
     lens_d = torch.from_numpy(lens).to(y.device) if lens is not None else None
     out = torch.empty(B, L_out, dtype=torch.float32, device=y.device)
-    _lib.call("nsg_audio_resample", _p(y), _p(lens_d), _p(table), _p(out), c_int32(B), c_int32(L), c_int32(P), c_int32(Q), c_int32(W), _stream())
+    _lib.call("nsg_audio_resample", _p(y), _p(lens_d), _p(table), _p(out), B, L, P, Q, W, _stream())
     if as_numpy:
         return out[0].cpu().numpy()
     src = lens.astype(np.int64) if lens is not None else np.full(B, L, dtype=np.int64)
@@ -374,10 +370,8 @@ def trim_silence(wav, top_db=20.0, frame_length=2048, hop_length=512, lengths=No
     _chk(y, "wav")
     lens_d = torch.from_numpy(lens).to(y.device) if lens is not None else None
     bounds = torch.empty(B, 2, dtype=torch.int32, device=y.device)
-    nb = _lib.query("nsg_audio_trim_workspace_bytes", c_int32(B), c_int32(L), c_int32(hop_length))
-    ws = WS.get(nb, y.device)
-    _lib.call("nsg_audio_trim_bounds", _p(y), _p(lens_d), _p(bounds), c_int32(B), c_int32(L), c_int32(frame_length), c_int32(hop_length),
-              c_float(top_db), _p(ws), c_size_t(nb), _stream())
+    ws, nb = _ws(y.device, "nsg_audio_trim_workspace_bytes", B, L, hop_length)
+    _lib.call("nsg_audio_trim_bounds", _p(y), _p(lens_d), _p(bounds), B, L, frame_length, hop_length, top_db, _p(ws), nb, _stream())
     if not as_numpy:
         return bounds
     start, end = (int(v) for v in bounds[0].cpu().numpy())

@@ -16,6 +16,7 @@ from concurrent.futures import ThreadPoolExecutor
 PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
+INCLUDE = os.path.join(ROOT, "include")      # nsg.h: the C ABI, which _lib.py binds from this very file
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(PKG, "libnsg.so")
 # The diagnostics library (scripts/ and the kernel-vs-kernel A/B tests): the same sources under -DNSG_DIAG -- run-time switches
@@ -27,7 +28,7 @@ SOURCES = ["api_common.hip", "gemm_gather.hip", "gemm_patch.hip", "gemm_wgrad.hi
 DIAG_SOURCES = SOURCES + ["diag.hip"]
 # -ffp-contract=off: the bit-exact VQ path spells out every fma itself; nothing may be re-fused.
 FLAGS = FLAGS_ = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "-fvisibility=hidden",
-         "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-Wall", "-Wno-unused-function"]
+         "-I" + INCLUDE, "-I" + CSRC, "-Wall", "-Wno-unused-function"]
 
 
 def hipcc() -> str:
@@ -50,7 +51,7 @@ def build(force: bool = False, verbose: bool = True, diag: bool = False) -> str:
                                 (globals()["OBJ"], globals()["LIB"], globals()["SOURCES"], FLAGS_))
     os.makedirs(OBJ, exist_ok=True)
     # every header any source may include: editing one rebuilds all objects (seconds per file)
-    headers = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join(ROOT, "include", "nsg.h")]
+    headers = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join(INCLUDE, "nsg.h")]
     cc = hipcc()
     jobs = []
     for src in SOURCES:

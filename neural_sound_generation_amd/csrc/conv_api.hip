@@ -9,41 +9,6 @@ NSG_DIAG_SWITCH(unsigned long long *, g_debug_stamps, nullptr)     // diagnostic
 extern "C" NSG_API void nsg_debug_set_stamp_buffer(unsigned long long *buf) { g_debug_stamps = buf; }
 #endif
 
-// stencil_c1.hip
-bool nsg_c1_stencil_supported(int C);
-size_t nsg_c1_stencil_wgrad_workspace_bytes(int C);
-int nsg_launch_c1_stencil_fwd(const float *img, const float *w, const float *bias, void *out, int out_dtype, int B, int LH, int LW,
-                              int HH, int WW, int C, hipStream_t s);
-// gemm_flat.hip: the ResBlock's 1x1 conv as a flat GEMM with BatchNorm work in its operand staging (nsg_bn_relu_conv1x1_*)
-bool nsg_flat1x1_supported(int dtype, int C);
-size_t nsg_flat1x1_workspace_bytes(int C);
-int nsg_launch_flat1x1_forward(const void *x, const float *mean, const float *invstd, const float *gamma, const float *beta, const float *w,
-                               const float *bias, void *y, int64_t M, int C, void *ws, int want_stats, int *nblocks, hipStream_t s);
-int nsg_launch_flat1x1_backward(const void *h, const void *dy, const float *mean, const float *invstd, const float *gamma, const float *dgamma,
-                                const float *dbeta, const float *w, void *dh, void *dx, int64_t M, int C, void *ws, int *nblocks,
-                                const void *prev_x, const float *prev_mean, const float *prev_invstd, const float *prev_gamma,
-                                const float *prev_beta, float **prev_partial, hipStream_t s);
-constexpr int C1_LOSS_BLOCKS = 1024;
-int nsg_launch_final_mean(const double *partial, int n, double denom, float *out, hipStream_t s);     // elementwise.hip
-bool nsg_flat1x1_fused_bwd_supported(int dtype, int C);
-size_t nsg_flat1x1_fused_bwd_workspace_bytes(int C);
-int nsg_launch_flat1x1_fused_bwd(const void *h, const void *dy, const float *mean, const float *invstd, const float *gamma, const float *dgamma,
-                                 const float *dbeta, const float *w, void *dx, float *dw, int64_t M, int C, void *ws, int *nblocks,
-                                 const void *prev_x, const float *prev_mean, const float *prev_invstd, const float *prev_gamma,
-                                 const float *prev_beta, float **colsum_partial, float **prev_partial, float **dw_partial, hipStream_t s);
-// c1_mfma.hip / stencil_c1.hip: pieces of the fused output layer (nsg_bn_relu_c1convt_*)
-bool nsg_c1m_supported(int C);
-int nsg_launch_bnrelu_dots(const void *u, const float *mean, const float *invstd, const float *gamma, const float *beta, const float *w,
-                           float *dots, int64_t M, int C, hipStream_t s);
-int nsg_launch_c1m_out_bwd_sums(const float *dimg, const float *w, const void *u, const float *mean, const float *invstd, const float *gamma,
-                                const float *beta, float *partial, int blocks, int B, int LH, int LW, int C, hipStream_t s);
-int nsg_launch_c1m_out_bwd_apply(const float *dimg, const float *w, const void *u, const float *mean, const float *invstd, const float *gamma,
-                                 const float *beta, const float *dgamma, const float *dbeta, float inv_m, float *partial17, void *du, int blocks,
-                                 int B, int LH, int LW, int C, hipStream_t s);
-int nsg_launch_c1_stencil_wgrad_final(const float *partial17, int blocks, int C, float *dw, float *colsum, hipStream_t s);
-int nsg_launch_c1_stencil_wgrad(const float *img, const void *t, int t_dtype, int relu_t, float *dw, float *colsum, int B, int LH,
-                                int LW, int HH, int WW, int C, void *ws, size_t ws_bytes, hipStream_t s);
-
 namespace {
 
 // One weight re-pack:  dst[(t*NN + n)*CC + c] = src[n*sn + c*sc + (flip ? T-1-t : t)]  (dst fp32 or bf16)

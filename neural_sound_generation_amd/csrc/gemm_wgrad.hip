@@ -802,11 +802,6 @@ int launch_wg(const WgradParams &p, int nslab, hipStream_t s)
 
 }  // namespace
 
-// gemm_wgrad_strip.hip: the row-strip kernel for the bf16 3x3/1 and 4x4/2 layers with channels in multiples of 128
-int nsg_wgrad_strip_slabs(int ntaps, int A, int C);
-bool nsg_wgrad_strip_applicable(const WgradParams &p);
-int nsg_launch_wgrad_strip(const WgradParams &p, int *nslab, hipStream_t s);
-
 // dst[(a*C + c)*ntaps + t] = sum over slabs (slab order) of partial[slab][t][a][c]: the closing pass of every weight gradient,
 // also used by gemm_flat.hip's fused data + weight gradient of the 1x1 conv
 int nsg_launch_wgrad_reduce(const float *partial, float *dst, int nslab, int ntaps, int A, int C, hipStream_t s)

@@ -299,3 +299,67 @@ int nsg_launch_bn_bwd_final_colsum(const float *partial, const float *colsum_par
                                    float *colsum, hipStream_t s);
 // out[c] = sum_s partial[s][c] over nslab <= 1024 slabs of [C] (fixed order, double)
 int nsg_launch_slab_sum_final(const float *partial, int nslab, int C, float *out, hipStream_t s);
+
+// ---- launchers and predicates one .hip file defines and another calls, grouped by the defining file.  No .hip file declares
+// a function it does not define: the definition is compiled against the declaration its callers see. -----------------------
+// stencil_c1.hip: the single-channel layers as stencils
+bool nsg_c1_stencil_supported(int C);
+size_t nsg_c1_stencil_wgrad_workspace_bytes(int C);
+int nsg_launch_c1_stencil_fwd(const float *img, const float *w, const float *bias, void *out, int out_dtype, int B, int LH, int LW,
+                              int HH, int WW, int C, hipStream_t s);
+int nsg_launch_c1_stencil_wgrad(const float *img, const void *t, int t_dtype, int relu_t, float *dw, float *colsum, int B, int LH,
+                                int LW, int HH, int WW, int C, void *ws, size_t ws_bytes, hipStream_t s);
+int nsg_launch_c1_stencil_wgrad_final(const float *partial17, int blocks, int C, float *dw, float *colsum, hipStream_t s);
+// gemm_flat.hip: the ResBlock's 1x1 conv as a flat GEMM with BatchNorm work in its operand staging (nsg_bn_relu_conv1x1_*)
+bool nsg_flat1x1_supported(int dtype, int C);
+size_t nsg_flat1x1_workspace_bytes(int C);
+int nsg_launch_flat1x1_forward(const void *x, const float *mean, const float *invstd, const float *gamma, const float *beta, const float *w,
+                               const float *bias, void *y, int64_t M, int C, void *ws, int want_stats, int *nblocks, hipStream_t s);
+int nsg_launch_flat1x1_backward(const void *h, const void *dy, const float *mean, const float *invstd, const float *gamma, const float *dgamma,
+                                const float *dbeta, const float *w, void *dh, void *dx, int64_t M, int C, void *ws, int *nblocks,
+                                const void *prev_x, const float *prev_mean, const float *prev_invstd, const float *prev_gamma,
+                                const float *prev_beta, float **prev_partial, hipStream_t s);
+bool nsg_flat1x1_fused_bwd_supported(int dtype, int C);
+size_t nsg_flat1x1_fused_bwd_workspace_bytes(int C);
+int nsg_launch_flat1x1_fused_bwd(const void *h, const void *dy, const float *mean, const float *invstd, const float *gamma, const float *dgamma,
+                                 const float *dbeta, const float *w, void *dx, float *dw, int64_t M, int C, void *ws, int *nblocks,
+                                 const void *prev_x, const float *prev_mean, const float *prev_invstd, const float *prev_gamma,
+                                 const float *prev_beta, float **colsum_partial, float **prev_partial, float **dw_partial, hipStream_t s);
+// elementwise.hip
+int nsg_launch_final_mean(const double *partial, int n, double denom, float *out, hipStream_t s);
+constexpr int C1_LOSS_BLOCKS = 1024;     // conv_api.hip: most blocks (= loss partials) of the output layer's col2im pass
+// c1_mfma.hip: pieces of the fused output layer (nsg_bn_relu_c1convt_*) ...
+bool nsg_c1m_supported(int C);
+int nsg_launch_bnrelu_dots(const void *u, const float *mean, const float *invstd, const float *gamma, const float *beta, const float *w,
+                           float *dots, int64_t M, int C, hipStream_t s);
+int nsg_launch_c1m_out_bwd_sums(const float *dimg, const float *w, const void *u, const float *mean, const float *invstd, const float *gamma,
+                                const float *beta, float *partial, int blocks, int B, int LH, int LW, int C, hipStream_t s);
+int nsg_launch_c1m_out_bwd_apply(const float *dimg, const float *w, const void *u, const float *mean, const float *invstd, const float *gamma,
+                                 const float *beta, const float *dgamma, const float *dbeta, float inv_m, float *partial17, void *du, int blocks,
+                                 int B, int LH, int LW, int C, hipStream_t s);
+// ... the input layer's four passes with the convolution on the matrix cores, for bf16 tensors ...
+int nsg_launch_c1m_stats(const float *img, const float *w, const float *bias, float *tiles, int blocks, int B, int LH, int LW, int HH, int WW,
+                         int C, hipStream_t s);
+int nsg_launch_c1m_apply(const float *img, const float *w, const float *bias, const float *mean, const float *invstd, const float *gamma,
+                         const float *beta, void *out, int blocks, int B, int LH, int LW, int HH, int WW, int C, hipStream_t s);
+int nsg_launch_c1m_bwd_sums(const float *img, const float *w, const float *bias, const void *dy, const float *mean, const float *invstd,
+                            const float *gamma, const float *beta, float *partial, int blocks, int B, int LH, int LW, int HH, int WW, int C,
+                            hipStream_t s);
+int nsg_launch_c1m_bwd_wgrad(const float *img, const float *w, const float *bias, const void *dy, const float *mean, const float *invstd,
+                             const float *gamma, const float *beta, const float *dgamma, const float *dbeta, float inv_m, float *partial,
+                             int blocks, int B, int LH, int LW, int HH, int WW, int C, hipStream_t s);
+// ... and the input layer by its tap moments: statistics without a pass over h, backward in one pass over dy
+size_t nsg_c1m_moments_bytes();
+int nsg_launch_c1m_moments(const float *img, int B, int LH, int LW, int HH, int WW, void *ws, double *mom_dst, const double **mom_out, hipStream_t s);
+int nsg_launch_c1m_stats_from_moments(const double *mom, const float *w, const float *bias, int64_t M, int C, float eps, float momentum,
+                                      float *mean, float *invstd, float *running_mean, float *running_var, hipStream_t s);
+int nsg_launch_c1m_bwd_onepass(const float *img, const float *w, const float *bias, const void *dy, const float *mean, const float *invstd,
+                               const float *gamma, const float *beta, float *sums, float *partial17, int blocks, int B, int LH, int LW,
+                               int HH, int WW, int C, hipStream_t s);
+int nsg_launch_c1m_onepass_fixup(const double *mom, const float *w, const float *bias, const float *mean, const float *invstd,
+                                 const float *gamma, const float *dgamma, const float *dbeta, int64_t M, int C, float *dw, float *dbias,
+                                 hipStream_t s);
+// gemm_wgrad_strip.hip: the row-strip kernel for the bf16 3x3/1 and 4x4/2 layers with channels in multiples of 128
+int nsg_wgrad_strip_slabs(int ntaps, int A, int C);
+bool nsg_wgrad_strip_applicable(const WgradParams &p);
+int nsg_launch_wgrad_strip(const WgradParams &p, int *nslab, hipStream_t s);

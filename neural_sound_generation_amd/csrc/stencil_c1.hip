@@ -640,30 +640,6 @@ int nsg_launch_c1_stencil_wgrad_final(const float *partial17, int blocks, int C,
 }
 
 // ---- the fused Conv2d(1, C, 4, 2, 1) + BatchNorm2d + ReLU layer (C ABI: include/nsg.h) ----
-// c1_mfma.hip: the same four passes with the convolution on the matrix cores, for bf16 tensors
-bool nsg_c1m_supported(int C);
-int nsg_launch_c1m_stats(const float *img, const float *w, const float *bias, float *tiles, int blocks, int B, int LH, int LW, int HH, int WW,
-                         int C, hipStream_t s);
-int nsg_launch_c1m_apply(const float *img, const float *w, const float *bias, const float *mean, const float *invstd, const float *gamma,
-                         const float *beta, void *out, int blocks, int B, int LH, int LW, int HH, int WW, int C, hipStream_t s);
-int nsg_launch_c1m_bwd_sums(const float *img, const float *w, const float *bias, const void *dy, const float *mean, const float *invstd,
-                            const float *gamma, const float *beta, float *partial, int blocks, int B, int LH, int LW, int HH, int WW, int C,
-                            hipStream_t s);
-int nsg_launch_c1m_bwd_wgrad(const float *img, const float *w, const float *bias, const void *dy, const float *mean, const float *invstd,
-                             const float *gamma, const float *beta, const float *dgamma, const float *dbeta, float inv_m, float *partial,
-                             int blocks, int B, int LH, int LW, int HH, int WW, int C, hipStream_t s);
-
-// ... and the input layer by its tap moments (c1_mfma.hip): statistics without a pass over h, backward in one pass over dy
-size_t nsg_c1m_moments_bytes();
-int nsg_launch_c1m_moments(const float *img, int B, int LH, int LW, int HH, int WW, void *ws, double *mom_dst, const double **mom_out, hipStream_t s);
-int nsg_launch_c1m_stats_from_moments(const double *mom, const float *w, const float *bias, int64_t M, int C, float eps, float momentum,
-                                      float *mean, float *invstd, float *running_mean, float *running_var, hipStream_t s);
-int nsg_launch_c1m_bwd_onepass(const float *img, const float *w, const float *bias, const void *dy, const float *mean, const float *invstd,
-                               const float *gamma, const float *beta, float *sums, float *partial17, int blocks, int B, int LH, int LW,
-                               int HH, int WW, int C, hipStream_t s);
-int nsg_launch_c1m_onepass_fixup(const double *mom, const float *w, const float *bias, const float *mean, const float *invstd,
-                                 const float *gamma, const float *dgamma, const float *dbeta, int64_t M, int C, float *dw, float *dbias,
-                                 hipStream_t s);
 NSG_DIAG_SWITCH(int, g_c1_moments, 1)     // nsg_debug_set_c1_moments (diagnostics library only): 0 = the two-pass forms (statistics pass over h; sums pass + gradient pass over dy)
 #ifdef NSG_DIAG
 extern "C" NSG_API void nsg_debug_set_c1_moments(int on) { g_c1_moments = on; }

@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import math
-from ctypes import byref, c_float, c_int32, c_int64, c_size_t, c_void_p
+from ctypes import byref, c_void_p
 from typing import NamedTuple
 
 import torch
@@ -77,6 +77,12 @@ class Workspace:
 
 
 WS = Workspace()
+
+
+def _ws(device, query, *args):
+    """(workspace on `device`, its size in bytes) as the size query `query` of an entry point asks for `args`."""
+    nb = _lib.query(query, *args)
+    return WS.get(nb, device), nb
 
 
 class KernelTimer:
@@ -202,31 +208,28 @@ def vq_forward(x2d, codebook, want_codes=True, want_dist=False, impl="mfma", cod
     dmin = torch.empty(N, dtype=torch.float32, device=x2d.device) if want_dist else None
     if N > 0:
         wsfn = "nsg_vq_bf16x3_workspace_bytes" if impl == "bf16x3" else "nsg_vq_workspace_bytes"
-        nb = _lib.query(wsfn, c_int64(N), c_int32(D), c_int32(K))
-        ws = WS.get(nb, x2d.device)
+        ws, nb = _ws(x2d.device, wsfn, N, D, K)
         fn = {"mfma": "nsg_vq_forward", "valu": "nsg_debug_vq_forward_valu", "bf16x3": "nsg_vq_forward_bf16x3"}[impl]
         if impl == "bf16x3":
             lp = torch.empty(N, D, dtype=torch.bfloat16, device=x2d.device) if codes_bf16 else None
             _lib.tag("vq_forward_bf16x3 (search + gather)", 2.0 * N * K * D)
             if bnres:
-                _lib.call("nsg_vq_forward_bf16x3_bnres", *x2d.pointers(), _p(codebook), c_int64(N), c_int32(D), c_int32(K), _p(idx), _p(None),
-                          _p(lp), c_int32(1 if codes_bf16 == "relu" else 0), _p(clip_rows),
-                          c_int64(N // clip_rows.shape[0] if clip_rows is not None else 0), _p(ws), c_size_t(nb), _stream())
+                _lib.call("nsg_vq_forward_bf16x3_bnres", *x2d.pointers(), _p(codebook), N, D, K, _p(idx), _p(None), _p(lp),
+                          1 if codes_bf16 == "relu" else 0, _p(clip_rows), N // clip_rows.shape[0] if clip_rows is not None else 0, _p(ws), nb,
+                          _stream())
             elif clip_rows is not None:
-                _lib.call("nsg_vq_forward_bf16x3_cond", _p(x2d), _p(codebook), c_int64(N), c_int32(D), c_int32(K), _p(idx), _p(codes), _p(dmin),
-                          _p(lp), c_int32(1 if codes_bf16 == "relu" else 0), _p(clip_rows), c_int64(N // clip_rows.shape[0]), _p(ws),
-                          c_size_t(nb), _stream())
+                _lib.call("nsg_vq_forward_bf16x3_cond", _p(x2d), _p(codebook), N, D, K, _p(idx), _p(codes), _p(dmin), _p(lp),
+                          1 if codes_bf16 == "relu" else 0, _p(clip_rows), N // clip_rows.shape[0], _p(ws), nb, _stream())
             else:
-                _lib.call(fn, _p(x2d), _p(codebook), c_int64(N), c_int32(D), c_int32(K), _p(idx), _p(codes), _p(dmin), _p(lp),
-                          c_int32(1 if codes_bf16 == "relu" else 0), _p(ws), c_size_t(nb), _stream())
+                _lib.call(fn, _p(x2d), _p(codebook), N, D, K, _p(idx), _p(codes), _p(dmin), _p(lp), 1 if codes_bf16 == "relu" else 0, _p(ws), nb,
+                          _stream())
             if codes_bf16:
                 return idx, codes, dmin, lp
             return idx, codes, dmin
         if codes_bf16:
             raise ValueError("vq_forward: codes_bf16 needs impl='bf16x3'")
         _lib.tag("vq_forward (fp32 exact search + gather)", 2.0 * N * K * D)
-        _lib.call(fn, _p(x2d), _p(codebook), c_int64(N), c_int32(D), c_int32(K), _p(idx), _p(codes), _p(dmin),
-                  _p(ws), c_size_t(nb), _stream())
+        _lib.call(fn, _p(x2d), _p(codebook), N, D, K, _p(idx), _p(codes), _p(dmin), _p(ws), nb, _stream())
     elif codes_bf16:
         return idx, codes, dmin, torch.empty(0, D, dtype=torch.bfloat16, device=x2d.device)
     return idx, codes, dmin
@@ -235,7 +238,7 @@ def vq_forward(x2d, codebook, want_codes=True, want_dist=False, impl="mfma", cod
 def rowsumsq(v):
     _chk(v, "v")
     out = torch.empty(v.shape[0], dtype=torch.float32, device=v.device)
-    _lib.call("nsg_rowsumsq", _p(v), c_int64(v.shape[0]), c_int32(v.shape[1]), _p(out), _stream())
+    _lib.call("nsg_rowsumsq", _p(v), v.shape[0], v.shape[1], _p(out), _stream())
     return out
 
 
@@ -277,21 +280,17 @@ def index_add_rows(idx, g2d, K, want_counts=False, impl="f32", out=None, counts=
             if counts is not None:
                 counts.zero_()
             return (out, counts) if want_counts else out
-        nb = _lib.query("nsg_index_add_sorted_workspace_bytes", c_int64(N), c_int32(D), c_int32(K))
-        ws = WS.get(nb, g2d.device)
+        ws, nb = _ws(g2d.device, "nsg_index_add_sorted_workspace_bytes", N, D, K)
         _lib.tag("index_add_rows (sorted segment sum)", 0, 4.0 * N * D + 8.0 * N)     # (two bf16 sources = the fp32 rows' bytes)
         if bnres:
-            _lib.call("nsg_index_add_rows_sorted_bnres", _p(idx), *g2d.pointers(), c_int64(N), c_int32(D), c_int32(K), _p(out), _p(counts), _p(ws),
-                      c_size_t(nb), _stream())
+            _lib.call("nsg_index_add_rows_sorted_bnres", _p(idx), *g2d.pointers(), N, D, K, _p(out), _p(counts), _p(ws), nb, _stream())
             return (out, counts) if want_counts else out
-        _lib.call("nsg_index_add_rows_sorted", _p(idx), _p(g2d), c_int64(N), c_int32(D), c_int32(K), _p(out), _p(counts), _p(ws), c_size_t(nb),
-                  _stream())
+        _lib.call("nsg_index_add_rows_sorted", _p(idx), _p(g2d), N, D, K, _p(out), _p(counts), _p(ws), nb, _stream())
         return (out, counts) if want_counts else out
-    nb = _lib.query("nsg_index_add_workspace_bytes", c_int64(N), c_int32(D), c_int32(K))
-    ws = WS.get(nb, g2d.device)
+    ws, nb = _ws(g2d.device, "nsg_index_add_workspace_bytes", N, D, K)
     _lib.tag("index_add_rows (one-hot GEMM, %s)" % impl, 2.0 * N * K * D, 4.0 * N * D + 8.0 * N)
-    _lib.call("nsg_index_add_rows_bf16x2" if impl == "bf16x2" else "nsg_index_add_rows", _p(idx), _p(g2d), c_int64(N), c_int32(D),
-              c_int32(K), _p(out), _p(counts), _p(ws), c_size_t(nb), _stream())
+    _lib.call("nsg_index_add_rows_bf16x2" if impl == "bf16x2" else "nsg_index_add_rows", _p(idx), _p(g2d), N, D, K, _p(out), _p(counts), _p(ws), nb,
+              _stream())
     return (out, counts) if want_counts else out
 
 
@@ -302,7 +301,7 @@ def codebook_grad_from_sums(codebook, n, s, scale, out):
     K, D = codebook.shape
     if n.numel() != K or s.numel() != K * D or out.numel() != K * D:
         raise _lib.NsgError("codebook_grad_from_sums: n, s and out must match the codebook's (K, D)")
-    _lib.call("nsg_codebook_grad_from_sums", _p(codebook), _p(n), _p(s), c_int32(K), c_int32(D), c_float(scale), _p(out), _stream())
+    _lib.call("nsg_codebook_grad_from_sums", _p(codebook), _p(n), _p(s), K, D, scale, _p(out), _stream())
     return out
 
 
@@ -323,7 +322,7 @@ def code_usage(idx, K, window, stats=None, batch_counts=None):
     elif _chk(stats, "stats", torch.float64).numel() != 2:
         raise _lib.NsgError("code_usage: stats must hold two float64 values")
     _lib.tag("code_usage (histogram + perplexity)", 0, 8.0 * idx.numel())
-    _lib.call("nsg_code_usage", _p(idx), c_int64(idx.numel()), c_int32(K), _p(batch_counts), _p(window), _p(stats), _stream())
+    _lib.call("nsg_code_usage", _p(idx), idx.numel(), K, _p(batch_counts), _p(window), _p(stats), _stream())
     return batch_counts, stats
 
 
@@ -357,8 +356,8 @@ def vq_revive(rows, codebook, window, min_count=1, base_row=0, stride=1, adam_m=
         stats = torch.zeros(2, dtype=torch.int64, device=codebook.device)
     elif _chk(stats, "stats", torch.int64).numel() != 2:
         raise _lib.NsgError("vq_revive: stats must hold two int64 values")
-    tail = (c_int64(N), c_int32(D), _p(codebook), c_int32(K), _p(window), c_int32(int(min_count)), c_int64(int(base_row)), c_int64(int(stride)),
-            _p(adam_m), _p(adam_v), _p(ema_count), _p(ema_sum), _p(slot), _p(stats), c_int32(1 if revive_all else 0), _stream())
+    tail = (N, D, _p(codebook), K, _p(window), int(min_count), int(base_row), int(stride),
+            _p(adam_m), _p(adam_v), _p(ema_count), _p(ema_sum), _p(slot), _p(stats), 1 if revive_all else 0, _stream())
     _lib.tag("vq_revive (dead-code re-seed)", 0, 8.0 * K * D)
     if bnres:
         _lib.call("nsg_vq_revive_bnres", *rows.pointers(), *tail)
@@ -377,7 +376,7 @@ def increment_counters(counters):
         if not t.is_cuda or t.dtype != torch.int64 or t.numel() != 1:
             raise _lib.NsgError("increment_counters: expected int64 GPU scalars")
         arr[i] = t.data_ptr()
-    _lib.call("nsg_increment_counters", ctypes.cast(arr, c_void_p), c_int32(n), _stream())
+    _lib.call("nsg_increment_counters", ctypes.cast(arr, c_void_p), n, _stream())
 
 
 def gather_rows(codebook, idx, out=None):
@@ -388,21 +387,19 @@ def gather_rows(codebook, idx, out=None):
         out = torch.empty(*idx.shape, D, dtype=torch.float32, device=codebook.device)
     elif _chk(out, "out").numel() != idx.numel() * D:
         raise _lib.NsgError(f"gather_rows: out {tuple(out.shape)} does not hold {idx.numel()} rows of {D}")
-    _lib.call("nsg_gather_rows", _p(codebook), _p(idx), c_int64(idx.numel()), c_int32(D), c_int32(K), _p(out), _stream())
+    _lib.call("nsg_gather_rows", _p(codebook), _p(idx), idx.numel(), D, K, _p(out), _stream())
     return out
 
 
 def vq_ema_update(codebook, ema_n, ema_s, n, s, decay=0.99, eps=1e-5):
     K, D = codebook.shape
     scratch = torch.empty(1, dtype=torch.float32, device=codebook.device)
-    _lib.call("nsg_vq_ema_update", _p(codebook), _p(ema_n), _p(ema_s), _p(n), _p(s), c_int32(K), c_int32(D),
-              c_float(decay), c_float(eps), _p(scratch), _stream())
+    _lib.call("nsg_vq_ema_update", _p(codebook), _p(ema_n), _p(ema_s), _p(n), _p(s), K, D, decay, eps, _p(scratch), _stream())
 
 
 def debug_dot(x, e, mode):
     out = torch.empty(x.shape[0], e.shape[0], dtype=torch.float32, device=x.device)
-    _lib.call("nsg_debug_dot", _p(x), _p(e), c_int32(x.shape[0]), c_int32(x.shape[1]), c_int32(e.shape[0]), c_int32(mode),
-              _p(out), _stream())
+    _lib.call("nsg_debug_dot", _p(x), _p(e), x.shape[0], x.shape[1], e.shape[0], mode, _p(out), _stream())
     return out
 
 
@@ -462,14 +459,19 @@ def pack_weights_batch(jobs):
         dp[i] = wd.data_ptr() if wd is not None else None
         out.append((wf, wd))
     _lib.tag("pack_weights_batch", 0, sum(4.0 * j[1].numel() for j in jobs) + sum((a.numel() * _es(a) if a is not None else 0) + (b.numel() * _es(b) if b is not None else 0) for a, b in out))
-    _lib.call("nsg_pack_conv_weights_batch", c_int32(n), ctypes.cast(descs, c_void_p), ctypes.cast(wp, c_void_p),
-              ctypes.cast(fp, c_void_p), ctypes.cast(dp, c_void_p), _stream())
+    _lib.call("nsg_pack_conv_weights_batch", n, descs, ctypes.cast(wp, c_void_p), ctypes.cast(fp, c_void_p), ctypes.cast(dp, c_void_p), _stream())
     return out
 
 
-def _conv_ws(d, device):
-    nb = _lib.query("nsg_conv_workspace_bytes", byref(d))
-    return WS.get(nb, device), nb
+def _gemm_call(d: ConvDesc, role, name, *args):
+    """One forward / dgrad launch of layer d: the census tag, and KERNEL_TIMER's events around the multi-channel layers (the
+    single-kernel gather GEMMs) when bench.py has set one."""
+    timed = KERNEL_TIMER is not None and d.C_in > 1 and d.C_out > 1
+    t0 = KERNEL_TIMER.begin() if timed else None
+    _lib.tag(_conv_label(d, role), _gemm_flops(d))
+    _lib.call(name, *args)
+    if timed:
+        KERNEL_TIMER.end("gather_gemm_f32", t0, _gemm_flops(d))
 
 
 def conv_forward(d: ConvDesc, x, w_fwd, bias, flags=0, out=None):
@@ -478,13 +480,8 @@ def conv_forward(d: ConvDesc, x, w_fwd, bias, flags=0, out=None):
     if tuple(x.shape) != (d.B, d.IH, d.IW, d.C_in):
         raise _lib.NsgError(f"conv_forward: input shape {tuple(x.shape)} does not match descriptor {d.key()}")
     y = out if out is not None else torch.empty(d.B, d.OH, d.OW, d.C_out, dtype=_out_dtype(d, flags), device=x.device)
-    ws, nb = _conv_ws(d, x.device)
-    timed = KERNEL_TIMER is not None and d.C_in > 1 and d.C_out > 1
-    t0 = KERNEL_TIMER.begin() if timed else None
-    _lib.tag(_conv_label(d, "forward"), _gemm_flops(d))
-    _lib.call("nsg_conv_forward", byref(d), _p(x), _p(w_fwd), _p(bias), _p(y), c_int32(flags), _p(ws), c_size_t(nb), _stream())
-    if timed:
-        KERNEL_TIMER.end("gather_gemm_f32", t0, _gemm_flops(d))
+    ws, nb = _ws(x.device, "nsg_conv_workspace_bytes", byref(d))
+    _gemm_call(d, "forward", "nsg_conv_forward", byref(d), _p(x), _p(w_fwd), _p(bias), _p(y), flags, _p(ws), nb, _stream())
     return y
 
 
@@ -497,14 +494,9 @@ def conv_forward_bnstats(d: ConvDesc, x, w_fwd, bias, flags=0, running_mean=None
     y = out if out is not None else torch.empty(d.B, d.OH, d.OW, d.C_out, dtype=_out_dtype(d, flags), device=x.device)
     mean = torch.empty(d.C_out, dtype=torch.float32, device=x.device)
     invstd = torch.empty(d.C_out, dtype=torch.float32, device=x.device)
-    ws, nb = _conv_ws(d, x.device)
-    timed = KERNEL_TIMER is not None and d.C_in > 1 and d.C_out > 1
-    t0 = KERNEL_TIMER.begin() if timed else None
-    _lib.tag(_conv_label(d, "forward"), _gemm_flops(d))
-    _lib.call("nsg_conv_forward_bnstats", byref(d), _p(x), _p(w_fwd), _p(bias), _p(y), c_int32(flags), c_float(eps),
-              c_float(momentum), _p(mean), _p(invstd), _p(running_mean), _p(running_var), _p(ws), c_size_t(nb), _stream())
-    if timed:
-        KERNEL_TIMER.end("gather_gemm_f32", t0, _gemm_flops(d))
+    ws, nb = _ws(x.device, "nsg_conv_workspace_bytes", byref(d))
+    _gemm_call(d, "forward", "nsg_conv_forward_bnstats", byref(d), _p(x), _p(w_fwd), _p(bias), _p(y), flags, eps, momentum, _p(mean), _p(invstd),
+               _p(running_mean), _p(running_var), _p(ws), nb, _stream())
     return y, mean, invstd
 
 
@@ -514,23 +506,16 @@ def conv_dgrad(d: ConvDesc, dy, w_dgrad, out=None, add=None, relu_x=None):
     if tuple(dy.shape) != (d.B, d.OH, d.OW, d.C_out):
         raise _lib.NsgError(f"conv_dgrad: dy shape {tuple(dy.shape)} does not match descriptor {d.key()}")
     dx = out if out is not None else torch.empty(d.B, d.IH, d.IW, d.C_in, dtype=_in_dtype(d), device=dy.device)
-    ws, nb = _conv_ws(d, dy.device)
-    timed = KERNEL_TIMER is not None and d.C_in > 1 and d.C_out > 1
-    t0 = KERNEL_TIMER.begin() if timed else None
+    ws, nb = _ws(dy.device, "nsg_conv_workspace_bytes", byref(d))
     if add is not None or relu_x is not None:
         for t, nm in ((add, "add"), (relu_x, "relu_x")):
             if t is not None:
                 _chk(t, nm, dx.dtype)
                 if t.shape != dx.shape:
                     raise _lib.NsgError(f"conv_dgrad: {nm} shape {tuple(t.shape)} does not match dx {tuple(dx.shape)}")
-        _lib.tag(_conv_label(d, "dgrad"), _gemm_flops(d))
-        _lib.call("nsg_conv_dgrad_relu_add", byref(d), _p(dy), _p(w_dgrad), _p(add), _p(relu_x), _p(dx), c_int32(0), _p(ws),
-                  c_size_t(nb), _stream())
+        _gemm_call(d, "dgrad", "nsg_conv_dgrad_relu_add", byref(d), _p(dy), _p(w_dgrad), _p(add), _p(relu_x), _p(dx), 0, _p(ws), nb, _stream())
     else:
-        _lib.tag(_conv_label(d, "dgrad"), _gemm_flops(d))
-        _lib.call("nsg_conv_dgrad", byref(d), _p(dy), _p(w_dgrad), _p(dx), c_int32(0), _p(ws), c_size_t(nb), _stream())
-    if timed:
-        KERNEL_TIMER.end("gather_gemm_f32", t0, _gemm_flops(d))
+        _gemm_call(d, "dgrad", "nsg_conv_dgrad", byref(d), _p(dy), _p(w_dgrad), _p(dx), 0, _p(ws), nb, _stream())
     return dx
 
 
@@ -540,9 +525,9 @@ def conv_wgrad(d: ConvDesc, x, dy, w_shape, flags=0, dw=None, dbias=None, want_b
         dw = torch.empty(w_shape, dtype=torch.float32, device=x.device)
     if dbias is None and want_bias:
         dbias = torch.empty(d.C_out, dtype=torch.float32, device=x.device)
-    ws, nb = _conv_ws(d, x.device)
+    ws, nb = _ws(x.device, "nsg_conv_workspace_bytes", byref(d))
     _lib.tag(_conv_label(d, "wgrad"), _gemm_flops(d))
-    _lib.call("nsg_conv_wgrad", byref(d), _p(x), _p(dy), _p(dw), _p(dbias), c_int32(flags), _p(ws), c_size_t(nb), _stream())
+    _lib.call("nsg_conv_wgrad", byref(d), _p(x), _p(dy), _p(dw), _p(dbias), flags, _p(ws), nb, _stream())
     return dw, dbias
 
 
@@ -554,11 +539,10 @@ def bn_stats(x, C, running_mean=None, running_var=None, eps=BN_EPS, momentum=BN_
     M = x.numel() // C
     mean = torch.empty(C, dtype=torch.float32, device=x.device)
     invstd = torch.empty(C, dtype=torch.float32, device=x.device)
-    nb = _lib.query("nsg_bn_workspace_bytes", c_int64(M), c_int32(C))
-    ws = WS.get(nb, x.device)
+    ws, nb = _ws(x.device, "nsg_bn_workspace_bytes", M, C)
     _lib.tag("bn_stats", 0, x.numel() * _es(x))
-    _lib.call("nsg_bn_stats", _p(x), c_int64(M), c_int32(C), c_int32(nsg_dtype(x.dtype)), c_float(eps), c_float(momentum), _p(mean), _p(invstd),
-              _p(running_mean), _p(running_var), _p(ws), c_size_t(nb), _stream())
+    _lib.call("nsg_bn_stats", _p(x), M, C, nsg_dtype(x.dtype), eps, momentum, _p(mean), _p(invstd), _p(running_mean), _p(running_var), _p(ws), nb,
+              _stream())
     return mean, invstd
 
 
@@ -566,7 +550,7 @@ def bn_eval_stats(running_mean, running_var, eps=BN_EPS):
     C = running_mean.numel()
     mean = torch.empty(C, dtype=torch.float32, device=running_mean.device)
     invstd = torch.empty(C, dtype=torch.float32, device=running_mean.device)
-    _lib.call("nsg_bn_eval_stats", _p(running_mean), _p(running_var), c_int32(C), c_float(eps), _p(mean), _p(invstd), _stream())
+    _lib.call("nsg_bn_eval_stats", _p(running_mean), _p(running_var), C, eps, _p(mean), _p(invstd), _stream())
     return mean, invstd
 
 
@@ -581,10 +565,8 @@ def bn_apply(x, mean, invstd, gamma, beta, relu=False, residual=None, relu_resid
     M = x.numel() // C
     y = out if out is not None else torch.empty(x.shape, dtype=out_dtype or x.dtype, device=x.device)
     _lib.tag("bn_apply", 0, x.numel() * _es(x) * (2 if residual is not None else 1) + y.numel() * _es(y))
-    _lib.call("nsg_bn_apply", _p(x), _p(mean), _p(invstd), _p(gamma), _p(beta), _p(residual), _p(y), c_int64(M), c_int32(C),
-              c_int32((1 if relu else 0) | (2 if relu_out else 0)), c_int32(1 if relu_residual else 0), c_int32(nsg_dtype(x.dtype)),
-              c_int32(nsg_dtype(y.dtype)),
-              _stream())
+    _lib.call("nsg_bn_apply", _p(x), _p(mean), _p(invstd), _p(gamma), _p(beta), _p(residual), _p(y), M, C,
+              (1 if relu else 0) | (2 if relu_out else 0), 1 if relu_residual else 0, nsg_dtype(x.dtype), nsg_dtype(y.dtype), _stream())
     return y
 
 
@@ -602,18 +584,17 @@ def bn_backward(x, y_relu, dy, mean, invstd, gamma, dgamma=None, dbeta=None, out
         dgamma = torch.empty(C, dtype=torch.float32, device=x.device)
     if dbeta is None:
         dbeta = torch.empty(C, dtype=torch.float32, device=x.device)
-    nb = _lib.query("nsg_bn_workspace_bytes", c_int64(M), c_int32(C))
-    ws = WS.get(nb, x.device)
+    ws, nb = _ws(x.device, "nsg_bn_workspace_bytes", M, C)
     _lib.tag("bn_backward (sums pass + apply pass)", 0, 5.0 * x.numel() * _es(x))
     _lib.call("nsg_bn_backward", _p(x), _p(y_relu), _p(dy), _p(mean), _p(invstd), _p(gamma), _p(relu_beta), _p(dx), _p(dgamma), _p(dbeta),
-              _p(dx_colsum), c_int64(M), c_int32(C), c_int32(nsg_dtype(x.dtype)), _p(ws), c_size_t(nb), _stream())
+              _p(dx_colsum), M, C, nsg_dtype(x.dtype), _p(ws), nb, _stream())
     return dx, dgamma, dbeta
 
 
 # ------------------------------------------------------------------------------------------------
 # encoder.0-2 as one operator: Conv2d(1, C, 4, 2, 1) -> BatchNorm2d -> ReLU   (src/models.py:165-167)
 # ------------------------------------------------------------------------------------------------
-C1_MOMENTS = 273      # include/nsg.h: NSG_C1_MOMENTS
+C1_MOMENTS = _lib.NSG_C1_MOMENTS
 
 
 def c1conv_bn_relu_forward(img, w, bias, gamma, beta, running_mean=None, running_var=None, training=True, eps=1e-5, momentum=0.1,
@@ -635,12 +616,10 @@ def c1conv_bn_relu_forward(img, w, bias, gamma, beta, running_mean=None, running
     elif mean is None or invstd is None:
         raise ValueError("c1conv_bn_relu_forward: eval mode needs mean and invstd")
     y = torch.empty((B, H // 2, W // 2, C), dtype=out_dtype, device=img.device)
-    nb = _lib.query("nsg_c1conv_bn_workspace_bytes", c_int32(C))
-    ws = WS.get(nb, img.device)
+    ws, nb = _ws(img.device, "nsg_c1conv_bn_workspace_bytes", C)
     _lib.tag("c1conv_bn_relu_forward (fused input layer)", 2.0 * 16 * y.numel() * (2 if training else 1), 4.0 * img.numel() * (2 if training else 1) + y.numel() * _es(y))
-    _lib.call("nsg_c1conv_bn_relu_forward", _p(img), _p(w), _p(bias), _p(gamma), _p(beta), _p(mean), _p(invstd), _p(running_mean),
-              _p(running_var), c_float(eps), c_float(momentum), c_int32(1 if training else 0), _p(y), c_int32(nsg_dtype(out_dtype)),
-              c_int32(B), c_int32(H), c_int32(W), c_int32(C), _p(ws), c_size_t(nb), _p(moments), _stream())
+    _lib.call("nsg_c1conv_bn_relu_forward", _p(img), _p(w), _p(bias), _p(gamma), _p(beta), _p(mean), _p(invstd), _p(running_mean), _p(running_var),
+              eps, momentum, 1 if training else 0, _p(y), nsg_dtype(out_dtype), B, H, W, C, _p(ws), nb, _p(moments), _stream())
     return y, mean, invstd
 
 
@@ -657,13 +636,11 @@ def c1conv_bn_relu_backward(img, w, bias, gamma, beta, mean, invstd, dy, dw=None
     dbias = dbias if dbias is not None else torch.empty(C, dtype=torch.float32, device=dev)
     dgamma = dgamma if dgamma is not None else torch.empty(C, dtype=torch.float32, device=dev)
     dbeta = dbeta if dbeta is not None else torch.empty(C, dtype=torch.float32, device=dev)
-    nb = _lib.query("nsg_c1conv_bn_workspace_bytes", c_int32(C))
-    ws = WS.get(nb, dev)
+    ws, nb = _ws(dev, "nsg_c1conv_bn_workspace_bytes", C)
     passes = 1.0 if dy.dtype == torch.bfloat16 else 2.0          # bf16: one pass over dy (tap moments), fp32: sums pass + gradient pass
     _lib.tag("c1conv_bn_relu_backward (fused input layer)", 2.0 * 16 * dy.numel() * 3, passes * (4.0 * img.numel() + dy.numel() * _es(dy)))
-    _lib.call("nsg_c1conv_bn_relu_backward", _p(img), _p(w), _p(bias), _p(gamma), _p(beta), _p(mean), _p(invstd), _p(dy),
-              c_int32(nsg_dtype(dy.dtype)), _p(dw), _p(dbias), _p(dgamma), _p(dbeta), c_int32(B), c_int32(H), c_int32(W), c_int32(C),
-              _p(ws), c_size_t(nb), _p(moments), _stream())
+    _lib.call("nsg_c1conv_bn_relu_backward", _p(img), _p(w), _p(bias), _p(gamma), _p(beta), _p(mean), _p(invstd), _p(dy), nsg_dtype(dy.dtype), _p(dw),
+              _p(dbias), _p(dgamma), _p(dbeta), B, H, W, C, _p(ws), nb, _p(moments), _stream())
     return dw, dbias, dgamma, dbeta
 
 
@@ -671,12 +648,7 @@ def c1conv_bn_relu_backward(img, w, bias, gamma, beta, mean, invstd, dy, dw=None
 # the ResBlock's 1x1 conv with the BatchNorm work around it folded in   (src/models.py:151-155)
 # ------------------------------------------------------------------------------------------------
 def bn_relu_conv1x1_supported(dtype, C) -> bool:
-    return bool(_lib.query("nsg_bn_relu_conv1x1_supported", c_int32(nsg_dtype(dtype)), c_int32(C)))
-
-
-def _ws_1x1(M, C, dev):
-    nb = _lib.query("nsg_bn_relu_conv1x1_workspace_bytes", c_int64(M), c_int32(C))
-    return WS.get(nb, dev), nb
+    return bool(_lib.query("nsg_bn_relu_conv1x1_supported", nsg_dtype(dtype), C))
 
 
 def bn_relu_conv1x1_forward(x, mean, invstd, gamma, beta, w, bias):
@@ -685,10 +657,10 @@ def bn_relu_conv1x1_forward(x, mean, invstd, gamma, beta, w, bias):
     C = x.shape[-1]
     M = x.numel() // C
     y = torch.empty_like(x)
-    ws, nb = _ws_1x1(M, C, x.device)
+    ws, nb = _ws(x.device, "nsg_bn_relu_conv1x1_workspace_bytes", M, C)
     _lib.tag("flat_gemm 1x1 forward (bn+relu on load)", 2.0 * M * C * C, 2.0 * x.numel() * _es(x))
-    _lib.call("nsg_bn_relu_conv1x1_forward", _p(x), _p(mean), _p(invstd), _p(gamma), _p(beta), _p(w), _p(bias), _p(y), c_int64(M), c_int32(C),
-              c_int32(nsg_dtype(x.dtype)), _p(ws), c_size_t(nb), _stream())
+    _lib.call("nsg_bn_relu_conv1x1_forward", _p(x), _p(mean), _p(invstd), _p(gamma), _p(beta), _p(w), _p(bias), _p(y), M, C, nsg_dtype(x.dtype),
+              _p(ws), nb, _stream())
     return y
 
 
@@ -702,11 +674,10 @@ def bn_relu_conv1x1_forward_bnstats(x, mean, invstd, gamma, beta, w, bias, runni
     y = torch.empty_like(x)
     mean_y = torch.empty(C, dtype=torch.float32, device=x.device)
     invstd_y = torch.empty(C, dtype=torch.float32, device=x.device)
-    ws, nb = _ws_1x1(M, C, x.device)
+    ws, nb = _ws(x.device, "nsg_bn_relu_conv1x1_workspace_bytes", M, C)
     _lib.tag("flat_gemm 1x1 forward (bn+relu on load, stats out)", 2.0 * M * C * C, 2.0 * x.numel() * _es(x))
-    _lib.call("nsg_bn_relu_conv1x1_forward_bnstats", _p(x), _p(mean), _p(invstd), _p(gamma), _p(beta), _p(w), _p(bias), _p(y), c_float(eps),
-              c_float(momentum), _p(mean_y), _p(invstd_y), _p(running_mean), _p(running_var), c_int64(M), c_int32(C),
-              c_int32(nsg_dtype(x.dtype)), _p(ws), c_size_t(nb), _stream())
+    _lib.call("nsg_bn_relu_conv1x1_forward_bnstats", _p(x), _p(mean), _p(invstd), _p(gamma), _p(beta), _p(w), _p(bias), _p(y), eps, momentum,
+              _p(mean_y), _p(invstd_y), _p(running_mean), _p(running_var), M, C, nsg_dtype(x.dtype), _p(ws), nb, _stream())
     return y, mean_y, invstd_y
 
 
@@ -716,10 +687,10 @@ def bn_relu_conv1x1_wgrad(x, mean, invstd, gamma, beta, dy, dw=None):
     C = x.shape[-1]
     M = x.numel() // C
     dw = dw if dw is not None else torch.empty((C, C, 1, 1), dtype=torch.float32, device=x.device)
-    ws, nb = _ws_1x1(M, C, x.device)
+    ws, nb = _ws(x.device, "nsg_bn_relu_conv1x1_workspace_bytes", M, C)
     _lib.tag("wgrad_gemm 1x1 (bn+relu on load)", 2.0 * M * C * C, 2.0 * x.numel() * _es(x))
-    _lib.call("nsg_bn_relu_conv1x1_wgrad", _p(x), _p(mean), _p(invstd), _p(gamma), _p(beta), _p(dy), _p(dw), c_int64(M), c_int32(C),
-              c_int32(nsg_dtype(x.dtype)), _p(ws), c_size_t(nb), _stream())
+    _lib.call("nsg_bn_relu_conv1x1_wgrad", _p(x), _p(mean), _p(invstd), _p(gamma), _p(beta), _p(dy), _p(dw), M, C, nsg_dtype(x.dtype), _p(ws), nb,
+              _stream())
     return dw
 
 
@@ -730,11 +701,10 @@ def bn_backward_sums(x, dy, mean, invstd, gamma, dgamma=None, dbeta=None, relu_b
     M = x.numel() // C
     dgamma = dgamma if dgamma is not None else torch.empty(C, dtype=torch.float32, device=x.device)
     dbeta = dbeta if dbeta is not None else torch.empty(C, dtype=torch.float32, device=x.device)
-    nb = _lib.query("nsg_bn_workspace_bytes", c_int64(M), c_int32(C))
-    ws = WS.get(nb, x.device)
+    ws, nb = _ws(x.device, "nsg_bn_workspace_bytes", M, C)
     _lib.tag("bn_backward_sums", 0, 2.0 * x.numel() * _es(x))
-    _lib.call("nsg_bn_backward_sums", _p(x), _p(None), _p(dy), _p(mean), _p(invstd), _p(gamma), _p(relu_beta), _p(dgamma), _p(dbeta),
-              c_int64(M), c_int32(C), c_int32(nsg_dtype(x.dtype)), _p(ws), c_size_t(nb), _stream())
+    _lib.call("nsg_bn_backward_sums", _p(x), _p(None), _p(dy), _p(mean), _p(invstd), _p(gamma), _p(relu_beta), _p(dgamma), _p(dbeta), M, C,
+              nsg_dtype(x.dtype), _p(ws), nb, _stream())
     return dgamma, dbeta
 
 
@@ -747,7 +717,7 @@ def bn_backward_conv1x1_dgrad(h, dy, mean, invstd, gamma, dgamma, dbeta, w, dh_c
     C = h.shape[-1]
     M = h.numel() // C
     dh, dx = torch.empty_like(h), torch.empty_like(h)
-    ws, nb = _ws_1x1(M, C, h.device)
+    ws, nb = _ws(h.device, "nsg_bn_relu_conv1x1_workspace_bytes", M, C)
     px = pm = pi = pg = pb = None
     if prev is not None:
         px, pm, pi, pg, pb = prev
@@ -757,14 +727,14 @@ def bn_backward_conv1x1_dgrad(h, dy, mean, invstd, gamma, dgamma, dbeta, w, dh_c
     _lib.tag("flat_gemm 1x1 dgrad (bn backward on load)", 2.0 * M * C * C, (5.0 if prev is not None else 4.0) * h.numel() * _es(h))
     _lib.call("nsg_bn_backward_conv1x1_dgrad", _p(h), _p(dy), _p(mean), _p(invstd), _p(gamma), _p(dgamma), _p(dbeta), _p(w), _p(dh), _p(dx),
               _p(dh_colsum), _p(px), _p(pm), _p(pi), _p(pg), _p(pb), _p(prev_dgamma if prev is not None else None),
-              _p(prev_dbeta if prev is not None else None), c_int64(M), c_int32(C), c_int32(nsg_dtype(h.dtype)), _p(ws), c_size_t(nb), _stream())
+              _p(prev_dbeta if prev is not None else None), M, C, nsg_dtype(h.dtype), _p(ws), nb, _stream())
     if prev is not None:
         return dh, dx, prev_dgamma, prev_dbeta
     return dh, dx
 
 
 def bn_backward_conv1x1_dgrad_wgrad_supported(dtype, C) -> bool:
-    return bool(_lib.query("nsg_bn_backward_conv1x1_dgrad_wgrad_supported", c_int32(nsg_dtype(dtype)), c_int32(C)))
+    return bool(_lib.query("nsg_bn_backward_conv1x1_dgrad_wgrad_supported", nsg_dtype(dtype), C))
 
 
 def bn_backward_conv1x1_dgrad_wgrad(h, dy, mean, invstd, gamma, dgamma, dbeta, w, prev, dh_colsum=None, dw=None, prev_dgamma=None,
@@ -781,12 +751,10 @@ def bn_backward_conv1x1_dgrad_wgrad(h, dy, mean, invstd, gamma, dgamma, dbeta, w
     dw = dw if dw is not None else torch.empty_like(w)
     prev_dgamma = prev_dgamma if prev_dgamma is not None else torch.empty(C, dtype=torch.float32, device=dev)
     prev_dbeta = prev_dbeta if prev_dbeta is not None else torch.empty(C, dtype=torch.float32, device=dev)
-    nb = _lib.query("nsg_bn_backward_conv1x1_dgrad_wgrad_workspace_bytes", c_int64(M), c_int32(C))
-    ws = WS.get(nb, dev)
+    ws, nb = _ws(dev, "nsg_bn_backward_conv1x1_dgrad_wgrad_workspace_bytes", M, C)
     _lib.tag("flat_gemm 1x1 dgrad + wgrad (bn backward on load)", 4.0 * M * C * C, 4.0 * h.numel() * _es(h))
     _lib.call("nsg_bn_backward_conv1x1_dgrad_wgrad", _p(h), _p(dy), _p(mean), _p(invstd), _p(gamma), _p(dgamma), _p(dbeta), _p(w), _p(dx), _p(dw),
-              _p(dh_colsum), _p(px), _p(pm), _p(pi), _p(pg), _p(pb), _p(prev_dgamma), _p(prev_dbeta), c_int64(M), c_int32(C),
-              c_int32(nsg_dtype(h.dtype)), _p(ws), c_size_t(nb), _stream())
+              _p(dh_colsum), _p(px), _p(pm), _p(pi), _p(pg), _p(pb), _p(prev_dgamma), _p(prev_dbeta), M, C, nsg_dtype(h.dtype), _p(ws), nb, _stream())
     return dx, dw, prev_dgamma, prev_dbeta
 
 
@@ -796,11 +764,10 @@ def bn_backward_apply(x, dy, mean, invstd, gamma, dgamma, dbeta, relu_beta=None,
     C = mean.numel()
     M = x.numel() // C
     dx = torch.empty_like(x)
-    nb = _lib.query("nsg_bn_workspace_bytes", c_int64(M), c_int32(C))
-    ws = WS.get(nb, x.device)
+    ws, nb = _ws(x.device, "nsg_bn_workspace_bytes", M, C)
     _lib.tag("bn_backward_apply", 0, 3.0 * x.numel() * _es(x))
     _lib.call("nsg_bn_backward_apply", _p(x), _p(None), _p(dy), _p(mean), _p(invstd), _p(gamma), _p(relu_beta), _p(dgamma), _p(dbeta), _p(dx),
-              _p(dx_colsum), c_int64(M), c_int32(C), c_int32(nsg_dtype(x.dtype)), _p(ws), c_size_t(nb), _stream())
+              _p(dx_colsum), M, C, nsg_dtype(x.dtype), _p(ws), nb, _stream())
     return dx
 
 
@@ -808,7 +775,7 @@ def bn_backward_apply(x, dy, mean, invstd, gamma, dgamma, dbeta, relu_beta=None,
 # decoder.4-7 as one operator: BatchNorm2d -> ReLU -> ConvTranspose2d(C, 1, 4, 2, 1) [-> Tanh]   (src/models.py:180-183)
 # ------------------------------------------------------------------------------------------------
 def bn_relu_c1convt_supported(dtype, C) -> bool:
-    return bool(_lib.query("nsg_bn_relu_c1convt_supported", c_int32(nsg_dtype(dtype)), c_int32(C)))
+    return bool(_lib.query("nsg_bn_relu_c1convt_supported", nsg_dtype(dtype), C))
 
 
 def bn_relu_c1convt_forward(u, mean, invstd, gamma, beta, w, bias, tanh=True):
@@ -817,11 +784,10 @@ def bn_relu_c1convt_forward(u, mean, invstd, gamma, beta, w, bias, tanh=True):
     _chk(u, "u", None); _chk(w, "w", torch.float32)
     B, H, W, C = u.shape
     y = torch.empty((B, 2 * H, 2 * W, 1), dtype=torch.float32, device=u.device)
-    nb = _lib.query("nsg_bn_relu_c1convt_workspace_bytes", c_int32(B), c_int32(H), c_int32(W), c_int32(C))
-    ws = WS.get(nb, u.device)
+    ws, nb = _ws(u.device, "nsg_bn_relu_c1convt_workspace_bytes", B, H, W, C)
     _lib.tag("bn_relu_c1convt_forward (fused output layer)", 2.0 * 16 * u.numel(), u.numel() * _es(u) + 4.0 * y.numel())
-    _lib.call("nsg_bn_relu_c1convt_forward", _p(u), c_int32(nsg_dtype(u.dtype)), _p(mean), _p(invstd), _p(gamma), _p(beta), _p(w), _p(bias),
-              _p(y), c_int32(NSG_TANH_OUT if tanh else 0), c_int32(B), c_int32(H), c_int32(W), c_int32(C), _p(ws), c_size_t(nb), _stream())
+    _lib.call("nsg_bn_relu_c1convt_forward", _p(u), nsg_dtype(u.dtype), _p(mean), _p(invstd), _p(gamma), _p(beta), _p(w), _p(bias), _p(y),
+              NSG_TANH_OUT if tanh else 0, B, H, W, C, _p(ws), nb, _stream())
     return y
 
 
@@ -838,13 +804,11 @@ def bn_relu_c1convt_forward_mse(u, mean, invstd, gamma, beta, w, bias, target, g
     loss = torch.empty(1, dtype=torch.float32, device=dev)
     dpre = torch.empty((B, 2 * H, 2 * W, 1), dtype=torch.float32, device=dev)
     y = torch.empty((B, 2 * H, 2 * W, 1), dtype=torch.float32, device=dev) if want_image else None
-    nb = _lib.query("nsg_bn_relu_c1convt_workspace_bytes", c_int32(B), c_int32(H), c_int32(W), c_int32(C))
-    ws = WS.get(nb, dev)
+    ws, nb = _ws(dev, "nsg_bn_relu_c1convt_workspace_bytes", B, H, W, C)
     _lib.tag("bn_relu_c1convt_forward_mse (fused output layer + loss)", 2.0 * 16 * u.numel(),
              u.numel() * _es(u) + 4.0 * (2 * dpre.numel() + (dpre.numel() if want_image else 0)))
-    _lib.call("nsg_bn_relu_c1convt_forward_mse", _p(u), c_int32(nsg_dtype(u.dtype)), _p(mean), _p(invstd), _p(gamma), _p(beta), _p(w), _p(bias),
-              _p(y), _p(target), c_int32(T), c_float(grad_scale), _p(loss), _p(dpre), _p(dbias), c_int32(B), c_int32(H), c_int32(W), c_int32(C),
-              _p(ws), c_size_t(nb), _stream())
+    _lib.call("nsg_bn_relu_c1convt_forward_mse", _p(u), nsg_dtype(u.dtype), _p(mean), _p(invstd), _p(gamma), _p(beta), _p(w), _p(bias), _p(y),
+              _p(target), T, grad_scale, _p(loss), _p(dpre), _p(dbias), B, H, W, C, _p(ws), nb, _stream())
     return loss, dpre, y
 
 
@@ -865,12 +829,10 @@ def bn_relu_c1convt_backward(u, mean, invstd, gamma, beta, w, dy, dw=None, dbias
         dbias = dbias if dbias is not None else torch.empty(1, dtype=torch.float32, device=dev)
     dgamma = dgamma if dgamma is not None else torch.empty(C, dtype=torch.float32, device=dev)
     dbeta = dbeta if dbeta is not None else torch.empty(C, dtype=torch.float32, device=dev)
-    nb = _lib.query("nsg_bn_relu_c1convt_workspace_bytes", c_int32(B), c_int32(H), c_int32(W), c_int32(C))
-    ws = WS.get(nb, dev)
+    ws, nb = _ws(dev, "nsg_bn_relu_c1convt_workspace_bytes", B, H, W, C)
     _lib.tag("bn_relu_c1convt_backward (fused output layer)", 2.0 * 16 * u.numel() * 3, 3.0 * u.numel() * _es(u) + 2.0 * 4.0 * dy.numel())
-    _lib.call("nsg_bn_relu_c1convt_backward", _p(u), c_int32(nsg_dtype(u.dtype)), _p(mean), _p(invstd), _p(gamma), _p(beta), _p(w), _p(dy),
-              _p(du), _p(du_colsum), _p(dw), _p(dbias if want_dbias else None), _p(dgamma), _p(dbeta), c_int32(B), c_int32(H), c_int32(W), c_int32(C), _p(ws),
-              c_size_t(nb), _stream())
+    _lib.call("nsg_bn_relu_c1convt_backward", _p(u), nsg_dtype(u.dtype), _p(mean), _p(invstd), _p(gamma), _p(beta), _p(w), _p(dy), _p(du),
+              _p(du_colsum), _p(dw), _p(dbias if want_dbias else None), _p(dgamma), _p(dbeta), B, H, W, C, _p(ws), nb, _stream())
     return du, dw, dbias, dgamma, dbeta
 
 
@@ -882,7 +844,7 @@ def relu_backward_add(a, b, x, out=None):
     if b is not None:
         _chk(b, "b", x.dtype)
     dx = out if out is not None else torch.empty_like(x)
-    _lib.call("nsg_relu_backward_add", _p(a), _p(b), _p(x), _p(dx), c_int64(x.numel()), c_int32(nsg_dtype(x.dtype)), _stream())
+    _lib.call("nsg_relu_backward_add", _p(a), _p(b), _p(x), _p(dx), x.numel(), nsg_dtype(x.dtype), _stream())
     return dx
 
 
@@ -893,21 +855,20 @@ def convert(src, dtype, out=None, relu=False):
         return src
     dst = out if out is not None else torch.empty(src.shape, dtype=dtype, device=src.device)
     _lib.tag("convert", 0, src.numel() * _es(src) + dst.numel() * _es(dst))
-    _lib.call("nsg_convert", _p(src), c_int32(nsg_dtype(src.dtype)), _p(dst), c_int32(nsg_dtype(dst.dtype)), c_int64(src.numel()),
-              c_int32(1 if relu else 0), _stream())
+    _lib.call("nsg_convert", _p(src), nsg_dtype(src.dtype), _p(dst), nsg_dtype(dst.dtype), src.numel(), 1 if relu else 0, _stream())
     return dst
 
 
 def tanh_backward(g, y, out=None):
     dx = out if out is not None else torch.empty_like(y)
     _lib.tag("tanh_backward", 0, 12.0 * y.numel())
-    _lib.call("nsg_tanh_backward", _p(g), _p(y), _p(dx), c_int64(y.numel()), _stream())
+    _lib.call("nsg_tanh_backward", _p(g), _p(y), _p(dx), y.numel(), _stream())
     return dx
 
 
 def add(a, b, out=None):
     y = out if out is not None else torch.empty_like(a)
-    _lib.call("nsg_add", _p(a), _p(b), _p(y), c_int64(a.numel()), _stream())
+    _lib.call("nsg_add", _p(a), _p(b), _p(y), a.numel(), _stream())
     return y
 
 
@@ -916,8 +877,7 @@ def add_per_clip(x, rows, out=None, out_dtype=torch.float32):
     _chk(x, "x"); _chk(rows, "rows")
     B, C = rows.shape
     y = out if out is not None else torch.empty(x.shape, dtype=out_dtype, device=x.device)
-    _lib.call("nsg_add_per_clip", _p(x), _p(rows), _p(y), c_int32(B), c_int64(x.numel() // (B * C)), c_int32(C),
-              c_int32(nsg_dtype(y.dtype)), _stream())
+    _lib.call("nsg_add_per_clip", _p(x), _p(rows), _p(y), B, x.numel() // (B * C), C, nsg_dtype(y.dtype), _stream())
     return y
 
 
@@ -926,10 +886,8 @@ def clip_colsum(x, B):
     _chk(x, "x", None)
     C = x.shape[-1]
     out = torch.empty(B, C, dtype=torch.float32, device=x.device)
-    nb = _lib.query("nsg_clip_colsum_workspace_bytes", c_int32(B), c_int32(C))
-    ws = WS.get(nb, x.device)
-    _lib.call("nsg_clip_colsum", _p(x), c_int32(nsg_dtype(x.dtype)), c_int32(B), c_int64(x.numel() // (B * C)), c_int32(C), _p(out), _p(ws),
-              c_size_t(nb), _stream())
+    ws, nb = _ws(x.device, "nsg_clip_colsum_workspace_bytes", B, C)
+    _lib.call("nsg_clip_colsum", _p(x), nsg_dtype(x.dtype), B, x.numel() // (B * C), C, _p(out), _p(ws), nb, _stream())
     return out
 
 
@@ -937,11 +895,9 @@ def mse_padded(a, c, rows, wa, wc, grad_scale=1.0, want_grad=True):
     """mean((pad(a) - c)^2) with a zero-padded from width wa to wc (train.py:118-129)."""
     loss = torch.empty(1, dtype=torch.float32, device=a.device)
     da = torch.empty_like(a) if want_grad else None
-    nb = _lib.query("nsg_reduce_workspace_bytes", c_int64(rows * wc))
-    ws = WS.get(nb, a.device)
+    ws, nb = _ws(a.device, "nsg_reduce_workspace_bytes", rows * wc)
     _lib.tag("mse_padded (loss + gradient)", 0, 4.0 * (a.numel() * (2 if want_grad else 1) + c.numel()))
-    _lib.call("nsg_mse_padded", _p(a), _p(c), c_int64(rows), c_int32(wa), c_int32(wc), c_float(grad_scale), _p(loss), _p(da),
-              _p(ws), c_size_t(nb), _stream())
+    _lib.call("nsg_mse_padded", _p(a), _p(c), rows, wa, wc, grad_scale, _p(loss), _p(da), _p(ws), nb, _stream())
     return loss, da
 
 
@@ -955,16 +911,15 @@ def vq_losses(z, q, dz_scale=1.0, dq_scale=1.0, dz_add=None, want_dz=True, want_
     loss = torch.empty(1, dtype=torch.float32, device=z.device)
     dz = torch.empty(z.shape, dtype=grad_dtype, device=z.device) if want_dz else None
     dq = torch.empty_like(z) if want_dq else None
-    nb = _lib.query("nsg_reduce_workspace_bytes", c_int64(n))
-    ws = WS.get(nb, z.device)
+    ws, nb = _ws(z.device, "nsg_reduce_workspace_bytes", n)
     _lib.tag("vq_losses", 0, 4.0 * n * 2 + (dz.numel() * _es(dz) * (2 if dz_add is not None else 1) if dz is not None else 0) + (4.0 * n if dq is not None else 0))
-    _lib.call("nsg_vq_losses", _p(z), _p(q), c_int64(n), c_float(dz_scale), c_float(dq_scale), _p(dz_add), _p(loss), _p(dz),
-              _p(dq), c_int32(nsg_dtype(grad_dtype)), _p(ws), c_size_t(nb), _stream())
+    _lib.call("nsg_vq_losses", _p(z), _p(q), n, dz_scale, dq_scale, _p(dz_add), _p(loss), _p(dz), _p(dq), nsg_dtype(grad_dtype), _p(ws), nb,
+              _stream())
     return loss, dz, dq
 
 
 def vq_losses_indexed_bn_supported(D) -> bool:
-    return bool(_lib.query("nsg_vq_losses_indexed_bn_supported", c_int32(D)))
+    return bool(_lib.query("nsg_vq_losses_indexed_bn_supported", D))
 
 
 def vq_losses_indexed(z2d, codebook, idx, dz_scale=1.0, dz_add=None, want_dz=True, grad_dtype=torch.float32, bn=None, dgamma=None,
@@ -988,18 +943,15 @@ def vq_losses_indexed(z2d, codebook, idx, dz_scale=1.0, dz_add=None, want_dz=Tru
             raise _lib.NsgError("vq_losses_indexed: bn= needs want_dz and a BatchNorm input of z's shape")
         dgamma = dgamma if dgamma is not None else torch.empty(D, dtype=torch.float32, device=z2d.device)
         dbeta = dbeta if dbeta is not None else torch.empty(D, dtype=torch.float32, device=z2d.device)
-        nb = _lib.query("nsg_vq_losses_indexed_bn_workspace_bytes", c_int64(N), c_int32(D))
-        ws = WS.get(nb, z2d.device)
+        ws, nb = _ws(z2d.device, "nsg_vq_losses_indexed_bn_workspace_bytes", N, D)
         _lib.tag("vq_losses_indexed", 0, 4.0 * N * D + 8.0 * N + dz.numel() * _es(dz) * (3 if dz_add is not None else 2))
-        _lib.call("nsg_vq_losses_indexed_bn", _p(z2d), _p(codebook), _p(idx), c_int64(N), c_int32(D), c_int32(codebook.shape[0]),
-                  c_float(dz_scale), _p(dz_add), _p(loss), _p(dz), c_int32(nsg_dtype(grad_dtype)), _p(x), _p(mean), _p(invstd), _p(dgamma),
-                  _p(dbeta), _p(ws), c_size_t(nb), _stream())
+        _lib.call("nsg_vq_losses_indexed_bn", _p(z2d), _p(codebook), _p(idx), N, D, codebook.shape[0], dz_scale, _p(dz_add), _p(loss), _p(dz),
+                  nsg_dtype(grad_dtype), _p(x), _p(mean), _p(invstd), _p(dgamma), _p(dbeta), _p(ws), nb, _stream())
         return loss, dz, dgamma, dbeta
-    nb = _lib.query("nsg_reduce_workspace_bytes", c_int64(N * D))
-    ws = WS.get(nb, z2d.device)
+    ws, nb = _ws(z2d.device, "nsg_reduce_workspace_bytes", N * D)
     _lib.tag("vq_losses_indexed", 0, 4.0 * N * D + 8.0 * N + (dz.numel() * _es(dz) * (2 if dz_add is not None else 1) if dz is not None else 0))
-    _lib.call("nsg_vq_losses_indexed", _p(z2d), _p(codebook), _p(idx), c_int64(N), c_int32(D), c_int32(codebook.shape[0]), c_float(dz_scale),
-              _p(dz_add), _p(loss), _p(dz), c_int32(nsg_dtype(grad_dtype)), _p(ws), c_size_t(nb), _stream())
+    _lib.call("nsg_vq_losses_indexed", _p(z2d), _p(codebook), _p(idx), N, D, codebook.shape[0], dz_scale, _p(dz_add), _p(loss), _p(dz),
+              nsg_dtype(grad_dtype), _p(ws), nb, _stream())
     return loss, dz
 
 
@@ -1015,19 +967,17 @@ def _vq_losses_indexed_bnres(z, codebook, idx, dz_scale, dz_add, want_dz, grad_d
     dz = torch.empty(z.shape, dtype=grad_dtype, device=z.device)
     dgamma = dgamma if dgamma is not None else torch.empty(D, dtype=torch.float32, device=z.device)
     dbeta = dbeta if dbeta is not None else torch.empty(D, dtype=torch.float32, device=z.device)
-    nb = _lib.query("nsg_vq_losses_indexed_bn_workspace_bytes", c_int64(N), c_int32(D))
-    ws = WS.get(nb, z.device)
+    ws, nb = _ws(z.device, "nsg_vq_losses_indexed_bn_workspace_bytes", N, D)
     # h, r and dz_add in, dz out (bf16), the indices; the codebook rows come from cache
     _lib.tag("vq_losses_indexed", 0, 2.0 * N * D * 2 + 8.0 * N + dz.numel() * _es(dz) * (2 if dz_add is not None else 1))
-    _lib.call("nsg_vq_losses_indexed_bnres", *z.pointers(), _p(codebook), _p(idx), c_int64(N), c_int32(D), c_int32(codebook.shape[0]),
-              c_float(dz_scale), _p(dz_add), _p(loss), _p(dz), _p(dgamma), _p(dbeta), _p(ws), c_size_t(nb), _stream())
+    _lib.call("nsg_vq_losses_indexed_bnres", *z.pointers(), _p(codebook), _p(idx), N, D, codebook.shape[0], dz_scale, _p(dz_add), _p(loss), _p(dz),
+              _p(dgamma), _p(dbeta), _p(ws), nb, _stream())
     return loss, dz, dgamma, dbeta
 
 
 def adam_step(p, g, m, v, step, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0):
     _lib.tag("adam_step", 0, 28.0 * p.numel())
-    _lib.call("nsg_adam_step", _p(p), _p(g), _p(m), _p(v), c_int64(p.numel()), c_float(lr), c_float(beta1), c_float(beta2),
-              c_float(eps), c_int32(step), c_float(grad_scale), _stream())
+    _lib.call("nsg_adam_step", _p(p), _p(g), _p(m), _p(v), p.numel(), lr, beta1, beta2, eps, step, grad_scale, _stream())
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1045,7 +995,7 @@ def gated_activation(x, cond=None, out=None):
         if cond.shape[-1] != C2 or M % cond.shape[0] != 0:
             raise _lib.NsgError(f"gated_activation: cond {tuple(cond.shape)} does not match x {tuple(x.shape)}")
         rpc = M // cond.shape[0]
-    _lib.call("nsg_gated_activation_forward", _p(x), _p(cond), _p(y), c_int64(M), c_int32(C2 // 2), c_int64(rpc), _stream())
+    _lib.call("nsg_gated_activation_forward", _p(x), _p(cond), _p(y), M, C2 // 2, rpc, _stream())
     return y
 
 
@@ -1055,7 +1005,7 @@ def gated_activation_backward(x, cond, dy):
     M = x.numel() // C2
     dx = torch.empty_like(x)
     rpc = M // cond.shape[0] if cond is not None else 1
-    _lib.call("nsg_gated_activation_backward", _p(x), _p(cond), _p(dy), _p(dx), c_int64(M), c_int32(C2 // 2), c_int64(rpc), _stream())
+    _lib.call("nsg_gated_activation_backward", _p(x), _p(cond), _p(dy), _p(dx), M, C2 // 2, rpc, _stream())
     return dx
 
 
@@ -1095,7 +1045,7 @@ def gated_activation_sum(a, b, cond=None, out=None):
     M, C, rpc, _ = _gate_extents("gated_activation_sum", a, cond, x2=b)
     y = _gate_out(out, a.shape[:-1] + (C,), a.device, "gated_activation_sum: out")
     _lib.tag("gated_activation_sum", 0, 4.0 * M * C * 5)
-    _lib.call("nsg_gated_activation_sum_forward", _p(a), _p(b), _p(cond), _p(y), c_int64(M), c_int32(C), c_int64(rpc), _stream())
+    _lib.call("nsg_gated_activation_sum_forward", _p(a), _p(b), _p(cond), _p(y), M, C, rpc, _stream())
     return y
 
 
@@ -1107,13 +1057,12 @@ def _gate_backward(fn, entry, x, x2, cond, dy, out, dcond, want_dcond, n_clips):
         if B is None:
             raise _lib.NsgError(f"{fn}: the column sums need cond or n_clips")
         dcond = _gate_out(dcond, (B, 2 * C), x.device, fn + ": dcond")
-        nb = _lib.query("nsg_gated_colsum_workspace_bytes", c_int64(M), c_int32(C), c_int64(rpc))
+        ws, nb = _ws(x.device, "nsg_gated_colsum_workspace_bytes", M, C, rpc)
         if nb == 0:
             raise _lib.NsgError(f"{fn}: the column sums take C % 4 == 0, C <= 1024 (C = {C})")
-        ws = WS.get(nb, x.device)
     _lib.tag(fn, 0, 4.0 * M * C * (5 + (2 if x2 is not None else 0)))
     head = (_p(x), _p(x2)) if x2 is not None else (_p(x),)
-    _lib.call(entry, *head, _p(cond), _p(dy), _p(dx), _p(dcond), c_int64(M), c_int32(C), c_int64(rpc), _p(ws), c_size_t(nb), _stream())
+    _lib.call(entry, *head, _p(cond), _p(dy), _p(dx), _p(dcond), M, C, rpc, _p(ws), nb, _stream())
     return dx, dcond
 
 
@@ -1134,10 +1083,8 @@ def cross_entropy(logits2d, target, want_grad=True, grad_scale=1.0):
     M, K = logits2d.shape
     loss = torch.empty(1, dtype=torch.float32, device=logits2d.device)
     dl = torch.empty_like(logits2d) if want_grad else None
-    nb = _lib.query("nsg_cross_entropy_workspace_bytes", c_int64(M))
-    ws = WS.get(nb, logits2d.device)
-    _lib.call("nsg_cross_entropy", _p(logits2d), _p(target), c_int64(M), c_int32(K), c_float(grad_scale), _p(loss), _p(dl), _p(ws),
-              c_size_t(nb), _stream())
+    ws, nb = _ws(logits2d.device, "nsg_cross_entropy_workspace_bytes", M)
+    _lib.call("nsg_cross_entropy", _p(logits2d), _p(target), M, K, grad_scale, _p(loss), _p(dl), _p(ws), nb, _stream())
     return loss, dl
 
 
@@ -1156,11 +1103,10 @@ def cross_entropy_masked(logits2d, target, rows_per_clip, want_grad=True, grad_s
     dl = _gate_out(out, (M, K), dev, "cross_entropy_masked: out") if (want_grad or out is not None) else None
     nll = torch.empty(B, dtype=torch.float32, device=dev) if want_clip else None
     cnt = torch.empty(B, dtype=torch.int64, device=dev) if want_clip else None
-    nb = _lib.query("nsg_cross_entropy_masked_workspace_bytes", c_int64(M), c_int64(rows_per_clip))
-    ws = WS.get(nb, dev)
+    ws, nb = _ws(dev, "nsg_cross_entropy_masked_workspace_bytes", M, rows_per_clip)
     _lib.tag("cross_entropy_masked", 0, 4.0 * M * K * (2 if dl is not None else 1))
-    _lib.call("nsg_cross_entropy_masked", _p(logits2d), _p(target), c_int64(M), c_int32(K), c_int64(rows_per_clip), c_float(grad_scale),
-              _p(loss), _p(dl), _p(nll), _p(cnt), _p(ws), c_size_t(nb), _stream())
+    _lib.call("nsg_cross_entropy_masked", _p(logits2d), _p(target), M, K, rows_per_clip, grad_scale, _p(loss), _p(dl), _p(nll), _p(cnt), _p(ws), nb,
+              _stream())
     return loss, dl, nll, cnt
 
 
@@ -1169,7 +1115,7 @@ def cross_entropy_masked(logits2d, target, rows_per_clip, want_grad=True, grad_s
 # ------------------------------------------------------------------------------------------------
 def prior_walk_weight_floats(dim, n_layers, input_dim) -> int:
     """Floats of the walk's packed weight blob (layout: include/nsg.h, nsg_prior_walk); 0 outside the kernel's envelope."""
-    return int(_lib.query("nsg_prior_walk_weight_floats", c_int32(dim), c_int32(n_layers), c_int32(input_dim)))
+    return int(_lib.query("nsg_prior_walk_weight_floats", dim, n_layers, input_dim))
 
 
 def _prior_walk_extents(fn, w, emb, cond, vh, e_row, H, row, tensors):
@@ -1208,8 +1154,8 @@ def prior_walk(w, emb, cond, vh, e_row, H, row, u=None, x_in=None, codes=None, l
     K = emb.shape[0]
     B, W, dim, L, K = _prior_walk_extents("prior_walk", w, emb, cond, vh, e_row, H, row, (
         (u, "u", torch.float32, ()), (x_in, "x_in", torch.int64, ()), (codes, "codes", torch.int64, ()), (logits, "logits", torch.float32, (K,))))
-    _lib.call("nsg_prior_walk", _p(w), _p(emb), _p(cond), _p(vh), _p(u), _p(x_in), _p(codes), _p(e_row), c_int64(e_row.stride(0)),
-              _p(logits), c_int32(B), c_int32(H), c_int32(W), c_int32(dim), c_int32(L), c_int32(K), c_int32(row), _stream())
+    _lib.call("nsg_prior_walk", _p(w), _p(emb), _p(cond), _p(vh), _p(u), _p(x_in), _p(codes), _p(e_row), e_row.stride(0), _p(logits), B, H, W, dim, L,
+              K, row, _stream())
 
 
 def prior_walk_ctl(w, emb, cond, vh, e_row, H, row, u, codes, x_in=None, keep=None, logits=None, temperature=1.0, top_k=0, top_p=1.0):
@@ -1231,9 +1177,8 @@ def prior_walk_ctl(w, emb, cond, vh, e_row, H, row, u, codes, x_in=None, keep=No
     B, W, dim, L, K = _prior_walk_extents("prior_walk_ctl", w, emb, cond, vh, e_row, H, row, (
         (u, "u", torch.float32, ()), (x_in, "x_in", torch.int64, ()), (keep, "keep", None, ()), (codes, "codes", torch.int64, ()),
         (logits, "logits", torch.float32, (K,))))
-    _lib.call("nsg_prior_walk_ctl", _p(w), _p(emb), _p(cond), _p(vh), _p(u), _p(x_in), _p(keep), _p(codes), _p(e_row),
-              c_int64(e_row.stride(0)), _p(logits), c_int32(B), c_int32(H), c_int32(W), c_int32(dim), c_int32(L), c_int32(K), c_int32(row),
-              c_float(temperature), c_int32(min(int(top_k), 2 ** 31 - 1)), c_float(top_p), _stream())
+    _lib.call("nsg_prior_walk_ctl", _p(w), _p(emb), _p(cond), _p(vh), _p(u), _p(x_in), _p(keep), _p(codes), _p(e_row), e_row.stride(0), _p(logits), B,
+              H, W, dim, L, K, row, temperature, min(int(top_k), 2 ** 31 - 1), top_p, _stream())
 
 
 def prepared_conv_forward(d: ConvDesc, x, w_fwd, bias, y, flags=0):
@@ -1242,9 +1187,9 @@ def prepared_conv_forward(d: ConvDesc, x, w_fwd, bias, y, flags=0):
     _chk(x, "x", _in_dtype(d)); _chk(y, "y", _out_dtype(d, flags))
     if tuple(x.shape) != (d.B, d.IH, d.IW, d.C_in) or tuple(y.shape) != (d.B, d.OH, d.OW, d.C_out):
         raise _lib.NsgError(f"prepared_conv_forward: x {tuple(x.shape)} / y {tuple(y.shape)} do not match descriptor {d.key()}")
-    ws, nb = _conv_ws(d, x.device)
+    ws, nb = _ws(x.device, "nsg_conv_workspace_bytes", byref(d))
     keep = (d, x, w_fwd, bias, y, ws)          # the closure owns every buffer whose address it passes
-    args = (byref(d), _p(x), _p(w_fwd), _p(bias), _p(y), c_int32(flags), _p(ws), c_size_t(nb))
+    args = (byref(d), _p(x), _p(w_fwd), _p(bias), _p(y), flags, _p(ws), nb)
     return lambda: (keep, _lib.call("nsg_conv_forward", *args, _stream()))
 
 
@@ -1256,5 +1201,5 @@ def prepared_gated_activation(x, cond, y):
     if cond.shape[-1] != C2 or M % cond.shape[0] != 0 or y.numel() != M * (C2 // 2):
         raise _lib.NsgError(f"prepared_gated_activation: x {tuple(x.shape)}, cond {tuple(cond.shape)}, y {tuple(y.shape)}")
     keep = (x, cond, y)
-    args = (_p(x), _p(cond), _p(y), c_int64(M), c_int32(C2 // 2), c_int64(M // cond.shape[0]))
+    args = (_p(x), _p(cond), _p(y), M, C2 // 2, M // cond.shape[0])
     return lambda: (keep, _lib.call("nsg_gated_activation_forward", *args, _stream()))

@@ -3,6 +3,7 @@ and the pure size queries work without a GPU (no kernel is launched here)."""
 import ctypes
 import os
 import re
+from ctypes import POINTER, c_char_p, c_float, c_int32, c_int64, c_size_t, c_void_p
 
 import pytest
 
@@ -153,3 +154,109 @@ def test_prior_walk_size_query_and_argument_checks():
     for change in unsupported:
         assert walk(**change) == -2, change
         assert b"outside the envelope" in lib.nsg_last_error_string()
+
+
+# ---- the binding is derived from include/nsg.h (_lib.parse_header): the tests below fail if the parser mis-maps a type ----
+_P = c_void_p
+FROZEN = {
+    "nsg_version": (c_int32, []),
+    "nsg_last_error_string": (c_char_p, []),
+    "nsg_vq_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32]),
+    "nsg_adam_step": (c_int32, [_P, _P, _P, _P, c_int64, c_float, c_float, c_float, c_float, c_int32, c_float, _P]),
+    "nsg_pack_conv_weights_batch": (c_int32, [c_int32, POINTER(_lib.ConvDesc), _P, _P, _P, _P]),
+    "nsg_bn_backward_conv1x1_dgrad_wgrad": (c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                                      c_int64, c_int32, c_int32, _P, c_size_t, _P]),
+}
+
+
+def test_frozen_signatures():
+    """Six prototypes that between them meet every mapping rule, written out by hand: return types int / const char * / size_t,
+    scalar parameters of each of the four kinds, plain and double pointers, the descriptor pointer, (void), 24 parameters."""
+    assert len(FROZEN["nsg_bn_backward_conv1x1_dgrad_wgrad"][1]) == 24
+    for name, want in FROZEN.items():
+        assert _lib._SIGS[name] == want, name
+    lib = _lib.load()
+    for name, (res, args) in FROZEN.items():
+        fn = getattr(lib, name)
+        assert fn.restype is res and list(fn.argtypes) == args, name
+
+
+def test_header_parser_on_snippets():
+    parse = _lib.parse_header
+    sigs, consts, fields = parse("""
+        /* NSG_API int nsg_in_a_block_comment(double x); spread
+           over lines */
+        // NSG_API int nsg_in_a_line_comment(double x);
+        int nsg_not_an_entry_point(double x);
+        NSG_API size_t
+        nsg_spread(const float *const *w,
+                   int64_t n,   /* a comment between parameters */
+                   const int flag, void *const *out,
+                   float
+                   scale);
+        NSG_API int32_t nsg_nothing(void);
+        #define NSG_SOME 7
+        #define NSG_NEG -3
+        #define NSG_NOT_AN_INT 1.5
+        enum { NSG_A = 4, NSG_B = -2 };
+        typedef struct nsg_conv_desc { int32_t a, b; int32_t c; /* note */ } nsg_conv_desc;
+    """)
+    assert sigs == {"nsg_spread": (c_size_t, [c_void_p, c_int64, c_int32, c_void_p, c_float]), "nsg_nothing": (c_int32, [])}
+    assert consts == {"NSG_SOME": 7, "NSG_NEG": -3, "NSG_A": 4, "NSG_B": -2}
+    assert fields == ["a", "b", "c"]
+    assert parse("NSG_API int nsg_f(const nsg_conv_desc *d, nsg_conv_desc *const e);")[0] == {
+        "nsg_f": (c_int32, [POINTER(_lib.ConvDesc)] * 2)}
+    for bad in ("NSG_API int nsg_f(double x);", "NSG_API int nsg_f(int32_t a, unsigned n);", "NSG_API int nsg_f(unsigned int n);",
+                "NSG_API int nsg_f(nsg_conv_desc d);", "NSG_API int nsg_f(const nsg_conv_desc d, void *s);",
+                "NSG_API double nsg_f(void);", "NSG_API void nsg_f(int32_t a);", "NSG_API float *nsg_f(int32_t a);",
+                "NSG_API int nsg_f(int32_t a, void (*cb)(int));", "NSG_API int nsg_f(int32_t a", "NSG_API int f(int32_t a);",
+                "NSG_API int nsg_f(int32_t a) { return a; }", "NSG_API int nsg_f();", "NSG_API int nsg_f(long n);",
+                "NSG_API int nsg_f(int32_t);\nNSG_API int nsg_g(uint8_t k);"):
+        with pytest.raises(_lib.NsgError, match="nsg.h") as e:
+            parse(bad)
+        assert bad.split("\n")[-1][:20] in str(e.value), (bad, str(e.value))       # the message names the prototype
+    with pytest.raises(_lib.NsgError):
+        parse("enum { NSG_A = 4, NSG_B };")
+    with pytest.raises(_lib.NsgError):
+        parse("struct nsg_conv_desc { int32_t a; int64_t b; };")
+
+
+def test_header_constants_and_struct_are_the_ones_the_package_exports(monkeypatch, tmp_path):
+    from neural_sound_generation_amd import ops
+    text = open(os.path.join(ROOT, "include", "nsg.h")).read()
+    sigs, consts, fields = _lib.parse_header(text)
+    assert sigs == _lib._SIGS and list(sigs) == _lib.HEADER_SYMBOLS == list(_lib._SIGS) and len(sigs) == len(header_symbols())
+    for name in ("NSG_RELU_IN", "NSG_TANH_OUT", "NSG_OUT_F32", "NSG_RELU_OUT", "NSG_F32", "NSG_BF16", "NSG_VERSION", "NSG_C1_MOMENTS"):
+        assert getattr(_lib, name) == consts[name] == int(re.search(r"\b%s\b\s*=?\s*(-?\d+)" % name, text).group(1)), name
+    for name in ("NSG_RELU_IN", "NSG_TANH_OUT", "NSG_OUT_F32", "NSG_RELU_OUT", "NSG_F32", "NSG_BF16"):
+        assert getattr(ops, name) == consts[name]
+    assert (consts["NSG_RELU_IN"], consts["NSG_TANH_OUT"], consts["NSG_RELU_IN2"], consts["NSG_OUT_F32"], consts["NSG_RELU_OUT"]) == (1, 2, 4, 8, 16)
+    assert (consts["NSG_OK"], consts["NSG_E_INVALID"], consts["NSG_E_UNSUPPORTED"], consts["NSG_E_WORKSPACE"]) == (0, -1, -2, -3)
+    assert ops.C1_MOMENTS == consts["NSG_C1_MOMENTS"] == 273 and (consts["NSG_F32"], consts["NSG_BF16"]) == (0, 1)
+    exported = [n for n, _ in _lib.ConvDesc._fields_]
+    assert fields == exported == ["B", "IH", "IW", "C_in", "OH", "OW", "C_out", "k", "stride", "pad", "transposed", "dtype", "k_w", "pad_w"]
+    assert all(t is c_int32 for _, t in _lib.ConvDesc._fields_) and ctypes.sizeof(_lib.ConvDesc) == 4 * len(fields)
+    swapped = text.replace("int32_t k, stride, pad;", "int32_t stride, k, pad;")
+    assert swapped != text
+    got = _lib.parse_header(swapped)[2]
+    assert got != exported and sorted(got) == sorted(exported) and got.index("stride") + 1 == got.index("k") == exported.index("k") + 1
+    # a missing header is an error that names the path
+    monkeypatch.setattr(_lib, "HEADER_PATH", str(tmp_path / "nsg.h"))
+    with pytest.raises(_lib.NsgError, match=re.escape(str(tmp_path / "nsg.h"))):
+        _lib._header()
+
+
+def test_bound_argtypes_convert_plain_numbers_and_refuse_a_float_for_an_integer():
+    """ops.py / audio.py pass plain Python and numpy numbers: the argtypes bound from the header convert them, and a float where
+    the header declares an integer raises before the call."""
+    import numpy as np
+    lib = _lib.load()
+    want = lib.nsg_vq_workspace_bytes(c_int64(1000), c_int32(128), c_int32(512))
+    assert want > 0 and _lib.query("nsg_vq_workspace_bytes", 1000, np.int64(128), np.int32(512)) == want
+    assert _lib.query("nsg_bn_relu_conv1x1_supported", True, 128) == 1                       # bool -> int32 (NSG_BF16 == 1)
+    with pytest.raises(ctypes.ArgumentError):
+        _lib.query("nsg_vq_workspace_bytes", 1000, 128.0, 512)
+    with pytest.raises(_lib.NsgError, match="nsg_adam_step"):                                # an int for a float, None for a pointer
+        _lib.call("nsg_adam_step", None, None, None, None, 4, 1, 0.9, np.float32(0.999), 1e-8, 1, 1, None)
+    descs = (_lib.ConvDesc * 1)()                                                            # a descriptor array passes as it is
+    assert lib.nsg_pack_conv_weights_batch(1, descs, None, None, None, None) == -1
