@@ -532,6 +532,34 @@ NSG_API int nsg_vq_losses_indexed_bnres(const void *h, const void *r, const floa
 NSG_API int nsg_adam_step(float *p, const float *g, float *m, float *v, int64_t n, float lr, float beta1, float beta2,
                           float eps, int32_t step, float grad_scale, void *stream);
 
+/* sumsq[0] = sum of g[i]^2 over n floats, accumulated in DOUBLE ((double)g * (double)g is exact) and left on the device.
+ * The partition of elements to threads and blocks depends only on n and on whether g is 16-byte aligned, and every combine
+ * is in a fixed order: two calls on the same input give the same bits.  n == 0 writes 0.  workspace:
+ * nsg_grad_sumsq_workspace_bytes(n) bytes; sumsq and workspace 8-byte aligned. */
+NSG_API size_t nsg_grad_sumsq_workspace_bytes(int64_t n);
+NSG_API int nsg_grad_sumsq(const float *g, int64_t n, double *sumsq, void *workspace, size_t workspace_bytes, void *stream);
+
+/* nsg_adam_step extended; each extension has a neutral value, and with all of them neutral (seg_end = seg_wd = sumsq =
+ * shadow = NULL, n_seg = 0, max_norm <= 0, skip_nonfinite = 0) p, m and v come out as nsg_adam_step's, bit for bit.
+ *   - clipping (sumsq = the device double nsg_grad_sumsq wrote, max_norm > 0):  norm = grad_scale * sqrt(sumsq[0]) formed in
+ *     double and rounded to fp32 once, coef = min(1, max_norm / (norm + 1e-6)) as torch.nn.utils.clip_grad_norm_; the gradient
+ *     used is (g * grad_scale) * coef, held as the exact double product where coef < 1 (g c - m and (g c)^2 (1 - beta2) round
+ *     once each; coef == 1 leaves nsg_adam_step's bits).  Every thread forms coef from the same double the same way;
+ *   - skip_nonfinite != 0: when that fp32 norm is not finite, p, m, v and shadow are not written at all;
+ *   - decoupled weight decay (torch.optim.AdamW): seg_end [n_seg] int64 ascending element offsets and seg_wd [n_seg] floats, in
+ *     device memory: element e belongs to the first segment s with seg_end[s] > e (none: no decay) and p <- p - p * (lr * wd_s)
+ *     before the Adam update.  Segments end on multiples of 4 elements (a 16-byte group takes its first element's segment);
+ *   - weight EMA (shadow [n], one_minus_decay = float(1 - decay)): shadow <- shadow - one_minus_decay * (shadow - p_new),
+ *     three fp32 roundings; one_minus_decay == 1 copies p_new;
+ *   - stats (or NULL; 16 bytes, 4-byte aligned): float norm (-1 without sumsq), float coef, int32 finite, int32 running count
+ *     of skipped steps (+= 1 when this call skipped; the caller zeroes it once).  One thread writes it with ordinary stores.
+ * NSG_E_INVALID: a null p / g / m / v, n < 0, step < 1, half a segment table or n_seg not matching it, max_norm > 0 or the
+ * guard without sumsq, a NaN max_norm, |one_minus_decay| > 1 (or NaN), a shadow overlapping p, a misaligned sumsq / stats. */
+NSG_API int nsg_adamw_step(float *p, const float *g, float *m, float *v, int64_t n, float lr, float beta1, float beta2, float eps,
+                           int32_t step, float grad_scale, const int64_t *seg_end, const float *seg_wd, int32_t n_seg,
+                           const double *sumsq, float max_norm, int32_t skip_nonfinite, float *shadow, float one_minus_decay,
+                           void *stats, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Self-checks used by the tests
  * ------------------------------------------------------------------------------------------- */

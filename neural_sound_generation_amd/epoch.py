@@ -6,6 +6,7 @@ main.py stays out of scope; `args` is any object with the 
 """
 from __future__ import annotations
 
+import contextlib
 import os
 
 import numpy as np
@@ -19,11 +20,34 @@ from .train import train_vqvae
 SAMPLING_RATE, FFT_SIZE, HOP_SIZE, N_MELS = 22050, 1024, 256, 80      # src/main.py:167-170
 
 
-def run_epoch(args, model, optimizer, train_loader, test_loader, device, epoch, checkpoint_path=None, export_audio=True):
-    """Returns a dict with the numbers and the files written."""
+def _averaged(optimizer, eval_with_ema):
+    """The context the evaluation runs in: the optimiser's averaged weights (FlatAdam(weight_ema_decay=).ema_weights()) or
+    nothing.  (Both drivers have called _require_average before they train.)"""
+    return optimizer.ema_weights() if eval_with_ema else contextlib.nullcontext()
+
+
+def _require_average(optimizer, eval_with_ema):
+    if eval_with_ema and getattr(optimizer, "shadow", None) is None:
+        raise ValueError("eval_with_ema needs an optimiser that keeps averaged weights (FlatAdam(weight_ema_decay=...))")
+
+
+def run_epoch(args, model, optimizer, train_loader, test_loader, device, epoch, checkpoint_path=None, export_audio=True,
+              eval_with_ema=False):
+    """Returns a dict with the numbers and the files written.  eval_with_ema: the test loop and the exported reconstruction
+    (nothing else) see the optimiser's averaged weights; BatchNorm running statistics are the raw model's.  The checkpoint
+    always holds the raw weights, and the averaged ones inside the optimiser's state."""
+    _require_average(optimizer, eval_with_ema)                         # (before an epoch is spent on training)
     train_loss = train_vqvae(args, model, optimizer, train_loader, device, epoch)
+    with _averaged(optimizer, eval_with_ema):
+        out = _evaluate_and_export(args, model, test_loader, device, epoch, export_audio)
+    out["train_loss"] = train_loss
+    out["checkpoint"] = save_checkpoint(args, checkpoint_state(epoch, args.model, model, optimizer), filename=checkpoint_path)
+    return out
+
+
+def _evaluate_and_export(args, model, test_loader, device, epoch, export_audio):
     loss_recons, loss_vq = test_vqvae(args, model, test_loader, device, epoch)
-    out = {"train_loss": train_loss, "test_loss_recons": loss_recons, "test_loss_vq": loss_vq}
+    out = {"test_loss_recons": loss_recons, "test_loss_vq": loss_vq}
     sample_dir = os.path.join(args.sampledir, format(args.dataset))
     os.makedirs(sample_dir, exist_ok=True)
     stem = '_' + str(args.model) + '_data_' + str(args.dataset) + '_dim_' + str(args.dim) + '_z_dim_' + str(args.z_dim) + '_epoch_' + str(epoch)
@@ -45,21 +69,24 @@ def run_epoch(args, model, optimizer, train_loader, test_loader, device, epoch, 
             signal = nsg_audio.inv_mel_spectrogram(mel, SAMPLING_RATE, FFT_SIZE, HOP_SIZE, N_MELS)[0].cpu().numpy()
             out["wav"] = os.path.join(sample_dir, 'audio_recon' + stem + '_fftsize_' + str(FFT_SIZE) + '_hopsize_' + str(HOP_SIZE) + '.wav')
             nsg_audio.save_wav(signal, out["wav"], SAMPLING_RATE)
-    out["checkpoint"] = save_checkpoint(args, checkpoint_state(epoch, args.model, model, optimizer), filename=checkpoint_path)
     return out
 
 
 def run_prior_epoch(args, vqvae, prior, step_or_optimizer, train_loader, test_loader, device, epoch, checkpoint_path=None,
-                    sample_label=None, sample_frames=64, generator=None):
+                    sample_label=None, sample_frames=64, generator=None, eval_with_ema=False):
     """Stage two's epoch: train_prior -> test_prior -> checkpoint ({'epoch', 'arch': 'pixelcnn', 'state_dict', 'optimizer'}, the
     layout of run_epoch's; evaluate.load_checkpoint into the prior and the step's optimiser resumes bit-identically) -> with
     sample_label (B,) int64: evaluate.sample_mels of those classes, sample_frames frames each, saved as a .npy of mels
     (B, 80, sample_frames).  step_or_optimizer: a PriorTrainStep or a torch optimiser (train_prior).  The VQ-VAE is only read.
+    eval_with_ema: test_prior and the samples (nothing else) see the prior's averaged weights (FlatAdam(weight_ema_decay=));
+    the checkpoint always holds the raw weights, and the averaged ones inside the optimiser's state.
     Returns a dict with the numbers and the files written."""
-    train_loss = train_prior(args, vqvae, prior, step_or_optimizer, train_loader, device, epoch)
-    nats = test_prior(args, vqvae, prior, test_loader, device, epoch)
-    out = {"train_loss": train_loss, "test_nats_per_code": nats, "test_bits_per_code": nats / float(np.log(2.0))}
     optimizer = step_or_optimizer.opt if isinstance(step_or_optimizer, PriorTrainStep) else step_or_optimizer
+    _require_average(optimizer, eval_with_ema)
+    train_loss = train_prior(args, vqvae, prior, step_or_optimizer, train_loader, device, epoch)
+    with _averaged(optimizer, eval_with_ema):
+        nats = test_prior(args, vqvae, prior, test_loader, device, epoch)
+    out = {"train_loss": train_loss, "test_nats_per_code": nats, "test_bits_per_code": nats / float(np.log(2.0))}
     if checkpoint_path is None:
         checkpoint_path = './models/pixelcnn/checkpoint_{}_{}_{}.pth.tar'.format(args.dataset, args.dim, args.z_dim)
     out["checkpoint"] = save_checkpoint(args, checkpoint_state(epoch, 'pixelcnn', prior, optimizer), filename=checkpoint_path)
@@ -70,7 +97,8 @@ def run_prior_epoch(args, vqvae, prior, step_or_optimizer, train_loader, test_lo
         was_training = vqvae.training
         vqvae.eval()
         try:
-            codes, mels = sample_mels(vqvae, prior, sample_label.to(device), sample_frames, generator=generator)
+            with _averaged(optimizer, eval_with_ema):
+                codes, mels = sample_mels(vqvae, prior, sample_label.to(device), sample_frames, generator=generator)
         finally:
             vqvae.train(was_training)
         out["sample_codes"] = codes

@@ -980,6 +980,59 @@ def adam_step(p, g, m, v, step, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, grad_
     _lib.call("nsg_adam_step", _p(p), _p(g), _p(m), _p(v), p.numel(), lr, beta1, beta2, eps, step, grad_scale, _stream())
 
 
+def grad_sumsq(g, out=None):
+    """sum(g^2) of a contiguous fp32 tensor, accumulated in double in a fixed order: a float64 tensor of one element that stays
+    on the device (`out` to reuse one).  No host synchronisation."""
+    _chk(g, "g")
+    if out is None:
+        out = torch.empty(1, dtype=torch.float64, device=g.device)
+    elif out.dtype != torch.float64 or not out.is_cuda or out.numel() != 1:
+        raise _lib.NsgError("grad_sumsq: out must be one float64 on the GPU")
+    ws, nb = _ws(g.device, "nsg_grad_sumsq_workspace_bytes", g.numel())
+    _lib.tag("grad_sumsq", 0, 4.0 * g.numel())
+    _lib.call("nsg_grad_sumsq", _p(g), g.numel(), _p(out), _p(ws), nb, _stream())
+    return out
+
+
+def new_adamw_stats(device):
+    """The 16-byte statistics block of adamw_step, zeroed: see read_adamw_stats."""
+    return torch.zeros(4, dtype=torch.int32, device=device)
+
+
+def read_adamw_stats(stats):
+    """(norm, coef, finite, skipped steps) of a statistics block; synchronises.  norm is -1 when no sum of squares was given."""
+    host = stats.cpu()
+    f = host.view(torch.float32)
+    return float(f[0]), float(f[1]), int(host[2]), int(host[3])
+
+
+def adamw_step(p, g, m, v, step, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0, seg_end=None, seg_wd=None, sumsq=None,
+               max_norm=0.0, skip_nonfinite=False, shadow=None, one_minus_decay=0.0, stats=None):
+    """adam_step with decoupled weight decay per segment (seg_end int64 / seg_wd fp32 device tables), clipping by the global
+    norm (sumsq from grad_sumsq, max_norm > 0), the non-finite guard, a weight EMA into `shadow` and the statistics block
+    (new_adamw_stats); every option off gives adam_step's bits."""
+    S = 0
+    if seg_end is not None or seg_wd is not None:
+        if seg_end is None or seg_wd is None:
+            raise _lib.NsgError("adamw_step: seg_end and seg_wd come together")
+        _chk(seg_end, "seg_end", torch.int64); _chk(seg_wd, "seg_wd", torch.float32)
+        S = seg_end.numel()
+        if seg_wd.numel() != S:
+            raise _lib.NsgError("adamw_step: seg_end and seg_wd differ in length")
+    if sumsq is not None:
+        _chk(sumsq, "sumsq", torch.float64)
+    if shadow is not None:
+        _chk(shadow, "shadow", torch.float32)
+        if shadow.numel() != p.numel():
+            raise _lib.NsgError("adamw_step: shadow and p differ in length")
+    if stats is not None and (not stats.is_cuda or stats.numel() * stats.element_size() < 16):
+        raise _lib.NsgError("adamw_step: stats must be 16 bytes on the GPU")
+    n = p.numel()
+    _lib.tag("adamw_step", 0, (28.0 + (8.0 if shadow is not None else 0.0)) * n)
+    _lib.call("nsg_adamw_step", _p(p), _p(g), _p(m), _p(v), n, lr, beta1, beta2, eps, step, grad_scale, _p(seg_end), _p(seg_wd), S,
+              _p(sumsq), float(max_norm), 1 if skip_nonfinite else 0, _p(shadow), float(one_minus_decay), _p(stats), _stream())
+
+
 # ------------------------------------------------------------------------------------------------
 # latent prior (GatedPixelCNN): element-wise pieces
 # ------------------------------------------------------------------------------------------------

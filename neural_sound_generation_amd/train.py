@@ -65,6 +65,8 @@ class FusedTrainStep:
             # broadcast -- everything outside it: BatchNorm running statistics and counters, an EMA-trained codebook
             # (requires_grad=False keeps it out of the bucket) with its ema_count / ema_sum buffers
             nsg_dist.broadcast_flat(self.opt.flat_param, 0, process_group)
+            if getattr(self.opt, "shadow", None) is not None:      # the averaged weights (weight_ema_decay) follow rank 0's too
+                nsg_dist.broadcast_flat(self.opt.shadow, 0, process_group)
             nsg_dist.broadcast_tensors_packed(nsg_dist.state_outside(model, self.opt), 0, process_group)
         if self.ema:
             # [n (K, padded to 256 bytes) | sum z (K x D)] lives BEHIND the gradients: ONE all-reduce carries both
