@@ -274,7 +274,15 @@ __global__ void preemphasis_kernel(const float *__restrict__ x, float *__restric
         y[i] = i % L ? x[i] - k * x[i - 1] : x[i];
 }
 
-inline int ew_blocks(int64_t n) { const int64_t b = nsg_cdiv(n, 256); return (int)(b > 4096 ? 4096 : (b < 1 ? 1 : b)); }
+// nsg_audio_griffin_lim's workspace: the spectrum [B][T][F] | the frames [B][T][n_fft]
+struct GriffinLimLayout { v2f *spec; float *frames; size_t bytes; };
+inline GriffinLimLayout griffin_lim_layout(void *ws, int B, int T, int n_fft)
+{
+    const size_t F = (size_t)n_fft / 2 + 1;
+    NsgCarver c(ws);
+    return {c.take<v2f>(nsg_align_up((size_t)B * T * F * 2 * sizeof(float), 256)),
+            c.take<float>(nsg_align_up((size_t)B * T * n_fft * sizeof(float), 256)), c.off};
+}
 inline int log2_of(int n) { int l = 0; while ((1 << l) < n) ++l; return (1 << l) == n ? l : -1; }
 
 }  // namespace
@@ -294,8 +302,7 @@ int nsg_audio_mel_to_linear(const float *mel, const float *inv_basis, float *S, 
 size_t nsg_audio_griffin_lim_workspace_bytes(int32_t B, int32_t T, int32_t n_fft)
 {
     if (B <= 0 || T <= 0 || n_fft <= 0) return 0;
-    const size_t F = (size_t)n_fft / 2 + 1;
-    return nsg_align_up((size_t)B * T * F * 2 * sizeof(float), 256) + nsg_align_up((size_t)B * T * n_fft * sizeof(float), 256);
+    return griffin_lim_layout(nullptr, B, T, n_fft).bytes;
 }
 
 // S [B][T][F] magnitudes, u [B][T][F] uniform numbers for the initial phases -> y [B][hop*(T-1)]
@@ -308,13 +315,14 @@ int nsg_audio_griffin_lim(const float *S, const float *u, float *y, int32_t B, i
     NSG_REQUIRE(n_fft % hop == 0, NSG_E_UNSUPPORTED, "nsg_audio_griffin_lim: hop must divide n_fft");
     NSG_REQUIRE((int64_t)hop * (T - 1) < 0x7fffffff, NSG_E_UNSUPPORTED, "nsg_audio_griffin_lim: too many samples (hop * (T - 1) >= 2^31)");
     NSG_REQUIRE((int64_t)hop * (T - 1) >= 2, NSG_E_UNSUPPORTED, "nsg_audio_griffin_lim: hop * (T - 1) must be at least 2 samples (a one-sample grid has no reflect padding)");
-    NSG_REQUIRE(workspace && workspace_bytes >= nsg_audio_griffin_lim_workspace_bytes(B, T, n_fft), NSG_E_WORKSPACE, "nsg_audio_griffin_lim: workspace too small");
+    const GriffinLimLayout G = griffin_lim_layout(workspace, B, T, n_fft);
+    NSG_REQUIRE(workspace && workspace_bytes >= G.bytes, NSG_E_WORKSPACE, "nsg_audio_griffin_lim: workspace too small");
     NSG_REQUIRE((int64_t)B * T < 0x7fffffff, NSG_E_UNSUPPORTED, "nsg_audio_griffin_lim: too many frames");
     hipStream_t s = (hipStream_t)stream;
     const int F = n_fft / 2 + 1;
     const int L = hop * (T - 1);
-    v2f *spec = reinterpret_cast<v2f *>(workspace);
-    float *frames = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + nsg_align_up((size_t)B * T * F * 2 * sizeof(float), 256));
+    v2f *spec = G.spec;
+    float *frames = G.frames;
     const int64_t nspec = (int64_t)B * T * F;
     const unsigned nfr = (unsigned)(B * T);
     hipLaunchKernelGGL(init_phase_kernel, dim3(ew_blocks(nspec)), dim3(256), 0, s, S, u, spec, nspec);

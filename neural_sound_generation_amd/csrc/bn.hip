@@ -13,7 +13,7 @@
 
 namespace {
 
-constexpr int MAX_SLABS = 1024;
+constexpr int MAX_SLABS = NSG_MAX_SLABS;
 
 struct SlabGeom {
     int nslab;
@@ -497,7 +497,6 @@ __global__ __launch_bounds__(256) void slab_sum_final_kernel(const float *__rest
     }
 }
 
-inline int ew_blocks(int64_t n) { return (int)(nsg_cdiv(n, 256) > 4096 ? 4096 : (nsg_cdiv(n, 256) < 1 ? 1 : nsg_cdiv(n, 256))); }
 
 inline int check_mc(const char *fn, int64_t M, int C, int dtype)
 {
@@ -566,6 +565,15 @@ __global__ __launch_bounds__(256) void bn_stats_tiles_onepass_kernel(const float
     }
 }
 
+// A tile-statistics buffer: the records [ntiles][3][C] | the finalizer's chunk records (callers size it with nsg_bn_tiles_bytes)
+struct BnTilesLayout { float *tiles; double *chunks; size_t bytes; };
+static BnTilesLayout bn_tiles_layout(void *buf, int64_t ntiles, int C)
+{
+    NsgCarver c(buf);
+    return {c.take<float>(nsg_align_up((size_t)ntiles * 3 * C, 64) * sizeof(float)),
+            c.take<double>((size_t)TILE_CHUNKS * 3 * C * sizeof(double)), c.off + 256};
+}
+
 // used by nsg_conv_forward_bnstats (conv_api.hip): merge the per-tile statistics the conv epilogue wrote
 int nsg_bn_stats_from_tiles(const float *tiles, int ntiles, int64_t M, int C, float eps, float momentum, float *mean,
                             float *invstd, float *running_mean, float *running_var, hipStream_t s)
@@ -575,19 +583,14 @@ int nsg_bn_stats_from_tiles(const float *tiles, int ntiles, int64_t M, int C, fl
                            running_mean, running_var);
         return nsg_check_launch("bn_stats_tiles_onepass_kernel");
     }
-    // the chunk records live behind the tile records (callers size the tile buffer with nsg_bn_tiles_bytes)
-    double *chunks = reinterpret_cast<double *>(const_cast<float *>(tiles) + nsg_align_up((size_t)ntiles * 3 * C, 64));
+    double *chunks = bn_tiles_layout(const_cast<float *>(tiles), ntiles, C).chunks;
     hipLaunchKernelGGL(bn_stats_tiles_fold_kernel, dim3(TILE_CHUNKS), dim3(256), 0, s, tiles, ntiles, C, chunks);
     hipLaunchKernelGGL(bn_stats_tiles_final_kernel, dim3((C + 255) / 256), dim3(256), 0, s, chunks, M, C, eps, momentum, mean, invstd,
                        running_mean, running_var);
     return nsg_check_launch("bn_stats_from_tiles");
 }
 
-// bytes of a tile-statistics buffer for ntiles records of C channels: the records + the finalizer's chunk records
-size_t nsg_bn_tiles_bytes(int64_t ntiles, int C)
-{
-    return nsg_align_up((size_t)ntiles * 3 * C, 64) * sizeof(float) + (size_t)TILE_CHUNKS * 3 * C * sizeof(double) + 256;
-}
+size_t nsg_bn_tiles_bytes(int64_t ntiles, int C) { return bn_tiles_layout(nullptr, ntiles, C).bytes; }
 
 // the slab structure of nsg_bn_backward_sums over M rows: a producer of dy that forms the same sums itself (elementwise.hip:
 // nsg_vq_losses_indexed_bn) walks the rows the same way, so its results are those of the separate pass, bit for bit
@@ -619,7 +622,7 @@ int nsg_launch_bn_bwd_final_wreduce(const float *partial, const float *colsum_pa
                                     const float *wpartial, float *wdst, int wn, hipStream_t s)
 {
     if (nslab < 1 || nslab > MAX_SLABS || C % 4) return nsg_fail(NSG_E_INVALID, "bn_bwd_final: %d slabs / %d channels not supported", nslab, C);
-    const int split = (nslab >= 64 && wn < 512 * 256) ? 8 : 1;      // (nsg_launch_wgrad_reduce's choice)
+    const int split = nsg_slab_split(nslab, wn);
     const int wblocks = (wn + 256 / split - 1) / (256 / split);
     hipLaunchKernelGGL(bn_bwd_final_wreduce_kernel, dim3(C / 4 + wblocks), dim3(256), 0, s, partial, nslab, C, dgamma, dbeta, colsum_partial, colsum,
                        wpartial, wdst, wn, split);

@@ -1036,14 +1036,23 @@ int nsg_launch_c1m_bwd_wgrad(const float *img, const float *w, const float *bias
 }
 
 // ---- the input layer by its tap moments ----
-size_t nsg_c1m_moments_bytes() { return nsg_align_up((size_t)MOM_BLOCKS * MOM_N * sizeof(float), 256) + nsg_align_up((size_t)NSG_C1_MOMENTS * sizeof(double), 256); }
+// workspace: the blocks' partial moments | the moments themselves (used when the caller keeps none)
+struct MomentsLayout { float *partial; double *mom; size_t bytes; };
+static MomentsLayout moments_layout(void *ws)
+{
+    NsgCarver c(ws);
+    return {c.take<float>(nsg_align_up((size_t)MOM_BLOCKS * MOM_N * sizeof(float), 256)),
+            c.take<double>(nsg_align_up((size_t)NSG_C1_MOMENTS * sizeof(double), 256)), c.off};
+}
+size_t nsg_c1m_moments_bytes() { return moments_layout(nullptr).bytes; }
 
 // ws: nsg_c1m_moments_bytes() bytes; the moments (NSG_C1_MOMENTS doubles) go to mom_dst, or into ws when that is null; *mom_out = where
 int nsg_launch_c1m_moments(const float *img, int B, int LH, int LW, int HH, int WW, void *ws, double *mom_dst, const double **mom_out, hipStream_t s)
 {
     const C1Geom g = make_geom(B, LH, LW, HH, WW, 32);
-    float *partial = reinterpret_cast<float *>(ws);
-    double *mom = mom_dst ? mom_dst : reinterpret_cast<double *>(reinterpret_cast<char *>(ws) + nsg_align_up((size_t)MOM_BLOCKS * MOM_N * sizeof(float), 256));
+    const MomentsLayout L = moments_layout(ws);
+    float *partial = L.partial;
+    double *mom = mom_dst ? mom_dst : L.mom;
     int64_t blocks = (g.ntiles + MOM_GROUP - 1) / MOM_GROUP;
     if (blocks > MOM_BLOCKS) blocks = MOM_BLOCKS;
     hipLaunchKernelGGL(c1_tap_moments_kernel, dim3((unsigned)blocks), dim3(256), 0, s, img, partial, g);

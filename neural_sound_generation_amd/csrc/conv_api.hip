@@ -338,14 +338,6 @@ int colsum(const void *x, int dtype, int64_t M, int C, float *out, void *ws, hip
     return nsg_check_launch("colsum");
 }
 
-inline int ew_blocks(int64_t n)
-{
-    int64_t b = nsg_cdiv(n, 256);
-    if (b > 4096) b = 4096;
-    if (b < 1) b = 1;
-    return (int)b;
-}
-
 enum Kind { K_CONV, K_CONVT, K_CONV_C1, K_CONVT_C1 };
 
 // kernel extent / padding per dimension: k, pad are the height's (and the width's for a square kernel, k_w == 0)
@@ -412,6 +404,59 @@ inline size_t stats_tiles_bytes(const nsg_conv_desc *d)
     const int64_t tiles = d->transposed ? 4 * nsg_cdiv(out_pix / 4 + d->B * (d->OH + d->OW), 128) + 8 : nsg_cdiv(out_pix, 128);
     return nsg_align_up(nsg_bn_tiles_bytes(tiles + 8, d->C_out), 256);
 }
+
+// nsg_conv_*'s workspace.  Layers with channels on both sides: the weight gradient's slabs | the column-sum partials of the
+// bias gradient | the tile statistics of nsg_conv_forward_bnstats.  Single-channel layers: the staging image of the GEMM-side
+// passes, overlaid by the stencil weight gradient's partials | the column-sum partials; no tile statistics.
+struct ConvLayout {
+    int kind;                   // classify()'s answer; < 0: the descriptor was rejected, bytes = 0 and there are no sections
+    float *dots, *tiles;        // the staging image (single-channel layers only); the tile statistics (the other layers only)
+    void *wgrad, *colsum;
+    size_t wgrad_bytes, tiles_bytes, bytes;
+};
+ConvLayout conv_layout(void *ws, const nsg_conv_desc *d, const char *fn)
+{
+    ConvLayout L = {};
+    L.kind = classify(d, fn);
+    if (L.kind < 0) return L;
+    const size_t cs_bytes = colsum_ws_bytes((int64_t)d->B * d->OH * d->OW, d->C_out);
+    NsgCarver c(ws);
+    if (L.kind == K_CONV_C1 || L.kind == K_CONVT_C1) {
+        L.wgrad_bytes = nsg_c1_stencil_wgrad_workspace_bytes(L.kind == K_CONV_C1 ? d->C_out : d->C_in);
+        L.wgrad = c.take<char>(L.wgrad_bytes);
+        L.colsum = c.take<char>(cs_bytes);
+        L.dots = reinterpret_cast<float *>(L.wgrad);       // forward and dgrad see the staging image where wgrad sees its two sections
+        if (patches_bytes(d) > L.wgrad_bytes) c.take<char>(patches_bytes(d) - L.wgrad_bytes);     // (sized as max(image, partials) + column sums)
+    } else {
+        const bool t = L.kind == K_CONVT;
+        L.wgrad_bytes = nsg_align_up(nsg_wgrad_workspace_bytes(lowres_pixels(d), kh_of(d) * kw_of(d), t ? d->C_in : d->C_out, t ? d->C_out : d->C_in), 256);
+        L.wgrad = c.take<char>(L.wgrad_bytes);
+        L.colsum = c.take<char>(cs_bytes);
+        L.tiles_bytes = stats_tiles_bytes(d);
+        L.tiles = c.take<float>(L.tiles_bytes);
+    }
+    L.bytes = c.off;
+    return L;
+}
+
+// nsg_bn_relu_c1convt_*'s workspace, forward: the tap products | the loss and bias-gradient partials; backward: the
+// BatchNorm-backward sums | the stencil weight gradient's partials | the column-sum partials of the bias gradient
+struct C1tFwdLayout { float *dots; double *partial; size_t bytes; };
+C1tFwdLayout c1t_fwd_layout(void *ws, int B, int H, int W)
+{
+    NsgCarver c(ws);
+    return {c.take<float>(nsg_align_up((size_t)B * H * W * 16 * sizeof(float), 256)), c.take<double>(2 * C1_LOSS_BLOCKS * sizeof(double)), c.off};
+}
+struct C1tBwdLayout { float *sums, *partial17; void *colsum; size_t bytes; };
+C1tBwdLayout c1t_bwd_layout(void *ws, int B, int H, int W, int C)
+{
+    NsgCarver c(ws);
+    return {c.take<float>(nsg_align_up((size_t)NSG_MAX_SLABS * 2 * C * sizeof(float), 256)), c.take<float>(nsg_c1_stencil_wgrad_workspace_bytes(C)),
+            c.take<char>(colsum_ws_bytes((int64_t)B * 4 * H * W, 1)), c.off};
+}
+
+// nsg_bn_relu_conv1x1_wgrad's part of the 1x1 operators' workspace: the weight gradient's slabs
+inline size_t wgrad_1x1_bytes(int64_t M, int C) { return nsg_align_up(nsg_wgrad_workspace_bytes(M, 1, C, C), 256); }
 
 GatherGemmParams gg_1x1(const void *in, const void *w, const float *bias, void *out, int64_t M, int CI, int CO, int flags, int in_dtype,
                         int out_dtype)
@@ -507,24 +552,7 @@ int nsg_pack_conv_weights_batch(int32_t n, const nsg_conv_desc *descs, const flo
 size_t nsg_conv_workspace_bytes(const nsg_conv_desc *d)
 {
     if (!d) return 0;
-    const int kind = classify(d, "nsg_conv_workspace_bytes");
-    if (kind < 0) return 0;
-    const int T = kh_of(d) * kw_of(d);
-    const int64_t Mp = lowres_pixels(d);
-    size_t bytes = 0;
-    int A, C, taps;
-    if (kind == K_CONV) { A = d->C_out; C = d->C_in; taps = T; }
-    else if (kind == K_CONVT) { A = d->C_in; C = d->C_out; taps = T; }
-    else {   // single-channel layers: the dots / patches staging image of the GEMM-side passes, or the stencil wgrad's partials
-        const size_t sb = nsg_c1_stencil_wgrad_workspace_bytes(kind == K_CONV_C1 ? d->C_out : d->C_in);
-        bytes += patches_bytes(d) > sb ? patches_bytes(d) : sb;
-        bytes += colsum_ws_bytes((int64_t)d->B * d->OH * d->OW, d->C_out);
-        return bytes;
-    }
-    bytes += nsg_align_up(nsg_wgrad_workspace_bytes(Mp, taps, A, C), 256);
-    bytes += colsum_ws_bytes((int64_t)d->B * d->OH * d->OW, d->C_out);
-    bytes += stats_tiles_bytes(d);
-    return bytes;
+    return conv_layout(nullptr, d, "nsg_conv_workspace_bytes").bytes;
 }
 
 static int conv_forward_impl(const nsg_conv_desc *d, const void *x, const void *w_fwd, const float *bias, void *y, int32_t flags,
@@ -551,19 +579,20 @@ static int conv_forward_impl(const nsg_conv_desc *d, const void *x, const void *
         if (stats_tiles) *stats_tiles = nsg_gather_gemm_row_tiles(p);
         return nsg_launch_gather_gemm(p, s);
     }
-    NSG_REQUIRE(workspace && workspace_bytes >= patches_bytes(d), NSG_E_WORKSPACE, "nsg_conv_forward: workspace too small");
+    const ConvLayout L = conv_layout(workspace, d, "nsg_conv_forward");       // (a single-channel layer)
+    NSG_REQUIRE(workspace && workspace_bytes >= L.bytes, NSG_E_WORKSPACE, "nsg_conv_forward: workspace too small");
     const int64_t Mp = lowres_pixels(d);
     if (kind == K_CONV_C1) {   // x is the fp32 single-channel image
         NSG_REQUIRE(!(flags & (NSG_RELU_IN | NSG_TANH_OUT | NSG_RELU_OUT)), NSG_E_UNSUPPORTED,
                     "nsg_conv_forward: no fused activations on the single-input-channel layer");
-        NSG_REQUIRE(stats == nullptr, NSG_E_INVALID, "nsg_conv_forward: internal: tile statistics on the stencil path");
+        NSG_REQUIRE(stats_tiles == nullptr, NSG_E_INVALID, "nsg_conv_forward: internal: tile statistics on the stencil path");
         NSG_REQUIRE(nsg_aligned16(w_fwd) && nsg_aligned16(y), NSG_E_INVALID, "nsg_conv_forward: operands must be 16-byte aligned");
         return nsg_launch_c1_stencil_fwd(reinterpret_cast<const float *>(x), reinterpret_cast<const float *>(w_fwd), bias, y, out_dtype,
                                          d->B, d->OH, d->OW, d->IH, d->IW, d->C_out, s);
     }
-    NSG_REQUIRE(stats == nullptr, NSG_E_UNSUPPORTED, "nsg_conv_forward_bnstats: not available for a single-channel output");
+    NSG_REQUIRE(stats_tiles == nullptr, NSG_E_UNSUPPORTED, "nsg_conv_forward_bnstats: not available for a single-channel output");
     // K_CONVT_C1: per-input-pixel tap products (fp32), then the 4-tap gather with bias (+tanh) into the fp32 image y
-    float *dots = reinterpret_cast<float *>(workspace);
+    float *dots = L.dots;
     int rc = nsg_launch_gather_gemm(gg_1x1(x, w_fwd, nullptr, dots, Mp, d->C_in, 16, flags & NSG_RELU_IN, d->dtype, NSG_F32), s);
     if (rc) return rc;
     hipLaunchKernelGGL(col2im_c1_kernel<false>, dim3(col2im_blocks(d->B, d->OH, d->OW)), dim3(256), 0, s, dots, bias,
@@ -584,7 +613,8 @@ int nsg_conv_forward_bnstats(const nsg_conv_desc *d, const void *x, const void *
 {
     NSG_REQUIRE(d && mean && invstd, NSG_E_INVALID, "nsg_conv_forward_bnstats: null pointer");
     NSG_REQUIRE(!(flags & (NSG_TANH_OUT | NSG_RELU_OUT)), NSG_E_UNSUPPORTED, "nsg_conv_forward_bnstats: statistics are of the linear output");
-    NSG_REQUIRE(workspace && workspace_bytes >= nsg_conv_workspace_bytes(d), NSG_E_WORKSPACE, "nsg_conv_forward_bnstats: workspace too small");
+    const ConvLayout L = conv_layout(workspace, d, "nsg_conv_workspace_bytes");
+    NSG_REQUIRE(workspace && workspace_bytes >= L.bytes, NSG_E_WORKSPACE, "nsg_conv_forward_bnstats: workspace too small");
     if (!d->transposed && d->C_in == 1) {   // stencil layer: the statistics are a separate pass over y
         int rc = conv_forward_impl(d, x, w_fwd, bias, y, flags, workspace, workspace_bytes, stream, nullptr, nullptr);
         if (rc) return rc;
@@ -592,15 +622,12 @@ int nsg_conv_forward_bnstats(const nsg_conv_desc *d, const void *x, const void *
         return nsg_bn_stats(y, (int64_t)d->B * d->OH * d->OW, d->C_out, ydt, eps, momentum, mean, invstd, running_mean, running_var,
                             workspace, workspace_bytes, stream);
     }
-    // the tile statistics live at the END of the workspace (the C=1 staging image uses its start)
-    const size_t tb = stats_tiles_bytes(d);
-    float *tiles = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + nsg_conv_workspace_bytes(d) - tb);
     int ntiles = 0;
-    int rc = conv_forward_impl(d, x, w_fwd, bias, y, flags, workspace, workspace_bytes, stream, tiles, &ntiles);
+    int rc = conv_forward_impl(d, x, w_fwd, bias, y, flags, workspace, workspace_bytes, stream, L.tiles, &ntiles);
     if (rc) return rc;
-    NSG_REQUIRE(nsg_bn_tiles_bytes(ntiles, d->C_out) <= tb, NSG_E_WORKSPACE, "nsg_conv_forward_bnstats: tile buffer too small");
+    NSG_REQUIRE(nsg_bn_tiles_bytes(ntiles, d->C_out) <= L.tiles_bytes, NSG_E_WORKSPACE, "nsg_conv_forward_bnstats: tile buffer too small");
     const int64_t M = (int64_t)d->B * d->OH * d->OW;
-    return nsg_bn_stats_from_tiles(tiles, ntiles, M, d->C_out, eps, momentum, mean, invstd, running_mean, running_var,
+    return nsg_bn_stats_from_tiles(L.tiles, ntiles, M, d->C_out, eps, momentum, mean, invstd, running_mean, running_var,
                                    (hipStream_t)stream);
 }
 
@@ -640,7 +667,8 @@ int nsg_conv_dgrad_relu_add(const nsg_conv_desc *d, const void *dy, const void *
         return nsg_launch_gather_gemm(p, s);
     }
     NSG_REQUIRE(!add && !relu_x, NSG_E_UNSUPPORTED, "nsg_conv_dgrad_relu_add: not available for the single-channel layers");
-    NSG_REQUIRE(workspace && workspace_bytes >= patches_bytes(d), NSG_E_WORKSPACE, "nsg_conv_dgrad: workspace too small");
+    const ConvLayout L = conv_layout(workspace, d, "nsg_conv_dgrad");
+    NSG_REQUIRE(workspace && workspace_bytes >= L.bytes, NSG_E_WORKSPACE, "nsg_conv_dgrad: workspace too small");
     const int64_t Mp = lowres_pixels(d);
     if (kind == K_CONVT_C1) {
         // dy is the fp32 image: dx[pix][ci] = sum_t patch(dy)[pix][t] * w[ci][t]
@@ -649,7 +677,7 @@ int nsg_conv_dgrad_relu_add(const nsg_conv_desc *d, const void *dy, const void *
                                          d->dtype, d->B, d->IH, d->IW, d->OH, d->OW, d->C_in, s);
     }
     // K_CONV_C1: dots[pix][t] = sum_co dy[pix][co] * w[co][t] (fp32), scattered back onto the fp32 image dx
-    float *dots = reinterpret_cast<float *>(workspace);
+    float *dots = L.dots;
     int rc = nsg_launch_gather_gemm(gg_1x1(dy, w_dgrad, nullptr, dots, Mp, d->C_out, 16, 0, d->dtype, NSG_F32), s);
     if (rc) return rc;
     hipLaunchKernelGGL(col2im_c1_kernel<false>, dim3(col2im_blocks(d->B, d->IH, d->IW)), dim3(256), 0, s, dots,
@@ -661,30 +689,27 @@ int nsg_conv_dgrad_relu_add(const nsg_conv_desc *d, const void *dy, const void *
 int nsg_conv_wgrad(const nsg_conv_desc *d, const void *x, const void *dy, float *dw, float *dbias, int32_t flags,
                    void *workspace, size_t workspace_bytes, void *stream)
 {
-    const int kind = classify(d, "nsg_conv_wgrad");
+    const ConvLayout L = conv_layout(workspace, d, "nsg_conv_wgrad");
+    const int kind = L.kind;
     if (kind < 0) return kind;
     NSG_REQUIRE(x && dy && dw, NSG_E_INVALID, "nsg_conv_wgrad: null pointer");
-    NSG_REQUIRE(workspace && workspace_bytes >= nsg_conv_workspace_bytes(d), NSG_E_WORKSPACE, "nsg_conv_wgrad: workspace too small");
+    NSG_REQUIRE(workspace && workspace_bytes >= L.bytes, NSG_E_WORKSPACE, "nsg_conv_wgrad: workspace too small");
     hipStream_t s = (hipStream_t)stream;
-    char *ws = reinterpret_cast<char *>(workspace);
     const int64_t Mp = lowres_pixels(d);
     const int relu_x = (flags & NSG_RELU_IN) ? 1 : 0;
     if (kind == K_CONV_C1 || kind == K_CONVT_C1) {
-        const size_t sb = nsg_c1_stencil_wgrad_workspace_bytes(kind == K_CONV_C1 ? d->C_out : d->C_in);
-        NSG_REQUIRE(workspace_bytes >= sb + colsum_ws_bytes((int64_t)d->B * d->OH * d->OW, d->C_out), NSG_E_WORKSPACE,
-                    "nsg_conv_wgrad: workspace too small");
         if (kind == K_CONV_C1) {   // x is the fp32 image, dy the C_out-channel tensor; dbias = its column sums
             NSG_REQUIRE(!relu_x, NSG_E_UNSUPPORTED, "nsg_conv_wgrad: NSG_RELU_IN on a single-channel input");
             NSG_REQUIRE(nsg_aligned16(dy), NSG_E_INVALID, "nsg_conv_wgrad: dy must be 16-byte aligned");
             return nsg_launch_c1_stencil_wgrad(reinterpret_cast<const float *>(x), dy, d->dtype, 0, dw, dbias, d->B, d->OH, d->OW, d->IH,
-                                               d->IW, d->C_out, ws, sb, s);
+                                               d->IW, d->C_out, L.wgrad, L.wgrad_bytes, s);
         }
         // K_CONVT_C1: dy is the fp32 image, x the C_in-channel tensor; dbias = sum of the image
         NSG_REQUIRE(nsg_aligned16(x), NSG_E_INVALID, "nsg_conv_wgrad: x must be 16-byte aligned");
         int rc = nsg_launch_c1_stencil_wgrad(reinterpret_cast<const float *>(dy), x, d->dtype, relu_x, dw, nullptr, d->B, d->IH, d->IW,
-                                             d->OH, d->OW, d->C_in, ws, sb, s);
+                                             d->OH, d->OW, d->C_in, L.wgrad, L.wgrad_bytes, s);
         if (rc) return rc;
-        if (dbias) return colsum(dy, NSG_F32, (int64_t)d->B * d->OH * d->OW, 1, dbias, ws + sb, s);
+        if (dbias) return colsum(dy, NSG_F32, (int64_t)d->B * d->OH * d->OW, 1, dbias, L.colsum, s);
         return NSG_OK;
     }
     WgradParams p = {};
@@ -698,11 +723,9 @@ int nsg_conv_wgrad(const nsg_conv_desc *d, const void *x, const void *dy, float 
         p.P = x; p.PH = d->IH; p.PW = d->IW; p.A = d->C_in; p.relu_p = relu_x;
         p.Q = dy; p.QH = d->OH; p.QW = d->OW; p.C = d->C_out;
     }
-    const size_t wg_bytes = nsg_align_up(nsg_wgrad_workspace_bytes(Mp, p.KH * p.KW, p.A, p.C), 256);
-    int rc = nsg_launch_wgrad(p, dw, ws, wg_bytes, s);
+    int rc = nsg_launch_wgrad(p, dw, L.wgrad, L.wgrad_bytes, s);
     if (rc) return rc;
-    ws += wg_bytes;
-    if (dbias) return colsum(dy, d->dtype, (int64_t)d->B * d->OH * d->OW, d->C_out, dbias, ws, s);
+    if (dbias) return colsum(dy, d->dtype, (int64_t)d->B * d->OH * d->OW, d->C_out, dbias, L.colsum, s);
     return NSG_OK;
 }
 
@@ -712,9 +735,7 @@ int32_t nsg_bn_relu_c1convt_supported(int32_t dtype, int32_t C) { return dtype =
 size_t nsg_bn_relu_c1convt_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t C)
 {
     if (B <= 0 || H <= 0 || W <= 0 || C <= 0) return 0;
-    const size_t fwd = nsg_align_up((size_t)B * H * W * 16 * sizeof(float), 256) + 2 * C1_LOSS_BLOCKS * sizeof(double);    // dots | loss, bias-gradient partials
-    const size_t bwd = nsg_align_up((size_t)1024 * 2 * C * sizeof(float), 256) + nsg_c1_stencil_wgrad_workspace_bytes(C) +
-                       colsum_ws_bytes((int64_t)B * 4 * H * W, 1);
+    const size_t fwd = c1t_fwd_layout(nullptr, B, H, W).bytes, bwd = c1t_bwd_layout(nullptr, B, H, W, C).bytes;
     return fwd > bwd ? fwd : bwd;
 }
 
@@ -732,7 +753,7 @@ int nsg_bn_relu_c1convt_forward(const void *u, int32_t dtype, const float *mean,
                 "nsg_bn_relu_c1convt_forward: workspace too small");
     NSG_REQUIRE((int64_t)B * H * W * C <= 0x7fffffffLL * 4, NSG_E_UNSUPPORTED, "nsg_bn_relu_c1convt_forward: tensor too large");
     hipStream_t s = (hipStream_t)stream;
-    float *dots = reinterpret_cast<float *>(workspace);
+    float *dots = c1t_fwd_layout(workspace, B, H, W).dots;
     int rc = nsg_launch_bnrelu_dots(u, mean, invstd, gamma, beta, w, dots, (int64_t)B * H * W, C, s);
     if (rc) return rc;
     hipLaunchKernelGGL(col2im_c1_kernel<false>, dim3(col2im_blocks(B, 2 * H, 2 * W)), dim3(256), 0, s, dots, bias, y, B, H, W, 2 * H,
@@ -759,8 +780,9 @@ int nsg_bn_relu_c1convt_forward_mse(const void *u, int32_t dtype, const float *m
                 "nsg_bn_relu_c1convt_forward_mse: workspace too small");
     NSG_REQUIRE((int64_t)B * H * W * C <= 0x7fffffffLL * 4, NSG_E_UNSUPPORTED, "nsg_bn_relu_c1convt_forward_mse: tensor too large");
     hipStream_t s = (hipStream_t)stream;
-    float *dots = reinterpret_cast<float *>(workspace);
-    double *partial = reinterpret_cast<double *>(reinterpret_cast<char *>(workspace) + nsg_align_up((size_t)B * H * W * 16 * sizeof(float), 256));
+    const C1tFwdLayout L = c1t_fwd_layout(workspace, B, H, W);
+    float *dots = L.dots;
+    double *partial = L.partial;
     int rc = nsg_launch_bnrelu_dots(u, mean, invstd, gamma, beta, w, dots, (int64_t)B * H * W, C, s);
     if (rc) return rc;
     const int64_t n = (int64_t)B * 2 * H * T;
@@ -789,13 +811,10 @@ int nsg_bn_relu_c1convt_backward(const void *u, int32_t dtype, const float *mean
                 "nsg_bn_relu_c1convt_backward: workspace too small");
     NSG_REQUIRE((int64_t)B * H * W * C <= 0x7fffffffLL * 4, NSG_E_UNSUPPORTED, "nsg_bn_relu_c1convt_backward: tensor too large");
     hipStream_t s = (hipStream_t)stream;
-    char *ws = reinterpret_cast<char *>(workspace);
-    float *sums = reinterpret_cast<float *>(ws);
-    ws += nsg_align_up((size_t)1024 * 2 * C * sizeof(float), 256);
-    float *partial17 = reinterpret_cast<float *>(ws);
-    ws += nsg_c1_stencil_wgrad_workspace_bytes(C);
+    const C1tBwdLayout L = c1t_bwd_layout(workspace, B, H, W, C);
+    float *sums = L.sums, *partial17 = L.partial17;
     const int64_t ntiles = (int64_t)B * H * ((W + 63) / 64);
-    const int blocks = (int)(ntiles < 1024 ? ntiles : 1024);
+    const int blocks = (int)(ntiles < NSG_MAX_SLABS ? ntiles : NSG_MAX_SLABS);
     const float inv_m = 1.f / (float)((int64_t)B * H * W);
     int rc = nsg_launch_c1m_out_bwd_sums(dy, w, u, mean, invstd, gamma, beta, sums, blocks, B, H, W, C, s);
     if (rc) return rc;
@@ -805,7 +824,7 @@ int nsg_bn_relu_c1convt_backward(const void *u, int32_t dtype, const float *mean
     if (rc) return rc;
     rc = nsg_launch_c1_stencil_wgrad_final(partial17, blocks, C, dw, du_colsum, s);
     if (rc) return rc;
-    if (dbias) return colsum(dy, NSG_F32, (int64_t)B * 4 * H * W, 1, dbias, ws, s);
+    if (dbias) return colsum(dy, NSG_F32, (int64_t)B * 4 * H * W, 1, dbias, L.colsum, s);
     return NSG_OK;
 }
 
@@ -815,7 +834,7 @@ int32_t nsg_bn_relu_conv1x1_supported(int32_t dtype, int32_t C) { return nsg_fla
 size_t nsg_bn_relu_conv1x1_workspace_bytes(int64_t M, int32_t C)
 {
     if (M <= 0 || C <= 0) return 0;
-    const size_t wg = nsg_align_up(nsg_wgrad_workspace_bytes(M, 1, C, C), 256);
+    const size_t wg = wgrad_1x1_bytes(M, C);
     const size_t fl = nsg_flat1x1_workspace_bytes(C);
     return wg > fl ? wg : fl;
 }
@@ -867,7 +886,6 @@ int nsg_bn_relu_conv1x1_wgrad(const void *x, const float *mean, const float *inv
     int rc = check_1x1("nsg_bn_relu_conv1x1_wgrad", M, C, dtype, workspace_bytes, workspace);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    char *ws = reinterpret_cast<char *>(workspace);
     WgradParams p = {};
     p.dtype = NSG_BF16;
     p.B = 1; p.KH = 1; p.KW = 1; p.stride = 1; p.pad = 0; p.pad_w = 0;
@@ -875,7 +893,7 @@ int nsg_bn_relu_conv1x1_wgrad(const void *x, const float *mean, const float *inv
     p.P = dy; p.PH = 1; p.PW = (int)M; p.A = C;
     p.Q = x;  p.QH = 1; p.QW = (int)M; p.C = C;
     p.q_mean = mean; p.q_invstd = invstd; p.q_gamma = gamma; p.q_beta = beta;
-    return nsg_launch_wgrad(p, dw, ws, nsg_align_up(nsg_wgrad_workspace_bytes(M, 1, C, C), 256), s);
+    return nsg_launch_wgrad(p, dw, workspace, wgrad_1x1_bytes(M, C), s);
 }
 
 int nsg_bn_backward_conv1x1_dgrad(const void *h, const void *dy, const float *mean, const float *invstd, const float *gamma,

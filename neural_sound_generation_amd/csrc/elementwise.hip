@@ -5,14 +5,6 @@
 
 namespace {
 
-inline int ew_blocks(int64_t n)
-{
-    int64_t b = nsg_cdiv(n, 256);
-    if (b > 4096) b = 4096;
-    if (b < 1) b = 1;
-    return (int)b;
-}
-
 template <int V>
 struct Vec;
 template <>
@@ -430,6 +422,7 @@ __global__ void clip_colsum_final_kernel(const float *__restrict__ partial, int 
 
 constexpr int CLIP_SLABS = 16;
 constexpr int RED_BLOCKS = 1024;
+static_assert(RED_BLOCKS >= NSG_MAX_SLABS, "the indexed losses write one loss partial per BatchNorm slab");
 
 }  // namespace
 
@@ -628,7 +621,6 @@ int nsg_vq_losses_indexed(const float *z, const float *codebook, const int64_t *
     const float zs = dz_scale * 2.0f / (float)n;
     int nb, rows;
     nsg_bn_slab_geom(N, &nb, &rows);
-    static_assert(RED_BLOCKS >= 1024, "one loss partial per slab");
     if (grad_dtype == NSG_BF16)
         hipLaunchKernelGGL((vq_losses_indexed_kernel<bf16_t, false>), dim3(nb), dim3(256), 0, s, z, codebook, idx, N, D, K, zs, (const bf16_t *)dz_add, (bf16_t *)dz, partial,
                            rows, (const bf16_t *)nullptr, (const float *)nullptr, (const float *)nullptr, (float *)nullptr);
@@ -641,10 +633,18 @@ int nsg_vq_losses_indexed(const float *z, const float *codebook, const int64_t *
 
 int32_t nsg_vq_losses_indexed_bn_supported(int32_t D) { return D >= 8 && D % 8 == 0 && D <= 2048 ? 1 : 0; }
 
+// workspace of nsg_vq_losses_indexed_bn / _bnres: the loss partials | the BatchNorm-backward sums [slabs][2][D]
+struct LossesBnLayout { double *partial; float *bnp; size_t bytes; };
+static LossesBnLayout losses_bn_layout(void *ws, int64_t N, int D)
+{
+    NsgCarver c(ws);
+    return {c.take<double>(nsg_align_up(nsg_reduce_workspace_bytes(N * D), 256)), c.take<float>((size_t)RED_BLOCKS * 2 * D * sizeof(float)), c.off};
+}
+
 size_t nsg_vq_losses_indexed_bn_workspace_bytes(int64_t N, int32_t D)
 {
     if (N <= 0 || D <= 0) return 0;
-    return nsg_align_up(nsg_reduce_workspace_bytes(N * D), 256) + (size_t)RED_BLOCKS * 2 * D * sizeof(float);
+    return losses_bn_layout(nullptr, N, D).bytes;
 }
 
 int nsg_vq_losses_indexed_bn(const float *z, const float *codebook, const int64_t *idx, int64_t N, int32_t D, int32_t K, float dz_scale,
@@ -659,10 +659,11 @@ int nsg_vq_losses_indexed_bn(const float *z, const float *codebook, const int64_
     NSG_REQUIRE(nsg_aligned16(z) && nsg_aligned16(codebook) && nsg_aligned16(dz) && nsg_aligned16(bn_x) && (!dz_add || nsg_aligned16(dz_add)), NSG_E_INVALID,
                 "nsg_vq_losses_indexed_bn: pointers must be 16-byte aligned");
     const int64_t n = N * D;
-    NSG_REQUIRE(workspace && workspace_bytes >= nsg_vq_losses_indexed_bn_workspace_bytes(N, D), NSG_E_WORKSPACE, "nsg_vq_losses_indexed_bn: workspace too small");
+    const LossesBnLayout L = losses_bn_layout(workspace, N, D);
+    NSG_REQUIRE(workspace && workspace_bytes >= L.bytes, NSG_E_WORKSPACE, "nsg_vq_losses_indexed_bn: workspace too small");
     hipStream_t s = (hipStream_t)stream;
-    double *partial = reinterpret_cast<double *>(workspace);
-    float *bnp = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + nsg_align_up(nsg_reduce_workspace_bytes(n), 256));
+    double *partial = L.partial;
+    float *bnp = L.bnp;
     const float zs = dz_scale * 2.0f / (float)n;
     int nb, rows;
     nsg_bn_slab_geom(N, &nb, &rows);
@@ -690,10 +691,11 @@ int nsg_vq_losses_indexed_bnres(const void *h, const void *r, const float *mean,
     NSG_REQUIRE(nsg_aligned16(h) && nsg_aligned16(r) && nsg_aligned16(codebook) && nsg_aligned16(dz) && (!dz_add || nsg_aligned16(dz_add)), NSG_E_INVALID,
                 "nsg_vq_losses_indexed_bnres: pointers must be 16-byte aligned");
     const int64_t n = N * D;
-    NSG_REQUIRE(workspace && workspace_bytes >= nsg_vq_losses_indexed_bn_workspace_bytes(N, D), NSG_E_WORKSPACE, "nsg_vq_losses_indexed_bnres: workspace too small");
+    const LossesBnLayout L = losses_bn_layout(workspace, N, D);
+    NSG_REQUIRE(workspace && workspace_bytes >= L.bytes, NSG_E_WORKSPACE, "nsg_vq_losses_indexed_bnres: workspace too small");
     hipStream_t s = (hipStream_t)stream;
-    double *partial = reinterpret_cast<double *>(workspace);
-    float *bnp = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + nsg_align_up(nsg_reduce_workspace_bytes(n), 256));
+    double *partial = L.partial;
+    float *bnp = L.bnp;
     const float zs = dz_scale * 2.0f / (float)n;
     int nb, rows;
     nsg_bn_slab_geom(N, &nb, &rows);

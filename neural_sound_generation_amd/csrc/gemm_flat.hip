@@ -887,6 +887,18 @@ int flat_blocks(int64_t M, int C)
     return (int)(nt < cap ? nt : cap);
 }
 
+// workspace of a backward pass: the column-sum partials of dh [blocks][C] | the partial sums of the BatchNorm in front
+// [blocks][2][C] | (fused form) the block partials of dw [blocks][C][C], each for the most blocks its form launches
+constexpr int FLAT_FUSED_BLOCKS = 256;
+struct FlatBwdLayout { float *colsum_partial, *prev_partial, *dw_partial; size_t bytes; };
+FlatBwdLayout flat_bwd_layout(void *ws, int C, bool fused)
+{
+    const size_t blocks = fused ? FLAT_FUSED_BLOCKS : FLAT_BLOCKS;
+    NsgCarver c(ws);
+    return {c.take<float>(nsg_align_up(blocks * C * sizeof(float), 256)), c.take<float>(nsg_align_up(blocks * 2 * C * sizeof(float), 256)),
+            c.take<float>(fused ? blocks * C * C * sizeof(float) : 0), c.off};
+}
+
 }  // namespace
 
 // (the staging keeps a thread on one channel group: 256 threads must be a whole number of tile rows, i.e. C / 8 divides 256)
@@ -894,8 +906,8 @@ bool nsg_flat1x1_supported(int dtype, int C) { return dtype == NSG_BF16 && (C ==
 
 size_t nsg_flat1x1_workspace_bytes(int C)
 {
-    const size_t bwd = nsg_align_up((size_t)FLAT_BLOCKS * C * sizeof(float), 256) + nsg_align_up((size_t)FLAT_BLOCKS * 2 * C * sizeof(float), 256);
-    const size_t fwd = nsg_align_up(nsg_bn_tiles_bytes(FLAT_BLOCKS, C), 256);
+    const size_t bwd = flat_bwd_layout(nullptr, C, false).bytes;
+    const size_t fwd = nsg_align_up(nsg_bn_tiles_bytes(FLAT_BLOCKS, C), 256);      // the forward's one section: a statistics record per block
     return bwd > fwd ? bwd : fwd;
 }
 
@@ -916,29 +928,22 @@ int nsg_launch_flat1x1_forward(const void *x, const float *mean, const float *in
 
 // The backward of the 1x1 conv in one pass (C = 128): dx, the column sums of dh, the sums of the BatchNorm in front, and dw
 // (partials per block in the workspace: *dw_partial [blocks][C][C], summed by the caller).  dh itself is not stored.
-constexpr int FLAT_FUSED_BLOCKS = 256;
 bool nsg_flat1x1_fused_bwd_supported(int dtype, int C) { return dtype == NSG_BF16 && C == 128; }
-size_t nsg_flat1x1_fused_bwd_workspace_bytes(int C)
-{
-    return nsg_align_up((size_t)FLAT_FUSED_BLOCKS * C * sizeof(float), 256) + nsg_align_up((size_t)FLAT_FUSED_BLOCKS * 2 * C * sizeof(float), 256) +
-           (size_t)FLAT_FUSED_BLOCKS * C * C * sizeof(float);
-}
+size_t nsg_flat1x1_fused_bwd_workspace_bytes(int C) { return flat_bwd_layout(nullptr, C, true).bytes; }
 int nsg_launch_flat1x1_fused_bwd(const void *h, const void *dy, const float *mean, const float *invstd, const float *gamma, const float *dgamma,
                                  const float *dbeta, const float *w, void *dx, float *dw, int64_t M, int C, void *ws, int *nblocks,
                                  const void *prev_x, const float *prev_mean, const float *prev_invstd, const float *prev_gamma,
                                  const float *prev_beta, float **colsum_partial, float **prev_partial, float **dw_partial, hipStream_t s)
 {
     (void)dw;       // (the caller sums the block partials of dw together with the BatchNorm sums: nsg_launch_bn_bwd_final_wreduce)
-    char *wsb = reinterpret_cast<char *>(ws);
+    const FlatBwdLayout L = flat_bwd_layout(ws, C, true);
     FlatParams p = {};
     p.x = reinterpret_cast<const bf16_t *>(h); p.g = reinterpret_cast<const bf16_t *>(dy); p.w = w;
     p.mean = mean; p.invstd = invstd; p.gamma = gamma; p.dgamma = dgamma; p.dbeta = dbeta; p.inv_m = 1.f / (float)M;
     p.prev_x = reinterpret_cast<const bf16_t *>(prev_x);
     p.prev_mean = prev_mean; p.prev_invstd = prev_invstd; p.prev_gamma = prev_gamma; p.prev_beta = prev_beta;
-    p.colsum_partial = reinterpret_cast<float *>(wsb);
-    p.prev_partial = reinterpret_cast<float *>(wsb + nsg_align_up((size_t)FLAT_FUSED_BLOCKS * C * sizeof(float), 256));
-    float *dwp = reinterpret_cast<float *>(wsb + nsg_align_up((size_t)FLAT_FUSED_BLOCKS * C * sizeof(float), 256) +
-                                           nsg_align_up((size_t)FLAT_FUSED_BLOCKS * 2 * C * sizeof(float), 256));
+    p.colsum_partial = L.colsum_partial; p.prev_partial = L.prev_partial;
+    float *dwp = L.dw_partial;
     p.out = reinterpret_cast<bf16_t *>(dx); p.M = M;
     const int64_t nt = (M + ROWS - 1) / ROWS;
     const int blocks = (int)(nt < FLAT_FUSED_BLOCKS ? nt : FLAT_FUSED_BLOCKS);
@@ -962,17 +967,17 @@ int nsg_launch_flat1x1_backward(const void *h, const void *dy, const float *mean
                                 const void *prev_x, const float *prev_mean, const float *prev_invstd, const float *prev_gamma,
                                 const float *prev_beta, float **prev_partial, hipStream_t s)
 {
-    float *partial = reinterpret_cast<float *>(ws);
+    const FlatBwdLayout L = flat_bwd_layout(ws, C, false);
     FlatParams p = {};
     p.x = reinterpret_cast<const bf16_t *>(h); p.g = reinterpret_cast<const bf16_t *>(dy); p.w = w;
     p.mean = mean; p.invstd = invstd; p.gamma = gamma; p.dgamma = dgamma; p.dbeta = dbeta; p.inv_m = 1.f / (float)M;
     if (prev_x) {
         p.prev_x = reinterpret_cast<const bf16_t *>(prev_x);
         p.prev_mean = prev_mean; p.prev_invstd = prev_invstd; p.prev_gamma = prev_gamma; p.prev_beta = prev_beta;
-        p.prev_partial = reinterpret_cast<float *>(reinterpret_cast<char *>(ws) + nsg_align_up((size_t)FLAT_BLOCKS * C * sizeof(float), 256));
+        p.prev_partial = L.prev_partial;
         if (prev_partial) *prev_partial = p.prev_partial;
     }
-    p.out = reinterpret_cast<bf16_t *>(dx); p.mid = reinterpret_cast<bf16_t *>(dh); p.colsum_partial = partial; p.M = M;
+    p.out = reinterpret_cast<bf16_t *>(dx); p.mid = reinterpret_cast<bf16_t *>(dh); p.colsum_partial = L.colsum_partial; p.M = M;
     const int blocks = flat_blocks(M, C);
     *nblocks = blocks;
     return dispatch_flat<1>(p, C, blocks, s);

@@ -807,7 +807,7 @@ int launch_wg(const WgradParams &p, int nslab, hipStream_t s)
 int nsg_launch_wgrad_reduce(const float *partial, float *dst, int nslab, int ntaps, int A, int C, hipStream_t s)
 {
     const int64_t total = (int64_t)ntaps * A * C;
-    const int split = (nslab >= 64 && total < 512 * 256) ? 8 : 1;   // few outputs, many slabs: share the slabs
+    const int split = nsg_slab_split(nslab, total);
     const int64_t nb = nsg_cdiv(total, 256 / split);
     const int blocks = (int)(nb > 4096 ? 4096 : nb);
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks), dim3(256), 0, s, partial, dst, nslab, ntaps, A, C, split);
@@ -818,7 +818,7 @@ size_t nsg_wgrad_workspace_bytes(int64_t Mp, int ntaps, int A, int C)
 {
     const SlabPlan sp = plan_slabs(Mp, ntaps, A, C);
     int nslab = sp.nslab;
-    if ((ntaps == 9 || ntaps == 16) && A % 128 == 0 && C % 128 == 0 && nsg_wgrad_strip_slabs(ntaps, A, C) > nslab)
+    if (nsg_wgrad_strip_shape(ntaps, A, C) && nsg_wgrad_strip_slabs(ntaps, A, C) > nslab)
         nslab = nsg_wgrad_strip_slabs(ntaps, A, C);       // whichever kernel runs, its slabs fit
     return (size_t)nslab * ntaps * A * C * sizeof(float);
 }
@@ -867,10 +867,5 @@ int nsg_launch_wgrad(WgradParams p, float *dst, void *ws, size_t ws_bytes, hipSt
         rc = launch_wg<2, 2, 2, 2>(p, sp.nslab, s);          // 128 x 128
     }
     if (rc != NSG_OK) return rc;
-    const int64_t total = (int64_t)ntaps * p.A * p.C;
-    const int split = (sp.nslab >= 64 && total < 512 * 256) ? 8 : 1;   // few outputs, many slabs: share the slabs
-    const int64_t nb = nsg_cdiv(total, 256 / split);
-    const int blocks = (int)(nb > 4096 ? 4096 : nb);
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks), dim3(256), 0, s, p.partial, dst, sp.nslab, ntaps, p.A, p.C, split);
-    return nsg_check_launch("wgrad_reduce_kernel");
+    return nsg_launch_wgrad_reduce(p.partial, dst, sp.nslab, ntaps, p.A, p.C, s);
 }

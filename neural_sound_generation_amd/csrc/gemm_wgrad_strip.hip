@@ -412,11 +412,13 @@ int nsg_wgrad_strip_slabs(int ntaps, int A, int C)
     return n < 8 ? 8 : n;
 }
 
+bool nsg_wgrad_strip_shape(int ntaps, int A, int C) { return (ntaps == 9 || ntaps == 16) && A % 128 == 0 && C % 128 == 0; }
+
 bool nsg_wgrad_strip_applicable(const WgradParams &p)
 {
     if (!g_wgrad_strip || p.onehot || p.q_mean || p.relu_p || p.relu_q) return false;
     if (p.dtype == NSG_BF16 ? !(g_wgrad_strip & 1) : !(p.dtype == NSG_F32 && (g_wgrad_strip & 2))) return false;   // bit 0: bf16 form, bit 1: fp32 form
-    if (p.A % 128 != 0 || p.C % 128 != 0) return false;
+    if (!nsg_wgrad_strip_shape(p.KH * p.KW, p.A, p.C)) return false;
     const bool k33 = p.KH == 3 && p.KW == 3 && p.stride == 1;
     const bool k44 = p.KH == 4 && p.KW == 4 && p.stride == 2;
     return k33 || k44;

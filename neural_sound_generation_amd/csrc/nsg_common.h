@@ -169,6 +169,29 @@ static inline bool nsg_aligned16(const void *p) { return (reinterpret_cast<uintp
 __device__ __forceinline__ bool nsg_aligned16_dev(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 static inline int64_t nsg_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline size_t nsg_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// grid of an element-wise, grid-stride kernel over n items, 256 threads per block
+static inline int ew_blocks(int64_t n)
+{
+    const int64_t b = nsg_cdiv(n, 256);
+    return (int)(b > 4096 ? 4096 : (b < 1 ? 1 : b));
+}
+
+// A caller-allocated workspace is cut into sections by ONE layout function per workspace: it walks the buffer front to back with
+// a carver and returns the sections' pointers and the total.  The size query calls it on a null base (null sections, the same
+// total), the entry point on the real pointer, so the two cannot disagree.  (A layout struct lists its sections in buffer order
+// and is returned as a braced list of take()s: the elements of a braced list are evaluated left to right.)
+struct NsgCarver {
+    char *base;
+    size_t off;
+    explicit NsgCarver(void *ws, size_t start = 0) : base(reinterpret_cast<char *>(ws)), off(start) {}
+    template <typename T> T *take(size_t bytes) { off += bytes; return base ? reinterpret_cast<T *>(base + off - bytes) : nullptr; }
+};
+
+// Most partial records a two-stage BatchNorm / weight-gradient reduction writes: bn.hip's finalisers hold MAX_SLABS / 256 of
+// them per thread, and stencil_c1.hip's and conv_api.hip's single-channel passes cap their grids and size their sections by it.
+constexpr int NSG_MAX_SLABS = 1024;
+// the closing slab sum of a weight gradient shares the slabs 8 ways when there are many slabs and few outputs
+static inline int nsg_slab_split(int nslab, int64_t outputs) { return (nslab >= 64 && outputs < 512 * 256) ? 8 : 1; }
 
 // W consecutive elements <-> floats, W a multiple of the type's 16-byte element count
 template <typename T, int W>
@@ -270,7 +293,10 @@ int nsg_launch_gather_gemm(const GatherGemmParams &p, hipStream_t s);
 // minimum over the slices in slice order -- the same (distance, index) the unsplit search returns, bit for bit -- and gathers.
 constexpr int NSG_SEARCH_CUS = 256;                         // CUs of an MI355X (speed only): two search blocks per CU up to D = 128, one beyond
 int nsg_vq_slices(int64_t N, int D, int K);                 // S: 1, 2, 4 or 8
-size_t nsg_vq_slice_bytes(int64_t N, int D, int K);         // [S][N] floats + [S][N] ints behind the searches' other workspace; 0 for S = 1
+// the search's workspace: |x|^2 [N] | |c|^2 [K] | the slices' distances [S][N] | their indices [S][N] (the last two null for
+// S = 1); vq_bf16.hip puts the codebook's bf16 parts behind it
+struct VqLayout { float *x2, *c2, *part_d; int *part_i; size_t bytes; };
+VqLayout nsg_vq_layout(void *ws, int64_t N, int D, int K);
 // idx / dmin / codes / bf16 codes (each optional except idx) from the S partial results; clip_rows as in nsg_vq_forward_bf16x3_cond
 int nsg_launch_vq_combine(const float *pd, const int *pi, int S, int64_t N, int D, int K, const float *e, int64_t *idx, float *codes,
                           float *dmin, bf16_t *codes_lp, int lp_relu, const float *clip_rows, int64_t rows_per_clip, hipStream_t s);
@@ -289,7 +315,7 @@ int nsg_launch_wgrad_reduce(const float *partial, float *dst, int nslab, int nta
 size_t nsg_bn_tiles_bytes(int64_t ntiles, int C);
 int nsg_bn_stats_from_tiles(const float *tiles, int ntiles, int64_t M, int C, float eps, float momentum, float *mean,
                             float *invstd, float *running_mean, float *running_var, hipStream_t s);
-// dbeta[c] = sum_s partial[s][0][c], dgamma[c] = sum_s partial[s][1][c] over nslab <= 1024 slabs of [2][C] (fixed order, double)
+// dbeta[c] = sum_s partial[s][0][c], dgamma[c] = sum_s partial[s][1][c] over nslab <= NSG_MAX_SLABS slabs of [2][C] (fixed order, double)
 void nsg_bn_slab_geom(int64_t M, int *nslab, int *rows);      // bn.hip: slabs of nsg_bn_backward_sums over M rows
 int nsg_launch_bn_bwd_final(const float *partial, int nslab, int C, float *dgamma, float *dbeta, hipStream_t s);
 // ... and colsum[c] = sum_s colsum_partial[s][c] in the same launch
@@ -297,7 +323,7 @@ int nsg_launch_bn_bwd_final_wreduce(const float *partial, const float *colsum_pa
                                     const float *wpartial, float *wdst, int wn, hipStream_t s);
 int nsg_launch_bn_bwd_final_colsum(const float *partial, const float *colsum_partial, int nslab, int C, float *dgamma, float *dbeta,
                                    float *colsum, hipStream_t s);
-// out[c] = sum_s partial[s][c] over nslab <= 1024 slabs of [C] (fixed order, double)
+// out[c] = sum_s partial[s][c] over nslab <= NSG_MAX_SLABS slabs of [C] (fixed order, double)
 int nsg_launch_slab_sum_final(const float *partial, int nslab, int C, float *out, hipStream_t s);
 
 // ---- launchers and predicates one .hip file defines and another calls, grouped by the defining file.  No .hip file declares
@@ -361,5 +387,6 @@ int nsg_launch_c1m_onepass_fixup(const double *mom, const float *w, const float 
                                  hipStream_t s);
 // gemm_wgrad_strip.hip: the row-strip kernel for the bf16 3x3/1 and 4x4/2 layers with channels in multiples of 128
 int nsg_wgrad_strip_slabs(int ntaps, int A, int C);
+bool nsg_wgrad_strip_shape(int ntaps, int A, int C);         // the shapes it exists for; its slabs count in nsg_wgrad_workspace_bytes
 bool nsg_wgrad_strip_applicable(const WgradParams &p);
 int nsg_launch_wgrad_strip(const WgradParams &p, int *nslab, hipStream_t s);

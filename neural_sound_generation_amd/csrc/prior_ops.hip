@@ -292,6 +292,13 @@ __global__ void ce_masked_final_kernel(const double *partial, int n, const CeSca
 }
 
 constexpr int SUM_BLOCKS = 256;
+// nsg_cross_entropy's workspace: the rows' losses | the block sums
+struct CeLayout { float *row_loss; double *partial; size_t bytes; };
+inline CeLayout ce_layout(void *ws, int64_t M)
+{
+    NsgCarver c(ws);
+    return {c.take<float>(nsg_align_up((size_t)M * sizeof(float), 256)), c.take<double>(SUM_BLOCKS * sizeof(double)), c.off};
+}
 struct CeMaskedLayout { size_t partial, count, scalars, bytes; };
 inline CeMaskedLayout ce_masked_layout(int64_t M, int64_t B)
 {
@@ -312,7 +319,6 @@ inline int gate_slabs(int64_t B, int64_t rows_per_clip, int C)
     if (s > most) s = most;
     return (int)(s < 1 ? 1 : s);
 }
-inline int ew_blocks(int64_t n) { const int64_t b = nsg_cdiv(n, 256); return (int)(b > 4096 ? 4096 : (b < 1 ? 1 : b)); }
 
 }  // namespace
 
@@ -340,16 +346,17 @@ int nsg_gated_activation_backward(const float *x, const float *cond, const float
     return nsg_check_launch("gated_bwd_kernel");
 }
 
-size_t nsg_cross_entropy_workspace_bytes(int64_t M) { return M > 0 ? nsg_align_up((size_t)M * sizeof(float), 256) + SUM_BLOCKS * sizeof(double) : 0; }
+size_t nsg_cross_entropy_workspace_bytes(int64_t M) { return M > 0 ? ce_layout(nullptr, M).bytes : 0; }
 
 int nsg_cross_entropy(const float *logits, const int64_t *target, int64_t M, int32_t K, float grad_scale, float *loss_out, float *dlogits,
                       void *workspace, size_t workspace_bytes, void *stream)
 {
     NSG_REQUIRE(logits && target && loss_out && M > 0 && K > 0, NSG_E_INVALID, "nsg_cross_entropy: bad argument");
-    NSG_REQUIRE(workspace && workspace_bytes >= nsg_cross_entropy_workspace_bytes(M), NSG_E_WORKSPACE, "nsg_cross_entropy: workspace too small");
+    const CeLayout L = ce_layout(workspace, M);
+    NSG_REQUIRE(workspace && workspace_bytes >= L.bytes, NSG_E_WORKSPACE, "nsg_cross_entropy: workspace too small");
     hipStream_t s = (hipStream_t)stream;
-    float *row_loss = reinterpret_cast<float *>(workspace);
-    double *partial = reinterpret_cast<double *>(reinterpret_cast<char *>(workspace) + nsg_align_up((size_t)M * sizeof(float), 256));
+    float *row_loss = L.row_loss;
+    double *partial = L.partial;
     int64_t blocks = nsg_cdiv(M, 4);
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(cross_entropy_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, logits, target, M, K, grad_scale / (float)M, (const float *)nullptr,

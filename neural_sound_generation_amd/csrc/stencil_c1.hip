@@ -594,7 +594,7 @@ __global__ __launch_bounds__(256) void c1_bn_bwd_wgrad_kernel(const float *__res
     }
 }
 
-constexpr int WGRAD_BLOCKS = 1024;
+constexpr int WGRAD_BLOCKS = NSG_MAX_SLABS;
 
 }  // namespace
 
@@ -646,9 +646,19 @@ extern "C" NSG_API void nsg_debug_set_c1_moments(int on) { g_c1_moments = on; }
 #endif
 
 namespace {
-constexpr int FUSED_BLOCKS = 1024;      // = bn.hip's MAX_SLABS (bn_bwd_final_kernel) and WGRAD_BLOCKS
-size_t fused_tiles_bytes(int C) { return nsg_align_up(nsg_bn_tiles_bytes(2 * FUSED_BLOCKS, C), 256); }
-size_t fused_sums_bytes(int C) { return nsg_align_up((size_t)FUSED_BLOCKS * 2 * C * sizeof(float), 256); }
+constexpr int FUSED_BLOCKS = NSG_MAX_SLABS;      // records per backward pass: bn_bwd_final_kernel and c1_stencil_wgrad_final_kernel read them
+// The workspace.  The forward's statistics records and the backward's sums | 17-column partials overlay each other at the
+// front; the tap moments (c1_mfma.hip) sit behind the larger of the two, where both directions find them.
+struct C1BnLayout { float *tiles, *sums, *partial17; void *moments; size_t bytes; };       // tiles: forward; sums, partial17: backward
+C1BnLayout c1bn_layout(void *ws, int C)
+{
+    NsgCarver f(ws), b(ws);
+    float *tiles = f.take<float>(nsg_align_up(nsg_bn_tiles_bytes(2 * FUSED_BLOCKS, C), 256));
+    float *sums = b.take<float>(nsg_align_up((size_t)FUSED_BLOCKS * 2 * C * sizeof(float), 256));
+    float *partial17 = b.take<float>(nsg_align_up(nsg_c1_stencil_wgrad_workspace_bytes(C), 256));
+    NsgCarver m(ws, f.off > b.off ? f.off : b.off);
+    return {tiles, sums, partial17, m.take<char>(nsg_c1m_moments_bytes()), m.off};
+}
 int check_c1bn(const char *fn, int B, int H, int W, int C)
 {
     if (B <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1)) return nsg_fail(NSG_E_INVALID, "%s: the image extent must be positive and even (H=%d, W=%d)", fn, H, W);
@@ -663,9 +673,7 @@ extern "C" {
 size_t nsg_c1conv_bn_workspace_bytes(int32_t C)
 {
     if (C <= 0) return 0;
-    const size_t fwd = fused_tiles_bytes(C);
-    const size_t bwd = fused_sums_bytes(C) + nsg_align_up(nsg_c1_stencil_wgrad_workspace_bytes(C), 256);
-    return (fwd > bwd ? fwd : bwd) + nsg_c1m_moments_bytes();       // (the moments sit behind the larger of the two)
+    return c1bn_layout(nullptr, C).bytes;
 }
 
 int nsg_c1conv_bn_relu_forward(const float *img, const float *w, const float *bias, const float *gamma, const float *beta, float *mean,
@@ -684,12 +692,13 @@ int nsg_c1conv_bn_relu_forward(const float *img, const float *w, const float *bi
     // same instruction sequence as the values they normalise
     const bool mfma = y_dtype == NSG_BF16 && nsg_c1m_supported(C);
     if (training) {
-        NSG_REQUIRE(workspace && workspace_bytes >= nsg_c1conv_bn_workspace_bytes(C), NSG_E_WORKSPACE, "nsg_c1conv_bn_relu_forward: workspace too small");
+        const C1BnLayout L = c1bn_layout(workspace, C);
+        NSG_REQUIRE(workspace && workspace_bytes >= L.bytes, NSG_E_WORKSPACE, "nsg_c1conv_bn_relu_forward: workspace too small");
         const int blocks = g.ntiles < 2 * FUSED_BLOCKS ? g.ntiles : 2 * FUSED_BLOCKS;
-        float *tiles = reinterpret_cast<float *>(workspace);
+        float *tiles = L.tiles;
         if (mfma && g_c1_moments) {      // statistics of h from the image's tap moments: no pass over h
             const double *mom = nullptr;
-            rc = nsg_launch_c1m_moments(img, B, g.LH, g.LW, H, W, reinterpret_cast<char *>(workspace) + nsg_c1conv_bn_workspace_bytes(C) - nsg_c1m_moments_bytes(), moments, &mom, s);
+            rc = nsg_launch_c1m_moments(img, B, g.LH, g.LW, H, W, L.moments, moments, &mom, s);
             if (rc) return rc;
             rc = nsg_launch_c1m_stats_from_moments(mom, w, bias, (int64_t)B * g.LH * g.LW, C, eps, momentum, mean, invstd, running_mean, running_var, s);
             if (rc) return rc;
@@ -725,18 +734,18 @@ int nsg_c1conv_bn_relu_backward(const float *img, const float *w, const float *b
     int rc = check_c1bn("nsg_c1conv_bn_relu_backward", B, H, W, C);
     if (rc) return rc;
     NSG_REQUIRE(nsg_aligned16(w) && nsg_aligned16(dy), NSG_E_INVALID, "nsg_c1conv_bn_relu_backward: w and dy must be 16-byte aligned");
-    NSG_REQUIRE(workspace && workspace_bytes >= nsg_c1conv_bn_workspace_bytes(C), NSG_E_WORKSPACE, "nsg_c1conv_bn_relu_backward: workspace too small");
+    const C1BnLayout L = c1bn_layout(workspace, C);
+    NSG_REQUIRE(workspace && workspace_bytes >= L.bytes, NSG_E_WORKSPACE, "nsg_c1conv_bn_relu_backward: workspace too small");
     hipStream_t s = (hipStream_t)stream;
     const C1Geom g = make_geom(B, H / 2, W / 2, H, W, C);
     const int blocks = g.ntiles < FUSED_BLOCKS ? g.ntiles : FUSED_BLOCKS;
-    float *sums = reinterpret_cast<float *>(workspace);
-    float *partial17 = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + fused_sums_bytes(C));
+    float *sums = L.sums, *partial17 = L.partial17;
     const float inv_m = 1.f / (float)((int64_t)B * g.LH * g.LW);
     if (dy_dtype == NSG_BF16 && nsg_c1m_supported(C) && g_c1_moments) {      // one pass over dy (c1_mfma.hip: "by its tap moments")
         const double *mom = moments;
         const int64_t M = (int64_t)B * g.LH * g.LW;
         if (!mom) {
-            rc = nsg_launch_c1m_moments(img, B, g.LH, g.LW, H, W, reinterpret_cast<char *>(workspace) + nsg_c1conv_bn_workspace_bytes(C) - nsg_c1m_moments_bytes(), nullptr, &mom, s);
+            rc = nsg_launch_c1m_moments(img, B, g.LH, g.LW, H, W, L.moments, nullptr, &mom, s);
             if (rc) return rc;
         }
         rc = nsg_launch_c1m_bwd_onepass(img, w, bias, dy, mean, invstd, gamma, beta, sums, partial17, blocks, B, g.LH, g.LW, H, W, C, s);

@@ -535,10 +535,24 @@ int nsg_vq_slices(int64_t N, int D, int K)
     return best;
 }
 
-size_t nsg_vq_slice_bytes(int64_t N, int D, int K)
+VqLayout nsg_vq_layout(void *ws, int64_t N, int D, int K)
 {
     const int S = nsg_vq_slices(N, D, K);
-    return S > 1 ? 2 * nsg_align_up((size_t)S * (size_t)N * sizeof(float), 256) : 0;
+    const size_t slice = S > 1 ? nsg_align_up((size_t)S * (size_t)N * sizeof(float), 256) : 0;
+    NsgCarver c(ws);
+    VqLayout L = {c.take<float>(nsg_align_up((size_t)N * sizeof(float), 256)), c.take<float>(nsg_align_up((size_t)K * sizeof(float), 256)),
+                  c.take<float>(slice), c.take<int>(slice), c.off};
+    if (S == 1) { L.part_d = nullptr; L.part_i = nullptr; }
+    return L;
+}
+
+// nsg_index_add_rows*'s workspace: the integer counts | the one-hot GEMM's slabs
+struct IndexAddLayout { int *cnt; void *slabs; size_t slab_bytes, bytes; };
+static IndexAddLayout index_add_layout(void *ws, int64_t N, int D, int K)
+{
+    const size_t slab_bytes = nsg_wgrad_workspace_bytes(N, 1, K, D);
+    NsgCarver c(ws);
+    return {c.take<int>(nsg_align_up((size_t)K * sizeof(int), 256)), c.take<char>(slab_bytes), slab_bytes, c.off};
 }
 
 int nsg_launch_vq_combine(const float *pd, const int *pi, int S, int64_t N, int D, int K, const float *e, int64_t *idx, float *codes,
@@ -554,7 +568,7 @@ extern "C" {
 size_t nsg_vq_workspace_bytes(int64_t N, int32_t D, int32_t K)
 {
     if (N < 0 || K < 0) return 0;
-    return nsg_align_up((size_t)N * sizeof(float), 256) + nsg_align_up((size_t)K * sizeof(float), 256) + nsg_vq_slice_bytes(N, D, K);
+    return nsg_vq_layout(nullptr, N, D, K).bytes;
 }
 
 int nsg_rowsumsq(const float *v, int64_t rows, int32_t D, float *out, void *stream)
@@ -573,17 +587,10 @@ static int vq_forward_impl(bool mfma, const float *x, const float *e, int64_t N,
     NSG_REQUIRE(x && e && idx_out && N >= 0 && D > 0 && K > 0, NSG_E_INVALID, "nsg_vq_forward: bad argument");
     NSG_REQUIRE(D <= 256, NSG_E_UNSUPPORTED, "nsg_vq_forward: D=%d > 256 is not supported", D);
     if (N == 0) return NSG_OK;
-    NSG_REQUIRE(workspace && workspace_bytes >= nsg_vq_workspace_bytes(N, D, K), NSG_E_WORKSPACE,
-                "nsg_vq_forward: workspace too small");
-    float *x2 = reinterpret_cast<float *>(workspace);
-    float *c2 = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + nsg_align_up((size_t)N * sizeof(float), 256));
-    float *part_d = nullptr;
-    int *part_i = nullptr;
-    if (nsg_vq_slices(N, D, K) > 1) {
-        char *base = reinterpret_cast<char *>(workspace) + nsg_align_up((size_t)N * sizeof(float), 256) + nsg_align_up((size_t)K * sizeof(float), 256);
-        part_d = reinterpret_cast<float *>(base);
-        part_i = reinterpret_cast<int *>(base + nsg_vq_slice_bytes(N, D, K) / 2);
-    }
+    const VqLayout L = nsg_vq_layout(workspace, N, D, K);
+    NSG_REQUIRE(workspace && workspace_bytes >= L.bytes, NSG_E_WORKSPACE, "nsg_vq_forward: workspace too small");
+    float *x2 = L.x2, *c2 = L.c2, *part_d = L.part_d;
+    int *part_i = L.part_i;
     int rc = nsg_rowsumsq(x, N, D, x2, stream);
     if (rc) return rc;
     rc = nsg_rowsumsq(e, K, D, c2, stream);
@@ -622,7 +629,7 @@ int nsg_debug_dot(const float *x, const float *e, int32_t N, int32_t D, int32_t 
 size_t nsg_index_add_workspace_bytes(int64_t N, int32_t D, int32_t K)
 {
     if (N <= 0 || D <= 0 || K <= 0) return 0;
-    return nsg_align_up((size_t)K * sizeof(int), 256) + nsg_wgrad_workspace_bytes(N, 1, K, D);
+    return index_add_layout(nullptr, N, D, K).bytes;
 }
 
 static int index_add_impl(int onehot_mode, const int64_t *idx, const float *g, int64_t N, int32_t D, int32_t K, float *out,
@@ -647,12 +654,11 @@ static int index_add_impl(int onehot_mode, const int64_t *idx, const float *g, i
     NSG_REQUIRE(idx && g && out && N > 0 && D > 0 && K > 0, NSG_E_INVALID, "nsg_index_add_rows: bad argument");
     NSG_REQUIRE(N < 0x7fffffff, NSG_E_UNSUPPORTED, "nsg_index_add_rows: too many rows");
     NSG_REQUIRE(D % 4 == 0, NSG_E_UNSUPPORTED, "nsg_index_add_rows: D=%d must be a multiple of 4", D);
-    NSG_REQUIRE(workspace && workspace_bytes >= nsg_index_add_workspace_bytes(N, D, K), NSG_E_WORKSPACE,
-                "nsg_index_add_rows: workspace too small");
+    const IndexAddLayout L = index_add_layout(workspace, N, D, K);
+    NSG_REQUIRE(workspace && workspace_bytes >= L.bytes, NSG_E_WORKSPACE, "nsg_index_add_rows: workspace too small");
     hipStream_t s = (hipStream_t)stream;
-    const size_t cnt_bytes = nsg_align_up((size_t)K * sizeof(int), 256);
     if (counts_out) {
-        int *cnt = reinterpret_cast<int *>(workspace);
+        int *cnt = L.cnt;
         hipError_t err = hipMemsetAsync(cnt, 0, (size_t)K * sizeof(int), s);
         if (err != hipSuccess) return nsg_fail((int)err, "nsg_index_add_rows: memset failed");
         const int nb = (int)(nsg_cdiv(N, 1024) > 256 ? 256 : nsg_cdiv(N, 1024));
@@ -670,7 +676,7 @@ static int index_add_impl(int onehot_mode, const int64_t *idx, const float *g, i
     p.KH = 1; p.KW = 1; p.stride = 1; p.pad = 0;
     p.Mp = (int)N;
     p.onehot = onehot_mode;
-    return nsg_launch_wgrad(p, out, reinterpret_cast<char *>(workspace) + cnt_bytes, workspace_bytes - cnt_bytes, s);
+    return nsg_launch_wgrad(p, out, L.slabs, L.slab_bytes, s);
 }
 
 int nsg_gather_rows(const float *e, const int64_t *idx, int64_t N, int32_t D, int32_t K, float *out, void *stream)

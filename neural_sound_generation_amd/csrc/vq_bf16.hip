@@ -252,7 +252,15 @@ int launch(const typename RowArg<BNRES>::T x, const bf16_t *ehi, const bf16_t *e
 }
 
 inline int dp_of(int D) { return D <= 16 ? 16 : D <= 32 ? 32 : D <= 64 ? 64 : D <= 128 ? 128 : 256; }
-inline size_t split_bytes(int D, int K) { return nsg_align_up((size_t)nsg_cdiv(K, 32) * 32 * dp_of(D) * sizeof(bf16_t), 256); }
+// the workspace: the exact search's sections (vq.hip; |x|^2 and |c|^2 are used) | the codebook's bf16 high parts | its low parts
+struct Bf16x3Layout { float *x2, *c2; bf16_t *ehi, *elo; size_t bytes; };
+Bf16x3Layout bf16x3_layout(void *ws, int64_t N, int D, int K)
+{
+    const VqLayout X = nsg_vq_layout(ws, N, D, K);
+    const size_t split = nsg_align_up((size_t)nsg_cdiv(K, 32) * 32 * dp_of(D) * sizeof(bf16_t), 256);
+    NsgCarver c(ws, X.bytes);
+    return {X.x2, X.c2, c.take<bf16_t>(split), c.take<bf16_t>(split), c.off};
+}
 
 // the entry points behind the null checks of their row operand (xf: the fp32 rows again, for the distances' |x|^2 pass)
 template <bool BNRES>
@@ -267,14 +275,11 @@ int search(const typename RowArg<BNRES>::T x, const float *xf, bool rows_aligned
                 NSG_E_INVALID, "nsg_vq_forward_bf16x3: pointers must be 16-byte aligned");
     bf16_t *lp = reinterpret_cast<bf16_t *>(codes_bf16_out);
     if (N == 0) return NSG_OK;
-    NSG_REQUIRE(workspace && workspace_bytes >= nsg_vq_bf16x3_workspace_bytes(N, D, K), NSG_E_WORKSPACE,
-                "nsg_vq_forward_bf16x3: workspace too small");
+    const Bf16x3Layout L = bf16x3_layout(workspace, N, D, K);
+    NSG_REQUIRE(workspace && workspace_bytes >= L.bytes, NSG_E_WORKSPACE, "nsg_vq_forward_bf16x3: workspace too small");
     hipStream_t s = (hipStream_t)stream;
-    char *ws = reinterpret_cast<char *>(workspace);
-    float *x2 = reinterpret_cast<float *>(ws);
-    float *c2 = reinterpret_cast<float *>(ws + nsg_align_up((size_t)N * sizeof(float), 256));
-    bf16_t *ehi = reinterpret_cast<bf16_t *>(ws + nsg_vq_workspace_bytes(N, D, K));
-    bf16_t *elo = reinterpret_cast<bf16_t *>(ws + nsg_vq_workspace_bytes(N, D, K) + split_bytes(D, K));
+    float *x2 = L.x2, *c2 = L.c2;
+    bf16_t *ehi = L.ehi, *elo = L.elo;
     // |x|^2 is constant along a row: it only matters for the reported distances.  Without dmin_out it is neither computed
     // (a pass over x) nor added (the sum c2 + x2 would round the small code norms away)
     int rc = NSG_OK;
@@ -305,7 +310,7 @@ extern "C" {
 size_t nsg_vq_bf16x3_workspace_bytes(int64_t N, int32_t D, int32_t K)
 {
     if (N < 0 || K <= 0 || D <= 0) return 0;
-    return nsg_vq_workspace_bytes(N, D, K) + 2 * split_bytes(D, K);
+    return bf16x3_layout(nullptr, N, D, K).bytes;
 }
 
 int nsg_vq_forward_bf16x3(const float *x, const float *e, int64_t N, int32_t D, int32_t K, int64_t *idx_out, float *codes_out,
