@@ -9,7 +9,7 @@
 // reproducible (no atomics).
 // The backward of a BatchNorm that was followed by a fused ReLU re-derives the ReLU mask from x itself
 // ((x-mean)*(invstd*gamma)+beta > 0, the forward's own expression) instead of reading the stored output.
-#include "nsg_common.h"
+#include "nsg_reduce.h"
 
 namespace {
 
@@ -30,8 +30,7 @@ inline SlabGeom slab_geom(int64_t M)
     return g;
 }
 
-// threads: cg = tid % CW owns channels W*cg .. W*cg+W-1, rg = tid / CW strides over the slab's rows.
-// partial[slab] = { mean[C], M2[C] } (count is implied by the slab geometry).
+// One block per slab, threads by NsgSlabMap.  partial[slab] = { mean[C], M2[C] } (count is implied by the slab geometry).
 // ONE pass: sums of d = v - pivot and d^2 with pivot = the slab's first row (a sample of the column, so
 // |mean - pivot| is of the order of the column's spread and M2 = S2 - S1^2/n loses no more than a few bits).
 template <typename T>
@@ -40,66 +39,75 @@ __global__ __launch_bounds__(256) void bn_stats_partial_kernel(const T *__restri
 {
     constexpr int W = Elem<T>::N;
     __shared__ float red[2 * 256 * W];
-    const int CW = C / W;
-    const int rgroups = 256 / CW;
+    const NsgSlabMap<W> m(C, blockIdx.x, slab_rows, M);
     const int tid = threadIdx.x;
-    const int cg = tid % CW, rg = tid / CW;
-    const bool active = rg < rgroups;
-    const int64_t r0 = (int64_t)blockIdx.x * slab_rows;
-    const int64_t r1 = min(M, r0 + slab_rows);
-    const int n = (int)(r1 - r0);
+    const int n = (int)(m.r1 - m.r0);
 
-    float pv[W];
-    if (active) {
-        float s1[W], s2[W];
-        ldw<T, W>(x + r0 * C + cg * W, pv);
+    float pv[W];               // set by the active threads; read by the fold's closing threads (tid < CW, so rg == 0: active)
+    if (m.active) {
+        float s[2][W];
+        ldw<T, W>(x + m.r0 * C + m.cg * W, pv);
 #pragma unroll
-        for (int e = 0; e < W; ++e) { s1[e] = 0.f; s2[e] = 0.f; }
+        for (int e = 0; e < W; ++e) { s[0][e] = 0.f; s[1][e] = 0.f; }
 #pragma unroll 4
-        for (int64_t r = r0 + rg; r < r1; r += rgroups) {
+        for (int64_t r = m.r0 + m.rg; r < m.r1; r += m.rgroups) {
             float v[W];
-            ldw<T, W>(x + r * C + cg * W, v);
+            ldw<T, W>(x + r * C + m.cg * W, v);
 #pragma unroll
-            for (int e = 0; e < W; ++e) { const float d = v[e] - pv[e]; s1[e] += d; s2[e] += d * d; }
+            for (int e = 0; e < W; ++e) { const float d = v[e] - pv[e]; s[0][e] += d; s[1][e] += d * d; }
         }
-#pragma unroll
-        for (int e = 0; e < W; ++e) { red[(rg * CW + cg) * W + e] = s1[e]; red[256 * W + (rg * CW + cg) * W + e] = s2[e]; }
+        nsg_slab_park(m, s, red);
     }
-    __syncthreads();
-    if (tid < CW) {
-        float *dst = partial + (size_t)blockIdx.x * 2 * C;
-        const float inv_n = 1.f / (float)n;
-#pragma unroll
-        for (int e = 0; e < W; ++e) {
-            float t1 = 0.f, t2 = 0.f;
-            for (int g = 0; g < rgroups; ++g) { t1 += red[(g * CW + tid) * W + e]; t2 += red[256 * W + (g * CW + tid) * W + e]; }
-            dst[tid * W + e] = pv[e] + t1 * inv_n;
-            dst[C + tid * W + e] = fmaxf(t2 - t1 * t1 * inv_n, 0.f);
-        }
-    }
+    float *dst = partial + (size_t)blockIdx.x * 2 * C;
+    const float inv_n = 1.f / (float)n;
+    nsg_slab_fold<2>(m, red, [&](int e, const float (&t)[2]) {
+        dst[tid * W + e] = pv[e] + t[0] * inv_n;
+        dst[C + tid * W + e] = fmaxf(t[1] - t[0] * t[0] * inv_n, 0.f);
+    });
 }
 
-// Fixed-shape sum of one double per thread over the 256 threads of a block (deterministic); result in every thread.
-// Xor-butterflies inside each wave (no barrier), then the 4 wave totals through LDS in wave order.
-__device__ __forceinline__ double block_sum256(double v, double *red, int tid)
+// Finalisers with one block per 4 channels: thread tid holds the records of slabs tid, tid + 256, ... (PER of them) of an
+// array [nslab][stride] at column c0.  The slab index is clamped to the last slab, so every load is unconditional, and all of a
+// kernel's slab_records_load calls come before its first add: one memory latency.
+constexpr int PER = MAX_SLABS / 256;
+__device__ __forceinline__ void slab_records_load(const float *__restrict__ p, size_t stride, int c0, int nslab, int tid, v4f (&a)[PER])
 {
 #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    if ((tid & 63) == 0) red[tid >> 6] = v;
-    __syncthreads();
-    const double r = ((red[0] + red[1]) + red[2]) + red[3];
-    __syncthreads();
-    return r;
+    for (int i = 0; i < PER; ++i) {
+        const int s = tid + 256 * i;
+        a[i] = *reinterpret_cast<const v4f *>(p + (size_t)(s < nslab ? s : nslab - 1) * stride + c0);
+    }
+}
+// sum over all slabs of element e of such records: the thread's live records in index order, then the butterfly block sum
+__device__ __forceinline__ double slab_records_sum(const v4f (&a)[PER], int e, int nslab, double *red, int tid)
+{
+    double t = 0.0;
+#pragma unroll
+    for (int i = 0; i < PER; ++i) t += (tid + 256 * i < nslab) ? (double)a[i][e] : 0.0;
+    return nsg_block_sum_butterfly(t, red, tid);
 }
 
-// One block per 4 channels; thread j takes slabs j, j+256, ... (16-byte loads of the 4 channels' partials, all issued
-// before any arithmetic: one memory latency), then two fixed-shape tree sums per channel in double:
+// mean, invstd and the running statistics (as nn.BatchNorm2d: biased variance for invstd, unbiased into running_var) of channel
+// c from its mean mu and M2 over M rows; rm0 / rv0 = the running values read before
+__device__ __forceinline__ void bn_stats_store(int c, double mu, double m2, int64_t M, float eps, float momentum, float rm0, float rv0,
+                                               float *mean, float *invstd, float *running_mean, float *running_var)
+{
+    const double var_b = m2 / (double)M;
+    mean[c] = (float)mu;
+    invstd[c] = (float)(1.0 / sqrt(var_b + (double)eps));
+    if (running_mean) running_mean[c] = (1.f - momentum) * rm0 + momentum * (float)mu;
+    if (running_var) {
+        const double var_u = M > 1 ? m2 / (double)(M - 1) : var_b;
+        running_var[c] = (1.f - momentum) * rv0 + momentum * (float)var_u;
+    }
+}
+
+// One block per 4 channels, then two butterfly block sums per channel in double:
 //   n = sum n_s,  mean = sum n_s m_s / n,  M2 = sum ( q_s + n_s (m_s - mean)^2 )       (the pooled-variance identity)
 __global__ __launch_bounds__(256) void bn_stats_final_kernel(const float *__restrict__ partial, int nslab, int slab_rows, int64_t M,
                                                              int C, float eps, float momentum, float *mean, float *invstd,
                                                              float *running_mean, float *running_var)
 {
-    constexpr int PER = MAX_SLABS / 256;
     __shared__ double red[256];
     const int tid = threadIdx.x;
     const int c0 = blockIdx.x * 4;
@@ -112,14 +120,12 @@ __global__ __launch_bounds__(256) void bn_stats_final_kernel(const float *__rest
         rm0[e] = running_mean ? running_mean[cc] : 0.f;
         rv0[e] = running_var ? running_var[cc] : 0.f;
     }
+    slab_records_load(partial, (size_t)2 * C, c0, nslab, tid, ms);
+    slab_records_load(partial, (size_t)2 * C, C + c0, nslab, tid, qs);
 #pragma unroll
     for (int i = 0; i < PER; ++i) {
-        const int s = tid + 256 * i;
-        const int sc = s < nslab ? s : nslab - 1;                     // clamped, unconditional loads
-        ms[i] = *reinterpret_cast<const v4f *>(partial + (size_t)sc * 2 * C + c0);
-        qs[i] = *reinterpret_cast<const v4f *>(partial + (size_t)sc * 2 * C + C + c0);
-        const int64_t r0 = (int64_t)sc * slab_rows;
-        ns[i] = s < nslab ? (float)(min(M, r0 + slab_rows) - r0) : 0.f;
+        const int64_t r0 = (int64_t)(tid + 256 * i) * slab_rows;
+        ns[i] = tid + 256 * i < nslab ? (float)(min(M, r0 + slab_rows) - r0) : 0.f;
     }
     double mu[4];
 #pragma unroll
@@ -127,7 +133,7 @@ __global__ __launch_bounds__(256) void bn_stats_final_kernel(const float *__rest
         double t = 0.0;
 #pragma unroll
         for (int i = 0; i < PER; ++i) t += (double)ns[i] * (double)ms[i][e];
-        mu[e] = block_sum256(t, red, tid) / (double)M;
+        mu[e] = nsg_block_sum_butterfly(t, red, tid) / (double)M;
     }
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -137,18 +143,8 @@ __global__ __launch_bounds__(256) void bn_stats_final_kernel(const float *__rest
             const double dl = (double)ms[i][e] - mu[e];
             t += ns[i] > 0.f ? (double)qs[i][e] + (double)ns[i] * dl * dl : 0.0;
         }
-        const double m2 = block_sum256(t, red, tid);
-        if (tid == 0 && c0 + e < C) {
-            const int c = c0 + e;
-            const double var_b = m2 / (double)M;
-            mean[c] = (float)mu[e];
-            invstd[c] = (float)(1.0 / sqrt(var_b + (double)eps));
-            if (running_mean) running_mean[c] = (1.f - momentum) * rm0[e] + momentum * (float)mu[e];
-            if (running_var) {
-                const double var_u = M > 1 ? m2 / (double)(M - 1) : var_b;
-                running_var[c] = (1.f - momentum) * rv0[e] + momentum * (float)var_u;
-            }
-        }
+        const double m2 = nsg_block_sum_butterfly(t, red, tid);
+        if (tid == 0 && c0 + e < C) bn_stats_store(c0 + e, mu[e], m2, M, eps, momentum, rm0[e], rv0[e], mean, invstd, running_mean, running_var);
     }
 }
 
@@ -209,14 +205,7 @@ __global__ __launch_bounds__(256) void bn_stats_tiles_final_kernel(const double 
     const double mu = S / N;
     double m2 = Q - S * S / N;
     if (m2 < 0.0) m2 = 0.0;
-    const double var_b = m2 / (double)M;
-    mean[c] = (float)mu;
-    invstd[c] = (float)(1.0 / sqrt(var_b + (double)eps));
-    if (running_mean) running_mean[c] = (1.f - momentum) * rm0 + momentum * (float)mu;
-    if (running_var) {
-        const double var_u = M > 1 ? m2 / (double)(M - 1) : var_b;
-        running_var[c] = (1.f - momentum) * rv0 + momentum * (float)var_u;
-    }
+    bn_stats_store(c, mu, m2, M, eps, momentum, rm0, rv0, mean, invstd, running_mean, running_var);
 }
 
 __global__ void bn_eval_stats_kernel(const float *rm, const float *rv, int C, float eps, float *mean, float *invstd)
@@ -277,22 +266,18 @@ __global__ __launch_bounds__(256) void bn_bwd_partial_kernel(const T *__restrict
 {
     constexpr int W = Elem<T>::N;
     __shared__ float red[2 * 256 * W];
-    const int CW = C / W;
-    const int rgroups = 256 / CW;
+    const NsgSlabMap<W> m(C, blockIdx.x, slab_rows, M);
     const int tid = threadIdx.x;
-    const int cg = tid % CW, rg = tid / CW;
-    const bool active = rg < rgroups;
-    const int64_t r0 = (int64_t)blockIdx.x * slab_rows;
-    const int64_t r1 = min(M, r0 + slab_rows);
-    if (active) {
-        float s1[W], s2[W], mu[W], is[W], sc[W], be[W];
+    const int cg = m.cg;
+    if (m.active) {
+        float s[2][W], mu[W], is[W], sc[W], be[W];
 #pragma unroll
         for (int e = 0; e < W; ++e) {
-            s1[e] = 0.f; s2[e] = 0.f; mu[e] = mean[cg * W + e]; is[e] = invstd[cg * W + e];
+            s[0][e] = 0.f; s[1][e] = 0.f; mu[e] = mean[cg * W + e]; is[e] = invstd[cg * W + e];
             sc[e] = relu_beta ? is[e] * gamma[cg * W + e] : 0.f;
             be[e] = relu_beta ? relu_beta[cg * W + e] : 0.f;
         }
-        for (int64_t r = r0 + rg; r < r1; r += rgroups) {
+        for (int64_t r = m.r0 + m.rg; r < m.r1; r += m.rgroups) {
             const size_t o = (size_t)r * C + cg * W;
             float g[W], xv[W];
             ldw<T, W>(dy + o, g);
@@ -307,56 +292,35 @@ __global__ __launch_bounds__(256) void bn_bwd_partial_kernel(const T *__restrict
                 for (int e = 0; e < W; ++e) g[e] = yv[e] > 0.f ? g[e] : 0.f;
             }
 #pragma unroll
-            for (int e = 0; e < W; ++e) { s1[e] += g[e]; s2[e] += g[e] * ((xv[e] - mu[e]) * is[e]); }
+            for (int e = 0; e < W; ++e) { s[0][e] += g[e]; s[1][e] += g[e] * ((xv[e] - mu[e]) * is[e]); }
         }
-#pragma unroll
-        for (int e = 0; e < W; ++e) { red[(rg * CW + cg) * W + e] = s1[e]; red[256 * W + (rg * CW + cg) * W + e] = s2[e]; }
+        nsg_slab_park(m, s, red);
     }
-    __syncthreads();
-    if (tid < CW) {
-        float *dst = partial + (size_t)blockIdx.x * 2 * C;
-#pragma unroll
-        for (int e = 0; e < W; ++e) {
-            float t1 = 0.f, t2 = 0.f;
-            for (int g = 0; g < rgroups; ++g) { t1 += red[(g * CW + tid) * W + e]; t2 += red[256 * W + (g * CW + tid) * W + e]; }
-            dst[tid * W + e] = t1;
-            dst[C + tid * W + e] = t2;
-        }
-    }
+    float *dst = partial + (size_t)blockIdx.x * 2 * C;
+    nsg_slab_fold<2>(m, red, [&](int e, const float (&t)[2]) {
+        dst[tid * W + e] = t[0];
+        dst[C + tid * W + e] = t[1];
+    });
 }
 
-// dbeta[c] = sum_s partial[s][c], dgamma[c] = sum_s partial[s][C + c]: one block per 4 channels, tree sums in double
+// dbeta[c] = sum_s partial[s][c], dgamma[c] = sum_s partial[s][C + c]: one block per 4 channels, slab_records_sum in double
 // colsum_partial != null: out3[c] = sum_s colsum_partial[s][c] in the same launch (slab_sum_final_kernel's job: a producer that
 // leaves both kinds of partials, the fused 1x1 backward, pays one finaliser launch instead of two)
 __device__ __forceinline__ void bn_bwd_final_body(int bid, const float *__restrict__ partial, int nslab, int C, float *dgamma, float *dbeta,
                                                   const float *__restrict__ colsum_partial, float *out3)
 {
-    constexpr int PER = MAX_SLABS / 256;
     __shared__ double red[256];
     const int tid = threadIdx.x;
     const int c0 = bid * 4;
     v4f a[PER], b[PER], c3[PER];
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-        const int s = tid + 256 * i;
-        const int sc = s < nslab ? s : nslab - 1;
-        a[i] = *reinterpret_cast<const v4f *>(partial + (size_t)sc * 2 * C + c0);
-        b[i] = *reinterpret_cast<const v4f *>(partial + (size_t)sc * 2 * C + C + c0);
-        c3[i] = colsum_partial ? *reinterpret_cast<const v4f *>(colsum_partial + (size_t)sc * C + c0) : v4f{0.f, 0.f, 0.f, 0.f};
-    }
+    slab_records_load(partial, (size_t)2 * C, c0, nslab, tid, a);
+    slab_records_load(partial, (size_t)2 * C, C + c0, nslab, tid, b);
+    if (colsum_partial) slab_records_load(colsum_partial, (size_t)C, c0, nslab, tid, c3);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        double t1 = 0.0, t2 = 0.0, t3 = 0.0;
-#pragma unroll
-        for (int i = 0; i < PER; ++i) {
-            const bool ok = tid + 256 * i < nslab;
-            t1 += ok ? (double)a[i][e] : 0.0;
-            t2 += ok ? (double)b[i][e] : 0.0;
-            t3 += ok ? (double)c3[i][e] : 0.0;
-        }
-        const double s1 = block_sum256(t1, red, tid);
-        const double s2 = block_sum256(t2, red, tid);
-        const double s3 = colsum_partial ? block_sum256(t3, red, tid) : 0.0;
+        const double s1 = slab_records_sum(a, e, nslab, red, tid);
+        const double s2 = slab_records_sum(b, e, nslab, red, tid);
+        const double s3 = colsum_partial ? slab_records_sum(c3, e, nslab, red, tid) : 0.0;
         if (tid == 0 && c0 + e < C) {
             dbeta[c0 + e] = (float)s1;
             dgamma[c0 + e] = (float)s2;
@@ -371,10 +335,9 @@ __global__ __launch_bounds__(256) void bn_bwd_final_kernel(const float *__restri
     bn_bwd_final_body(blockIdx.x, partial, nslab, C, dgamma, dbeta, colsum_partial, out3);
 }
 
-// bn_bwd_final_kernel in blocks 0 .. C / 4 - 1 and, in the blocks behind them, wdst[e] = sum over slabs (slab order) of
-// wpartial[slab][e], e < wn -- wgrad_reduce_kernel for one tap, its sharing of the slabs among 8 lanes and its order of adds: the
-// two finalisers of the fused 1x1 backward (BatchNorm sums in front, the weight gradient's block partials) in ONE launch (a
-// dependent launch costs 4.7 us here whatever it does).
+// bn_bwd_final_kernel in blocks 0 .. C / 4 - 1 and, in the blocks behind them, wdst[e] = nsg_split_slab_sum over the slabs of
+// wpartial[slab][e], e < wn (what wgrad_reduce_kernel does for one tap): the two finalisers of the fused 1x1 backward (BatchNorm
+// sums in front, the weight gradient's block partials) in ONE launch (a dependent launch costs 4.7 us here whatever it does).
 __global__ __launch_bounds__(256) void bn_bwd_final_wreduce_kernel(const float *__restrict__ partial, int nslab, int C, float *dgamma, float *dbeta,
                                                                    const float *__restrict__ colsum_partial, float *out3,
                                                                    const float *__restrict__ wpartial, float *__restrict__ wdst, int wn, int wsplit)
@@ -384,25 +347,11 @@ __global__ __launch_bounds__(256) void bn_bwd_final_wreduce_kernel(const float *
         bn_bwd_final_body(blockIdx.x, partial, nslab, C, dgamma, dbeta, colsum_partial, out3);
         return;
     }
-    __shared__ float wred[256];
     const int per_block = 256 / wsplit;
     const int tid = threadIdx.x;
     const int sub = tid / per_block, loc = tid - sub * per_block;
     const int e = ((int)blockIdx.x - nbn) * per_block + loc;
-    float sacc = 0.f;
-    if (e < wn) {
-        const int chunk = (nslab + wsplit - 1) / wsplit;
-        const int s0 = sub * chunk, s1 = min(nslab, s0 + chunk);
-        if (s1 > s0) sacc = nsg_strided_sum<float>(wpartial + (size_t)s0 * wn + e, (size_t)wn, s1 - s0);
-    }
-    if (wsplit > 1) {
-        wred[tid] = sacc;
-        __syncthreads();
-        if (sub == 0) {
-            sacc = 0.f;
-            for (int k = 0; k < wsplit; ++k) sacc += wred[k * per_block + loc];
-        }
-    }
+    const float sacc = nsg_split_slab_sum<false>(wpartial + e, (size_t)wn, nslab, wsplit, e < wn);
     if (sub == 0 && e < wn) wdst[e] = sacc;
 }
 
@@ -418,17 +367,13 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T *__restrict__
 {
     constexpr int W = Elem<T>::N;
     __shared__ float red[256 * W];
-    const int CW = C / W;
-    const int rgroups = 256 / CW;
+    const NsgSlabMap<W> m(C, blockIdx.x, slab_rows, M);
     const int tid = threadIdx.x;
-    const int cg = tid % CW, rg = tid / CW;
-    const bool active = rg < rgroups;
-    const int64_t r0 = (int64_t)blockIdx.x * slab_rows;
-    const int64_t r1 = min(M, r0 + slab_rows);
-    float s[W];
+    const int cg = m.cg;
+    float s[1][W];
 #pragma unroll
-    for (int e = 0; e < W; ++e) s[e] = 0.f;
-    if (active) {
+    for (int e = 0; e < W; ++e) s[0][e] = 0.f;
+    if (m.active) {
         float mu[W], is[W], sc[W], dg[W], db[W], fs[W], be[W];
 #pragma unroll
         for (int e = 0; e < W; ++e) {
@@ -437,7 +382,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T *__restrict__
             fs[e] = is[e] * gamma[c];                  // the forward's scale, in the forward's operand order
             be[e] = relu_beta ? relu_beta[c] : 0.f;
         }
-        for (int64_t r = r0 + rg; r < r1; r += rgroups) {
+        for (int64_t r = m.r0 + m.rg; r < m.r1; r += m.rgroups) {
             const size_t o = (size_t)r * C + cg * W;
             float g[W], xv[W], d[W];
             ldw<T, W>(dy + o, g);
@@ -454,45 +399,27 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T *__restrict__
 #pragma unroll
             for (int e = 0; e < W; ++e) {
                 d[e] = sc[e] * (g[e] - db[e] - ((xv[e] - mu[e]) * is[e]) * dg[e]);
-                s[e] += d[e];
+                s[0][e] += d[e];
             }
             stw<T, W>(dx + o, d);
         }
     }
-    if (partial == nullptr) return;
-    if (active)
-#pragma unroll
-        for (int e = 0; e < W; ++e) red[(rg * CW + cg) * W + e] = s[e];
-    __syncthreads();
-    if (tid < CW) {
-#pragma unroll
-        for (int e = 0; e < W; ++e) {
-            float t = 0.f;
-            for (int g = 0; g < rgroups; ++g) t += red[(g * CW + tid) * W + e];
-            partial[(size_t)blockIdx.x * C + tid * W + e] = t;
-        }
-    }
+    if (partial == nullptr) return;        // (uniform: a kernel argument)
+    if (m.active) nsg_slab_park(m, s, red);
+    nsg_slab_fold<1>(m, red, [&](int e, const float (&t)[1]) { partial[(size_t)blockIdx.x * C + tid * W + e] = t[0]; });
 }
 
 // out[c] = sum_s partial[s][c]: one block per 4 channels
 __global__ __launch_bounds__(256) void slab_sum_final_kernel(const float *__restrict__ partial, int nslab, int C, float *out)
 {
-    constexpr int PER = MAX_SLABS / 256;
     __shared__ double red[256];
     const int tid = threadIdx.x;
     const int c0 = blockIdx.x * 4;
     v4f a[PER];
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-        const int s = tid + 256 * i;
-        a[i] = *reinterpret_cast<const v4f *>(partial + (size_t)(s < nslab ? s : nslab - 1) * C + c0);
-    }
+    slab_records_load(partial, (size_t)C, c0, nslab, tid, a);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        double t = 0.0;
-#pragma unroll
-        for (int i = 0; i < PER; ++i) t += (tid + 256 * i < nslab) ? (double)a[i][e] : 0.0;
-        const double sm = block_sum256(t, red, tid);
+        const double sm = slab_records_sum(a, e, nslab, red, tid);
         if (tid == 0 && c0 + e < C) out[c0 + e] = (float)sm;
     }
 }
@@ -510,13 +437,12 @@ inline int check_mc(const char *fn, int64_t M, int C, int dtype)
 
 }  // namespace
 
-// The same in ONE launch for up to MAX_SLABS records (the flat 1x1 GEMM writes 256-512): one block per 4 channels, thread j takes
-// records j, j + 256, ... (all loads first), three fixed-shape tree sums in double: N, S, T = sum (Q_t + S_t^2 / n_t).
+// The same in ONE launch for up to MAX_SLABS records (the flat 1x1 GEMM writes 256-512): one block per 4 channels, three butterfly
+// block sums in double: N, S, T = sum (Q_t + S_t^2 / n_t).
 __global__ __launch_bounds__(256) void bn_stats_tiles_onepass_kernel(const float *__restrict__ tiles, int ntiles, int64_t M, int C, float eps,
                                                                      float momentum, float *mean, float *invstd, float *running_mean,
                                                                      float *running_var)
 {
-    constexpr int PER = MAX_SLABS / 256;
     __shared__ double red[256];
     const int tid = threadIdx.x;
     const int c0 = blockIdx.x * 4;
@@ -527,15 +453,9 @@ __global__ __launch_bounds__(256) void bn_stats_tiles_onepass_kernel(const float
         rm0[e] = running_mean ? running_mean[c0 + e] : 0.f;
         rv0[e] = running_var ? running_var[c0 + e] : 0.f;
     }
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-        const int t = tid + 256 * i;
-        const int tc = t < ntiles ? t : ntiles - 1;                  // clamped, unconditional loads; masked below
-        const float *rec = tiles + (size_t)tc * 3 * C + c0;
-        nv[i] = *reinterpret_cast<const v4f *>(rec);
-        sv[i] = *reinterpret_cast<const v4f *>(rec + C);
-        qv[i] = *reinterpret_cast<const v4f *>(rec + 2 * C);
-    }
+    slab_records_load(tiles, (size_t)3 * C, c0, ntiles, tid, nv);
+    slab_records_load(tiles, (size_t)3 * C, C + c0, ntiles, tid, sv);
+    slab_records_load(tiles, (size_t)3 * C, 2 * C + c0, ntiles, tid, qv);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         double n = 0.0, sm = 0.0, tq = 0.0;
@@ -547,20 +467,11 @@ __global__ __launch_bounds__(256) void bn_stats_tiles_onepass_kernel(const float
             sm += si;
             tq += ni > 0.0 ? qi + si * si / ni : 0.0;
         }
-        const double N = block_sum256(n, red, tid), S = block_sum256(sm, red, tid), T = block_sum256(tq, red, tid);
+        const double N = nsg_block_sum_butterfly(n, red, tid), S = nsg_block_sum_butterfly(sm, red, tid), T = nsg_block_sum_butterfly(tq, red, tid);
         if (tid == 0) {
-            const int c = c0 + e;
-            const double mu = S / N;
             double m2 = T - S * S / N;
             if (m2 < 0.0) m2 = 0.0;
-            const double var_b = m2 / (double)M;
-            mean[c] = (float)mu;
-            invstd[c] = (float)(1.0 / sqrt(var_b + (double)eps));
-            if (running_mean) running_mean[c] = (1.f - momentum) * rm0[e] + momentum * (float)mu;
-            if (running_var) {
-                const double var_u = M > 1 ? m2 / (double)(M - 1) : var_b;
-                running_var[c] = (1.f - momentum) * rv0[e] + momentum * (float)var_u;
-            }
+            bn_stats_store(c0 + e, S / N, m2, M, eps, momentum, rm0[e], rv0[e], mean, invstd, running_mean, running_var);
         }
     }
 }
@@ -592,8 +503,7 @@ int nsg_bn_stats_from_tiles(const float *tiles, int ntiles, int64_t M, int C, fl
 
 size_t nsg_bn_tiles_bytes(int64_t ntiles, int C) { return bn_tiles_layout(nullptr, ntiles, C).bytes; }
 
-// the slab structure of nsg_bn_backward_sums over M rows: a producer of dy that forms the same sums itself (elementwise.hip:
-// nsg_vq_losses_indexed_bn) walks the rows the same way, so its results are those of the separate pass, bit for bit
+// the slab structure of nsg_bn_backward_sums over M rows (a producer of dy that forms the same sums itself launches over it)
 void nsg_bn_slab_geom(int64_t M, int *nslab, int *rows)
 {
     const SlabGeom g = slab_geom(M);
@@ -601,27 +511,24 @@ void nsg_bn_slab_geom(int64_t M, int *nslab, int *rows)
     *rows = g.rows;
 }
 
+// what the one-block-per-4-channels finalisers can take
+static int check_slabs(const char *what, int nslab, int C)
+{
+    if (nslab < 1 || nslab > MAX_SLABS || C % 4) return nsg_fail(NSG_E_INVALID, "%s: %d slabs / %d channels not supported", what, nslab, C);
+    return NSG_OK;
+}
+
 int nsg_launch_bn_bwd_final(const float *partial, int nslab, int C, float *dgamma, float *dbeta, hipStream_t s)
 {
-    if (nslab < 1 || nslab > MAX_SLABS || C % 4) return nsg_fail(NSG_E_INVALID, "bn_bwd_final: %d slabs / %d channels not supported", nslab, C);
+    if (int rc = check_slabs("bn_bwd_final", nslab, C)) return rc;
     hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(C / 4), dim3(256), 0, s, partial, nslab, C, dgamma, dbeta, (const float *)nullptr, (float *)nullptr);
     return nsg_check_launch("bn_bwd_final_kernel");
 }
 
-// ... and the column sums of a second partial array [nslab][C] in the same launch
-int nsg_launch_bn_bwd_final_colsum(const float *partial, const float *colsum_partial, int nslab, int C, float *dgamma, float *dbeta,
-                                   float *colsum, hipStream_t s)
-{
-    if (nslab < 1 || nslab > MAX_SLABS || C % 4) return nsg_fail(NSG_E_INVALID, "bn_bwd_final: %d slabs / %d channels not supported", nslab, C);
-    hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(C / 4), dim3(256), 0, s, partial, nslab, C, dgamma, dbeta, colsum_partial, colsum);
-    return nsg_check_launch("bn_bwd_final_kernel");
-}
-
-// ... and the slab sum of the weight gradient's block partials wpartial [nslab][wn] -> wdst [wn] (one tap: nsg_launch_wgrad_reduce's result, bit for bit)
 int nsg_launch_bn_bwd_final_wreduce(const float *partial, const float *colsum_partial, int nslab, int C, float *dgamma, float *dbeta, float *colsum,
                                     const float *wpartial, float *wdst, int wn, hipStream_t s)
 {
-    if (nslab < 1 || nslab > MAX_SLABS || C % 4) return nsg_fail(NSG_E_INVALID, "bn_bwd_final: %d slabs / %d channels not supported", nslab, C);
+    if (int rc = check_slabs("bn_bwd_final", nslab, C)) return rc;
     const int split = nsg_slab_split(nslab, wn);
     const int wblocks = (wn + 256 / split - 1) / (256 / split);
     hipLaunchKernelGGL(bn_bwd_final_wreduce_kernel, dim3(C / 4 + wblocks), dim3(256), 0, s, partial, nslab, C, dgamma, dbeta, colsum_partial, colsum,
@@ -631,9 +538,63 @@ int nsg_launch_bn_bwd_final_wreduce(const float *partial, const float *colsum_pa
 
 int nsg_launch_slab_sum_final(const float *partial, int nslab, int C, float *out, hipStream_t s)
 {
-    if (nslab < 1 || nslab > MAX_SLABS || C % 4) return nsg_fail(NSG_E_INVALID, "slab_sum_final: %d slabs / %d channels not supported", nslab, C);
+    if (int rc = check_slabs("slab_sum_final", nslab, C)) return rc;
     hipLaunchKernelGGL(slab_sum_final_kernel, dim3(C / 4), dim3(256), 0, s, partial, nslab, C, out);
     return nsg_check_launch("slab_sum_final_kernel");
+}
+
+// f(T()) with T the storage type of dtype (checked by check_mc): a launch is written once, for T
+template <typename F>
+static void by_dtype(int dtype, F f)
+{
+    if (dtype == NSG_BF16) f(bf16_t());
+    else f(float());
+}
+
+// The backward over [M][C] in its two halves, which nsg_bn_backward runs one after the other.
+struct BnBwd {
+    const void *x, *y_relu, *dy;
+    const float *mean, *invstd, *gamma, *relu_beta;
+    int64_t M;
+    int C, dtype;
+    float *partial;      // the workspace: [nslab][2][C]
+    hipStream_t s;
+};
+
+// the entry points' shared argument checks; dx: the apply half's output (its null check is the caller's), null for the sums alone
+static int bn_bwd_check(const char *fn, const BnBwd &b, const float *dgamma, const float *dbeta, const void *dx, size_t workspace_bytes)
+{
+    NSG_REQUIRE(b.x && b.dy && b.mean && b.invstd && b.gamma && dgamma && dbeta, NSG_E_INVALID, "%s: null pointer", fn);
+    if (int rc = check_mc(fn, b.M, b.C, b.dtype)) return rc;
+    NSG_REQUIRE(nsg_aligned16(b.x) && nsg_aligned16(b.dy) && nsg_aligned16(dx) && (!b.y_relu || nsg_aligned16(b.y_relu)), NSG_E_INVALID,
+                "%s: pointers must be 16-byte aligned", fn);
+    NSG_REQUIRE(b.partial && workspace_bytes >= nsg_bn_workspace_bytes(b.M, b.C), NSG_E_WORKSPACE, "%s: workspace too small", fn);
+    return NSG_OK;
+}
+
+// dgamma, dbeta <- the per-slab sums and their finaliser
+static void bn_bwd_launch_sums(const BnBwd &b, float *dgamma, float *dbeta)
+{
+    const SlabGeom g = slab_geom(b.M);
+    by_dtype(b.dtype, [&](auto t) {
+        typedef decltype(t) T;
+        hipLaunchKernelGGL((bn_bwd_partial_kernel<T>), dim3(g.nslab), dim3(256), 0, b.s, (const T *)b.x, (const T *)b.y_relu, (const T *)b.dy, b.mean,
+                           b.invstd, b.gamma, b.relu_beta, b.M, b.C, g.rows, b.partial);
+    });
+    hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(b.C / 4), dim3(256), 0, b.s, b.partial, g.nslab, b.C, dgamma, dbeta, (const float *)nullptr, (float *)nullptr);
+}
+
+// dx (and dx_colsum) from dgamma, dbeta.  Whatever sat in the workspace has been consumed (stream order): it takes the dx column sums.
+static void bn_bwd_launch_apply(const BnBwd &b, const float *dgamma, const float *dbeta, void *dx, float *dx_colsum)
+{
+    const SlabGeom g = slab_geom(b.M);
+    const float inv_m = 1.0f / (float)b.M;
+    by_dtype(b.dtype, [&](auto t) {
+        typedef decltype(t) T;
+        hipLaunchKernelGGL((bn_bwd_apply_kernel<T>), dim3(g.nslab), dim3(256), 0, b.s, (const T *)b.x, (const T *)b.y_relu, (const T *)b.dy, b.mean,
+                           b.invstd, b.gamma, dgamma, dbeta, b.relu_beta, (T *)dx, b.M, b.C, g.rows, inv_m, dx_colsum ? b.partial : nullptr);
+    });
+    if (dx_colsum) hipLaunchKernelGGL(slab_sum_final_kernel, dim3(b.C / 4), dim3(256), 0, b.s, b.partial, g.nslab, b.C, dx_colsum);
 }
 
 extern "C" {
@@ -655,10 +616,10 @@ int nsg_bn_stats(const void *x, int64_t M, int32_t C, int32_t dtype, float eps, 
     const SlabGeom g = slab_geom(M);
     hipStream_t s = (hipStream_t)stream;
     float *partial = reinterpret_cast<float *>(workspace);
-    if (dtype == NSG_BF16)
-        hipLaunchKernelGGL((bn_stats_partial_kernel<bf16_t>), dim3(g.nslab), dim3(256), 0, s, reinterpret_cast<const bf16_t *>(x), M, C, g.rows, partial);
-    else
-        hipLaunchKernelGGL((bn_stats_partial_kernel<float>), dim3(g.nslab), dim3(256), 0, s, reinterpret_cast<const float *>(x), M, C, g.rows, partial);
+    by_dtype(dtype, [&](auto t) {
+        typedef decltype(t) T;
+        hipLaunchKernelGGL((bn_stats_partial_kernel<T>), dim3(g.nslab), dim3(256), 0, s, reinterpret_cast<const T *>(x), M, C, g.rows, partial);
+    });
     hipLaunchKernelGGL(bn_stats_final_kernel, dim3(C / 4), dim3(256), 0, s, partial, g.nslab, g.rows, M, C, eps,
                        momentum, mean, invstd, running_mean, running_var);
     return nsg_check_launch("bn_stats");
@@ -712,31 +673,11 @@ int nsg_bn_backward(const void *x, const void *y_relu, const void *dy, const flo
                     const float *gamma, const float *relu_beta, void *dx, float *dgamma, float *dbeta, float *dx_colsum,
                     int64_t M, int32_t C, int32_t dtype, void *workspace, size_t workspace_bytes, void *stream)
 {
-    NSG_REQUIRE(x && dy && mean && invstd && gamma && dx && dgamma && dbeta, NSG_E_INVALID, "nsg_bn_backward: null pointer");
-    int rc = check_mc("nsg_bn_backward", M, C, dtype);
-    if (rc) return rc;
-    NSG_REQUIRE(nsg_aligned16(x) && nsg_aligned16(dy) && nsg_aligned16(dx) && (!y_relu || nsg_aligned16(y_relu)), NSG_E_INVALID,
-                "nsg_bn_backward: pointers must be 16-byte aligned");
-    NSG_REQUIRE(workspace && workspace_bytes >= nsg_bn_workspace_bytes(M, C), NSG_E_WORKSPACE, "nsg_bn_backward: workspace too small");
-    const SlabGeom g = slab_geom(M);
-    hipStream_t s = (hipStream_t)stream;
-    float *partial = reinterpret_cast<float *>(workspace);
-    const float inv_m = 1.0f / (float)M;
-    if (dtype == NSG_BF16) {
-        typedef bf16_t T;
-        hipLaunchKernelGGL((bn_bwd_partial_kernel<T>), dim3(g.nslab), dim3(256), 0, s, (const T *)x, (const T *)y_relu, (const T *)dy, mean, invstd, gamma, relu_beta, M, C, g.rows, partial);
-        hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(C / 4), dim3(256), 0, s, partial, g.nslab, C, dgamma, dbeta, (const float *)nullptr, (float *)nullptr);
-        // the stage-1 partials have been consumed by bn_bwd_final (stream order): the buffer is reused for the dx column sums
-        hipLaunchKernelGGL((bn_bwd_apply_kernel<T>), dim3(g.nslab), dim3(256), 0, s, (const T *)x, (const T *)y_relu, (const T *)dy, mean, invstd, gamma,
-                           dgamma, dbeta, relu_beta, (T *)dx, M, C, g.rows, inv_m, dx_colsum ? partial : nullptr);
-    } else {
-        typedef float T;
-        hipLaunchKernelGGL((bn_bwd_partial_kernel<T>), dim3(g.nslab), dim3(256), 0, s, (const T *)x, (const T *)y_relu, (const T *)dy, mean, invstd, gamma, relu_beta, M, C, g.rows, partial);
-        hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(C / 4), dim3(256), 0, s, partial, g.nslab, C, dgamma, dbeta, (const float *)nullptr, (float *)nullptr);
-        hipLaunchKernelGGL((bn_bwd_apply_kernel<T>), dim3(g.nslab), dim3(256), 0, s, (const T *)x, (const T *)y_relu, (const T *)dy, mean, invstd, gamma,
-                           dgamma, dbeta, relu_beta, (T *)dx, M, C, g.rows, inv_m, dx_colsum ? partial : nullptr);
-    }
-    if (dx_colsum) hipLaunchKernelGGL(slab_sum_final_kernel, dim3(C / 4), dim3(256), 0, s, partial, g.nslab, C, dx_colsum);
+    const BnBwd b = {x, y_relu, dy, mean, invstd, gamma, relu_beta, M, C, dtype, reinterpret_cast<float *>(workspace), (hipStream_t)stream};
+    NSG_REQUIRE(dx, NSG_E_INVALID, "nsg_bn_backward: null pointer");
+    if (int rc = bn_bwd_check("nsg_bn_backward", b, dgamma, dbeta, dx, workspace_bytes)) return rc;
+    bn_bwd_launch_sums(b, dgamma, dbeta);
+    bn_bwd_launch_apply(b, dgamma, dbeta, dx, dx_colsum);
     return nsg_check_launch("bn_backward");
 }
 
@@ -746,26 +687,10 @@ int nsg_bn_backward_apply(const void *x, const void *y_relu, const void *dy, con
                           const float *relu_beta, const float *dgamma, const float *dbeta, void *dx, float *dx_colsum, int64_t M, int32_t C,
                           int32_t dtype, void *workspace, size_t workspace_bytes, void *stream)
 {
-    NSG_REQUIRE(x && dy && mean && invstd && gamma && dx && dgamma && dbeta, NSG_E_INVALID, "nsg_bn_backward_apply: null pointer");
-    int rc = check_mc("nsg_bn_backward_apply", M, C, dtype);
-    if (rc) return rc;
-    NSG_REQUIRE(nsg_aligned16(x) && nsg_aligned16(dy) && nsg_aligned16(dx) && (!y_relu || nsg_aligned16(y_relu)), NSG_E_INVALID,
-                "nsg_bn_backward_apply: pointers must be 16-byte aligned");
-    NSG_REQUIRE(workspace && workspace_bytes >= nsg_bn_workspace_bytes(M, C), NSG_E_WORKSPACE, "nsg_bn_backward_apply: workspace too small");
-    const SlabGeom g = slab_geom(M);
-    hipStream_t s = (hipStream_t)stream;
-    float *partial = reinterpret_cast<float *>(workspace);
-    const float inv_m = 1.0f / (float)M;
-    if (dtype == NSG_BF16) {
-        typedef bf16_t T;
-        hipLaunchKernelGGL((bn_bwd_apply_kernel<T>), dim3(g.nslab), dim3(256), 0, s, (const T *)x, (const T *)y_relu, (const T *)dy, mean, invstd, gamma,
-                           dgamma, dbeta, relu_beta, (T *)dx, M, C, g.rows, inv_m, dx_colsum ? partial : nullptr);
-    } else {
-        typedef float T;
-        hipLaunchKernelGGL((bn_bwd_apply_kernel<T>), dim3(g.nslab), dim3(256), 0, s, (const T *)x, (const T *)y_relu, (const T *)dy, mean, invstd, gamma,
-                           dgamma, dbeta, relu_beta, (T *)dx, M, C, g.rows, inv_m, dx_colsum ? partial : nullptr);
-    }
-    if (dx_colsum) hipLaunchKernelGGL(slab_sum_final_kernel, dim3(C / 4), dim3(256), 0, s, partial, g.nslab, C, dx_colsum);
+    const BnBwd b = {x, y_relu, dy, mean, invstd, gamma, relu_beta, M, C, dtype, reinterpret_cast<float *>(workspace), (hipStream_t)stream};
+    NSG_REQUIRE(dx, NSG_E_INVALID, "nsg_bn_backward_apply: null pointer");
+    if (int rc = bn_bwd_check("nsg_bn_backward_apply", b, dgamma, dbeta, dx, workspace_bytes)) return rc;
+    bn_bwd_launch_apply(b, dgamma, dbeta, dx, dx_colsum);
     return nsg_check_launch("bn_backward_apply");
 }
 
@@ -774,23 +699,9 @@ int nsg_bn_backward_sums(const void *x, const void *y_relu, const void *dy, cons
                          const float *relu_beta, float *dgamma, float *dbeta, int64_t M, int32_t C, int32_t dtype, void *workspace,
                          size_t workspace_bytes, void *stream)
 {
-    NSG_REQUIRE(x && dy && mean && invstd && gamma && dgamma && dbeta, NSG_E_INVALID, "nsg_bn_backward_sums: null pointer");
-    int rc = check_mc("nsg_bn_backward_sums", M, C, dtype);
-    if (rc) return rc;
-    NSG_REQUIRE(nsg_aligned16(x) && nsg_aligned16(dy) && (!y_relu || nsg_aligned16(y_relu)), NSG_E_INVALID,
-                "nsg_bn_backward_sums: pointers must be 16-byte aligned");
-    NSG_REQUIRE(workspace && workspace_bytes >= nsg_bn_workspace_bytes(M, C), NSG_E_WORKSPACE, "nsg_bn_backward_sums: workspace too small");
-    const SlabGeom g = slab_geom(M);
-    hipStream_t s = (hipStream_t)stream;
-    float *partial = reinterpret_cast<float *>(workspace);
-    if (dtype == NSG_BF16) {
-        typedef bf16_t T;
-        hipLaunchKernelGGL((bn_bwd_partial_kernel<T>), dim3(g.nslab), dim3(256), 0, s, (const T *)x, (const T *)y_relu, (const T *)dy, mean, invstd, gamma, relu_beta, M, C, g.rows, partial);
-    } else {
-        typedef float T;
-        hipLaunchKernelGGL((bn_bwd_partial_kernel<T>), dim3(g.nslab), dim3(256), 0, s, (const T *)x, (const T *)y_relu, (const T *)dy, mean, invstd, gamma, relu_beta, M, C, g.rows, partial);
-    }
-    hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(C / 4), dim3(256), 0, s, partial, g.nslab, C, dgamma, dbeta, (const float *)nullptr, (float *)nullptr);
+    const BnBwd b = {x, y_relu, dy, mean, invstd, gamma, relu_beta, M, C, dtype, reinterpret_cast<float *>(workspace), (hipStream_t)stream};
+    if (int rc = bn_bwd_check("nsg_bn_backward_sums", b, dgamma, dbeta, nullptr, workspace_bytes)) return rc;
+    bn_bwd_launch_sums(b, dgamma, dbeta);
     return nsg_check_launch("bn_backward_sums");
 }
 

@@ -22,7 +22,7 @@
 //   sums:  sum g,  sum g*(h - mean)   (x invstd at the end);
 //   dh = gamma*invstd*(g - mean(g) - xhat*mean(g*xhat)) = fma(sc, g, -fma(k1, h, k0)),
 //        sc = gamma*invstd, k1 = sc*invstd*dgamma/M, k0 = sc*dbeta/M - k1*mean.
-#include "nsg_common.h"
+#include "nsg_reduce.h"
 #include "c1_geom.h"
 #include <type_traits>
 
@@ -628,24 +628,12 @@ __global__ __launch_bounds__(256) void c1_tap_moments_kernel(const float *__rest
 __global__ __launch_bounds__(256) void c1_tap_moments_final_kernel(const float *__restrict__ partial, int nblocks, double *__restrict__ mom,
                                                                    const float *__restrict__ img, int64_t nimg)
 {
-    __shared__ double red[256];
     __shared__ float reds[4];
     const int tid = threadIdx.x;
     const float sft = mom_shift(img, nimg, reds, tid);
     if (blockIdx.x == 0 && tid == 0) mom[MOM_N] = (double)sft;
-    const int k = blockIdx.x * 32 + (tid >> 3), j = tid & 7;          // 8 lanes share a moment
-    double s = 0.0;
-    if (k < MOM_N) {
-        const int per = (nblocks + 7) / 8;
-        const int b0 = j * per, b1 = min(nblocks, b0 + per);
-        if (b1 > b0) s = nsg_strided_sum<double>(partial + (size_t)b0 * MOM_N + k, (size_t)MOM_N, b1 - b0);
-    }
-    red[tid] = s;
-    __syncthreads();
-    if (j != 0 || k >= MOM_N) return;
-    s = 0.0;
-    for (int q = 0; q < 8; ++q) s += red[tid + q];
-    mom[k] = s;
+    const int k = blockIdx.x * 32 + (tid >> 3);          // 8 lanes share a moment
+    nsg_lane_split_slab_sum<8>(partial + k, (size_t)MOM_N, nblocks, k < MOM_N, [&](double s) { mom[k] = s; });
 }
 
 __device__ __forceinline__ int mom_index(int t, int u) { return t * 17 + u; }      // P[t][u]

@@ -1,7 +1,7 @@
 // Convolution entry points: geometry checks, weight re-packing, the single-channel (C == 1)
 // col2im staging, bias gradients, and dispatch onto the two GEMM kernels.
 // Reference call sites: src/models.py:150,153,165,168 (nn.Conv2d), :179,182 (nn.ConvTranspose2d).
-#include "nsg_common.h"
+#include "nsg_reduce.h"
 
 // diagnostics: when set, the next gather_gemm launches stamp their main-loop clocks into this buffer
 NSG_DIAG_SWITCH(unsigned long long *, g_debug_stamps, nullptr)     // diagnostics library only (-DNSG_DIAG)
@@ -196,27 +196,10 @@ __global__ __launch_bounds__(256) void col2im_c1_kernel(const float *__restrict_
         lacc += (double)l4;
         gacc += (double)g4;
     }
-    if (LOSS) {       // block-level sum in double, fixed order (elementwise.hip: block_sum_store)
-        __shared__ double red[256];
-        red[threadIdx.x] = lacc;
-        __syncthreads();
-        if (threadIdx.x < 64) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + 64] + red[threadIdx.x + 128] + red[threadIdx.x + 192];
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double t = 0.0;
-            for (int q = 0; q < 64; ++q) t += red[q];
-            partial[blockIdx.x] = t;
-        }
-        __syncthreads();
-        red[threadIdx.x] = gacc;
-        __syncthreads();
-        if (threadIdx.x < 64) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + 64] + red[threadIdx.x + 128] + red[threadIdx.x + 192];
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double t = 0.0;
-            for (int q = 0; q < 64; ++q) t += red[q];
-            partial[gridDim.x + blockIdx.x] = t;
-        }
+    if (LOSS) {
+        nsg_block_sum_four_walk(lacc, partial);
+        __syncthreads();        // thread 0 has walked the first sum: the LDS array is free for the second
+        nsg_block_sum_four_walk(gacc, partial + gridDim.x);
     }
 }
 
@@ -291,22 +274,8 @@ __global__ __launch_bounds__(256) void colsum_partial_vec_kernel(const TI *__res
 }
 __global__ __launch_bounds__(256) void colsum_final_kernel(const float *__restrict__ partial, int nslab, int C, float *out)
 {
-    __shared__ double red[256];
-    const int tid = threadIdx.x;
-    const int j = tid & 31;
-    const int c = blockIdx.x * 8 + (tid >> 5);
-    double s = 0.0;
-    if (c < C) {
-        const int per = (nslab + 31) / 32;
-        const int b0 = j * per, b1 = min(nslab, b0 + per);
-        if (b1 > b0) s = nsg_strided_sum<double>(partial + (size_t)b0 * C + c, (size_t)C, b1 - b0);
-    }
-    red[tid] = s;
-    __syncthreads();
-    if (j != 0 || c >= C) return;
-    s = 0.0;
-    for (int k = 0; k < 32; ++k) s += red[tid + k];
-    out[c] = (float)s;
+    const int c = blockIdx.x * 8 + (threadIdx.x >> 5);       // 32 lanes share a column
+    nsg_lane_split_slab_sum<32>(partial + c, (size_t)C, nslab, c < C, [&](double s) { out[c] = (float)s; });
 }
 
 struct CsGeom { int nslab, rows; };

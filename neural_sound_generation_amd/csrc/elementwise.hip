@@ -1,7 +1,7 @@
 // Element-wise, loss and optimiser kernels (HBM-bound; float4 where alignment allows, grid-stride).
 // Reference call sites: src/train.py:118-136 (zero-pad, 3x F.mse_loss, Adam step), the ReLU / Tanh
 // backward of src/models.py:149,183.
-#include "nsg_common.h"
+#include "nsg_reduce.h"
 
 namespace {
 
@@ -108,39 +108,10 @@ __global__ void increment_counters_kernel(const CounterPtrs c, int n)
     if (i < n) *c.p[i] += 1;
 }
 
-// block-level sum in double, fixed order: thread partials -> LDS -> thread 0 walks them
-__device__ __forceinline__ void block_sum_store(double part, double *dst)
-{
-    __shared__ double red[256];
-    red[threadIdx.x] = part;
-    __syncthreads();
-    if (threadIdx.x < 64) {
-        double t = red[threadIdx.x] + red[threadIdx.x + 64] + red[threadIdx.x + 128] + red[threadIdx.x + 192];
-        red[threadIdx.x] = t;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int i = 0; i < 64; ++i) t += red[i];
-        dst[blockIdx.x] = t;
-    }
-}
-
-// one wave: each lane sums a strided share of the block partials, then a fixed-order lane walk
+// one wave closes a loss: out[0] = (sum of the n block partials) / denom
 __global__ void final_mean_kernel(const double *partial, int n, double denom, float *out)
 {
-    __shared__ double red[64];
-    const int lane = threadIdx.x;
-    double t = 0.0;
-#pragma unroll 8
-    for (int i = lane; i < n; i += 64) t += partial[i];
-    red[lane] = t;
-    __syncthreads();
-    if (lane == 0) {
-        double s = 0.0;
-        for (int i = 0; i < 64; ++i) s += red[i];
-        out[0] = (float)(s / denom);
-    }
+    nsg_wave_close_sum(partial, n, [&](double s) { out[0] = (float)(s / denom); });
 }
 
 // sum over [rows][wc] of (pad(a) - c)^2, a is [rows][wa] (wa <= wc); optional gradient wrt a
@@ -162,7 +133,7 @@ __global__ __launch_bounds__(256) void mse_padded_kernel(const float *__restrict
         }
         acc += (double)(d * d);
     }
-    block_sum_store(acc, partial);
+    nsg_block_sum_four_walk(acc, partial);
 }
 
 // z, q fp32 (the VQ works in fp32 in both modes); dz / dz_add of type TG (the encoder-side gradient),
@@ -200,7 +171,7 @@ __global__ __launch_bounds__(256) void vq_losses_kernel(const float *__restrict_
             if constexpr (VEC) stw<float, 8>(dq + i * 8, g); else dq[i] = g[0];
         }
     }
-    block_sum_store(acc, partial);
+    nsg_block_sum_four_walk(acc, partial);
 }
 
 // The same loss and encoder-side gradient with q given as (codebook, indices): q[row] = e[idx[row]] is read from the
@@ -209,12 +180,11 @@ template <typename T> __device__ __forceinline__ float round_as(float v);       
 template <> __device__ __forceinline__ float round_as<float>(float v) { return v; }
 template <> __device__ __forceinline__ float round_as<bf16_t>(float v) { return nsg_bf2f(nsg_f2bf(v)); }
 
-// Slab-structured exactly as bn_bwd_partial_kernel (bn.hip): block = one slab of slab_rows rows, thread (cg = tid % (D / 8),
-// rg = tid / (D / 8)) takes channels 8 cg .. + 7 of rows r0 + rg, + 256 / (D / 8), ...  (threads past the last whole row group idle).
+// Block = one slab of slab_rows rows of nsg_bn_slab_geom, threads by NsgSlabMap<8>.
 // BN: dz is the incoming gradient of a BatchNorm whose input is bn_x (the encoder's last ResBlock, src/models.py:154): the two
 // sums of that BatchNorm's backward -- bn_partial[slab][2][D] = (sum dz, sum dz * xhat) of the values AS STORED -- are formed
-// while dz is written, with bn_bwd_partial_kernel's expressions in its order: for bf16 gradients (8 channels per thread there
-// too) the finished sums equal those of the separate pass over (bn_x, dz) bit for bit.
+// while dz is written, with bn_bwd_partial_kernel's expressions, its slabs, its thread map and its fold (nsg_slab_park / nsg_slab_fold): for bf16
+// gradients (8 channels per thread there too) the finished sums equal those of the separate pass over (bn_x, dz) bit for bit.
 // BNRES (with BN and bf16 gradients): z is not read as fp32 but formed from its sources (BnResRows, nsg_common.h) -- it IS the
 // output of that BatchNorm plus the skip connection, so bn_x is the sources' h (loaded once) and bn_mean / bn_invstd are theirs.
 template <typename TG, bool BN, bool BNRES = false>
@@ -225,22 +195,18 @@ __global__ __launch_bounds__(256) void vq_losses_indexed_kernel(const typename R
                                                                 const float *__restrict__ bn_mean, const float *__restrict__ bn_invstd,
                                                                 float *__restrict__ bn_partial)
 {
-    const int D8 = D >> 3;
-    const int rgroups = 256 / D8;
-    const int cg = threadIdx.x % D8, rg = threadIdx.x / D8;
-    const int d8 = cg * 8;
-    const int64_t r0 = (int64_t)blockIdx.x * slab_rows;
-    const int64_t r1 = min(N, r0 + (int64_t)slab_rows);
+    const NsgSlabMap<8> m(D, blockIdx.x, slab_rows, N);
+    const int d8 = m.cg * 8;
     double acc = 0.0;
-    float s1[8], s2[8], mu[8], is[8];
+    float s[2][8], mu[8], is[8];
 #pragma unroll
-    for (int c = 0; c < 8; ++c) { s1[c] = 0.f; s2[c] = 0.f; mu[c] = BN ? bn_mean[d8 + c] : 0.f; is[c] = BN ? bn_invstd[d8 + c] : 0.f; }
+    for (int c = 0; c < 8; ++c) { s[0][c] = 0.f; s[1][c] = 0.f; mu[c] = BN ? bn_mean[d8 + c] : 0.f; is[c] = BN ? bn_invstd[d8 + c] : 0.f; }
     // BNRES: the four constants per channel -- mean, sc = invstd * gamma, beta, invstd -- wait in LDS (the sums' reduction buffer,
     // idle until the rows are done) and are read per row, four channels at a time: held in registers beside the sums they would
     // cost the kernel two of its seven waves per SIMD (86 registers against 72)
     __shared__ float red[BN ? 2 * 256 * 8 : 1];
     if constexpr (BNRES) {
-        if (rg == 0) {
+        if (m.rg == 0) {
 #pragma unroll
             for (int c = 0; c < 8; ++c) {
                 red[d8 + c] = mu[c];
@@ -251,8 +217,8 @@ __global__ __launch_bounds__(256) void vq_losses_indexed_kernel(const typename R
         }
         __syncthreads();
     }
-    for (int64_t row = r0 + rg; row < r1 && rg < rgroups; row += rgroups) {
-        const int64_t i = row * D8 + cg;
+    for (int64_t row = m.r0 + m.rg; row < m.r1 && m.active; row += m.rgroups) {
+        const int64_t i = row * m.CW + m.cg;
         int64_t k = idx[row];
         k = k < 0 ? 0 : (k >= K ? K - 1 : k);                 // (validated indices; clamped so a bad one cannot fault)
         float zv[8], qv[8], g[8], xv[8];
@@ -304,29 +270,21 @@ __global__ __launch_bounds__(256) void vq_losses_indexed_kernel(const typename R
 #pragma unroll
                 for (int c = 0; c < 8; ++c) {
                     const float gs = round_as<TG>(g[c]);
-                    s1[c] += gs;
-                    s2[c] += gs * (BNRES ? xv[c] * isl[c] : (xv[c] - mu[c]) * is[c]);
+                    s[0][c] += gs;
+                    s[1][c] += gs * (BNRES ? xv[c] * isl[c] : (xv[c] - mu[c]) * is[c]);
                 }
             }
         }
     }
-    block_sum_store(acc, partial);
+    nsg_block_sum_four_walk(acc, partial);
     if constexpr (BN) {
-        __syncthreads();
-#pragma unroll
-        for (int c = 0; c < 8; ++c)
-            if (rg < rgroups) { red[(rg * D8 + cg) * 8 + c] = s1[c]; red[256 * 8 + (rg * D8 + cg) * 8 + c] = s2[c]; }
-        __syncthreads();
-        if ((int)threadIdx.x < D8) {
-            float *dst = bn_partial + (size_t)blockIdx.x * 2 * D;
-#pragma unroll
-            for (int c = 0; c < 8; ++c) {
-                float t1 = 0.f, t2 = 0.f;
-                for (int gq = 0; gq < rgroups; ++gq) { t1 += red[(gq * D8 + threadIdx.x) * 8 + c]; t2 += red[256 * 8 + (gq * D8 + threadIdx.x) * 8 + c]; }
-                dst[threadIdx.x * 8 + c] = t1;
-                dst[D + threadIdx.x * 8 + c] = t2;
-            }
-        }
+        __syncthreads();        // (BNRES: the last reads of the constants parked in red)
+        float *dst = bn_partial + (size_t)blockIdx.x * 2 * D;
+        if (m.active) nsg_slab_park(m, s, red);
+        nsg_slab_fold<2>(m, red, [&](int c, const float (&t)[2]) {
+            dst[threadIdx.x * 8 + c] = t[0];
+            dst[D + threadIdx.x * 8 + c] = t[1];
+        });
     }
 }
 
@@ -379,36 +337,24 @@ __global__ __launch_bounds__(256) void clip_colsum_partial_kernel(const T *__res
 {
     constexpr int W = Elem<T>::N;
     __shared__ float red[256 * W];
-    const int CW = C / W;
-    const int rgroups = 256 / CW;
-    const int tid = threadIdx.x;
-    const int cg = tid % CW, rg = tid / CW;
     const int b = blockIdx.x / slabs, sl = blockIdx.x % slabs;
     const int R = (rows_per_clip + slabs - 1) / slabs;
-    const int r0 = sl * R, r1 = min(rows_per_clip, r0 + R);
+    const NsgSlabMap<W> m(C, sl, R, rows_per_clip);       // the clip's rows in `slabs` slabs of R
     const T *base = x + (size_t)b * rows_per_clip * C;
-    if (rg < rgroups) {
-        float s[W];
+    const int tid = threadIdx.x;
+    if (m.active) {
+        float s[1][W];
 #pragma unroll
-        for (int e = 0; e < W; ++e) s[e] = 0.f;
-        for (int r = r0 + rg; r < r1; r += rgroups) {
+        for (int e = 0; e < W; ++e) s[0][e] = 0.f;
+        for (int r = (int)m.r0 + m.rg; r < (int)m.r1; r += m.rgroups) {
             float v[W];
-            ldw<T, W>(base + (size_t)r * C + cg * W, v);
+            ldw<T, W>(base + (size_t)r * C + m.cg * W, v);
 #pragma unroll
-            for (int e = 0; e < W; ++e) s[e] += v[e];
+            for (int e = 0; e < W; ++e) s[0][e] += v[e];
         }
-#pragma unroll
-        for (int e = 0; e < W; ++e) red[(rg * CW + cg) * W + e] = s[e];
+        nsg_slab_park(m, s, red);
     }
-    __syncthreads();
-    if (tid < CW) {
-#pragma unroll
-        for (int e = 0; e < W; ++e) {
-            float t = 0.f;
-            for (int g = 0; g < rgroups; ++g) t += red[(g * CW + tid) * W + e];
-            partial[(size_t)blockIdx.x * C + tid * W + e] = t;
-        }
-    }
+    nsg_slab_fold<1>(m, red, [&](int e, const float (&t)[1]) { partial[(size_t)blockIdx.x * C + tid * W + e] = t[0]; });
 }
 __global__ void clip_colsum_final_kernel(const float *__restrict__ partial, int B, int slabs, int C, float *__restrict__ out)
 {

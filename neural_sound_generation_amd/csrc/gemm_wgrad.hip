@@ -13,7 +13,7 @@
 // which is exactly how NHWC rows sit in memory: the LDS tiles are plain [32 pixels][channels]
 // copies, and an MFMA operand read is 32 consecutive floats of one pixel row (ds_read_b32,
 // conflict-free).  Block = 4 waves, tile TA x TC of one tap for one slab of pixels.
-#include "nsg_common.h"
+#include "nsg_reduce.h"
 #include <type_traits>
 
 // Diagnostics library only (-DNSG_DIAG): run-time switches; constants in libnsg.so
@@ -669,12 +669,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void o
 }
 
 // dst[(a*C + c)*ntaps + t] = sum_slab partial[slab][t][a][c]
-// One thread per output when there are few slabs; otherwise 8 lanes per output split the slabs and
-// the partial sums are added in lane order (fixed order either way: bitwise reproducible).
+// One thread per output when there are few slabs; otherwise `split` threads per output share the slabs
+// (nsg_split_slab_sum: fixed order either way, bitwise reproducible).
 __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float *__restrict__ partial, float *__restrict__ dst, int nslab, int ntaps,
                                                            int A, int C, int split)
 {
-    __shared__ float red[256];
     const int64_t total = (int64_t)ntaps * A * C;
     const int per_block = 256 / split;
     const int tid = threadIdx.x;
@@ -682,21 +681,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float *__restri
     const int loc = tid - sub * per_block;    // which output inside the block (consecutive -> coalesced)
     for (int64_t e0 = (int64_t)blockIdx.x * per_block; e0 < total; e0 += (int64_t)gridDim.x * per_block) {
         const int64_t e = e0 + loc;
-        float sacc = 0.f;
-        if (e < total) {
-            const int chunk = (nslab + split - 1) / split;
-            const int s0 = sub * chunk, s1 = min(nslab, s0 + chunk);
-            if (s1 > s0) sacc = nsg_strided_sum<float>(partial + (size_t)s0 * total + e, (size_t)total, s1 - s0);
-        }
-        if (split > 1) {
-            red[tid] = sacc;
-            __syncthreads();
-            if (sub == 0) {
-                sacc = 0.f;
-                for (int k = 0; k < split; ++k) sacc += red[k * per_block + loc];
-            }
-            __syncthreads();
-        }
+        const float sacc = nsg_split_slab_sum<true>(partial + e, (size_t)total, nslab, split, e < total);
         if (sub == 0 && e < total) {
             const int c = (int)(e % C);
             const int a = (int)((e / C) % A);

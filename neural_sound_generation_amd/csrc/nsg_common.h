@@ -94,50 +94,6 @@ struct BnResLane {
     }
 };
 
-// Fixed-order sum of n floats p[0], p[stride], p[2*stride], ... : the loads are issued 16 at a time (the
-// finalize kernels are otherwise a chain of dependent global-load latencies), the adds stay in index order.
-template <typename ACC>
-__device__ __forceinline__ ACC nsg_strided_sum(const float *__restrict__ p, size_t stride, int n)
-{
-    ACC s = (ACC)0;
-    int i = 0;
-    for (; i + 16 <= n; i += 16) {
-        float v[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) v[k] = p[(size_t)(i + k) * stride];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) s += (ACC)v[k];
-    }
-    if (i + 8 <= n) {
-        float v[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v[k] = p[(size_t)(i + k) * stride];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) s += (ACC)v[k];
-        i += 8;
-    }
-    for (; i < n; ++i) s += (ACC)p[(size_t)i * stride];
-    return s;
-}
-
-// two arrays at once (their loads share the latency)
-__device__ __forceinline__ void nsg_strided_sum2(const float *__restrict__ p, const float *__restrict__ q, size_t stride, int n,
-                                                 double &sp, double &sq)
-{
-    double a = 0.0, b = 0.0;
-    int i = 0;
-    for (; i + 16 <= n; i += 16) {
-        float v[16], w[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) { v[k] = p[(size_t)(i + k) * stride]; w[k] = q[(size_t)(i + k) * stride]; }
-#pragma unroll
-        for (int k = 0; k < 16; ++k) { a += (double)v[k]; b += (double)w[k]; }
-    }
-    for (; i < n; ++i) { a += (double)p[(size_t)i * stride]; b += (double)q[(size_t)i * stride]; }
-    sp = a;
-    sq = b;
-}
-
 // thread-local error text (never thrown across the ABI)
 void nsg_set_error(const char *fmt, ...);
 int nsg_fail(int code, const char *fmt, ...);
@@ -318,11 +274,10 @@ int nsg_bn_stats_from_tiles(const float *tiles, int ntiles, int64_t M, int C, fl
 // dbeta[c] = sum_s partial[s][0][c], dgamma[c] = sum_s partial[s][1][c] over nslab <= NSG_MAX_SLABS slabs of [2][C] (fixed order, double)
 void nsg_bn_slab_geom(int64_t M, int *nslab, int *rows);      // bn.hip: slabs of nsg_bn_backward_sums over M rows
 int nsg_launch_bn_bwd_final(const float *partial, int nslab, int C, float *dgamma, float *dbeta, hipStream_t s);
-// ... and colsum[c] = sum_s colsum_partial[s][c] in the same launch
+// ... and colsum[c] = sum_s colsum_partial[s][c] (colsum_partial may be null) and the slab sum of a weight gradient's block
+// partials wpartial [nslab][wn] -> wdst [wn] in the same launch
 int nsg_launch_bn_bwd_final_wreduce(const float *partial, const float *colsum_partial, int nslab, int C, float *dgamma, float *dbeta, float *colsum,
                                     const float *wpartial, float *wdst, int wn, hipStream_t s);
-int nsg_launch_bn_bwd_final_colsum(const float *partial, const float *colsum_partial, int nslab, int C, float *dgamma, float *dbeta,
-                                   float *colsum, hipStream_t s);
 // out[c] = sum_s partial[s][c] over nslab <= NSG_MAX_SLABS slabs of [C] (fixed order, double)
 int nsg_launch_slab_sum_final(const float *partial, int nslab, int C, float *out, hipStream_t s);
 

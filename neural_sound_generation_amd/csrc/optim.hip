@@ -2,7 +2,7 @@
 // Adam step -- decoupled weight decay per segment, clipping by the global norm, a non-finite guard and a weight EMA folded
 // into the one pass.  With every extension neutral the step's arithmetic is adam_kernel's (elementwise.hip), operation for
 // operation; the library is built with -ffp-contract=off, so the bits are too.
-#include "nsg_common.h"
+#include "nsg_reduce.h"
 #include <math.h>
 
 namespace {
@@ -18,11 +18,10 @@ inline int opt_blocks(int64_t n, int cap)
 }
 
 // partial[block] = sum of g^2 over the block's grid-stride share: a thread adds its elements in index order, the block's 256
-// thread sums are combined as 64 lanes of four, then lane by lane.  (double)g * (double)g is exact.
+// thread sums go through nsg_block_sum_four_walk.  (double)g * (double)g is exact.
 template <int V>
 __global__ __launch_bounds__(256) void grad_sumsq_kernel(const float *__restrict__ g, int64_t nv, double *__restrict__ partial)
 {
-    __shared__ double red[256];
     double acc = 0.0;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nv; i += (int64_t)gridDim.x * blockDim.x) {
         float x[V];
@@ -30,31 +29,12 @@ __global__ __launch_bounds__(256) void grad_sumsq_kernel(const float *__restrict
 #pragma unroll
         for (int e = 0; e < V; ++e) acc += (double)x[e] * (double)x[e];
     }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    if (threadIdx.x < 64) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + 64] + red[threadIdx.x + 128] + red[threadIdx.x + 192];
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int i = 0; i < 64; ++i) t += red[i];
-        partial[blockIdx.x] = t;
-    }
+    nsg_block_sum_four_walk(acc, partial);
 }
 
-// one wave: lane l sums partials l, l + 64, ... in that order, then lane 0 walks the 64 lane sums
 __global__ __launch_bounds__(64) void grad_sumsq_final_kernel(const double *__restrict__ partial, int n, double *__restrict__ out)
 {
-    __shared__ double red[64];
-    const int lane = threadIdx.x;
-    double t = 0.0;
-    for (int i = lane; i < n; i += 64) t += partial[i];
-    red[lane] = t;
-    __syncthreads();
-    if (lane == 0) {
-        double s = 0.0;
-        for (int i = 0; i < 64; ++i) s += red[i];
-        out[0] = s;
-    }
+    nsg_wave_close_sum(partial, n, [&](double s) { out[0] = s; });
 }
 
 struct AdamwScalars {

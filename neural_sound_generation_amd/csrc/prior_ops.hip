@@ -7,7 +7,7 @@
 //   cross-entropy     mean over rows of  logsumexp(l) - l[target]  and its gradient (what F.cross_entropy computes on
 //                     the prior's logits); the masked form leaves rows with a negative target out and returns per-clip sums.
 // fp32, NHWC rows [M][channels]; deterministic (fixed-order reductions).
-#include "nsg_common.h"
+#include "nsg_reduce.h"
 #include <math.h>
 
 namespace {
@@ -204,18 +204,11 @@ __global__ __launch_bounds__(256) void cross_entropy_kernel(const float *__restr
 // sum of n floats in double, two fixed-order stages
 __global__ __launch_bounds__(256) void sum_partial_kernel(const float *__restrict__ v, int64_t n, double *__restrict__ partial)
 {
-    __shared__ double red[256];
     double acc = 0.0;
     const int64_t per = (n + gridDim.x - 1) / gridDim.x;
     const int64_t i0 = blockIdx.x * per, i1 = min(n, i0 + per);
     for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) acc += (double)v[i];
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int k = 0; k < 256; ++k) t += red[k];
-        partial[blockIdx.x] = t;
-    }
+    nsg_block_sum_walk256(acc, [&](double t) { partial[blockIdx.x] = t; });
 }
 __global__ void sum_final_kernel(const double *partial, int n, double denom, float *out)
 {
@@ -270,17 +263,10 @@ __global__ __launch_bounds__(256) void ce_scale_kernel(const int64_t *__restrict
 // nothing outside the clip's own rows enters
 __global__ __launch_bounds__(256) void ce_clip_nll_kernel(const float *__restrict__ row_loss, int64_t rows_per_clip, float *__restrict__ clip_nll)
 {
-    __shared__ double red[256];
     const float *v = row_loss + blockIdx.x * rows_per_clip;
     double acc = 0.0;
     for (int64_t r = threadIdx.x; r < rows_per_clip; r += 256) acc += (double)v[r];
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int k = 0; k < 256; ++k) t += red[k];
-        clip_nll[blockIdx.x] = (float)t;
-    }
+    nsg_block_sum_walk256(acc, [&](double t) { clip_nll[blockIdx.x] = (float)t; });
 }
 __global__ void ce_masked_final_kernel(const double *partial, int n, const CeScalars *sc, float *out)
 {

@@ -11,7 +11,7 @@
 // rows of a tile sit in LDS and are read as wave-broadcasts; the 64 weights (or 64+4 accumulators) a thread needs
 // stay in registers across a persistent loop over tiles.  w is the parameter's own layout: Conv2d (C,1,4,4) and
 // ConvTranspose2d (C,1,4,4) are both [c][16].
-#include "nsg_common.h"
+#include "nsg_reduce.h"
 #include "c1_geom.h"
 
 namespace {
@@ -275,25 +275,13 @@ __global__ __launch_bounds__(256) void c1_stencil_wgrad_kernel(const float *__re
 __global__ __launch_bounds__(256) void c1_stencil_wgrad_final_kernel(const float *__restrict__ partial, int nblocks, int C,
                                                                      float *__restrict__ dw, float *__restrict__ colsum)
 {
-    __shared__ double red[256];
-    const int tid = threadIdx.x;
-    const int j = tid & 7;                       // 8 lanes share an output
-    const int e = blockIdx.x * 32 + (tid >> 3);  // output index in [0, C*17)
+    const int e = blockIdx.x * 32 + (threadIdx.x >> 3);  // output index in [0, C*17): 8 lanes share an output
     const int total = C * 17;
-    double s = 0.0;
-    if (e < total) {
-        const int per = (nblocks + 7) / 8;
-        const int b0 = j * per, b1 = min(nblocks, b0 + per);
-        if (b1 > b0) s = nsg_strided_sum<double>(partial + (size_t)b0 * total + e, (size_t)total, b1 - b0);
-    }
-    red[tid] = s;
-    __syncthreads();
-    if (j != 0 || e >= total) return;
-    s = 0.0;
-    for (int k = 0; k < 8; ++k) s += red[tid + k];
-    const int c = e / 17, tap = e - c * 17;
-    if (tap < 16) dw[c * 16 + tap] = (float)s;
-    else if (colsum) colsum[c] = (float)s;
+    nsg_lane_split_slab_sum<8>(partial + e, (size_t)total, nblocks, e < total, [&](double s) {
+        const int c = e / 17, tap = e - c * 17;
+        if (tap < 16) dw[c * 16 + tap] = (float)s;
+        else if (colsum) colsum[c] = (float)s;
+    });
 }
 
 

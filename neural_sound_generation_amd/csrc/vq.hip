@@ -9,7 +9,7 @@
 // accumulator), so feeding it d = 2s (lanes 0-31) and d = 2s+1 (lanes 32-63) at step s reproduces
 // the chain exactly on the matrix pipe.  tests/test_gpu_ops.py checks MFMA == VALU chain bit for bit
 // (nsg_debug_dot) and the indices against fixtures generated from the reference.
-#include "nsg_common.h"
+#include "nsg_reduce.h"
 #include <math.h>
 
 #ifndef NSG_VQ_W1_DP
@@ -395,7 +395,6 @@ __global__ void counts_to_float_kernel(const int *counts, int K, float *out)
 // fixed order, so every rank / launch computes the identical value.  Kernel 2: the K x D part.
 __global__ void ema_counts_kernel(float *ema_n, const float *n, int K, float decay, float *total)
 {
-    __shared__ double red[256];
     const int tid = threadIdx.x;
     double part = 0.0;
     for (int k = tid; k < K; k += 256) {
@@ -403,13 +402,7 @@ __global__ void ema_counts_kernel(float *ema_n, const float *n, int K, float dec
         ema_n[k] = v;
         part += (double)v;
     }
-    red[tid] = part;
-    __syncthreads();
-    if (tid == 0) {
-        double t = 0.0;
-        for (int i = 0; i < 256; ++i) t += red[i];
-        total[0] = (float)t;
-    }
+    nsg_block_sum_walk256(part, [&](double t) { total[0] = (float)t; });
 }
 __global__ void ema_codes_kernel(float *e, const float *ema_n, float *ema_s, const float *s, int K, int D, float decay,
                                  float eps, const float *total)
