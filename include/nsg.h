@@ -38,7 +38,7 @@ extern "C" {
 #define NSG_API
 #endif
 
-#define NSG_VERSION 103 /* bumped HERE on ANY change of an existing entry point's signature; _lib.py binds from this header and refuses a library of another version */
+#define NSG_VERSION 104 /* bumped HERE on ANY change of an existing entry point's signature; _lib.py binds from this header and refuses a library of another version */
 
 enum {
     NSG_OK = 0,
@@ -64,8 +64,10 @@ enum {
  * transposed = 1: nn.ConvTranspose2d(C_in, C_out, k, stride, pad).  (IH,IW) is the layer's input
  * extent, (OH,OW) its output extent; both are given so the library never has to guess.
  * Supported: Conv2d with any k <= 7 (rectangular: see k_w), stride in {1,2}; ConvTranspose2d with k=4, stride=2, pad=1
- * (the only transposed geometry on the path: src/models.py:179,182).  C_in and C_out must be
- * multiples of 4 or equal to 1. */
+ * (the VQ-VAE's transposed geometry: src/models.py:179,182) and, fp32 only, ConvTranspose2d with stride=1, square k <= 7,
+ * 0 <= pad < k, OH = IH + k - 1 - 2 pad (the VAE decoder's: src/models.py:85,88), C_in and C_out multiples of 4, C_out > 1:
+ * its forward is the data gradient of Conv2d(C_out, C_in, k, 1, pad) over the same weight tensor and runs on that kernel.
+ * C_in and C_out must be multiples of 4 or equal to 1. */
 typedef struct nsg_conv_desc {
     int32_t B, IH, IW, C_in;
     int32_t OH, OW, C_out;
@@ -559,6 +561,33 @@ NSG_API int nsg_adamw_step(float *p, const float *g, float *m, float *v, int64_t
                            int32_t step, float grad_scale, const int64_t *seg_end, const float *seg_wd, int32_t n_seg,
                            const double *sumsq, float max_norm, int32_t skip_nonfinite, float *shadow, float one_minus_decay,
                            void *stats, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Gaussian latent of the continuous VAE                   src/models.py:77,103-112
+ *   encoder.9 Conv2d -> encoder.10 BatchNorm2d(2Z) -> chunk(2, dim=1) -> KL to N(0, I) -> mu + exp(.5 logvar) * eps
+ * Rows are the NHWC pixels of the encoder output, 2Z channels per row: [0, Z) is mu, [Z, 2Z) is logvar.  h [M][2Z] is the
+ * BatchNorm's INPUT; its output y = (h - mean) * (invstd * gamma) + beta (nsg_bn_apply's arithmetic) is formed on load by
+ * both kernels and never stored.  mean / invstd: nsg_conv_forward_bnstats (training) or nsg_bn_eval_stats (eval).
+ * The kernels hold no random-number generator: eps [M][Z] is an argument.  fp32; no clamping: non-finite values propagate.
+ * NSG_E_INVALID: a null required pointer, M < 1, tensors not 16-byte aligned; NSG_E_UNSUPPORTED: Z < 4, Z % 4 != 0, Z > 512,
+ * M * 2Z >= 2^31; NSG_E_WORKSPACE: fewer than nsg_vae_latent_workspace_bytes(M, Z) bytes.  Every sum is in a fixed order.
+ * ------------------------------------------------------------------------------------------- */
+NSG_API size_t nsg_vae_latent_workspace_bytes(int64_t M, int32_t Z);
+/* sigma = expf(0.5 lv);  z [M][Z] = mu + sigma * eps;  kl_out[0] = (1 / M) * sum over rows and channels of
+ * 0.5 * (mu^2 + sigma^2 - 1 - lv): kl_divergence(Normal(mu, sigma), Normal(0, 1)).sum(1).mean() of models.py:108-110. */
+NSG_API int nsg_vae_latent_forward(const float *h, const float *mean, const float *invstd, const float *gamma, const float *beta,
+                                   const float *eps, float *z, float *kl_out, int64_t M, int32_t Z, void *workspace,
+                                   size_t workspace_bytes, void *stream);
+/* dy [M][2Z] = the gradient w.r.t. the BatchNorm's OUTPUT, given dz [M][Z] = dL/dz and the KL term's weight
+ * s = kl_scale * (kl_grad ? kl_grad[0] : 1) / M (kl_grad: one device float, the gradient arriving at kl_out, or NULL):
+ *   dy_mu = dz + s * mu,   dy_lv = 0.5 * dz * sigma * eps + 0.5 * s * (sigma^2 - 1);
+ * and that BatchNorm's backward sums over the dy values as stored, dbeta[c] = sum_m dy[m][c], dgamma[c] = sum_m dy[m][c] *
+ * (h[m][c] - mean[c]) * invstd[c] ([2Z] each, overwritten): what nsg_bn_backward_sums(h, NULL, dy, ...) returns, bit for bit
+ * (the same slabs, the same order), so nsg_bn_backward_apply(h, NULL, dy, ..., dgamma, dbeta, dh, ...) finishes dh. */
+NSG_API int nsg_vae_latent_backward(const float *h, const float *mean, const float *invstd, const float *gamma, const float *beta,
+                                    const float *eps, const float *dz, float kl_scale, const float *kl_grad, float *dy,
+                                    float *dgamma, float *dbeta, int64_t M, int32_t Z, void *workspace, size_t workspace_bytes,
+                                    void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Self-checks used by the tests

@@ -307,7 +307,11 @@ int colsum(const void *x, int dtype, int64_t M, int C, float *out, void *ws, hip
     return nsg_check_launch("colsum");
 }
 
-enum Kind { K_CONV, K_CONVT, K_CONV_C1, K_CONVT_C1 };
+// K_CONVT_S1: ConvTranspose2d(C_in, C_out, k, 1, pad), fp32: no kernel of its own.  Its forward is the data gradient of
+// Conv2d(C_out, C_in, k, 1, pad) over the same weight tensor = a stride-1 gather with pad' = k - 1 - pad over the flipped,
+// in/out-swapped taps; its data gradient is that Conv2d's forward (pad, taps as they are); its weight gradient is that
+// Conv2d's with x and dy in each other's roles, which lands in the (C_in, C_out, k, k) layout as it is.
+enum Kind { K_CONV, K_CONVT, K_CONV_C1, K_CONVT_C1, K_CONVT_S1 };
 
 // kernel extent / padding per dimension: k, pad are the height's (and the width's for a square kernel, k_w == 0)
 inline int kh_of(const nsg_conv_desc *d) { return d->k; }
@@ -347,6 +351,15 @@ int classify(const nsg_conv_desc *d, const char *fn)
             return nsg_fail(NSG_E_UNSUPPORTED, "%s: stride-2 Conv2d needs k=4,pad=1", fn);
         return K_CONV;
     }
+    if (d->stride == 1) {
+        if (d->dtype != NSG_F32) return nsg_fail(NSG_E_UNSUPPORTED, "%s: stride-1 ConvTranspose2d is fp32 only", fn);
+        if (d->k_w != 0 || d->k > 7 || d->pad < 0 || d->pad >= d->k)
+            return nsg_fail(NSG_E_UNSUPPORTED, "%s: stride-1 ConvTranspose2d needs a square k <= 7 and 0 <= pad < k", fn);
+        if (d->C_in % 4 || d->C_out % 4) return nsg_fail(NSG_E_UNSUPPORTED, "%s: stride-1 ConvTranspose2d channels must be multiples of 4", fn);
+        if (d->OH != d->IH + d->k - 1 - 2 * d->pad || d->OW != d->IW + d->k - 1 - 2 * d->pad)
+            return nsg_fail(NSG_E_INVALID, "%s: output extent does not match ConvTranspose2d geometry", fn);
+        return K_CONVT_S1;
+    }
     if (!(d->k == 4 && d->stride == 2 && d->pad == 1) || rect(d)) return nsg_fail(NSG_E_UNSUPPORTED, "%s: ConvTranspose2d needs k=4,stride=2,pad=1", fn);
     if (d->OH != 2 * d->IH || d->OW != 2 * d->IW) return nsg_fail(NSG_E_INVALID, "%s: output extent does not match ConvTranspose2d geometry", fn);
     if (d->C_out == 1) {
@@ -361,7 +374,7 @@ int classify(const nsg_conv_desc *d, const char *fn)
 inline size_t esize(const nsg_conv_desc *d) { return d->dtype == NSG_BF16 ? 2 : 4; }
 inline int64_t lowres_pixels(const nsg_conv_desc *d)
 {
-    return d->transposed ? (int64_t)d->B * d->IH * d->IW : (int64_t)d->B * d->OH * d->OW;
+    return d->transposed ? (int64_t)d->B * d->IH * d->IW : (int64_t)d->B * d->OH * d->OW;     // (stride-1 transposed: the weight gradient's rows)
 }
 // staging image of the single-channel layers: [low-res pixels][16]: patches (dtype) or tap products (fp32)
 inline size_t patches_bytes(const nsg_conv_desc *d) { return nsg_align_up((size_t)lowres_pixels(d) * 16 * sizeof(float), 256); }
@@ -370,12 +383,12 @@ inline size_t patches_bytes(const nsg_conv_desc *d) { return nsg_align_up((size_
 inline size_t stats_tiles_bytes(const nsg_conv_desc *d)
 {
     const int64_t out_pix = (int64_t)d->B * d->OH * d->OW;
-    const int64_t tiles = d->transposed ? 4 * nsg_cdiv(out_pix / 4 + d->B * (d->OH + d->OW), 128) + 8 : nsg_cdiv(out_pix, 128);
+    const int64_t tiles = (d->transposed && d->stride == 2) ? 4 * nsg_cdiv(out_pix / 4 + d->B * (d->OH + d->OW), 128) + 8 : nsg_cdiv(out_pix, 128);
     return nsg_align_up(nsg_bn_tiles_bytes(tiles + 8, d->C_out), 256);
 }
 
-// nsg_conv_*'s workspace.  Layers with channels on both sides: the weight gradient's slabs | the column-sum partials of the
-// bias gradient | the tile statistics of nsg_conv_forward_bnstats.  Single-channel layers: the staging image of the GEMM-side
+// nsg_conv_*'s workspace.  Layers with channels on both sides (Conv2d, both transposed kinds): the weight gradient's slabs | the
+// column-sum partials of the bias gradient | the tile statistics of nsg_conv_forward_bnstats.  Single-channel layers: the staging image of the GEMM-side
 // passes, overlaid by the stencil weight gradient's partials | the column-sum partials; no tile statistics.
 struct ConvLayout {
     int kind;                   // classify()'s answer; < 0: the descriptor was rejected, bytes = 0 and there are no sections
@@ -397,7 +410,7 @@ ConvLayout conv_layout(void *ws, const nsg_conv_desc *d, const char *fn)
         L.dots = reinterpret_cast<float *>(L.wgrad);       // forward and dgrad see the staging image where wgrad sees its two sections
         if (patches_bytes(d) > L.wgrad_bytes) c.take<char>(patches_bytes(d) - L.wgrad_bytes);     // (sized as max(image, partials) + column sums)
     } else {
-        const bool t = L.kind == K_CONVT;
+        const bool t = L.kind == K_CONVT || L.kind == K_CONVT_S1;
         L.wgrad_bytes = nsg_align_up(nsg_wgrad_workspace_bytes(lowres_pixels(d), kh_of(d) * kw_of(d), t ? d->C_in : d->C_out, t ? d->C_out : d->C_in), 256);
         L.wgrad = c.take<char>(L.wgrad_bytes);
         L.colsum = c.take<char>(cs_bytes);
@@ -504,6 +517,10 @@ int nsg_pack_conv_weights_batch(int32_t n, const nsg_conv_desc *descs, const flo
             add(w[i], w_fwd[i], T, CO, CI, T, CO * T, 0, bf);
             add(w[i], w_dgrad[i], T, CI, CO, CO * T, T, 0, bf);
             break;
+        case K_CONVT_S1:  // w[ci][co][t]: forward = stride-1 gather over the flipped, in/out-swapped taps; data gradient = the taps as they are
+            add(w[i], w_fwd[i], T, CO, CI, T, CO * T, 1, 0);
+            add(w[i], w_dgrad[i], T, CI, CO, CO * T, T, 0, 0);
+            break;
         case K_CONV_C1:  // w[co][t] : forward is the stencil kernel (fp32 [co][16] = the parameter's own layout)
             add(w[i], w_fwd[i], 1, CO, 16, 16, 1, 0, 0);
             add(w[i], w_dgrad[i], 1, 16, CO, 1, 16, 0, bf);   // [n=t][c=co]
@@ -532,7 +549,7 @@ static int conv_forward_impl(const nsg_conv_desc *d, const void *x, const void *
     NSG_REQUIRE(x && w_fwd && y, NSG_E_INVALID, "nsg_conv_forward: null pointer");
     hipStream_t s = (hipStream_t)stream;
     const int out_dtype = (flags & NSG_OUT_F32) ? NSG_F32 : d->dtype;
-    if (kind == K_CONV || kind == K_CONVT) {
+    if (kind == K_CONV || kind == K_CONVT || kind == K_CONVT_S1) {
         GatherGemmParams p = {};
         p.in = x; p.w = w_fwd; p.bias = bias; p.out = y;
         p.in_dtype = d->dtype; p.out_dtype = out_dtype;
@@ -541,6 +558,7 @@ static int conv_forward_impl(const nsg_conv_desc *d, const void *x, const void *
         p.KH = kh_of(d); p.KW = kw_of(d); p.stride = d->stride; p.pad = ph_of(d); p.pad_w = pw_of(d);
         p.flags = flags & (NSG_RELU_IN | NSG_TANH_OUT | NSG_RELU_OUT);
         if (kind == K_CONV) { p.mode = 0; p.RH = d->OH; p.RW = d->OW; }
+        else if (kind == K_CONVT_S1) { p.mode = 0; p.pad = p.pad_w = d->k - 1 - d->pad; p.RH = d->OH; p.RW = d->OW; }   // pad' < k: flipped taps
         else                { p.mode = 1; p.RH = d->IH; p.RW = d->IW; }
         p.M = d->B * p.RH * p.RW;
         p.stats = stats;
@@ -614,7 +632,7 @@ int nsg_conv_dgrad_relu_add(const nsg_conv_desc *d, const void *dy, const void *
     if (kind < 0) return kind;
     NSG_REQUIRE(dy && w_dgrad && dx, NSG_E_INVALID, "nsg_conv_dgrad: null pointer");
     hipStream_t s = (hipStream_t)stream;
-    if (kind == K_CONV || kind == K_CONVT) {
+    if (kind == K_CONV || kind == K_CONVT || kind == K_CONVT_S1) {
         // roles swap: the gradient of a conv is a transposed conv and vice versa
         GatherGemmParams p = {};
         p.in = dy; p.w = w_dgrad; p.bias = nullptr; p.out = dx;
@@ -626,6 +644,8 @@ int nsg_conv_dgrad_relu_add(const nsg_conv_desc *d, const void *dy, const void *
         p.flags = 0;
         if (kind == K_CONV && d->stride == 1) {
             p.mode = 0; p.stride = 1; p.pad = kh_of(d) - 1 - ph_of(d); p.pad_w = kw_of(d) - 1 - pw_of(d); p.RH = d->IH; p.RW = d->IW;  // flipped taps
+        } else if (kind == K_CONVT_S1) {
+            p.mode = 0; p.stride = 1; p.pad = p.pad_w = d->pad; p.RH = d->IH; p.RW = d->IW;  // the Conv2d this layer is the gradient of
         } else if (kind == K_CONV) {
             p.mode = 1; p.stride = 2; p.pad = 1; p.pad_w = 1; p.RH = (d->IH + 1) / 2; p.RW = (d->IW + 1) / 2;  // 4/2/1: transposed classes
         } else {
@@ -688,7 +708,7 @@ int nsg_conv_wgrad(const nsg_conv_desc *d, const void *x, const void *dy, float 
     if (kind == K_CONV) {
         p.P = dy; p.PH = d->OH; p.PW = d->OW; p.A = d->C_out;
         p.Q = x; p.QH = d->IH; p.QW = d->IW; p.C = d->C_in; p.relu_q = relu_x;
-    } else {   // K_CONVT
+    } else {   // K_CONVT, K_CONVT_S1: x on the reduction's pixel grid, dy gathered per tap -> dw[ci][co][t]
         p.P = x; p.PH = d->IH; p.PW = d->IW; p.A = d->C_in; p.relu_p = relu_x;
         p.Q = dy; p.QH = d->OH; p.QW = d->OW; p.C = d->C_out;
     }

@@ -13,9 +13,10 @@ import numpy as np
 import torch
 
 from . import audio as nsg_audio
-from .evaluate import checkpoint_state, sample_mels, save_checkpoint, test_prior, test_vqvae
+from .evaluate import checkpoint_state, sample_mels, save_checkpoint, test_prior, test_vae, test_vqvae
 from .prior_train import PriorTrainStep, train_prior
 from .train import train_vqvae
+from .vae_train import VAETrainStep, train_vae
 
 SAMPLING_RATE, FFT_SIZE, HOP_SIZE, N_MELS = 22050, 1024, 256, 80      # src/main.py:167-170
 
@@ -48,6 +49,12 @@ def run_epoch(args, model, optimizer, train_loader, test_loader, device, epoch, 
 def _evaluate_and_export(args, model, test_loader, device, epoch, export_audio):
     loss_recons, loss_vq = test_vqvae(args, model, test_loader, device, epoch)
     out = {"test_loss_recons": loss_recons, "test_loss_vq": loss_vq}
+    return _export_first_batch(args, model, test_loader, device, epoch, export_audio, out)
+
+
+def _export_first_batch(args, model, test_loader, device, epoch, export_audio, out):
+    """Reconstruct the loader's first batch in eval mode (model(c)[0]: both autoencoders return the image first), save it as
+    a .npy and, with export_audio, invert the last clip to a wav (main.py:150-187); the files' names go into `out`."""
     sample_dir = os.path.join(args.sampledir, format(args.dataset))
     os.makedirs(sample_dir, exist_ok=True)
     stem = '_' + str(args.model) + '_data_' + str(args.dataset) + '_dim_' + str(args.dim) + '_z_dim_' + str(args.z_dim) + '_epoch_' + str(epoch)
@@ -56,7 +63,7 @@ def _evaluate_and_export(args, model, test_loader, device, epoch, export_audio):
         c = c.to(device).unsqueeze(1)
         print("Evaluating samples")
         model.eval()
-        reconstruction, _, _ = model(c)                                   # main.py:150-153
+        reconstruction = model(c)[0]                                      # main.py:150-153
         reconstruction = reconstruction.squeeze(1)
         rec_np = reconstruction.float().cpu().numpy()
         out["reconstruction"] = os.path.join(sample_dir, 'reconstruction' + stem + '.npy')
@@ -69,6 +76,32 @@ def _evaluate_and_export(args, model, test_loader, device, epoch, export_audio):
             signal = nsg_audio.inv_mel_spectrogram(mel, SAMPLING_RATE, FFT_SIZE, HOP_SIZE, N_MELS)[0].cpu().numpy()
             out["wav"] = os.path.join(sample_dir, 'audio_recon' + stem + '_fftsize_' + str(FFT_SIZE) + '_hopsize_' + str(HOP_SIZE) + '.wav')
             nsg_audio.save_wav(signal, out["wav"], SAMPLING_RATE)
+    return out
+
+
+def run_vae_epoch(args, model, step_or_optimizer, train_loader, test_loader, device, epoch, checkpoint_path=None, export_audio=True):
+    """The same epoch for the continuous VAE (args.model == 'vae', the reference's default): train_vae -> test_vae ->
+    reconstruction .npy -> Griffin-Lim wav of the last clip -> checkpoint ({'epoch', 'arch': 'vae', 'state_dict', 'optimizer'},
+    checkpoint_filename's layout).  step_or_optimizer: a VAETrainStep (its fused step runs every batch) or a torch optimiser
+    (train_vae's autograd step)."""
+    if isinstance(step_or_optimizer, VAETrainStep):
+        step, optimizer = step_or_optimizer, step_or_optimizer.opt
+        model.train()
+        total, n = torch.zeros((), device=device), 0
+        for x, y, c, g, input_lengths in train_loader:
+            rec, kl = step.step(c.to(device).unsqueeze(1))
+            total += rec + step.kl_weight * kl
+            n += 1
+        if n == 0:
+            raise ValueError("run_vae_epoch: empty loader")
+        train_loss = float(total / n)
+        print('====> Epoch: {} Average loss: {:.4f}'.format(epoch, train_loss))
+    else:
+        optimizer = step_or_optimizer
+        train_loss = train_vae(args, model, optimizer, train_loader, device, epoch)
+    out = {"train_loss": train_loss, "test_loss": test_vae(args, model, test_loader, device, epoch)}
+    _export_first_batch(args, model, test_loader, device, epoch, export_audio, out)
+    out["checkpoint"] = save_checkpoint(args, checkpoint_state(epoch, 'vae', model, optimizer), filename=checkpoint_path)
     return out
 
 

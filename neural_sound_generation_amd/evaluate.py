@@ -5,6 +5,7 @@ checkpoint layout, restated from the reference's src/test.py:73-106 and src/main
     (ljspeech branch): model.eval(), forward, zero-pad the reconstruction to the input width, accumulate
     mse(target, c) and mse(z_q, z_e) over the batches, divide by the number of batches, print their sum.
     Returns (loss_recons, loss_vq) as floats (the reference returns nothing).
+  * `test_vae(args, model, test_loader, device, epoch)` -- the continuous VAE's test loop (src/test.py:32-49).
   * `eval_losses(model, c)` -- the same two numbers for one batch with no autograd and no host round trip: the
     HIP forward stacks and the fused loss kernels (nsg_mse_padded folds the zero-pad).
   * `export_reconstruction(model, c, path)` -- main.py:150-163: x_tilde.squeeze(1) as a float32 .npy of shape (B, 80, T').
@@ -70,6 +71,27 @@ def test_vqvae(args, model, test_loader, device, epoch):
     loss_recons, loss_vq = float(loss_recons / n), float(loss_vq / n)
     print('====> Test set loss: {:.4f}'.format(loss_recons + loss_vq))
     return loss_recons, loss_vq
+
+
+def test_vae(args, model, test_loader, device, epoch):
+    """Drop-in for src/test.py:32-49 (ljspeech branch) for the continuous VAE: model.eval() (running BatchNorm statistics; the
+    latent is still sampled, as there), forward, vae_train.vae_loss.  Returns the mean over the batches (the reference divides
+    a sum of batch losses by the dataset size and returns nothing)."""
+    from .vae_train import vae_loss
+    model.eval()
+    loss = torch.zeros((), device=device)
+    n = 0
+    with torch.no_grad():
+        for step, (x, y, c, g, input_lengths) in enumerate(test_loader):
+            c = c.to(device).unsqueeze(1)
+            x_tilde, kl_d = model(c)
+            loss += vae_loss(x_tilde, c, kl_d)
+            n += 1
+    if n == 0:
+        raise ValueError("test_vae: empty loader")
+    loss = float(loss / n)
+    print('====> Test set loss: {:.4f}'.format(loss))
+    return loss
 
 
 @torch.no_grad()

@@ -23,7 +23,7 @@ from __future__ import annotations
 import torch
 from torch import nn
 
-from . import engine, functional as Fn, ops
+from . import engine, functional as Fn, ops, vae_engine
 from .vector_quantization import vq, vq_st, codebook_lookup, add_per_clip
 
 
@@ -191,3 +191,103 @@ class VQVAE(nn.Module):
         z_q_x_st, z_q_x = self.codebook.straight_through(z_e_x)
         x_tilde = self.decoder(self._condition(z_q_x_st, g))
         return x_tilde, z_e_x, z_q_x
+
+
+class _VAEEncoder(nn.Sequential):
+    """encoder.0-10 as the parameter container; VAE.forward drives the fused stack (vae_engine.py) itself, because the closing
+    BatchNorm's output is never stored.  Called on its own it returns that output (the reference's encoder(x))."""
+
+    def forward(self, x):
+        P = vae_engine.encoder_params(self)
+        with torch.no_grad():
+            h, mean, invstd, _ = vae_engine.encoder_forward(Fn.to_nhwc(x), P, self.training)
+            return Fn.to_nchw_view(ops.bn_apply(h, mean, invstd, P.bn10.weight, P.bn10.bias))
+
+
+class _VAEDecoder(nn.Sequential):
+    def forward(self, z):
+        return Fn.vae_decoder_apply(z, vae_engine.decoder_params(self), self.training)
+
+
+class VAE(nn.Module):
+    """The reference's continuous VAE(input_dim, dim, z_dim) (models.py:64-118), fp32: same child containers, state_dict keys and
+    shapes, same RNG consumption at construction.  forward(x) -> (x_tilde, kl_div) composes with autograd; the noise of the
+    reparameterised sample may be passed in (eps) so that a run can be reproduced and compared."""
+
+    def __init__(self, input_dim, dim, z_dim):
+        super().__init__()
+        if input_dim != 1:
+            raise NotImplementedError("the HIP path implements the speech configuration (input_dim == 1: "
+                                      "one-channel 80-bin mel images, src/train.py:59)")
+        if dim % 4 or z_dim % 4:
+            raise ValueError("VAE: dim and z_dim must be multiples of 4 (16-byte channel groups)")
+        self.z_dim = z_dim
+        self.encoder = _VAEEncoder(
+            nn.Conv2d(input_dim, dim, 4, 2, 1),
+            nn.BatchNorm2d(dim),
+            nn.ReLU(True),
+            nn.Conv2d(dim, dim, 4, 2, 1),
+            nn.BatchNorm2d(dim),
+            nn.ReLU(True),
+            nn.Conv2d(dim, dim, 5, 1, 0),
+            nn.BatchNorm2d(dim),
+            nn.ReLU(True),
+            nn.Conv2d(dim, z_dim * 2, 3, 1, 0),
+            nn.BatchNorm2d(z_dim * 2)
+        )
+        self.decoder = _VAEDecoder(
+            nn.ConvTranspose2d(z_dim, dim, 3, 1, 0),
+            nn.BatchNorm2d(dim),
+            nn.ReLU(True),
+            nn.ConvTranspose2d(dim, dim, 5, 1, 0),
+            nn.BatchNorm2d(dim),
+            nn.ReLU(True),
+            nn.ConvTranspose2d(dim, dim, 4, 2, 1),
+            nn.BatchNorm2d(dim),
+            nn.ReLU(True),
+            nn.ConvTranspose2d(dim, input_dim, 4, 2, 1),
+            nn.Tanh()
+        )
+        self.apply(weights_init)
+
+    @staticmethod
+    def latent_grid(x_shape):
+        """(14, T // 4 - 6) for a (B, 1, 80, T) batch; ValueError when the clip is too short for one latent column."""
+        if len(x_shape) != 4 or x_shape[1] != 1 or x_shape[2] != 80:
+            raise ValueError(f"VAE: expected a (B, 1, 80, T) mel batch, got {tuple(x_shape)}")
+        w = vae_engine.latent_width(x_shape[3])
+        if w < 1:
+            raise ValueError(f"VAE: T = {x_shape[3]} frames leave no latent column (T >= 28)")
+        return 14, w
+
+    def _noise(self, B, h, w, device, generator):
+        return torch.randn(B, self.z_dim, h, w, device=device, generator=generator)
+
+    def encode(self, x):
+        """-> (mu, logvar), each (B, z_dim, 14, T // 4 - 6); not differentiable."""
+        self.latent_grid(x.shape)
+        return self.encoder(x).chunk(2, dim=1)
+
+    def decode(self, z):
+        return self.decoder(z)
+
+    def forward(self, x, eps=None, generator=None):
+        """eps: the sample's noise (B, z_dim, 14, T // 4 - 6); None draws torch.randn on the device (from generator if given).
+        eval() uses the running statistics and still samples, as the reference's test_vae does."""
+        h, w = self.latent_grid(x.shape)
+        B = x.shape[0]
+        if eps is None:
+            eps = self._noise(B, h, w, x.device, generator)
+        elif tuple(eps.shape) != (B, self.z_dim, h, w):
+            raise ValueError(f"VAE: eps must be {(B, self.z_dim, h, w)}, got {tuple(eps.shape)}")
+        P = vae_engine.encoder_params(self.encoder)
+        h9, mean, invstd = Fn.vae_encoder_apply(x, P, self.training)
+        z, kl_div = Fn.vae_latent_apply(h9, mean, invstd, P.bn10, Fn.to_nhwc(eps.detach()), self.training)
+        return self.decoder(Fn.to_nchw_view(z)), kl_div
+
+    @torch.no_grad()
+    def sample(self, n, frames, generator=None):
+        """n draws from the prior N(0, I) on the latent grid of a `frames`-frame clip, decoded: (n, 1, 80, 4 * (frames // 4))."""
+        h, w = self.latent_grid((n, 1, 80, frames))
+        dev = self.decoder[0].weight.device
+        return self.decoder(self._noise(n, h, w, dev, generator))

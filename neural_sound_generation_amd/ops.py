@@ -124,12 +124,13 @@ def _es(t) -> int:
 
 def _conv_label(d: "ConvDesc", role: str) -> str:
     """Kernel + geometry label for the census: which gather_gemm mode a forward / dgrad of this layer runs (a transposed conv's
-    forward and a stride-2 conv's data gradient are the 4-parity-class form, MODE 1; everything else is the conv gather, MODE 0)."""
+    forward and a stride-2 conv's data gradient are the 4-parity-class form, MODE 1; everything else is the conv gather, MODE 0).
+    (As before for every stride-2 transposed layer: mode1 = transposed; the stride-1 transposed kind runs MODE 0.)"""
     kw = d.k_w if d.k_w > 0 else d.k
     geom = f"{d.k}x{kw}" + (f"/s{d.stride}" if d.stride != 1 else "")
     if role == "wgrad":
         return f"wgrad_gemm {geom}{' transposed' if d.transposed else ''} {d.C_in}->{d.C_out}"
-    mode1 = bool(d.transposed) if role == "forward" else (not d.transposed and d.stride == 2)
+    mode1 = (bool(d.transposed) if role == "forward" else not d.transposed) and d.stride == 2      # (stride-1 transposed: MODE 0 both ways)
     return f"gather_gemm MODE {1 if mode1 else 0} {geom} {role} {d.C_in}->{d.C_out}"
 
 
@@ -769,6 +770,45 @@ def bn_backward_apply(x, dy, mean, invstd, gamma, dgamma, dbeta, relu_beta=None,
     _lib.call("nsg_bn_backward_apply", _p(x), _p(None), _p(dy), _p(mean), _p(invstd), _p(gamma), _p(relu_beta), _p(dgamma), _p(dbeta), _p(dx),
               _p(dx_colsum), M, C, nsg_dtype(x.dtype), _p(ws), nb, _stream())
     return dx
+
+
+# ------------------------------------------------------------------------------------------------
+# the VAE's Gaussian latent: closing BatchNorm2d(2Z) -> chunk -> KL -> mu + sigma * eps   (src/models.py:77,103-112)
+# ------------------------------------------------------------------------------------------------
+def _latent_extents(fn, h, eps, dz=None):
+    _chk(h, "h"); _chk(eps, "eps")
+    C = h.shape[-1]
+    M = h.numel() // C
+    if C % 2 or eps.numel() != M * (C // 2) or (dz is not None and dz.numel() != eps.numel()):
+        raise _lib.NsgError(f"{fn}: h {tuple(h.shape)} holds [M][2Z] rows; eps / dz must hold [M][Z]")
+    return M, C // 2
+
+
+def vae_latent_forward(h, mean, invstd, gamma, beta, eps, z=None, kl=None):
+    """h: the closing BatchNorm's INPUT, rows [M][2Z] (mu | logvar after the affine map, formed on load); eps [M][Z].
+    Returns (z [M][Z] shaped like eps, kl [1]).  include/nsg.h: nsg_vae_latent_forward."""
+    M, Z = _latent_extents("vae_latent_forward", h, eps)
+    z = z if z is not None else torch.empty_like(eps)
+    kl = kl if kl is not None else torch.empty(1, dtype=torch.float32, device=h.device)
+    ws, nb = _ws(h.device, "nsg_vae_latent_workspace_bytes", M, Z)
+    _lib.tag("vae_latent_forward", 0, 4.0 * (h.numel() + 2 * eps.numel()))
+    _lib.call("nsg_vae_latent_forward", _p(h), _p(mean), _p(invstd), _p(gamma), _p(beta), _p(eps), _p(z), _p(kl), M, Z, _p(ws), nb, _stream())
+    return z, kl
+
+
+def vae_latent_backward(h, mean, invstd, gamma, beta, eps, dz, kl_scale=1.0, kl_grad=None, dy=None, dgamma=None, dbeta=None):
+    """(dy [M][2Z] = the gradient at the BatchNorm's output, dgamma, dbeta [2Z] = that BatchNorm's backward sums over dy):
+    bn_backward_apply(h, dy, ..., dgamma, dbeta) finishes dh.  kl_grad: one device float (the gradient arriving at kl) or None."""
+    M, Z = _latent_extents("vae_latent_backward", h, eps, _chk(dz, "dz"))
+    dev = h.device
+    dy = dy if dy is not None else torch.empty_like(h)
+    dgamma = dgamma if dgamma is not None else torch.empty(2 * Z, dtype=torch.float32, device=dev)
+    dbeta = dbeta if dbeta is not None else torch.empty(2 * Z, dtype=torch.float32, device=dev)
+    ws, nb = _ws(dev, "nsg_vae_latent_workspace_bytes", M, Z)
+    _lib.tag("vae_latent_backward", 0, 4.0 * (2 * h.numel() + 2 * eps.numel()))
+    _lib.call("nsg_vae_latent_backward", _p(h), _p(mean), _p(invstd), _p(gamma), _p(beta), _p(eps), _p(dz), float(kl_scale), _p(kl_grad), _p(dy),
+              _p(dgamma), _p(dbeta), M, Z, _p(ws), nb, _stream())
+    return dy, dgamma, dbeta
 
 
 # ------------------------------------------------------------------------------------------------
