@@ -371,7 +371,7 @@ NSG_API int nsg_c1conv_bn_relu_backward(const float *img, const float *w, const 
  * data gradient from the gradient image (16 taps per element, on the matrix cores) inside the BatchNorm-backward
  * passes and the weight gradient from a rebuilt on the spot -- 4 tensor reads + 1 write against 8 reads + 3 writes
  * of nsg_bn_apply + nsg_conv_forward + nsg_conv_wgrad + nsg_conv_dgrad + nsg_bn_backward.
- * Available for bf16 tensors with C = 32, 64, 96, 128 (nsg_bn_relu_c1convt_supported); other shapes use the
+ * Available for bf16 tensors with C = 32, 64, 96, 128, 256 (nsg_bn_relu_c1convt_supported); other shapes use the
  * separate operators.  w: the parameter's own layout (C,1,4,4) = [C][16] fp32; y / dy: [B][2H][2W] fp32.
  * ------------------------------------------------------------------------------------------- */
 NSG_API int32_t nsg_bn_relu_c1convt_supported(int32_t dtype, int32_t C);
@@ -404,7 +404,7 @@ NSG_API int nsg_bn_relu_c1convt_backward(const void *u, int32_t dtype, const flo
  * A 1x1 conv over NHWC rows is a flat GEMM [M][C] x [C][C]: a stream kernel.  These entry points apply the
  * BatchNorm arithmetic of the neighbouring layers on the operand's way from the global-load registers into LDS,
  * so the activated tensor relu(bn(x)) is never stored and the second BatchNorm's input gradient is produced and
- * consumed in one pass.  bf16 tensors, C = 32, 64, 128 (nsg_bn_relu_conv1x1_supported); w: (C, C, 1, 1) fp32.
+ * consumed in one pass.  bf16 tensors, C = 32, 64, 128, 256 (nsg_bn_relu_conv1x1_supported); w: (C, C, 1, 1) fp32.
  * ------------------------------------------------------------------------------------------- */
 NSG_API int32_t nsg_bn_relu_conv1x1_supported(int32_t dtype, int32_t C);
 NSG_API size_t nsg_bn_relu_conv1x1_workspace_bytes(int64_t M, int32_t C);

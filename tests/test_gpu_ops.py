@@ -763,6 +763,7 @@ def test_fused_output_layer_with_reconstruction_loss(B, H, W, C, T):
     """nsg_bn_relu_c1convt_forward_mse = the fused output layer (with Tanh) + nsg_mse_padded + nsg_tanh_backward in one pass over
     the tap products: the same image bit for bit, the loss to the order of its double sums, the gradient at the Tanh's input to
     one rounding; with a target wider than the image (the reference zero-pads x_tilde on the host, train.py:118-127)."""
+    # (tests/test_gpu_fused_output_envelope.py::test_loss_form covers these checks strictly: fp64, T = 2W | 2W + 1 | 2W + 37, poison, canaries)
     g = torch.Generator().manual_seed(B + W + C)
     u = gpu(torch.randn(B, H, W, C, generator=g) * 1.2 + 0.3).bfloat16()
     w = gpu(torch.randn(C, 1, 4, 4, generator=g) * 0.2)
@@ -824,6 +825,7 @@ def test_bn_relu_c1convt_fused_output_layer(B, H, W, C):
     tensors, against CPU PyTorch autograd on the same bf16-rounded input.  The operator rounds relu(bn(u)) and the conv
     weights to bf16 on their way into the MFMA (as the separate bf16 operators do) and stores du as bf16: 1e-2 of the largest
     reference value; the image-sized outputs see the bf16 products averaged over C channels: 4e-3."""
+    # (the comparisons with CPU autograd are covered strictly by tests/test_gpu_fused_output_envelope.py: fp64, derived bounds, no exclusions)
     g = torch.Generator().manual_seed(B * 100 + C + W)
     u = (torch.randn(B, C, H, W, generator=g) * 1.5 + 0.5).bfloat16().float().requires_grad_(True)
     w = (torch.randn(C, 1, 4, 4, generator=g) * 0.2).requires_grad_(True)
@@ -877,6 +879,7 @@ def test_resblock_1x1_conv_with_batchnorm_in_the_operand_staging(B, H, W, C):
     """nsg_bn_relu_conv1x1_* / nsg_bn_backward_conv1x1_dgrad / nsg_bn_backward_sums (bf16): against the separate operators of
     this library on the same tensors (which store the intermediate tensors as bf16 too: differences are single bf16
     roundings of O(1) values accumulated over C products -> 4e-3 of the largest value) and against CPU PyTorch."""
+    # (the bit-for-bit contracts and the fp32 comparison are covered strictly, at every boundary M, by tests/test_gpu_fused_1x1_envelope.py)
     g = torch.Generator().manual_seed(C + W)
     M = B * H * W
     x = gpu(torch.randn(B, H, W, C, generator=g) * 1.3 + 0.4).bfloat16()
