@@ -108,7 +108,9 @@ NSG_API int nsg_vq_forward(const float *x, const float *e, int64_t N, int32_t D,
 /* The same search for the bf16 compute mode: the contraction runs on the bf16 matrix pipe with both fp32 operands
  * split into bf16 hi + lo parts (3 MFMAs per 16 channels, fp32 accumulate): distances carry a relative error of
  * ~2^-16, so on near-ties the chosen code may differ from the reference's (NOT the bit-exact search; the fp32
- * parity mode uses nsg_vq_forward).  D % 8 == 0.  Workspace: nsg_vq_bf16x3_workspace_bytes.
+ * parity mode uses nsg_vq_forward).  D % 8 == 0, D <= 256.  Workspace: nsg_vq_bf16x3_workspace_bytes.
+ * idx_out is the FIRST minimum of the COMPUTED distances: codes whose computed distances are equal -- exact duplicates of a
+ * code row always are -- resolve to the lowest index; dmin_out (or NULL) is that computed distance.
  * codes_bf16_out (or NULL): the chosen code rows as bf16 [N][D], with max(0, .) applied when bf16_relu != 0 -- the
  * decoder's input after its leading ReLU (models.py:176) in the bf16 mode, written here instead of by a separate
  * conversion pass over an fp32 copy (codes_out may then be NULL: nsg_vq_losses_indexed reads the codebook itself). */
@@ -150,7 +152,10 @@ NSG_API size_t nsg_index_add_workspace_bytes(int64_t N, int32_t D, int32_t K);
  * Replaces grad_codebook.index_add_(0, indices, grad_output) (vector_quantization.py:60-61) and the
  * autograd of torch.index_select(self.embedding.weight, 0, indices) (src/models.py:137-138); also
  * yields the per-code sums of the EMA codebook extension.  Deterministic (fixed summation order).
- * counts_out [K] fp32 (rows per code) or NULL. */
+ * counts_out [K] fp32 (rows per code) or NULL.
+ * Out-of-range indices, in ALL index-add forms (this one, _bf16x2, _sorted, _sorted_bnres): a row whose index lies outside
+ * [0, K) contributes nothing to the sums and nothing to the counts.  The index is compared as the 64-bit value it is (2^32 + 3
+ * is out of range, not code 3); no address is ever formed from such an index.  A batch with no index in range gives zeros. */
 NSG_API int nsg_index_add_rows(const int64_t *idx, const float *g, int64_t N, int32_t D, int32_t K, float *out,
                                float *counts_out, void *workspace, size_t workspace_bytes, void *stream);
 
@@ -162,8 +167,9 @@ NSG_API int nsg_index_add_rows_bf16x2(const int64_t *idx, const float *g, int64_
 
 /* The same sums as a sorted segment sum: a stable counting sort of the row INDICES by code, then every code's rows added in
  * row order (fp32, bitwise reproducible).  Moves N*D*4 bytes instead of doing 2*N*K*D flops: the form for large codebooks
- * (K = 8192) and the default of the training step.  Rows whose index lies outside [0, K) contribute nothing.
- * Needs D % 4 == 0 with D / 4 a power of two up to 64 (or D a multiple of 256), K <= 8192, N < 2^31. */
+ * (K = 8192) and the default of the training step.  Rows whose index lies outside [0, K) contribute nothing (see above).
+ * Shapes: D in {4, 8, 16, 32, 64, 128, 256} (D / 4 a power of two up to 64) or D a multiple of 256; K <= 8192; N < 2^31.
+ * Every other width (D = 260, say) is refused with NSG_E_UNSUPPORTED; ops.index_add_sorted_supported states the same rule. */
 NSG_API size_t nsg_index_add_sorted_workspace_bytes(int64_t N, int32_t D, int32_t K);
 NSG_API int nsg_index_add_rows_sorted(const int64_t *idx, const float *g, int64_t N, int32_t D, int32_t K, float *out,
                                       float *counts_out, void *workspace, size_t workspace_bytes, void *stream);

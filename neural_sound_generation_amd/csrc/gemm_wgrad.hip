@@ -88,7 +88,8 @@ __global__ __launch_bounds__(256) void wgrad_gemm_f32(const WgradParams p)
             const int m = mb + pix;
             const int ok = (pix < KP) & (m < mend) & ((a0 + a4) < p.A);
             if (ONEHOT) {
-                ridx[S][j] = (int)p.idx[ok ? m : mbeg];
+                const int64_t code = p.idx[ok ? m : mbeg];
+                ridx[S][j] = (code >= 0 && code < p.A) ? (int)code : -1;     // compared in 64 bits: an index outside [0, K) matches no code
             } else {
                 const size_t off = ok ? ((size_t)m * p.A + a0 + a4) : 0;
                 rp[S][j] = *reinterpret_cast<const v4f *>(gP + off);
@@ -548,7 +549,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void o
         for (int j = 0; j < PJ; ++j) {
             const int m = mb + ppix + PSTEP * j;
             const int64_t code = gidx[m < mend ? m : mbeg];      // clamped, unconditional
-            ri[j] = m < mend ? (int)code : -0x40000000;          // a pixel past the slab matches no code
+            ri[j] = (m < mend && code >= 0 && code < p.A) ? (int)code : -0x40000000;   // a pixel past the slab, or an index outside [0, K) (compared in 64 bits), matches no code
         }
 #pragma unroll
         for (int j = 0; j < QJ; ++j) {

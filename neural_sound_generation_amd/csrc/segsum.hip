@@ -335,7 +335,7 @@ int nsg_index_add_rows_sorted(const int64_t *idx, const float *g, int64_t N, int
 {
     NSG_REQUIRE(idx && g && out && N > 0 && D > 0 && K > 0, NSG_E_INVALID, "nsg_index_add_rows_sorted: bad argument");
     NSG_REQUIRE(D % 4 == 0 && nsg_aligned16(g) && nsg_aligned16(out), NSG_E_UNSUPPORTED, "nsg_index_add_rows_sorted: D %% 4 == 0 and 16-byte aligned tensors");
-    NSG_REQUIRE(N < 0x7fffffffll && K <= 8192 && 64 % (D / 4 > 64 ? 64 : D / 4) == 0, NSG_E_UNSUPPORTED,
+    NSG_REQUIRE(N < 0x7fffffffll && K <= 8192 && (D > 256 ? D % 256 == 0 : 64 % (D / 4) == 0), NSG_E_UNSUPPORTED,
                 "nsg_index_add_rows_sorted: N < 2^31, K <= 8192, D a power of two up to 256 (or a multiple of 256)");
     return seg_sums<false>(idx, g, N, D, K, out, counts_out, workspace, workspace_bytes, stream);
 }

@@ -253,6 +253,7 @@ def index_add_rows(idx, g2d, K, want_counts=False, impl="f32", out=None, counts=
     """out[k] = sum of rows of g2d whose idx == k; deterministic.  impl: "sorted" (a sorted segment sum in fp32: N*D*4 bytes
     moved; the training step's default), "f32" (one-hot GEMM on the fp32 matrix pipe, exact products) or "bf16x2" (one-hot GEMM
     on the bf16 pipe: rows split into bf16 hi + lo, relative error of a sum ~2^-17).
+    A row whose index lies outside [0, K) (compared as the 64-bit value it is) adds to no sum and to no count, in every form.
     out (K, D) / counts (K,): optional preallocated fp32 destinations (e.g. views of a communication buffer)."""
     _chk(idx, "idx", torch.int64)
     bnres = isinstance(g2d, BnResRows)
