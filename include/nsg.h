@@ -822,6 +822,26 @@ NSG_API int nsg_audio_trim_bounds(const float *wav, const int32_t *lengths, int3
                                   int32_t frame_length, int32_t hop, float top_db, void *workspace, size_t workspace_bytes,
                                   void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The loader's batch from a corpus resident in device memory   src/dataloader.py:324-434 (collate_fn, the mel case): crop,
+ * zero-pad to the batch's longest item, transpose to mel-major -- one launch, no host work per batch.
+ * ------------------------------------------------------------------------------------------- */
+
+/* corpus [corpus_frames][n_mels] fp32, frame-major: the clips' (frames, n_mels) arrays as they are on disk, concatenated.
+ * plan [B][3] int64, device: per item (clip, start, count) -- start = its first corpus frame, count = frames to copy; clip is
+ * not read here (the loader gathers speaker ids with it).  out [B][n_mels][T] fp32, the memory of the model's (B, 1, n_mels, T):
+ *     out[b][m][t] = corpus[start_b + t][m]   for t < count_b,        +0.0f   for count_b <= t < T
+ * A copy, bit for bit; every element of out is written exactly once (out need not be initialised).  One workgroup per tile of
+ * 32 frames of one item; B is not bound by a grid dimension; every element offset is 64-bit (corpus and out may pass 2^31
+ * elements).  16-byte accesses are used only where they are aligned (loads: n_mels % 4 == 0 and corpus 16-byte aligned;
+ * stores: T % 4 == 0 and out 16-byte aligned); any n_mels, T and alignment of 4 is served.
+ * NSG_E_INVALID: a null pointer, B < 1, T < 1, n_mels outside [1, 128], corpus_frames < 0.
+ * PRECONDITION the entry point cannot check (plan is device memory): 0 <= count_b <= T, start_b >= 0 and
+ * start_b + count_b <= corpus_frames for every b; the caller checks it on the host copy it built the plan from.  (The kernel
+ * clamps count_b into [0, T] and reads a frame outside [0, corpus_frames) as zero, so no access leaves either buffer.) */
+NSG_API int nsg_collate_mels(const float *corpus, int64_t corpus_frames, int32_t n_mels, const int64_t *plan, int32_t B, int32_t T,
+                             float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

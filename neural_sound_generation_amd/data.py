@@ -16,7 +16,10 @@ Pieces (names and behaviour follow src/dataloader.py:97-202,324-434):
   * `collate_fn` -- random crop to `max_time_steps` aligned to the hop size, zero-pad to the longest item:
     returns the reference's 5-tuple (x, y, c, g, input_lengths) with c (B, 80, T) channel-first;
   * `get_data_loaders` -- {"train", "test"} loaders;  `DevicePrefetcher` -- pinned-memory, side-stream H2D copies so
-    the next batch's mel is resident when the step starts (the timed path of bench.py assumes resident inputs).
+    the next batch's mel is resident when the step starts (the timed path of bench.py assumes resident inputs);
+  * `ResidentMelCorpus` / `plan_batch` / `ResidentMelLoader` / `get_resident_loaders` -- the same loaders with the whole mel
+    corpus in device memory: an epoch's crops are planned here (the sampler and `Collate`'s rule, so equal seeds give the host
+    loader's batches bit for bit), uploaded once, and a batch is one launch of csrc/collate.hip (ops.collate_mels).
 
 parity unpinned: the reference's loader cannot be imported here (ordinary missing dependencies); tests/test_host_logic.py
 checks the format invariants on a synthetic data root.
@@ -266,6 +269,175 @@ class DevicePrefetcher:
     @property
     def dataset(self):
         return self.loader.dataset
+
+
+# ------------------------------------------------------------------------------------------------
+# The corpus resident in device memory: batches built by one kernel, no host work or copy per step
+# ------------------------------------------------------------------------------------------------
+
+class ResidentMelCorpus:
+    """Every mel of a `MelSpecDataSource`, read once and kept in ONE tensor on `device`: `frames` (sum of frames, 80) fp32,
+    frame-major -- the clips' on-disk arrays concatenated (LJSpeech: ~2.4 GB).  On the host: `offsets` (n + 1,) int64, clip i is
+    frames[offsets[i]:offsets[i + 1]]; `n_frames` (n,) int64; `lengths`, the source's `timesteps` column (what the sampler sorts
+    by).  `speaker_ids` (n,) int64 on `device` for a multi-speaker root, else None.  The arrays are read into host memory
+    first (the corpus' size of it, freed afterwards) and staged through a pinned chunk.  device "cpu" keeps `frames` on the
+    host: enough for planning and for tests, not for `ResidentMelLoader`'s batches (ops.collate_mels has no CPU path)."""
+
+    CHUNK_FRAMES = 1 << 16          # the pinned staging buffer: 65 536 frames = 21 MB
+
+    def __init__(self, mel_source: MelSpecDataSource, device="cuda:0"):
+        self.device = torch.device(device)
+        self.multi_speaker = mel_source.multi_speaker
+        self.lengths = list(mel_source.lengths)
+        arrays = []
+        for path in mel_source.paths:
+            c = mel_source.collect_features(path)
+            if c.ndim != 2 or c.shape[1] != NUM_MELS:
+                raise ValueError(f"{path}: expected a (frames, {NUM_MELS}) array, got {c.shape}")
+            arrays.append(c.astype(np.float32, copy=False))
+        self.n_frames = np.array([len(c) for c in arrays], dtype=np.int64)
+        self.offsets = np.concatenate([np.zeros(1, np.int64), np.cumsum(self.n_frames, dtype=np.int64)])
+        total = int(self.offsets[-1])
+        self.frames = torch.empty(total, NUM_MELS, dtype=torch.float32, device=self.device)
+        self._upload(arrays)
+        self.speaker_ids = (torch.tensor(mel_source.speaker_ids, dtype=torch.int64, device=self.device)
+                            if self.multi_speaker else None)
+
+    def _upload(self, arrays):
+        cuda = self.device.type == "cuda"
+        stage = torch.empty(self.CHUNK_FRAMES, NUM_MELS, dtype=torch.float32, pin_memory=cuda)
+        stage_np = stage.numpy()
+        done = fill = 0                                      # frames already on the device / waiting in the chunk
+
+        def flush():
+            nonlocal done, fill
+            self.frames[done:done + fill].copy_(stage[:fill])    # blocking: the chunk is free again when it returns
+            done, fill = done + fill, 0
+
+        for c in arrays:
+            at = 0
+            while at < len(c):
+                n = min(len(c) - at, self.CHUNK_FRAMES - fill)
+                stage_np[fill:fill + n] = c[at:at + n]
+                at, fill = at + n, fill + n
+                if fill == self.CHUNK_FRAMES:
+                    flush()
+        if fill:
+            flush()
+
+    def __len__(self):
+        return len(self.n_frames)
+
+
+def plan_batch(n_frames_of_items, max_time_steps: Optional[int], hop_size: int, frame_multiple: int, rng):
+    """`Collate.__call__`'s crop rule for items of these frame counts, in its order and with its draws from `rng`: per item
+    (s, count) -- the item is frames [s, s + count) of its clip.  Host only."""
+    s_out, count_out = [], []
+    for frames in n_frames_of_items:
+        s, count = 0, int(frames)
+        if max_time_steps is not None:
+            max_frames = ensure_divisible(max_time_steps, hop_size, True) // hop_size
+            if count > max_frames:
+                s = int(rng.randint(0, count - max_frames))      # drawn only for a clip that is cropped, in item order
+                count = max_frames
+        if frame_multiple > 1 and count >= frame_multiple:
+            count -= count % frame_multiple
+        s_out.append(s)
+        count_out.append(count)
+    return np.array(s_out, dtype=np.int64), np.array(count_out, dtype=np.int64)
+
+
+class EpochPlan:
+    """One epoch of a `ResidentMelLoader` as the host knows it: `plan` (n_batches, B_max, 3) int64 rows of (clip, first corpus
+    frame, frames) -- rows past a short batch's size are zeros and are never launched --, `sizes` (n_batches,) items per batch,
+    `widths` (n_batches,) = the batch's longest item = its T."""
+
+    def __init__(self, plan, sizes, widths):
+        self.plan, self.sizes, self.widths = plan, sizes, widths
+
+    def __len__(self):
+        return len(self.sizes)
+
+
+class ResidentMelLoader:
+    """The loader of `get_data_loaders` + `DevicePrefetcher` over a `ResidentMelCorpus`: yields (None, None, c, g,
+    input_lengths) with c (B, 80, T) fp32 on the device (a fresh tensor per batch), g (B,) int64 on the device or None,
+    input_lengths (B,) int64 on the CPU = frames * hop.  With equal seeds (Python's `random` for the order, `rng` for the crops)
+    the batches are the host loader's, bit for bit: the epoch's order comes from the same sampler class (train) or is sequential
+    with a smaller last batch (test), the crops from `plan_batch`.
+
+    `__iter__` plans the whole epoch on the host, checks the plan and uploads it once; a step is then one ops.collate_mels
+    launch on the current stream with T = the batch's longest item, and one gather of speaker ids: nothing is copied from the
+    host and nothing is synchronised per step.
+
+    shard=(rank, world): this rank takes the batches k with k % world == rank among the first (n_batches // world) * world
+    batches of the epoch; the remaining n_batches % world batches are DROPPED, so that every rank runs the same number of steps
+    (the gradient all-reduce would hang otherwise).  Every rank must seed Python's `random` and `rng` alike: all of them draw
+    the same order and the same plan, then keep their share.  len() is then the rank's number of batches."""
+
+    def __init__(self, corpus: ResidentMelCorpus, batch_size: int, max_time_steps: Optional[int] = None, frame_multiple: int = 1,
+                 train: bool = True, rng=None, shard=None, hop_size: int = HOP_SIZE):
+        if batch_size < 1:
+            raise ValueError("ResidentMelLoader: batch_size < 1")
+        if shard is not None and not (len(shard) == 2 and shard[1] >= 1 and 0 <= shard[0] < shard[1]):
+            raise ValueError(f"ResidentMelLoader: shard = {shard} is not (rank, world) with 0 <= rank < world")
+        self.dataset = corpus
+        self.batch_size, self.max_time_steps, self.frame_multiple, self.hop = batch_size, max_time_steps, frame_multiple, hop_size
+        self.train, self.shard = train, shard
+        self.rng = rng if rng is not None else np.random
+        self.sampler = PartialyRandomizedSimilarTimeLengthSampler(corpus.lengths, batch_size=batch_size) if train else None
+
+    def __len__(self):
+        n = -(-len(self.dataset) // self.batch_size)
+        return n if self.shard is None else n // self.shard[1]
+
+    def plan_epoch(self) -> EpochPlan:
+        """Draw the epoch's order and crops (host only; consumes `random` and `rng` exactly as iterating the host loader does)."""
+        corpus, bs = self.dataset, self.batch_size
+        order = list(iter(self.sampler)) if self.train else list(range(len(corpus)))
+        batches = [order[i:i + bs] for i in range(0, len(order), bs)]
+        plan = np.zeros((len(batches), bs, 3), dtype=np.int64)
+        sizes = np.array([len(b) for b in batches], dtype=np.int64)
+        widths = np.zeros(len(batches), dtype=np.int64)
+        for k, clips in enumerate(batches):
+            clips = np.array(clips, dtype=np.int64)
+            s, count = plan_batch(corpus.n_frames[clips], self.max_time_steps, self.hop, self.frame_multiple, self.rng)
+            plan[k, :len(clips), 0], plan[k, :len(clips), 1], plan[k, :len(clips), 2] = clips, corpus.offsets[clips] + s, count
+            widths[k] = count.max()
+        if self.shard is not None:
+            rank, world = self.shard
+            keep = np.arange(rank, len(batches) // world * world, world)
+            plan, sizes, widths = plan[keep], sizes[keep], widths[keep]
+        return EpochPlan(plan, sizes, widths)
+
+    def __iter__(self):
+        from . import ops
+        corpus = self.dataset
+        ep = self.plan_epoch()
+        if len(ep) == 0:
+            return
+        ops.check_collate_plan(ep.plan, ep.widths[:, None], len(corpus.frames))
+        plan_dev = torch.from_numpy(ep.plan).to(corpus.device)          # the epoch's one upload
+        for k in range(len(ep)):
+            B, rows = int(ep.sizes[k]), plan_dev[k, :int(ep.sizes[k])]
+            c = ops.collate_mels(corpus.frames, rows, int(ep.widths[k]))
+            g = corpus.speaker_ids[rows[:, 0]] if corpus.speaker_ids is not None else None
+            yield None, None, c, g, torch.from_numpy(ep.plan[k, :B, 2] * self.hop)
+
+
+def get_resident_loaders(data_root: str, batch_size: int, max_time_steps: Optional[int] = None, speaker_id=None, test_size=0.05,
+                         test_num_samples=None, random_state: int = 1234, frame_multiple: int = 1, device="cuda:0", rng=None,
+                         shard=None):
+    """`get_data_loaders` with the corpus resident on `device`: {"train": ResidentMelLoader, "test": ResidentMelLoader} over the
+    same train / test split (mels only: raw audio stays on the host path).  `shard` applies to the train loader only."""
+    loaders = {}
+    for phase in ("train", "test"):
+        train = phase == "train"
+        mel = MelSpecDataSource(data_root, speaker_id=speaker_id, train=train, test_size=test_size, test_num_samples=test_num_samples,
+                                random_state=random_state)
+        loaders[phase] = ResidentMelLoader(ResidentMelCorpus(mel, device), batch_size, max_time_steps, frame_multiple, train=train,
+                                           rng=rng, shard=shard if train else None)
+    return loaders
 
 
 def write_synthetic_data_root(data_root: str, n_utts: int = 12, min_frames: int = 40, max_frames: int = 200, n_speakers: int = 0,

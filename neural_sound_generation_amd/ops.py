@@ -393,6 +393,58 @@ def gather_rows(codebook, idx, out=None):
     return out
 
 
+COLLATE_MAX_MELS = 128
+
+
+def check_collate_plan(plan, T, corpus_frames):
+    """The precondition of nsg_collate_mels, checked where the plan is built: `plan` (..., 3) int64 ON THE HOST (a numpy array or
+    a CPU tensor), rows (clip, start, count); `T` the width of the batch, or an array that broadcasts against plan[..., 0] (one
+    width per batch of an epoch's plan).  Raises NsgError for start < 0, count outside [0, T] or start + count > corpus_frames."""
+    import numpy as np
+    p = plan.numpy() if isinstance(plan, torch.Tensor) else np.asarray(plan)
+    if p.dtype != np.int64 or p.ndim < 1 or p.shape[-1] != 3:
+        raise _lib.NsgError(f"collate plan: expected int64 rows of (clip, start, count), got {p.dtype} {p.shape}")
+    start, count = p[..., 1], p[..., 2]
+    if (start < 0).any():
+        raise _lib.NsgError(f"collate plan: start < 0 (least {int(start.min())})")
+    if (count < 0).any() or (count > np.asarray(T)).any():
+        raise _lib.NsgError(f"collate plan: count outside [0, T] (counts {int(count.min())} .. {int(count.max())}, T = {T})")
+    if (start + count > corpus_frames).any():
+        raise _lib.NsgError(f"collate plan: start + count = {int((start + count).max())} is past the corpus' {corpus_frames} frames")
+
+
+def collate_mels(corpus, plan, T, out=None):
+    """corpus (frames, n_mels) fp32 frame-major, plan (B, 3) int64 rows of (clip, start, count), T -> (B, n_mels, T) mel-major:
+    out[b, :, t] = corpus[start_b + t] for t < count_b, +0.0 up to T (data.Collate's crop, padding and transpose; one launch).
+    A plan on the device is the caller's to have checked (check_collate_plan on its host copy: ResidentMelLoader checks an epoch's
+    plan once, before the upload); a plan on the host is checked here and uploaded."""
+    for t, name, dtype in ((corpus, "corpus", torch.float32), (plan, "plan", torch.int64)):
+        if t.dtype != dtype:
+            raise _lib.NsgError(f"collate_mels: {name}: expected {dtype}, got {t.dtype}")
+        if not t.is_contiguous():
+            raise _lib.NsgError(f"collate_mels: {name}: expected a contiguous tensor")
+    if corpus.dim() != 2 or not 1 <= corpus.shape[1] <= COLLATE_MAX_MELS:
+        raise _lib.NsgError(f"collate_mels: corpus {tuple(corpus.shape)} is not (frames, n_mels) with n_mels in [1, {COLLATE_MAX_MELS}]")
+    if plan.dim() != 2 or plan.shape[1] != 3 or plan.shape[0] < 1:
+        raise _lib.NsgError(f"collate_mels: plan {tuple(plan.shape)} is not (B, 3) with B >= 1")
+    T = int(T)
+    if T < 1:
+        raise _lib.NsgError(f"collate_mels: T = {T} < 1")
+    frames, n_mels = corpus.shape
+    B = plan.shape[0]
+    if not plan.is_cuda:
+        check_collate_plan(plan, T, frames)
+    _chk(corpus, "collate_mels: corpus")
+    if not plan.is_cuda:
+        plan = plan.to(corpus.device)
+    if out is None:
+        out = torch.empty(B, n_mels, T, dtype=torch.float32, device=corpus.device)
+    elif _chk(out, "collate_mels: out").numel() != B * n_mels * T:
+        raise _lib.NsgError(f"collate_mels: out {tuple(out.shape)} does not hold {B} x {n_mels} x {T}")
+    _lib.call("nsg_collate_mels", _p(corpus), frames, n_mels, _p(plan), B, T, _p(out), _stream())
+    return out
+
+
 def vq_ema_update(codebook, ema_n, ema_s, n, s, decay=0.99, eps=1e-5):
     K, D = codebook.shape
     scratch = torch.empty(1, dtype=torch.float32, device=codebook.device)
