@@ -270,7 +270,10 @@ NSG_API int nsg_conv_forward(const nsg_conv_desc *d, const void *x, const void *
  * nn.Conv2d / nn.ConvTranspose2d followed by nn.BatchNorm2d (src/models.py:165-166, 150-151,
  * 153-154, 179-180).  The conv epilogue reduces each 128-row output tile to (count, mean, M2) while
  * the tile is still in LDS; the tiles are merged exactly as nsg_bn_stats merges its slabs.
- * mean/invstd/running_* as in nsg_bn_stats.  NSG_TANH_OUT is not allowed here. */
+ * mean/invstd/running_* as in nsg_bn_stats.  NSG_TANH_OUT is not allowed here.
+ * CONTRACT: nsg_conv_workspace_bytes(d) holds the statistics records of whichever kernel runs the layer (one per 128-row tile, or
+ * one per workgroup of the patch-staged bf16 kernel: up to 512, whatever the image's shape); a smaller workspace is refused with
+ * NSG_E_WORKSPACE BEFORE anything is launched. */
 NSG_API int nsg_conv_forward_bnstats(const nsg_conv_desc *d, const void *x, const void *w_fwd, const float *bias,
                                      void *y, int32_t flags, float eps, float momentum, float *mean, float *invstd,
                                      float *running_mean, float *running_var, void *workspace, size_t workspace_bytes,

@@ -383,7 +383,12 @@ inline size_t patches_bytes(const nsg_conv_desc *d) { return nsg_align_up((size_
 inline size_t stats_tiles_bytes(const nsg_conv_desc *d)
 {
     const int64_t out_pix = (int64_t)d->B * d->OH * d->OW;
-    const int64_t tiles = (d->transposed && d->stride == 2) ? 4 * nsg_cdiv(out_pix / 4 + d->B * (d->OH + d->OW), 128) + 8 : nsg_cdiv(out_pix, 128);
+    int64_t tiles = (d->transposed && d->stride == 2) ? 4 * nsg_cdiv(out_pix / 4 + d->B * (d->OH + d->OW), 128) + 8 : nsg_cdiv(out_pix, 128);
+    // gemm_patch.hip writes one record per WORKGROUP instead: min(its tiles of 4 x 32 output pixels, 512) (patch_grid), which is more
+    // than the 128-row tiles of a narrow image (1 x 79 x 3 pixels: 20 records against 2)
+    const int64_t rh = d->transposed ? d->IH : d->OH, rw = d->transposed ? d->IW : d->OW;
+    const int64_t patch = (int64_t)d->B * nsg_cdiv(rh, 4) * nsg_cdiv(rw, 32);
+    if ((patch < 512 ? patch : 512) > tiles) tiles = patch < 512 ? patch : 512;
     return nsg_align_up(nsg_bn_tiles_bytes(tiles + 8, d->C_out), 256);
 }
 
@@ -542,7 +547,7 @@ size_t nsg_conv_workspace_bytes(const nsg_conv_desc *d)
 }
 
 static int conv_forward_impl(const nsg_conv_desc *d, const void *x, const void *w_fwd, const float *bias, void *y, int32_t flags,
-                             void *workspace, size_t workspace_bytes, void *stream, float *stats, int *stats_tiles)
+                             void *workspace, size_t workspace_bytes, void *stream, float *stats, int *stats_tiles, size_t stats_bytes = 0)
 {
     const int kind = classify(d, "nsg_conv_forward");
     if (kind < 0) return kind;
@@ -563,7 +568,10 @@ static int conv_forward_impl(const nsg_conv_desc *d, const void *x, const void *
         p.M = d->B * p.RH * p.RW;
         p.stats = stats;
         p.stamps = g_debug_stamps;
-        if (stats_tiles) *stats_tiles = nsg_gather_gemm_row_tiles(p);
+        if (stats_tiles) {      // checked BEFORE the launch: the kernel writes every record it has
+            *stats_tiles = nsg_gather_gemm_row_tiles(p);
+            NSG_REQUIRE(nsg_bn_tiles_bytes(*stats_tiles, d->C_out) <= stats_bytes, NSG_E_WORKSPACE, "nsg_conv_forward_bnstats: tile buffer too small");
+        }
         return nsg_launch_gather_gemm(p, s);
     }
     const ConvLayout L = conv_layout(workspace, d, "nsg_conv_forward");       // (a single-channel layer)
@@ -610,9 +618,8 @@ int nsg_conv_forward_bnstats(const nsg_conv_desc *d, const void *x, const void *
                             workspace, workspace_bytes, stream);
     }
     int ntiles = 0;
-    int rc = conv_forward_impl(d, x, w_fwd, bias, y, flags, workspace, workspace_bytes, stream, L.tiles, &ntiles);
+    int rc = conv_forward_impl(d, x, w_fwd, bias, y, flags, workspace, workspace_bytes, stream, L.tiles, &ntiles, L.tiles_bytes);
     if (rc) return rc;
-    NSG_REQUIRE(nsg_bn_tiles_bytes(ntiles, d->C_out) <= L.tiles_bytes, NSG_E_WORKSPACE, "nsg_conv_forward_bnstats: tile buffer too small");
     const int64_t M = (int64_t)d->B * d->OH * d->OW;
     return nsg_bn_stats_from_tiles(L.tiles, ntiles, M, d->C_out, eps, momentum, mean, invstd, running_mean, running_var,
                                    (hipStream_t)stream);
