@@ -845,6 +845,48 @@ NSG_API int nsg_audio_trim_bounds(const float *wav, const int32_t *lengths, int3
 NSG_API int nsg_collate_mels(const float *corpus, int64_t corpus_frames, int32_t n_mels, const int64_t *plan, int32_t B, int32_t T,
                              float *out, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Judging a converted utterance: mel cepstra and dynamic time warping (extension; the reference has no objective figure
+ * for the speaker-conditioned decoder).  evaluate.test_conversion reports the mel-cepstral distortion of parallel pairs.
+ * ------------------------------------------------------------------------------------------- */
+
+/* mel [B][n_mels][T] fp32, mel-major (the model's (B, 1, n_mels, T); what nsg_audio_melspectrogram writes with frame_major 0)
+ * -> c [B][T][K] fp32, frame-major:
+ *     c[b][t][k] = sum_j mel[b][j][t] * table[k][j]        for t < frames[b]   (frames NULL: every t < T)
+ * one fp32 chain per output: the accumulator starts at +0.0 and takes j = 0, 1, ... in order, each product rounded to fp32 and
+ * each sum rounded to fp32, never contracted.  Frames t >= frames[b] are written as +0.0 and their mels are not read.
+ * table [K][n_mels] fp32 is the caller's (audio.cepstra_table: rows 1 .. K of the orthonormal DCT-II, scaled to the natural-log
+ * amplitude).  Every element of c is written exactly once.  One workgroup per 64 frames of one clip: the loads run along t.
+ * NSG_E_INVALID: a null mel / table / c, B < 1, T < 1, B * ceil(T / 64) >= 2^31;  NSG_E_UNSUPPORTED: K outside [1, 64], n_mels outside
+ * [1, 128].  frames[b] is device memory: the kernel clamps it into [0, T]. */
+NSG_API int nsg_mel_cepstra(const float *mel, const int32_t *frames, const float *table, float *c, int32_t B, int32_t n_mels,
+                            int32_t T, int32_t K, void *stream);
+
+/* Batched dynamic time warping of feature sequences under the Euclidean frame distance.
+ *   a [B][Ta][K], b [B][Tb][K] fp32; len_a, len_b [B] int32: pair p compares a[p][0 : len_a[p]] with b[p][0 : len_b[p]];
+ *   d(i, j) = sqrtf( sum_k (a[i][k] - b[j][k])^2 ): the accumulator starts at +0.0, k ascending; the subtraction, the product and
+ *             the sum are each rounded to fp32 and never contracted; the square root is correctly rounded;
+ *   D(0, 0) = d(0, 0),  D(i, j) = fl( min(D(i-1, j-1), D(i-1, j), D(i, j-1)) + d(i, j) ), predecessors outside the grid absent;
+ *             among equal predecessors the first of (i-1, j-1), (i-1, j), (i, j-1) is taken;
+ *   n(0, 0) = 1,  n(i, j) = n(the predecessor taken) + 1: the length of the path, carried along with D;
+ *   cost[p] = D(len_a - 1, len_b - 1),  steps[p] = n(len_a - 1, len_b - 1)      (cost [B] fp32, steps [B] int32);
+ *   path (or NULL) [B][Ta + Tb - 1][2] int32: the cells (i, j) of the path from (0, 0) to the end cell, steps[p] of them; rows
+ *             past that are not written.
+ * Elements of a and b past a pair's lengths are never read.  One wave per pair: lane l owns NSG_DTW_BLOCK_COLS / 64 adjacent
+ * columns of b and walks the rows of a one row behind lane l - 1; a sequence b longer than NSG_DTW_BLOCK_COLS runs as
+ * successive blocks of that many columns, a block's last column handed to the next in LDS.  Without path nothing of size
+ * Ta x Tb is stored; with it the workspace holds the predecessor taken at each cell, which the same launch walks back.
+ * NSG_E_INVALID: a null required pointer, B < 1;  NSG_E_UNSUPPORTED: K outside [1, 64], Ta or Tb outside [1, NSG_DTW_MAX_FRAMES];
+ * NSG_E_WORKSPACE: path given with less than nsg_dtw_workspace_bytes(B, Ta, Tb, 1) bytes (path == NULL needs none).
+ * PRECONDITION the entry point cannot check (the lengths are device memory): 1 <= len_a[p] <= Ta, 1 <= len_b[p] <= Tb; the
+ * caller checks it on the host copy it built them from.  (The kernel clamps them into that range, so no access leaves a buffer.) */
+#define NSG_DTW_MAX_FRAMES 2048
+#define NSG_DTW_BLOCK_COLS 256
+NSG_API size_t nsg_dtw_workspace_bytes(int32_t B, int32_t Ta, int32_t Tb, int32_t want_path);
+NSG_API int nsg_dtw(const float *a, const float *b, const int32_t *len_a, const int32_t *len_b, float *cost, int32_t *steps,
+                    int32_t *path, int32_t B, int32_t Ta, int32_t Tb, int32_t K, void *workspace, size_t workspace_bytes,
+                    void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -96,6 +96,7 @@ HEADER_SYMBOLS = list(_SIGS)
 NSG_VERSION = _CONSTS["NSG_VERSION"]      # bumped in the header on ANY signature change; a library of another version is refused
 NSG_RELU_IN, NSG_TANH_OUT, NSG_OUT_F32, NSG_RELU_OUT, NSG_F32, NSG_BF16, NSG_C1_MOMENTS = (_CONSTS[n] for n in (
     "NSG_RELU_IN", "NSG_TANH_OUT", "NSG_OUT_F32", "NSG_RELU_OUT", "NSG_F32", "NSG_BF16", "NSG_C1_MOMENTS"))
+NSG_DTW_MAX_FRAMES, NSG_DTW_BLOCK_COLS = _CONSTS["NSG_DTW_MAX_FRAMES"], _CONSTS["NSG_DTW_BLOCK_COLS"]
 
 _lib = None
 

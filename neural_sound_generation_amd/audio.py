@@ -26,6 +26,10 @@ phase from a table built in fp64 on the host (csrc/resample.hip; it makes no cla
 interpolation); trim_silence restates librosa's frame energies and threshold.  read_wav reads PCM files with scipy at their
 own rate; load_wav refuses a file at another rate unless resample=True, which sends it through the kernel.
 
+Judging a converted utterance (evaluate.test_conversion): mel_cepstra (the DCT-II of each frame's log amplitude, coefficients
+1 .. n_ceps), dtw (batched dynamic time warping, csrc/dtw.hip) and mel_cepstral_distortion, the two combined into the dB
+figure of the voice-conversion literature.  An extension: the reference has no objective figure for converted speech.
+
 parity unpinned: librosa is absent (here, on the GPU box, and from the reference's own tree), and no file of the reference
 holds a waveform; tests compare with the numpy restatement in oracle/audio_oracle.py (same initial phases) and check the
 transform identities (istft(stft(y)) == y, the spectral error falls over the iterations).
@@ -39,7 +43,7 @@ from ctypes import c_void_p
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ops
 from .ops import _chk, _p, _stream, _ws
 
 MIN_LEVEL_DB, REF_LEVEL_DB, MAX_ABS_VALUE = -100.0, 20.0, 1.0     # hparams_tacotron.py:99,110,111
@@ -186,6 +190,75 @@ def melspectrogram(wav, sample_rate=22050, fft_size=1024, hop_size=256, n_mels=8
     _lib.call("nsg_audio_melspectrogram", _p(y), _p(lens_d), _p(basis), c_void_p(bands.ctypes.data), _p(out), B, L, fft_size, hop_size, n_mels,
               PREEMPHASIS, MIN_LEVEL_DB, REF_LEVEL_DB, MAX_ABS_VALUE, LAYOUTS[layout], _stream())
     return out[0].cpu().numpy() if as_numpy else out
+
+
+@functools.lru_cache(maxsize=8)
+def cepstra_table(n_mels: int, n_ceps: int, min_level_db: float = MIN_LEVEL_DB) -> np.ndarray:
+    """(n_ceps, n_mels) float32: rows 1 .. n_ceps of the orthonormal DCT-II over the bands, scaled from the normalised mel to
+    the natural-log amplitude (a normalised mel m is the level min_level_db * (1 - m) dB + constants, i.e. ln amplitude =
+    m * (-min_level_db) * ln 10 / 20 + constants).  Row 0 (the energy) is left out, and with it every additive constant.
+        table[k][j] = (-min_level_db ln 10 / 20) sqrt(2 / n_mels) cos(pi (k + 1) (j + 1/2) / n_mels)
+    computed in fp64 and rounded once."""
+    k = np.arange(1, n_ceps + 1, dtype=np.float64)[:, None]
+    j = np.arange(n_mels, dtype=np.float64)[None, :]
+    t = (-float(min_level_db) * math.log(10.0) / 20.0) * math.sqrt(2.0 / n_mels) * np.cos(math.pi * k * (j + 0.5) / n_mels)
+    return np.ascontiguousarray(t.astype(np.float32))
+
+
+@functools.lru_cache(maxsize=8)
+def _cepstra_table_on(n_mels, n_ceps, min_level_db, device):
+    return torch.from_numpy(cepstra_table(n_mels, n_ceps, min_level_db)).to(device)
+
+
+def _mel3(mel, name):
+    if torch.is_tensor(mel) and mel.dim() == 4 and mel.shape[1] == 1:
+        mel = mel[:, 0]
+    if not torch.is_tensor(mel) or mel.dim() != 3:
+        raise ValueError(f"{name}: expected a mel tensor (B, n_mels, T) or (B, 1, n_mels, T)")
+    return mel
+
+
+def mel_cepstra(mel, frames=None, n_ceps=13, min_level_db=MIN_LEVEL_DB):
+    """Normalised mels (B, n_mels, T) or (B, 1, n_mels, T) on the GPU -> their mel cepstra (B, T, n_ceps), frame-major:
+    coefficients 1 .. n_ceps of the DCT-II of each frame's log amplitude (cepstra_table).  frames (B,): valid frames per clip;
+    the coefficients of later frames are +0.0."""
+    mel = _mel3(mel, "mel_cepstra")
+    if not 1 <= int(n_ceps) < mel.shape[1]:
+        raise ValueError(f"mel_cepstra: n_ceps = {n_ceps} outside [1, n_mels - 1 = {mel.shape[1] - 1}] (the DCT of n_mels bands has that many rows past the energy)")
+    return ops.mel_cepstra(mel, _cepstra_table_on(mel.shape[1], int(n_ceps), float(min_level_db), mel.device), frames)
+
+
+def dtw(a, b, len_a=None, len_b=None, want_path=False):
+    """Dynamic time warping of feature sequences a (B, Ta, K), b (B, Tb, K) under the Euclidean frame distance, steps
+    (1, 1), (1, 0), (0, 1) -> cost (B,), steps (B,) [, path (B, Ta + Tb - 1, 2)] (ops.dtw).  A length of None is the whole
+    tensor's."""
+    if not torch.is_tensor(a) or not torch.is_tensor(b) or a.dim() != 3 or b.dim() != 3:
+        raise ValueError("dtw: expected tensors a (B, Ta, K) and b (B, Tb, K)")
+    B = a.shape[0]
+    return ops.dtw(a, b, np.full(B, a.shape[1], dtype=np.int32) if len_a is None else len_a,
+                   np.full(B, b.shape[1], dtype=np.int32) if len_b is None else len_b, want_path)
+
+
+MCD_DB = 10.0 * math.sqrt(2.0) / math.log(10.0)       # nepers of cepstral distance -> dB
+
+
+def mel_cepstral_distortion(mel_a, mel_b, frames_a=None, frames_b=None, n_ceps=13):
+    """Mel-cepstral distortion of parallel clips after dynamic time warping: the Euclidean distance of the two frames' mel
+    cepstra (coefficients 1 .. n_ceps), summed along the cheapest warping path and divided by its length, in dB:
+        mcd = (10 sqrt(2) / ln 10) * cost / steps
+    (the constant is applied once, to the quotient).  mel_a (B, n_mels, Ta), mel_b (B, n_mels, Tb) normalised mels (or
+    (B, 1, n_mels, T)); frames_a, frames_b (B,) valid frames per clip, at least 1 (None: all).  Returns (mcd (B,) float32,
+    steps (B,) int32) on the device; nothing here synchronises when the frame counts are given on the host."""
+    mel_a, mel_b = _mel3(mel_a, "mel_cepstral_distortion"), _mel3(mel_b, "mel_cepstral_distortion")
+    if mel_a.shape[0] != mel_b.shape[0] or mel_a.shape[1] != mel_b.shape[1]:
+        raise ValueError(f"mel_cepstral_distortion: {tuple(mel_a.shape)} and {tuple(mel_b.shape)} are not parallel batches of one band count")
+    B = mel_a.shape[0]
+    fa = np.full(B, mel_a.shape[2], dtype=np.int32) if frames_a is None else frames_a
+    fb = np.full(B, mel_b.shape[2], dtype=np.int32) if frames_b is None else frames_b
+    fa = ops._lengths_on(fa, "mel_cepstral_distortion: frames_a", B, 1, mel_a.shape[2], mel_a.device)
+    fb = ops._lengths_on(fb, "mel_cepstral_distortion: frames_b", B, 1, mel_b.shape[2], mel_b.device)
+    cost, steps = ops.dtw(mel_cepstra(mel_a, fa, n_ceps), mel_cepstra(mel_b, fb, n_ceps), fa, fb)
+    return (cost / steps.to(torch.float32)) * MCD_DB, steps
 
 
 def inv_preemphasis(y: torch.Tensor, k=PREEMPHASIS) -> torch.Tensor:

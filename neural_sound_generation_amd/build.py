@@ -24,7 +24,7 @@ LIB = os.path.join(PKG, "libnsg.so")
 # libnsg.so: the product library exports exactly what include/nsg.h declares.
 OBJ_DIAG = os.path.join(CSRC, "_obj_diag")
 LIB_DIAG = os.path.join(PKG, "libnsg_diag.so")
-SOURCES = ["api_common.hip", "gemm_gather.hip", "gemm_patch.hip", "gemm_wgrad.hip", "gemm_wgrad_strip.hip", "gemm_flat.hip", "vq.hip", "segsum.hip", "vq_revive.hip", "vq_bf16.hip", "bn.hip", "elementwise.hip", "optim.hip", "conv_api.hip", "vae_latent.hip", "stencil_c1.hip", "c1_mfma.hip", "prior_ops.hip", "prior_sample.hip", "audio.hip", "resample.hip", "collate.hip"]
+SOURCES = ["api_common.hip", "gemm_gather.hip", "gemm_patch.hip", "gemm_wgrad.hip", "gemm_wgrad_strip.hip", "gemm_flat.hip", "vq.hip", "segsum.hip", "vq_revive.hip", "vq_bf16.hip", "bn.hip", "elementwise.hip", "optim.hip", "conv_api.hip", "vae_latent.hip", "stencil_c1.hip", "c1_mfma.hip", "prior_ops.hip", "prior_sample.hip", "audio.hip", "resample.hip", "collate.hip", "dtw.hip"]
 DIAG_SOURCES = SOURCES + ["diag.hip"]
 # -ffp-contract=off: the bit-exact VQ path spells out every fma itself; nothing may be re-fused.
 FLAGS = FLAGS_ = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "-fvisibility=hidden",

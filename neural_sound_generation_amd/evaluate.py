@@ -21,6 +21,10 @@ checkpoint layout, restated from the reference's src/test.py:73-106 and src/main
     encode, keep the leading latent columns, sample the rest (GatedPixelCNN.continue_codes), decode.
   * `continue_audio(vqvae, prior, wav, label, keep_frames, frames)` -- wav in, wav out: audio.melspectrogram, continue_mels,
     audio.inv_mel_spectrogram.
+  * `convert_voice(vqvae, mel, g_target)` -- what the speaker-conditioned decoder is for: encode, decode under another speaker's
+    id; `test_conversion(args, vqvae, pair_loader, device, epoch)` -- its figure over parallel utterances: the mel-cepstral
+    distortion after dynamic time warping (audio.mel_cepstral_distortion) of converted against target, and of source against
+    target for context.
   * `codebook_usage(model, loader, device)` -- how much of the codebook a dataset uses: per-code counts and their perplexity.
 """
 from __future__ import annotations
@@ -230,6 +234,65 @@ def test_prior(args, vqvae, prior, test_loader, device, epoch):
     nats = float(nll / count)
     print('====> Prior test set: {:.4f} nats per code ({:.4f} bits)'.format(nats, nats / float(np.log(2.0))))
     return nats
+
+
+def convert_voice(vqvae, mel: torch.Tensor, g_target: torch.Tensor):
+    """Re-voice clips as other speakers: mel (B, 1, 80, T) (or (B, 80, T)) on the GPU, T a multiple of 4, is encoded to its
+    codes and decoded under the speaker ids g_target (B,) int64 -> (codes (B, 20, T // 4) int64, mels (B, 1, 80, T)).  The
+    VQ-VAE runs in eval mode (its mode is restored) and is not changed.  ValueError: a model without a speaker embedding, or a
+    g_target that is not (B,) int64 within [0, n_speakers) -- checked on the host before anything is launched."""
+    if getattr(vqvae, "n_speakers", None) is None:
+        raise ValueError("convert_voice: the model has no speaker embedding (VQVAE(..., n_speakers=N))")
+    if mel.dim() == 3:
+        mel = mel.unsqueeze(1)
+    if mel.dim() != 4 or mel.shape[1] != 1:
+        raise ValueError("convert_voice: mel must be (B, 1, 80, T) or (B, 80, T)")
+    B = mel.shape[0]
+    if not isinstance(g_target, torch.Tensor) or tuple(g_target.shape) != (B,) or g_target.dtype != torch.int64:
+        raise ValueError(f"convert_voice: g_target must be an int64 tensor of shape ({B},)")
+    if B and (int(g_target.min()) < 0 or int(g_target.max()) >= vqvae.n_speakers):
+        raise ValueError(f"convert_voice: g_target must lie in [0, {vqvae.n_speakers}), got {int(g_target.min())} .. {int(g_target.max())}")
+    was_training = vqvae.training
+    vqvae.eval()
+    try:
+        with torch.no_grad():
+            codes = vqvae.encode(mel).contiguous()
+            mels = vqvae.decode(codes, g_target.to(mel.device))
+    finally:
+        vqvae.train(was_training)
+    return codes, mels
+
+
+def test_conversion(args, vqvae, pair_loader, device, epoch):
+    """The conversion figure of a speaker-conditioned VQ-VAE over parallel utterances: `pair_loader` yields
+    (c_src (B, 80, Ts), frames_src (B,), c_tgt (B, 80, Tt), frames_tgt (B,), g_tgt (B,) int64) -- the same sentences by a source
+    and a target speaker, zero-padded mels with their valid frame counts (host integers), and the target speakers' ids.  Each
+    source batch is converted to its target speakers (convert_voice; Ts is cut to a multiple of 4, and the converted mel keeps
+    the source's valid frames, floored to a multiple of 4) and compared with the target by audio.mel_cepstral_distortion;
+    MCD(source, target) is measured beside it for context.  Returns (mcd_converted, mcd_source): means over the clips of the
+    loader (not over its batches), in dB, read back with one host synchronisation at the end."""
+    from . import audio
+    total = torch.zeros(2, dtype=torch.float64, device=device)
+    n = 0
+    for c_src, frames_src, c_tgt, frames_tgt, g_tgt in pair_loader:
+        c_src, c_tgt = c_src.to(device), c_tgt.to(device).contiguous()
+        fs = np.asarray(frames_src.cpu() if torch.is_tensor(frames_src) else frames_src).astype(np.int64)
+        ft = np.asarray(frames_tgt.cpu() if torch.is_tensor(frames_tgt) else frames_tgt).astype(np.int64)
+        Ts = c_src.shape[2] // 4 * 4
+        fc = np.minimum(fs, Ts) // 4 * 4
+        if Ts < 4 or fc.min() < 4:
+            raise ValueError("test_conversion: every source clip needs at least 4 valid frames (one latent column)")
+        c_cut = c_src[:, :, :Ts].contiguous()
+        _, converted = convert_voice(vqvae, c_cut, g_tgt)
+        mcd_c, _ = audio.mel_cepstral_distortion(converted, c_tgt, fc, ft)
+        mcd_s, _ = audio.mel_cepstral_distortion(c_src.contiguous(), c_tgt, fs, ft)
+        total += torch.stack((mcd_c.double().sum(), mcd_s.double().sum()))
+        n += len(c_src)
+    if n == 0:
+        raise ValueError("test_conversion: empty loader")
+    mcd_c, mcd_s = (total / n).tolist()
+    print('====> Conversion test set: MCD {:.4f} dB converted, {:.4f} dB source against target ({} clips)'.format(mcd_c, mcd_s, n))
+    return mcd_c, mcd_s
 
 
 @torch.no_grad()

@@ -445,6 +445,78 @@ def collate_mels(corpus, plan, T, out=None):
     return out
 
 
+DTW_MAX_FRAMES, DTW_BLOCK_COLS = _lib.NSG_DTW_MAX_FRAMES, _lib.NSG_DTW_BLOCK_COLS     # include/nsg.h: longest sequence; columns of one sweep
+
+
+def _lengths_on(lengths, name, B, lo, hi, device):
+    """`lengths` as the (B,) int32 device tensor an entry point reads.  On the host (a sequence, a numpy array or a CPU tensor)
+    they are checked against [lo, hi] here and uploaded; an int32 tensor already on the device is the caller's to have checked on
+    the host copy it came from (include/nsg.h: the kernels clamp, so no access leaves a buffer)."""
+    if isinstance(lengths, torch.Tensor) and lengths.is_cuda:
+        if lengths.dtype != torch.int32 or tuple(lengths.shape) != (B,):
+            raise _lib.NsgError(f"{name}: expected an int32 tensor of shape ({B},), got {lengths.dtype} {tuple(lengths.shape)}")
+        return _chk(lengths, name, torch.int32)
+    import numpy as np
+    host = lengths.numpy() if isinstance(lengths, torch.Tensor) else np.asarray(lengths)
+    if host.shape != (B,) or not np.issubdtype(host.dtype, np.integer):
+        raise _lib.NsgError(f"{name}: expected {B} integers, got {host.dtype} {host.shape}")
+    if host.min() < lo or host.max() > hi:
+        raise _lib.NsgError(f"{name}: every length must be in [{lo}, {hi}], got {int(host.min())} .. {int(host.max())}")
+    return torch.from_numpy(np.ascontiguousarray(host, dtype=np.int32)).to(device)
+
+
+def mel_cepstra(mel, table, frames=None, out=None):
+    """mel (B, n_mels, T) fp32 mel-major, table (K, n_mels) fp32 -> (B, T, K) fp32 frame-major: c[b, t] = table @ mel[b, :, t] as
+    one fp32 chain per output over the bands in order (include/nsg.h), +0.0 for t >= frames[b].  frames: None (all T), or (B,)
+    lengths in [0, T] (host: checked here; int32 on the device: the caller's)."""
+    _chk(mel, "mel_cepstra: mel"); _chk(table, "mel_cepstra: table")
+    if mel.dim() != 3 or table.dim() != 2 or table.shape[1] != mel.shape[1] or table.device != mel.device:
+        raise _lib.NsgError(f"mel_cepstra: mel {tuple(mel.shape)} / table {tuple(table.shape)} are not (B, n_mels, T) / (K, n_mels) on one device")
+    B, n_mels, T = mel.shape
+    K = table.shape[0]
+    if B < 1 or T < 1:
+        raise _lib.NsgError(f"mel_cepstra: empty mel {tuple(mel.shape)}")
+    fr = None if frames is None else _lengths_on(frames, "mel_cepstra: frames", B, 0, T, mel.device)
+    if out is None:
+        out = torch.empty(B, T, K, dtype=torch.float32, device=mel.device)
+    elif _chk(out, "mel_cepstra: out").numel() != B * T * K or out.device != mel.device:
+        raise _lib.NsgError(f"mel_cepstra: out {tuple(out.shape)} does not hold {B} x {T} x {K}")
+    _lib.call("nsg_mel_cepstra", _p(mel), _p(fr), _p(table), _p(out), B, n_mels, T, K, _stream())
+    return out
+
+
+def dtw(a, b, len_a, len_b, want_path=False, out=None):
+    """Batched dynamic time warping (include/nsg.h: nsg_dtw).  a (B, Ta, K), b (B, Tb, K) fp32; len_a, len_b (B,) lengths in
+    [1, Ta] / [1, Tb] (host: checked here and uploaded; int32 on the device: the caller's) -> cost (B,) fp32, steps (B,) int32 and,
+    with want_path, path (B, Ta + Tb - 1, 2) int32 whose first steps[p] rows are pair p's cells (the rest is not written).  out: the
+    result tensors to write instead of new ones, (cost, steps) or (cost, steps, path).  K and the
+    sequence lengths the kernel serves are the entry point's to state and to refuse (K <= 64, Ta, Tb <= DTW_MAX_FRAMES)."""
+    _chk(a, "dtw: a"); _chk(b, "dtw: b")
+    if a.dim() != 3 or b.dim() != 3 or a.shape[0] != b.shape[0] or a.shape[2] != b.shape[2] or a.device != b.device:
+        raise _lib.NsgError(f"dtw: a {tuple(a.shape)} / b {tuple(b.shape)} are not (B, Ta, K) / (B, Tb, K) on one device")
+    B, Ta, K = a.shape
+    Tb = b.shape[1]
+    if B < 1 or Ta < 1 or Tb < 1:
+        raise _lib.NsgError(f"dtw: empty a {tuple(a.shape)} or b {tuple(b.shape)}")
+    la = _lengths_on(len_a, "dtw: len_a", B, 1, Ta, a.device)
+    lb = _lengths_on(len_b, "dtw: len_b", B, 1, Tb, a.device)
+    if out is None:
+        cost = torch.empty(B, dtype=torch.float32, device=a.device)
+        steps = torch.empty(B, dtype=torch.int32, device=a.device)
+        path = torch.empty(B, Ta + Tb - 1, 2, dtype=torch.int32, device=a.device) if want_path else None
+    else:
+        cost, steps, path = out if want_path else (*out, None)
+        for t, name, dtype, n in ((cost, "cost", torch.float32, B), (steps, "steps", torch.int32, B), (path, "path", torch.int32, B * (Ta + Tb - 1) * 2)):
+            if t is not None and (_chk(t, f"dtw: out {name}", dtype).numel() != n or t.device != a.device):
+                raise _lib.NsgError(f"dtw: out {name} {tuple(t.shape)} does not hold {n} elements")
+    if not want_path:
+        _lib.call("nsg_dtw", _p(a), _p(b), _p(la), _p(lb), _p(cost), _p(steps), None, B, Ta, Tb, K, None, 0, _stream())
+        return cost, steps
+    ws, nb = _ws(a.device, "nsg_dtw_workspace_bytes", B, Ta, Tb, 1)
+    _lib.call("nsg_dtw", _p(a), _p(b), _p(la), _p(lb), _p(cost), _p(steps), _p(path), B, Ta, Tb, K, _p(ws), nb, _stream())
+    return cost, steps, path
+
+
 def vq_ema_update(codebook, ema_n, ema_s, n, s, decay=0.99, eps=1e-5):
     K, D = codebook.shape
     scratch = torch.empty(1, dtype=torch.float32, device=codebook.device)
