@@ -887,6 +887,58 @@ NSG_API int nsg_dtw(const float *a, const float *b, const int32_t *len_a, const 
                     int32_t *path, int32_t B, int32_t Ta, int32_t Tb, int32_t K, void *workspace, size_t workspace_bytes,
                     void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Judging a converted utterance by its pitch: F0 tracking (YIN, de Cheveigne & Kawahara 2002) and F0 statistics along a
+ * warping path (extension; the reference has no pitch code).  parity unpinned: the contract is the one stated here, restated in
+ * fp32 and fp64 by tests/helpers/f0_ref.py.  evaluate.test_conversion_f0 reports F0 error, voicing error and log-F0 correlation.
+ * ------------------------------------------------------------------------------------------- */
+
+/* Per clip b of len_b = lengths[b] samples (lengths NULL: all L), x = wav[b] read as zero outside [0, len_b) (samples past
+ * len_b are never read), W = frame_length, and frame t < T_b = 1 + len_b / hop of T = 1 + L / hop (the front end's frame count;
+ * frame t is centred on sample t hop, as mel frame t is):
+ *     s0      = t hop - W / 2
+ *     d(tau)  = sum_{j=0}^{W-1} (x[s0 + j] - x[s0 + j + tau])^2                          tau = 1 .. tau_max
+ *     c(tau)  = sum_{k=1}^{tau} d(k)
+ *     d'(tau) = d(tau) * tau / c(tau)  if c(tau) > 0,  else 1                            (cumulative-mean-normalised difference)
+ *     tau*    = the smallest tau in [tau_min, tau_max] with d'(tau) < threshold, then advanced while tau + 1 <= tau_max and
+ *               d'(tau + 1) < d'(tau)
+ *     voiced:     a, b, c = d'(tau* - 1), d'(tau*), d'(tau* + 1);  if tau* - 1 >= 1, tau* + 1 <= tau_max, a >= b, c >= b and
+ *                 a - 2b + c > 0:  delta = 0.5 (a - c) / (a - 2b + c)  (so |delta| <= 0.5),  else delta = 0
+ *                 f0[b][t] = sample_rate / (tau* + delta),   ap[b][t] = d'(tau*)
+ *     no such tau:  f0[b][t] = +0.0 (unvoiced),   ap[b][t] = min over tau in [tau_min, tau_max] of d'(tau)
+ *     t >= T_b:     f0[b][t] = +0.0,  ap[b][t] = 1.0
+ * The direct sum of squared differences, never an autocorrelation or FFT identity: at a period d is a sum of tiny squares with
+ * nothing to cancel, which is what makes fp32 enough.  Everything is fp32; each subtraction, product, sum and quotient is rounded
+ * to fp32 and never contracted, in this order (the one place it is stated):
+ *     d(tau):   one chain per lag: the accumulator starts at +0.0 and takes fl(fl(x[s0+j] - x[s0+j+tau])^2) for j = 0, 1, ... in order;
+ *     c(tau):   the lags in groups of NSG_F0_LAG_GROUP = 8 (1 .. 8, 9 .. 16, ...), tau in group g = (tau - 1) / 8 with first lag
+ *               g0 = 8 g + 1:  p(tau) = the chain d(g0) + d(g0 + 1) + ... + d(tau) in that order;  G(g) = the chain from +0.0 over
+ *               the totals p(8 g' + 8) of the groups g' = 0 .. g - 1 in order;  c(tau) = fl(G(g) + p(tau));
+ *     d'(tau):  fl(fl(d(tau) * (float)tau) / c(tau)), the division correctly rounded;
+ *     delta:    fl(fl(0.5 * fl(a - c)) / fl(fl(a - fl(2 b)) + c));   f0 = fl(sample_rate / fl((float)tau* + delta)).
+ * A frame's result is a function of its own samples only: bit for bit independent of B, L, the clip's row and any tiling.
+ * wav [B][L]; f0, ap [B][T] fp32, every element written exactly once; no workspace.  Lanes own runs of adjacent lags over a
+ * frame's span of samples staged once in LDS (csrc/f0.hip).
+ * NSG_E_INVALID: a null wav / f0 / ap, a non-positive B, L, frame_length, hop, tau_min or tau_max, threshold not in (0, 1],
+ * sample_rate not > 0;  NSG_E_UNSUPPORTED: frame_length odd or outside [64, 2048], tau_min > tau_max, tau_max > 1024,
+ * B * T >= 2^31.  lengths[b] is device memory: the kernel clamps it into [0, L], so no read leaves wav; the caller checks it on the
+ * host copy it built lengths from. */
+#define NSG_F0_LAG_GROUP 8
+NSG_API int nsg_audio_f0(const float *wav, const int32_t *lengths, float *f0, float *ap, int32_t B, int32_t L, int32_t frame_length,
+                         int32_t hop, int32_t tau_min, int32_t tau_max, float threshold, float sample_rate, void *stream);
+
+/* F0 statistics along warping paths.  f0_a [B][Ta], f0_b [B][Tb] fp32 (a value that is not > 0 means unvoiced); path
+ * [B][Ta + Tb - 1][2] int32 and steps [B] int32 in nsg_dtw's layout; stats [B][10] fp64, over the first steps[p] cells (i, j) of
+ * pair p, with x = log2((double)f0_a[p][i]), y = log2((double)f0_b[p][j]) on the cells both clips voice:
+ *     { steps, n_vv, n_a_only, n_b_only, sum x, sum y, sum x^2, sum y^2, sum x y, sum (x - y)^2 }
+ * (n_vv: both voiced; n_a_only / n_b_only: one voiced).  The counts are exact integers held in doubles.  One wave per pair:
+ * lane l adds the cells l, l + 64, ... to 0.0 in that order, then an xor-butterfly (offsets 32 .. 1) adds the lanes, so a pair's
+ * result does not depend on the batch.  steps[p] is clamped into [0, Ta + Tb - 1] and each cell into the grid, so no access
+ * leaves a buffer; path rows past steps[p] are not read.
+ * NSG_E_INVALID: a null pointer, B < 1, Ta < 1, Tb < 1;  NSG_E_UNSUPPORTED: Ta + Tb - 1 >= 2^30. */
+NSG_API int nsg_f0_path_stats(const float *f0_a, const float *f0_b, const int32_t *path, const int32_t *steps, double *stats,
+                              int32_t B, int32_t Ta, int32_t Tb, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -116,7 +116,8 @@ DIAG_LIB_PATH = os.path.join(_PKG, "libnsg_diag.so")
 # run-time switches of the DIAGNOSTICS library (never of libnsg.so): name -> argument type
 _DIAG_SWITCHES = {"nsg_debug_set_patch_gemm": c_int32, "nsg_debug_set_patch_grid": c_int32, "nsg_debug_set_wgrad_strip": c_int32,
                   "nsg_debug_set_c1_moments": c_int32, "nsg_debug_set_wgrad_bf16_native": c_int32, "nsg_debug_set_wgrad_stagger": c_int32,
-                  "nsg_debug_set_wgrad_diag": c_int32, "nsg_debug_set_wgrad_stamp_buffer": c_void_p, "nsg_debug_set_stamp_buffer": c_void_p}
+                  "nsg_debug_set_wgrad_diag": c_int32, "nsg_debug_set_wgrad_stamp_buffer": c_void_p, "nsg_debug_set_stamp_buffer": c_void_p,
+                  "nsg_debug_set_f0_direct": c_int32}
 _diag = None
 
 

@@ -29,6 +29,8 @@ own rate; load_wav refuses a file at another rate unless resample=True, which se
 Judging a converted utterance (evaluate.test_conversion): mel_cepstra (the DCT-II of each frame's log amplitude, coefficients
 1 .. n_ceps), dtw (batched dynamic time warping, csrc/dtw.hip) and mel_cepstral_distortion, the two combined into the dB
 figure of the voice-conversion literature.  An extension: the reference has no objective figure for converted speech.
+Beside the envelope, the pitch (evaluate.test_conversion_f0): f0 (YIN on the waveform, csrc/f0.hip; frame t is mel frame t),
+f0_distortion / f0_figures (F0 error in cents, voiced / unvoiced disagreement, log-F0 correlation along a dtw path).
 
 parity unpinned: librosa is absent (here, on the GPU box, and from the reference's own tree), and no file of the reference
 holds a waveform; tests compare with the numpy restatement in oracle/audio_oracle.py (same initial phases) and check the
@@ -259,6 +261,70 @@ def mel_cepstral_distortion(mel_a, mel_b, frames_a=None, frames_b=None, n_ceps=1
     fb = ops._lengths_on(fb, "mel_cepstral_distortion: frames_b", B, 1, mel_b.shape[2], mel_b.device)
     cost, steps = ops.dtw(mel_cepstra(mel_a, fa, n_ceps), mel_cepstra(mel_b, fb, n_ceps), fa, fb)
     return (cost / steps.to(torch.float32)) * MCD_DB, steps
+
+
+F0_MAX_LAG = 1024                     # include/nsg.h: the longest lag nsg_audio_f0 searches
+
+
+def f0_lags(sample_rate, fmin, fmax):
+    """(tau_min, tau_max) = (ceil(sample_rate / fmax), floor(sample_rate / fmin)): the lags, in samples, of the periods of
+    [fmin, fmax].  ValueError unless 0 < fmin <= fmax and 1 <= tau_min <= tau_max <= F0_MAX_LAG."""
+    if not (sample_rate > 0 and 0 < fmin <= fmax):
+        raise ValueError(f"f0: need sample_rate > 0 and 0 < fmin <= fmax, got {sample_rate!r}, {fmin!r}, {fmax!r}")
+    tau_min, tau_max = int(math.ceil(sample_rate / fmax)), int(math.floor(sample_rate / fmin))
+    if not 1 <= tau_min <= tau_max <= F0_MAX_LAG:
+        raise ValueError(f"f0: [{fmin}, {fmax}] Hz at {sample_rate} Hz are the lags [{tau_min}, {tau_max}]; need 1 <= tau_min <= tau_max <= {F0_MAX_LAG}")
+    return tau_min, tau_max
+
+
+def f0(wav, sample_rate=22050, hop_size=256, frame_length=1024, fmin=65.0, fmax=500.0, threshold=0.1, lengths=None, device="cuda:0"):
+    """Fundamental frequency by YIN (de Cheveigne & Kawahara 2002; include/nsg.h states the arithmetic, csrc/f0.hip runs it): per
+    frame t, centred on sample t * hop_size as mel frame t is, the cumulative-mean-normalised difference d' over the lags
+    f0_lags(sample_rate, fmin, fmax) of a window of frame_length samples, the first lag with d' < threshold followed to its local
+    minimum, refined by a parabola.  wav: a 1-D numpy waveform (returns numpy (f0 (T,), aperiodicity (T,)), T = 1 + len //
+    hop_size), or a float32 GPU tensor (B, L) of zero-padded clips with optional lengths (B,) integers in [0, L] (returns GPU
+    tensors (B, T)).  f0 is in Hz, +0.0 where a frame is unvoiced or past its clip's 1 + length // hop_size frames; aperiodicity
+    is d' at the chosen lag (the least d' of an unvoiced frame, 1.0 past the clip).  The waveform is zero outside the clip; a
+    clip's frames are bit for bit what they are alone.  With inv_mel_spectrogram's hop_size * (T - 1) samples this gives T
+    frames: mel frame t and F0 frame t are the same instant.  Every argument is checked before anything is launched."""
+    if isinstance(frame_length, bool) or not isinstance(frame_length, (int, np.integer)) or frame_length % 2 or not 64 <= frame_length <= 2048:
+        raise ValueError(f"f0: frame_length must be an even integer in [64, 2048], got {frame_length!r}")
+    if isinstance(hop_size, bool) or not isinstance(hop_size, (int, np.integer)) or hop_size < 1:
+        raise ValueError(f"f0: hop_size must be a positive integer, got {hop_size!r}")
+    if not 0 < threshold <= 1:
+        raise ValueError(f"f0: threshold must be in (0, 1], got {threshold!r}")
+    tau_min, tau_max = f0_lags(sample_rate, fmin, fmax)
+    as_numpy, B, L, lens = _clip_batch("f0", wav, lengths, 0)
+    if L < 1:
+        raise ValueError("f0: an empty waveform")
+    if B * (1 + L // hop_size) >= 2 ** 31:
+        raise ValueError(f"f0: {B} clips of {1 + L // hop_size} frames are 2^31 frames or more")
+    y = torch.from_numpy(np.ascontiguousarray(wav, dtype=np.float32)[None]).to(device) if as_numpy else wav
+    freq, ap = ops.f0(y, int(frame_length), int(hop_size), tau_min, tau_max, float(threshold), float(sample_rate), lens)
+    return (freq[0].cpu().numpy(), ap[0].cpu().numpy()) if as_numpy else (freq, ap)
+
+
+def f0_figures(stats):
+    """The three pitch figures from rows of nsg_f0_path_stats sums, stats (..., 10) fp64 -> (rmse_cents, vuv_error, corr) fp64 (...):
+        rmse_cents = 1200 sqrt(sum (x - y)^2 / n_vv)            the log-F0 error in cents over the cells both clips voice
+        vuv_error  = (n_a_only + n_b_only) / steps              the share of cells one clip voices and the other does not
+        corr       = (n sxy - sx sy) / sqrt((n sxx - sx^2)(n syy - sy^2))        Pearson's r of log2 F0 over those cells, n = n_vv
+    rmse_cents and corr are NaN where n_vv < 2.  Rows may be sums of rows (pooling clips).  Computed where stats lives; nothing
+    synchronises."""
+    steps, n, na, nb, sx, sy, sxx, syy, sxy, sdd = stats.unbind(-1)
+    nan = torch.full_like(n, float("nan"))
+    few = n < 2
+    rmse = torch.where(few, nan, 1200.0 * torch.sqrt(sdd / n))
+    corr = torch.where(few, nan, (n * sxy - sx * sy) / torch.sqrt((n * sxx - sx * sx) * (n * syy - sy * sy)))
+    return rmse, (na + nb) / steps, corr
+
+
+def f0_distortion(f0_a, f0_b, path, steps):
+    """How two F0 tracks differ along a warping path (what ops.dtw / dtw(..., want_path=True) returns for the clips' cepstra):
+    f0_a (B, Ta), f0_b (B, Tb) fp32 GPU tensors (+0.0: unvoiced), path (B, Ta + Tb - 1, 2) int32, steps (B,) int32 ->
+    (rmse_cents (B,), vuv_error (B,), corr (B,), stats (B, 10)) fp64 on the device: f0_figures of ops.f0_path_stats."""
+    stats = ops.f0_path_stats(f0_a, f0_b, path, steps)
+    return (*f0_figures(stats), stats)
 
 
 def inv_preemphasis(y: torch.Tensor, k=PREEMPHASIS) -> torch.Tensor:

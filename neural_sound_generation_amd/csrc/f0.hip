@@ -1,0 +1,337 @@
+// F0 tracking (YIN) and F0 statistics along a warping path: the kernels behind audio.f0 and audio.f0_distortion
+// (evaluate.test_conversion_f0).  include/nsg.h states the arithmetic and its order; this file is how it is laid on the machine.
+//
+// f0_kernel: the work is W * tau_max subtract-square-add triples a frame out of a span of W + tau_max samples, VALU work fed from
+// LDS.  A lane owns F0_RUN adjacent lags tau = F0_RUN g .. F0_RUN g + F0_RUN - 1 (lag 0 rides along: its d is 0 and is never
+// read) and keeps the F0_RUN + 3 samples x[s0 + j + tau] that four consecutive j need in registers: a step of four j costs one
+// 16-byte read of the next four samples (consecutive lanes 16 bytes apart, conflict-free) and one 16-byte read of x[s0 + j .. j + 3]
+// at an address the frame's lanes share (a broadcast), for 4 * F0_RUN triples; the one-read-per-pair loop would pay 4 * F0_RUN
+// reads.  One fp32 chain per lag over j in order, so a lag's sum does not know which lane or workgroup formed it.  The loop is
+// bound by the VALU issue rate (three uncontracted instructions a pair); build.py compiles this file with -fno-slp-vectorize:
+// packed into v_pk_add_f32 / v_pk_mul_f32 the triples pay for the register shuffles and the launch is 1.3 x slower.
+// G = ceil((tau_max + 1) / F0_RUN) lanes serve a frame; a workgroup takes F = 256 / G adjacent frames of one clip (as many as
+// F0_LDS_BUDGET holds), lane = (frame, run), so that few lanes idle (3 frames of 85 runs at tau_max = 339).  Each frame has its
+// own span in LDS: frames with gaps between them (hop > W + tau_max) cost no more than adjacent ones.
+//   LDS (floats, per frame):  sx [stride]  the span x[s0 .. s0 + W + F0_RUN G), zero outside the clip; stride = that rounded up
+//                                          to 4, + 4: 16-byte rows, a frame's broadcast reads 4 banks from its neighbour's
+//                             dl [F0_RUN G] d(tau), then d'(tau) in place
+//                             gt [NG4]     the totals of the groups of 8 lags (nsg.h: NSG_F0_LAG_GROUP)
+//                             ctl [2]      the first lag below the threshold; the bits of min d' (d' >= 0: its bits order as integers)
+// The tail (running sum, d', the search) is a thread per group of 8 lags: its own chain over the group, then its own chain over
+// the earlier groups' totals (at most 127 adds); integer minima through LDS atomics (exact, order-free); the frame's first
+// thread advances to the local minimum, refines and stores.
+//
+// f0_path_stats_kernel: one wave per pair, lane l the cells l, l + 64, ..., then nsg_wave_sum_butterfly (nsg_reduce.h).
+#include "nsg_common.h"
+#include "nsg_reduce.h"
+
+namespace {
+
+constexpr int F0_RUN = 4;                          // adjacent lags a lane owns
+constexpr int F0_THREADS = 256;                    // lanes a workgroup shares among its frames (one frame may need more: F0_MAX_THREADS)
+constexpr int F0_MAX_THREADS = 320;                // ceil((1024 + 1) / 4) = 257 runs, rounded up to whole waves
+constexpr int F0_MIN_W = 64, F0_MAX_W = 2048, F0_MAX_TAU = 1024;
+constexpr int F0_GROUP = NSG_F0_LAG_GROUP;
+constexpr size_t F0_LDS_BUDGET = 60 * 1024;        // below the 64 KiB a kernel has without opting in
+static_assert(F0_RUN % 4 == 0 && F0_RUN <= F0_GROUP, "16-byte window reads; a frame's runs are at least as many as its groups");
+static_assert((F0_MAX_TAU + 1 + F0_RUN - 1) / F0_RUN <= F0_MAX_THREADS, "one frame's runs fit a workgroup");
+
+struct F0Geom {
+    int W, hop, tau_min, tau_max;
+    int G;          // runs (lanes) of a frame
+    int RG;         // F0_RUN * G >= tau_max + 1: lags a frame forms
+    int stride;     // floats between the frames' spans
+    int NG, NG4;    // groups of 8 lags; rounded up to 4
+    int F;          // frames of a workgroup
+    int tiles_t;    // workgroups of a clip
+    int threads;
+};
+inline size_t f0_frame_floats(const F0Geom &q) { return (size_t)q.stride + q.RG + q.NG4 + 2; }
+
+inline F0Geom f0_geom(int W, int hop, int tau_min, int tau_max, int T)
+{
+    F0Geom q;
+    q.W = W; q.hop = hop; q.tau_min = tau_min; q.tau_max = tau_max;
+    q.G = (tau_max + 1 + F0_RUN - 1) / F0_RUN;
+    q.RG = F0_RUN * q.G;
+    q.stride = (W + q.RG + 3) / 4 * 4 + 4;
+    q.NG = (tau_max + F0_GROUP - 1) / F0_GROUP;
+    q.NG4 = (q.NG + 3) / 4 * 4;
+    const int by_lanes = F0_THREADS / q.G, by_lds = (int)(F0_LDS_BUDGET / (f0_frame_floats(q) * sizeof(float)));
+    q.F = by_lanes < by_lds ? by_lanes : by_lds;
+    q.F = q.F > T ? T : q.F;
+    q.F = q.F < 1 ? 1 : q.F;
+    q.tiles_t = (T + q.F - 1) / q.F;
+    q.threads = (q.F * q.G + 63) / 64 * 64;
+    return q;
+}
+
+// NJ consecutive j from j0 for a lane's F0_RUN lags: w[0 .. F0_RUN + NJ - 1) holds x[s0 + j0 + tau0 ...], u the NJ samples x[s0 + j0 ...]
+template <int NJ>
+__device__ __forceinline__ void f0_step(float (&acc)[F0_RUN], const float (&w)[F0_RUN + 4], const float (&u)[4])
+{
+#pragma unroll
+    for (int jj = 0; jj < NJ; ++jj)
+#pragma unroll
+        for (int r = 0; r < F0_RUN; ++r) {
+            const float t = u[jj] - w[jj + r];
+            const float sq = t * t;
+            acc[r] = acc[r] + sq;
+        }
+}
+
+// DIRECT (the diagnostics library's switch, for scripts/f0_timing.py): the loop the sliding window replaces -- a lane's lags are
+// g, g + G, ..., each pair reads its own x[s0 + j + tau] (consecutive lanes consecutive words) -- with the same chains, so the same bits.
+template <bool DIRECT>
+__global__ __launch_bounds__(F0_MAX_THREADS) void f0_kernel(const float *__restrict__ wav, const int32_t *__restrict__ lengths,
+                                                            float *__restrict__ f0, float *__restrict__ ap, int L, int T, F0Geom q,
+                                                            float threshold, float sample_rate)
+{
+    extern __shared__ __attribute__((aligned(16))) float f0_lds[];
+    float *sx = f0_lds;                                // [F][stride]
+    float *dl = sx + q.F * q.stride;                   // [F][RG]
+    float *gt = dl + q.F * q.RG;                       // [F][NG4]
+    int *ctl = reinterpret_cast<int *>(gt + q.F * q.NG4);   // [F][2]
+    const int tid = threadIdx.x, nthr = blockDim.x;
+    const int b = blockIdx.x / q.tiles_t, t0 = (blockIdx.x - b * q.tiles_t) * q.F;
+    int len = lengths ? lengths[b] : L;
+    len = len < 0 ? 0 : (len > L ? L : len);           // the caller's to get right (nsg.h); clamped so that no read leaves wav
+    const int Tb = 1 + len / q.hop;
+    const int nf = T - t0 < q.F ? T - t0 : q.F;        // frames of this tile inside the tensor
+    float *of = f0 + (int64_t)b * T + t0, *oa = ap + (int64_t)b * T + t0;
+    if (t0 >= Tb) {                                    // the whole tile is past the clip (uniform over the workgroup)
+        for (int i = tid; i < nf; i += nthr) { of[i] = 0.f; oa[i] = 1.f; }
+        return;
+    }
+    const float *xb = wav + (int64_t)b * L;
+    const int S = q.W + q.RG;
+    for (int f = 0; f < q.F; ++f) {                    // a frame's span, zero outside the clip and for frames past it
+        const bool livef = f < nf && t0 + f < Tb;
+        const int64_t s0 = (int64_t)(t0 + f) * q.hop - q.W / 2;
+        for (int i = tid; i < q.stride; i += nthr) {
+            const int64_t n = s0 + i;
+            const bool in = livef && i < S && n >= 0 && n < len;
+            sx[f * q.stride + i] = in ? xb[in ? n : 0] : 0.f;
+        }
+    }
+    if (tid < q.F) { ctl[2 * tid] = 0x7fffffff; ctl[2 * tid + 1] = 0x7f800000; }
+    __syncthreads();
+
+    const int f = tid / q.G, g = tid - f * q.G;
+    const bool act = f < q.F;
+    if (act && DIRECT) {
+        const float *base = sx + f * q.stride, *win = base + g;
+        float acc[F0_RUN];
+#pragma unroll
+        for (int r = 0; r < F0_RUN; ++r) acc[r] = 0.f;
+#pragma unroll 4
+        for (int j = 0; j < q.W; ++j) {
+            const float u = base[j];
+#pragma unroll
+            for (int r = 0; r < F0_RUN; ++r) {
+                const float t = u - win[j + q.G * r];
+                const float sq = t * t;
+                acc[r] = acc[r] + sq;
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < F0_RUN; ++r) dl[f * q.RG + g + q.G * r] = acc[r];
+    } else if (act) {
+        const float *base = sx + f * q.stride;         // x[s0 + j] at base[j]: the frame's lanes read it at one address
+        const float *win = base + F0_RUN * g;          // x[s0 + j + tau0] at win[j], tau0 = F0_RUN g
+        float acc[F0_RUN], w[F0_RUN + 4], u[4];
+#pragma unroll
+        for (int r = 0; r < F0_RUN; ++r) acc[r] = 0.f;
+#pragma unroll
+        for (int r = 0; r < F0_RUN; r += 4) {
+            const v4f v = *reinterpret_cast<const v4f *>(win + r);
+            w[r] = v.x; w[r + 1] = v.y; w[r + 2] = v.z; w[r + 3] = v.w;
+        }
+        int j0 = 0;
+        for (; j0 + 4 <= q.W; j0 += 4) {
+            const v4f uv = *reinterpret_cast<const v4f *>(base + j0);
+            const v4f nv = *reinterpret_cast<const v4f *>(win + j0 + F0_RUN);
+            u[0] = uv.x; u[1] = uv.y; u[2] = uv.z; u[3] = uv.w;
+            w[F0_RUN] = nv.x; w[F0_RUN + 1] = nv.y; w[F0_RUN + 2] = nv.z; w[F0_RUN + 3] = nv.w;
+            f0_step<4>(acc, w, u);
+#pragma unroll
+            for (int r = 0; r < F0_RUN; ++r) w[r] = w[r + 4];
+        }
+        if (j0 < q.W) {                                // W = 2 mod 4: the last two j (the rows are long enough for these reads)
+            const v4f uv = *reinterpret_cast<const v4f *>(base + j0);
+            const v4f nv = *reinterpret_cast<const v4f *>(win + j0 + F0_RUN);
+            u[0] = uv.x; u[1] = uv.y; u[2] = uv.z; u[3] = uv.w;
+            w[F0_RUN] = nv.x; w[F0_RUN + 1] = nv.y; w[F0_RUN + 2] = nv.z; w[F0_RUN + 3] = nv.w;
+            f0_step<2>(acc, w, u);
+        }
+        float *dst = dl + f * q.RG + F0_RUN * g;
+#pragma unroll
+        for (int r = 0; r < F0_RUN; r += 4) {
+            const v4f v = {acc[r], acc[r + 1], acc[r + 2], acc[r + 3]};
+            *reinterpret_cast<v4f *>(dst + r) = v;
+        }
+    }
+    __syncthreads();
+
+    // the running sum in nsg.h's order: thread (f, g) is group g of frame f, lags 8 g + 1 .. 8 g + 8
+    const bool grp = act && g < q.NG;
+    float dv[F0_GROUP], p[F0_GROUP];
+    if (grp) {
+        const float *d = dl + f * q.RG + F0_GROUP * g + 1;
+        float run = 0.f;
+#pragma unroll
+        for (int r = 0; r < F0_GROUP; ++r) {
+            const bool in = F0_GROUP * g + 1 + r <= q.tau_max;
+            dv[r] = in ? d[in ? r : 0] : 0.f;
+            run = r == 0 ? dv[0] : run + dv[r];
+            p[r] = run;
+        }
+        gt[f * q.NG4 + g] = run;
+    }
+    __syncthreads();
+    if (grp) {
+        float G = 0.f;
+        for (int k = 0; k < g; ++k) G = G + gt[f * q.NG4 + k];
+        float *d = dl + f * q.RG + F0_GROUP * g + 1;
+        int first = 0x7fffffff;
+        float mn = __builtin_inff();
+        bool any = false;
+#pragma unroll
+        for (int r = 0; r < F0_GROUP; ++r) {
+            const int tau = F0_GROUP * g + 1 + r;
+            if (tau <= q.tau_max) {
+                const float c = G + p[r];
+                const float num = dv[r] * (float)tau;
+                const float dp = c > 0.f ? num / c : 1.f;
+                d[r] = dp;
+                if (tau >= q.tau_min) {
+                    any = true;
+                    mn = dp < mn ? dp : mn;
+                    if (dp < threshold && first == 0x7fffffff) first = tau;
+                }
+            }
+        }
+        if (first != 0x7fffffff) atomicMin(&ctl[2 * f], first);
+        if (any) atomicMin(reinterpret_cast<unsigned *>(&ctl[2 * f + 1]), nsg_fbits(mn));
+    }
+    __syncthreads();
+
+    if (act && g == 0 && f < nf) {
+        float r_f0 = 0.f, r_ap = 1.f;
+        if (t0 + f < Tb) {
+            const float *dp = dl + f * q.RG;
+            int ts = ctl[2 * f];
+            if (ts == 0x7fffffff) {
+                r_ap = nsg_bitsf((unsigned)ctl[2 * f + 1]);
+            } else {
+                while (ts + 1 <= q.tau_max && dp[ts + 1] < dp[ts]) ++ts;
+                const float bb = dp[ts];
+                float delta = 0.f;
+                if (ts - 1 >= 1 && ts + 1 <= q.tau_max) {
+                    const float a = dp[ts - 1], c = dp[ts + 1];
+                    const float two_b = 2.f * bb;
+                    const float den = (a - two_b) + c;
+                    if (a >= bb && c >= bb && den > 0.f) {
+                        const float diff = a - c;
+                        const float half = 0.5f * diff;
+                        delta = half / den;
+                    }
+                }
+                const float period = (float)ts + delta;
+                r_f0 = sample_rate / period;
+                r_ap = bb;
+            }
+        }
+        of[f] = r_f0;
+        oa[f] = r_ap;
+    }
+}
+
+__global__ __launch_bounds__(64) void f0_path_stats_kernel(const float *__restrict__ fa, const float *__restrict__ fb,
+                                                           const int32_t *__restrict__ path, const int32_t *__restrict__ steps,
+                                                           double *__restrict__ stats, int Ta, int Tb)
+{
+    const int pair = blockIdx.x, lane = threadIdx.x;
+    const int P = Ta + Tb - 1;
+    int n = steps[pair];
+    n = n < 0 ? 0 : (n > P ? P : n);                   // the caller's to get right; clamped so that no access leaves a buffer
+    const int32_t *pp = path + (int64_t)pair * P * 2;
+    const float *A = fa + (int64_t)pair * Ta, *Bv = fb + (int64_t)pair * Tb;
+    double s[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) s[k] = 0.0;            // n_vv, n_a_only, n_b_only, then the six sums
+    for (int c = lane; c < n; c += 64) {
+        int i = pp[2 * c], j = pp[2 * c + 1];
+        i = i < 0 ? 0 : (i > Ta - 1 ? Ta - 1 : i);
+        j = j < 0 ? 0 : (j > Tb - 1 ? Tb - 1 : j);
+        const float va = A[i], vb = Bv[j];
+        const bool a_on = va > 0.f, b_on = vb > 0.f;
+        if (a_on && b_on) {
+            const double x = log2((double)va), y = log2((double)vb), d = x - y;
+            s[0] += 1.0;
+            s[3] += x;
+            s[4] += y;
+            s[5] += x * x;
+            s[6] += y * y;
+            s[7] += x * y;
+            s[8] += d * d;
+        } else if (a_on) {
+            s[1] += 1.0;
+        } else if (b_on) {
+            s[2] += 1.0;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 9; ++k) s[k] = nsg_wave_sum_butterfly(s[k]);
+    if (lane == 0) {
+        double *o = stats + (int64_t)pair * 10;
+        o[0] = (double)n;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) o[1 + k] = s[k];
+    }
+}
+
+}  // namespace
+
+NSG_DIAG_SWITCH(int, g_f0_direct, 0)       // nsg_debug_set_f0_direct (diagnostics library only): 1 = the one-read-per-pair loop
+#ifdef NSG_DIAG
+extern "C" NSG_API void nsg_debug_set_f0_direct(int on) { g_f0_direct = on; }
+#endif
+
+extern "C" {
+
+int nsg_audio_f0(const float *wav, const int32_t *lengths, float *f0, float *ap, int32_t B, int32_t L, int32_t frame_length, int32_t hop,
+                 int32_t tau_min, int32_t tau_max, float threshold, float sample_rate, void *stream)
+{
+    NSG_REQUIRE(wav && f0 && ap, NSG_E_INVALID, "nsg_audio_f0: null pointer");
+    NSG_REQUIRE(B >= 1 && L >= 1 && frame_length >= 1 && hop >= 1 && tau_min >= 1 && tau_max >= 1, NSG_E_INVALID,
+                "nsg_audio_f0: non-positive size (B = %d, L = %d, frame_length = %d, hop = %d, tau_min = %d, tau_max = %d)", B, L, frame_length,
+                hop, tau_min, tau_max);
+    NSG_REQUIRE(threshold > 0.f && threshold <= 1.f, NSG_E_INVALID, "nsg_audio_f0: threshold = %g not in (0, 1]", (double)threshold);
+    NSG_REQUIRE(sample_rate > 0.f && sample_rate <= 3.0e38f, NSG_E_INVALID, "nsg_audio_f0: sample_rate = %g not positive and finite", (double)sample_rate);
+    NSG_REQUIRE(frame_length % 2 == 0 && frame_length >= F0_MIN_W && frame_length <= F0_MAX_W, NSG_E_UNSUPPORTED,
+                "nsg_audio_f0: frame_length = %d is odd or outside [%d, %d]", frame_length, F0_MIN_W, F0_MAX_W);
+    NSG_REQUIRE(tau_min <= tau_max && tau_max <= F0_MAX_TAU, NSG_E_UNSUPPORTED, "nsg_audio_f0: lags [%d, %d] outside 1 <= tau_min <= tau_max <= %d",
+                tau_min, tau_max, F0_MAX_TAU);
+    const int T = 1 + L / hop;
+    NSG_REQUIRE((int64_t)B * T < 0x7fffffffLL, NSG_E_UNSUPPORTED, "nsg_audio_f0: too many frames (B * T = %lld >= 2^31, outside the envelope)",
+                (long long)B * T);
+    const F0Geom q = f0_geom(frame_length, hop, tau_min, tau_max, T);
+    const size_t lds = (size_t)q.F * f0_frame_floats(q) * sizeof(float);
+    hipLaunchKernelGGL(g_f0_direct ? f0_kernel<true> : f0_kernel<false>, dim3((unsigned)(B * q.tiles_t)), dim3(q.threads), lds,
+                       (hipStream_t)stream, wav, lengths, f0, ap, L, T, q, threshold, sample_rate);
+    return nsg_check_launch("f0_kernel");
+}
+
+int nsg_f0_path_stats(const float *f0_a, const float *f0_b, const int32_t *path, const int32_t *steps, double *stats, int32_t B, int32_t Ta,
+                      int32_t Tb, void *stream)
+{
+    NSG_REQUIRE(f0_a && f0_b && path && steps && stats, NSG_E_INVALID, "nsg_f0_path_stats: null pointer");
+    NSG_REQUIRE(B >= 1 && Ta >= 1 && Tb >= 1, NSG_E_INVALID, "nsg_f0_path_stats: non-positive size (B = %d, Ta = %d, Tb = %d)", B, Ta, Tb);
+    NSG_REQUIRE((int64_t)Ta + Tb - 1 < (1LL << 30), NSG_E_UNSUPPORTED, "nsg_f0_path_stats: Ta + Tb - 1 = %lld outside [1, 2^30)",
+                (long long)Ta + Tb - 1);
+    hipLaunchKernelGGL(f0_path_stats_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, f0_a, f0_b, path, steps, stats, Ta, Tb);
+    return nsg_check_launch("f0_path_stats_kernel");
+}
+
+}  // extern "C"

@@ -71,12 +71,20 @@ __device__ __forceinline__ void nsg_block_sum_walk256(double part, Done done)
     }
 }
 
-// Butterfly.  Order: xor-butterflies inside each wave (offsets 32, 16, ..., 1; no barrier), then the 4 wave totals through
-// red[0..3] as ((w0 + w1) + w2) + w3.  The result is in every thread.  Two barriers (the second frees red for the next call).
-__device__ __forceinline__ double nsg_block_sum_butterfly(double v, double *red, int tid)
+// The butterfly's wave stage.  Order: xor-butterflies over the 64 lanes (offsets 32, 16, ..., 1).  The result is in every lane.
+// No barrier, no LDS.
+__device__ __forceinline__ double nsg_wave_sum_butterfly(double v)
 {
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+// Butterfly.  Order: nsg_wave_sum_butterfly inside each wave, then the 4 wave totals through
+// red[0..3] as ((w0 + w1) + w2) + w3.  The result is in every thread.  Two barriers (the second frees red for the next call).
+__device__ __forceinline__ double nsg_block_sum_butterfly(double v, double *red, int tid)
+{
+    v = nsg_wave_sum_butterfly(v);
     if ((tid & 63) == 0) red[tid >> 6] = v;
     __syncthreads();
     const double r = ((red[0] + red[1]) + red[2]) + red[3];

@@ -24,7 +24,9 @@ checkpoint layout, restated from the reference's src/test.py:73-106 and src/main
   * `convert_voice(vqvae, mel, g_target)` -- what the speaker-conditioned decoder is for: encode, decode under another speaker's
     id; `test_conversion(args, vqvae, pair_loader, device, epoch)` -- its figure over parallel utterances: the mel-cepstral
     distortion after dynamic time warping (audio.mel_cepstral_distortion) of converted against target, and of source against
-    target for context.
+    target for context; `test_conversion_f0(args, vqvae, pair_loader, device, epoch)` -- the same pairs as waveforms, judged by
+    pitch: the converted mel inverted to a waveform, F0 by YIN (audio.f0), and along the same warping paths the F0 error in
+    cents, the voiced / unvoiced disagreement and the log-F0 correlation (audio.f0_figures), pooled over all clips.
   * `codebook_usage(model, loader, device)` -- how much of the codebook a dataset uses: per-code counts and their perplexity.
 """
 from __future__ import annotations
@@ -293,6 +295,70 @@ def test_conversion(args, vqvae, pair_loader, device, epoch):
     mcd_c, mcd_s = (total / n).tolist()
     print('====> Conversion test set: MCD {:.4f} dB converted, {:.4f} dB source against target ({} clips)'.format(mcd_c, mcd_s, n))
     return mcd_c, mcd_s
+
+
+def test_conversion_f0(args, vqvae, pair_loader, device, epoch, iters=None, angles0=None):
+    """The pitch figures of a speaker-conditioned VQ-VAE over parallel utterances, from waveforms: `pair_loader` yields
+    (wav_src (B, Ls), len_src (B,), wav_tgt (B, Lt), len_tgt (B,), g_tgt (B,) int64) -- the same sentences by a source and a target
+    speaker as zero-padded float32 waveforms at 22 050 Hz with their lengths in samples (host integers), and the target speakers'
+    ids.  Per batch: audio.melspectrogram of both (frame t centred on sample 256 t); the source mel cut to a multiple of 4 frames
+    and converted (convert_voice; the converted mel keeps the source's valid frames floored to a multiple of 4);
+    audio.inv_mel_spectrogram of the converted mel (iters Griffin-Lim iterations, default audio.GRIFFIN_LIM_ITERS; angles0: the
+    initial phases (B, frames, 513) for every batch, or a sequence of them, one per batch; None draws them); audio.f0 of the
+    converted, the target and the source waveforms (F0 frame t is mel frame t); mel cepstra and ops.dtw with the path of converted
+    against target and of source against target; ops.f0_path_stats along each path.  Returns
+        {"converted": figures, "source": figures, "clips": n},   figures = {"f0_rmse_cents", "vuv_error", "f0_corr", "mcd", "stats"}
+    each set pooled over all clips of the loader from the summed stats (audio.f0_figures of the sum, not a mean of per-clip
+    ratios), "mcd" the mean over clips of the mel-cepstral distortion along the same paths in dB, "stats" the ten sums.  One host
+    synchronisation, at the end.  ValueError, before anything of the batch is launched: a model without a speaker embedding, a
+    clip tensor of more than ops.DTW_MAX_FRAMES frames, a source clip of fewer than 4 frames; before anything at all: an empty loader."""
+    from . import audio
+    if getattr(vqvae, "n_speakers", None) is None:
+        raise ValueError("test_conversion_f0: the model has no speaker embedding (VQVAE(..., n_speakers=N))")
+    hop, fft = 256, 1024
+    iters = audio.GRIFFIN_LIM_ITERS if iters is None else int(iters)
+    total = torch.zeros(2, 11, dtype=torch.float64, device=device)          # per set: the ten sums, the sum of the clips' MCD
+    n = 0
+    for k, (wav_src, len_src, wav_tgt, len_tgt, g_tgt) in enumerate(pair_loader):
+        ls = np.asarray(len_src.cpu() if torch.is_tensor(len_src) else len_src).astype(np.int64)
+        lt = np.asarray(len_tgt.cpu() if torch.is_tensor(len_tgt) else len_tgt).astype(np.int64)
+        Ts, Tt = 1 + wav_src.shape[1] // hop, 1 + wav_tgt.shape[1] // hop
+        if max(Ts, Tt) > ops.DTW_MAX_FRAMES:
+            raise ValueError(f"test_conversion_f0: clips of {Ts} / {Tt} frames; the warping serves at most {ops.DTW_MAX_FRAMES}")
+        fs, ft = 1 + ls // hop, 1 + lt // hop
+        Tc = Ts // 4 * 4
+        fc = np.minimum(fs, Tc) // 4 * 4
+        if Tc < 4 or fc.min() < 4:
+            raise ValueError("test_conversion_f0: every source clip needs at least 4 valid frames (one latent column)")
+        wav_src, wav_tgt = wav_src.to(device).contiguous(), wav_tgt.to(device).contiguous()
+        mel_s = audio.melspectrogram(wav_src, fft_size=fft, hop_size=hop, lengths=ls)
+        mel_t = audio.melspectrogram(wav_tgt, fft_size=fft, hop_size=hop, lengths=lt)
+        _, converted = convert_voice(vqvae, mel_s[:, :, :Tc].contiguous(), g_tgt)
+        a0 = angles0[k] if isinstance(angles0, (list, tuple)) else angles0
+        wav_c = audio.inv_mel_spectrogram(converted.squeeze(1), fft_size=fft, hop_size=hop, iters=iters, angles0=a0)
+        f0_c, _ = audio.f0(wav_c, hop_size=hop, lengths=hop * (fc - 1))   # hop (Tc - 1) samples: Tc frames, fc of them the clip's
+        f0_t, _ = audio.f0(wav_tgt, hop_size=hop, lengths=lt)
+        f0_s, _ = audio.f0(wav_src, hop_size=hop, lengths=ls)
+        cep_t = audio.mel_cepstra(mel_t, ft)
+        for row, (mel, frames, f0_x) in enumerate(((converted, fc, f0_c), (mel_s, fs, f0_s))):
+            cost, steps, path = ops.dtw(audio.mel_cepstra(mel, frames), cep_t, frames, ft, want_path=True)
+            stats = ops.f0_path_stats(f0_x, f0_t, path, steps)
+            mcd = (cost / steps.to(torch.float32)) * audio.MCD_DB
+            total[row, :10] += stats.sum(0)
+            total[row, 10] += mcd.double().sum()
+        n += len(wav_src)
+    if n == 0:
+        raise ValueError("test_conversion_f0: empty loader")
+    sums = torch.cat((total, torch.stack(audio.f0_figures(total[:, :10]), dim=1)), dim=1).tolist()      # the one read-back
+    out = {"clips": n}
+    for row, name in enumerate(("converted", "source")):
+        rmse, vuv, corr = sums[row][11:]
+        out[name] = {"f0_rmse_cents": rmse, "vuv_error": vuv, "f0_corr": corr, "mcd": sums[row][10] / n, "stats": sums[row][:10]}
+    print('====> Conversion test set: F0 RMSE {:.2f} cents, V/UV error {:.4f}, log-F0 correlation {:.4f}, MCD {:.4f} dB converted; '
+          '{:.2f} cents, {:.4f}, {:.4f}, {:.4f} dB source against target ({} clips)'.format(
+              *(out["converted"][k] for k in ("f0_rmse_cents", "vuv_error", "f0_corr", "mcd")),
+              *(out["source"][k] for k in ("f0_rmse_cents", "vuv_error", "f0_corr", "mcd")), n))
+    return out
 
 
 @torch.no_grad()

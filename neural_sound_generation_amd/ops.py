@@ -517,6 +517,53 @@ def dtw(a, b, len_a, len_b, want_path=False, out=None):
     return cost, steps, path
 
 
+def f0(wav, frame_length, hop, tau_min, tau_max, threshold, sample_rate, lengths=None, out=None):
+    """YIN F0 tracking (include/nsg.h: nsg_audio_f0).  wav (B, L) fp32 zero-padded clips; lengths: None (all L), or (B,) lengths
+    in [0, L] (host: checked here and uploaded; int32 on the device: the caller's) -> (f0 (B, T), aperiodicity (B, T)) fp32,
+    T = 1 + L // hop; f0 is +0.0 on unvoiced frames and past a clip's 1 + length // hop frames.  out: (f0, ap) to write instead of
+    new tensors.  The frame length, lag range, threshold and rate the kernel serves are the entry point's to state and refuse."""
+    _chk(wav, "f0: wav")
+    if wav.dim() != 2 or wav.shape[0] < 1 or wav.shape[1] < 1:
+        raise _lib.NsgError(f"f0: wav {tuple(wav.shape)} is not (B, L) with B, L >= 1")
+    B, L = wav.shape
+    if int(hop) < 1:
+        raise _lib.NsgError(f"f0: hop = {hop} < 1")
+    T = 1 + L // int(hop)
+    lens = None if lengths is None else _lengths_on(lengths, "f0: lengths", B, 0, L, wav.device)
+    if out is None:
+        f, ap = (torch.empty(B, T, dtype=torch.float32, device=wav.device) for _ in range(2))
+    else:
+        f, ap = out
+        for t, name in ((f, "f0"), (ap, "ap")):
+            if _chk(t, f"f0: out {name}").numel() != B * T or t.device != wav.device:
+                raise _lib.NsgError(f"f0: out {name} {tuple(t.shape)} does not hold {B} x {T}")
+    _lib.call("nsg_audio_f0", _p(wav), _p(lens), _p(f), _p(ap), B, L, int(frame_length), int(hop), int(tau_min), int(tau_max),
+              float(threshold), float(sample_rate), _stream())
+    return f, ap
+
+
+def f0_path_stats(f0_a, f0_b, path, steps, out=None):
+    """F0 statistics along warping paths (include/nsg.h: nsg_f0_path_stats).  f0_a (B, Ta), f0_b (B, Tb) fp32 (not > 0: unvoiced),
+    path (B, Ta + Tb - 1, 2) int32 and steps (B,) int32 as ops.dtw returns them -> stats (B, 10) fp64:
+    steps, n_vv, n_a_only, n_b_only, sum x, sum y, sum x^2, sum y^2, sum x y, sum (x - y)^2 with x, y = log2 f0 on the cells both voice."""
+    _chk(f0_a, "f0_path_stats: f0_a"); _chk(f0_b, "f0_path_stats: f0_b")
+    _chk(path, "f0_path_stats: path", torch.int32); _chk(steps, "f0_path_stats: steps", torch.int32)
+    if f0_a.dim() != 2 or f0_b.dim() != 2 or f0_a.shape[0] != f0_b.shape[0] or f0_a.shape[0] < 1 or f0_a.shape[1] < 1 or f0_b.shape[1] < 1:
+        raise _lib.NsgError(f"f0_path_stats: f0_a {tuple(f0_a.shape)} / f0_b {tuple(f0_b.shape)} are not (B, Ta) / (B, Tb)")
+    B, Ta = f0_a.shape
+    Tb = f0_b.shape[1]
+    if tuple(path.shape) != (B, Ta + Tb - 1, 2) or tuple(steps.shape) != (B,):
+        raise _lib.NsgError(f"f0_path_stats: path {tuple(path.shape)} / steps {tuple(steps.shape)} are not ({B}, {Ta + Tb - 1}, 2) / ({B},)")
+    if len({t.device for t in (f0_a, f0_b, path, steps)}) != 1:
+        raise _lib.NsgError("f0_path_stats: the tensors are not on one device")
+    if out is None:
+        out = torch.empty(B, 10, dtype=torch.float64, device=f0_a.device)
+    elif _chk(out, "f0_path_stats: out", torch.float64).numel() != B * 10 or out.device != f0_a.device:
+        raise _lib.NsgError(f"f0_path_stats: out {tuple(out.shape)} does not hold {B} x 10")
+    _lib.call("nsg_f0_path_stats", _p(f0_a), _p(f0_b), _p(path), _p(steps), _p(out), B, Ta, Tb, _stream())
+    return out
+
+
 def vq_ema_update(codebook, ema_n, ema_s, n, s, decay=0.99, eps=1e-5):
     K, D = codebook.shape
     scratch = torch.empty(1, dtype=torch.float32, device=codebook.device)
