@@ -939,6 +939,63 @@ NSG_API int nsg_audio_f0(const float *wav, const int32_t *lengths, float *f0, fl
 NSG_API int nsg_f0_path_stats(const float *f0_a, const float *f0_b, const int32_t *path, const int32_t *steps, double *stats,
                               int32_t B, int32_t Ta, int32_t Tb, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * A path finder over per-frame F0 candidates (Boersma 1993; RAPT): instead of deciding each frame on its own, keep the local
+ * minima of d' and let a dynamic programme choose one per frame, or "unvoiced" (extension; parity unpinned: the contract is
+ * the one stated here, restated in fp32 and fp64 by tests/helpers/f0_track_ref.py).  audio.f0_track runs the two in turn.
+ * ------------------------------------------------------------------------------------------- */
+
+/* The candidates of every frame.  wav, lengths, the frames, the zero padding, d(tau), c(tau) and d'(tau) are nsg_audio_f0's, in
+ * its fp32 order (csrc/f0.hip: the two kernels share that half as code).  Per frame t < T_b a lag tau in
+ * [max(tau_min, 2), tau_max] is a candidate iff
+ *     d'(tau) < d'(tau - 1)    (the left neighbour is used also where it lies below tau_min),
+ *     tau = tau_max  or  d'(tau) <= d'(tau + 1)    (the first lag of a plateau),    and    d'(tau) < 1.
+ * Of a frame's candidates the NSG_F0_MAX_CANDIDATES = 8 with the smallest pairs (d'(tau), tau) in lexicographic order are kept
+ * (exactly, whatever order the machine meets them in) and stored by ASCENDING LAG: slot 0 is the highest frequency.  Each is
+ * refined by nsg_audio_f0's parabola, under its conditions (tau - 1 >= 1, tau + 1 <= tau_max, a >= b, c >= b, a - 2b + c > 0) and
+ * in its fp32 order:
+ *     cand_f0 = fl(sample_rate / fl((float)tau + delta)),   cand_ap = d'(tau),   cand_logf = (float)log2((double)cand_f0)
+ * (the fp64 logarithm rounded once to fp32, as nsg_f0_path_stats takes logarithms).
+ * cand_f0, cand_ap, cand_logf [B][T][8] fp32, count [B][T] int32 (the candidates kept, 0 .. 8); every element is written exactly
+ * once: slots past count hold +0.0, 1.0 and +0.0, frames t >= T_b have count 0.  No workspace.  A frame's result is a function
+ * of its own samples only.
+ * NSG_E_INVALID / NSG_E_UNSUPPORTED: as nsg_audio_f0 (there is no threshold), a null output among them. */
+#define NSG_F0_MAX_CANDIDATES 8
+NSG_API int nsg_audio_f0_candidates(const float *wav, const int32_t *lengths, float *cand_f0, float *cand_ap, float *cand_logf,
+                                    int32_t *count, int32_t B, int32_t L, int32_t frame_length, int32_t hop, int32_t tau_min,
+                                    int32_t tau_max, float sample_rate, void *stream);
+
+/* A min-sum path over candidate tensors; nothing here knows of audio.  cand_logf, cand_ap, cand_f0 [B][T][8] fp32, count [B][T]
+ * int32 (each value clamped into [0, 8]; slots past it are never read), frames [B] int32 device memory (NULL: T; clamped into
+ * [0, T]): clip b has T_b = frames[b] frames.  The states of frame t are 0 (unvoiced) and k = 1 .. count[t] (slot k - 1).  All
+ * arithmetic is fp32, each operation rounded and never contracted, with logf_k, ap_k of frame t and logf'_j of frame t - 1:
+ *     local(t, 0) = unvoiced_cost
+ *     local(t, k) = fl(ap_k + fl(octave_cost * fl(logf_top - logf_k)))
+ *     trans(j, k) = +0.0                                      j = k = 0
+ *                 = vuv_cost                                  exactly one of j, k is 0
+ *                 = fl(jump_cost * |fl(logf_k - logf'_j)|)    both voiced
+ *     D(0, k)     = local(0, k)
+ *     D(t, k)     = fl(local(t, k) + min_j fl(D(t - 1, j) + trans(j, k)))       (the sum with trans = +0.0 is formed too)
+ * The minimum is taken over j = 0, 1, ..., count[t - 1] ascending with a strict <: ties go to the smallest j, which is the
+ * back-pointer.  The end state is the smallest k that minimises D(T_b - 1, k) (strict <, k ascending); the back-pointers give the
+ * path.  state [B][T] int32: the path, -1 for t >= T_b.  cost [B] fp32: D(T_b - 1, end state), +0.0 when T_b = 0.
+ * f0, ap [B][T] fp32: the chosen candidate's cand_f0 and cand_ap; on an unvoiced frame +0.0 and the least cand_ap of the frame's
+ * candidates (slot 0 first, then each later slot that is < the least so far), 1.0 when it has none; (+0.0, 1.0) for t >= T_b,
+ * nsg_audio_f0's convention.  Every element is written exactly once.  A clip's result does not depend on B or on its row.
+ * One wave per clip: lanes 0 .. 8 own the states and read frame t - 1's D and logf out of one another's registers; the
+ * candidate rows are staged into LDS 64 frames at a time; a lane packs its back-pointers 4 bits a frame, a 32-bit word per 8
+ * frames, into LDS when T <= NSG_F0_VITERBI_LDS_FRAMES = 2048 and into the workspace beyond (csrc/f0_track.hip).
+ * nsg_f0_viterbi_workspace_bytes(B, T): 0 for T <= 2048 (workspace may then be NULL).
+ * NSG_E_INVALID: a null pointer other than frames (and workspace where none is needed), B < 1, T < 1, a cost that is negative or
+ * not finite, logf_top not finite;  NSG_E_UNSUPPORTED: B * T >= 2^31;  NSG_E_WORKSPACE: fewer than
+ * nsg_f0_viterbi_workspace_bytes(B, T) bytes. */
+#define NSG_F0_VITERBI_LDS_FRAMES 2048
+NSG_API size_t nsg_f0_viterbi_workspace_bytes(int32_t B, int32_t T);
+NSG_API int nsg_f0_viterbi(const float *cand_logf, const float *cand_ap, const float *cand_f0, const int32_t *count,
+                           const int32_t *frames, int32_t *state, float *cost, float *f0, float *ap, int32_t B, int32_t T,
+                           float logf_top, float octave_cost, float jump_cost, float vuv_cost, float unvoiced_cost,
+                           void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

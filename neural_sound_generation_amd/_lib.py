@@ -97,6 +97,7 @@ NSG_VERSION = _CONSTS["NSG_VERSION"]      # bumped in the header on ANY signatur
 NSG_RELU_IN, NSG_TANH_OUT, NSG_OUT_F32, NSG_RELU_OUT, NSG_F32, NSG_BF16, NSG_C1_MOMENTS = (_CONSTS[n] for n in (
     "NSG_RELU_IN", "NSG_TANH_OUT", "NSG_OUT_F32", "NSG_RELU_OUT", "NSG_F32", "NSG_BF16", "NSG_C1_MOMENTS"))
 NSG_DTW_MAX_FRAMES, NSG_DTW_BLOCK_COLS = _CONSTS["NSG_DTW_MAX_FRAMES"], _CONSTS["NSG_DTW_BLOCK_COLS"]
+NSG_F0_MAX_CANDIDATES, NSG_F0_VITERBI_LDS_FRAMES = _CONSTS["NSG_F0_MAX_CANDIDATES"], _CONSTS["NSG_F0_VITERBI_LDS_FRAMES"]
 
 _lib = None
 

@@ -30,7 +30,9 @@ Judging a converted utterance (evaluate.test_conversion): mel_cepstra (the DCT-I
 1 .. n_ceps), dtw (batched dynamic time warping, csrc/dtw.hip) and mel_cepstral_distortion, the two combined into the dB
 figure of the voice-conversion literature.  An extension: the reference has no objective figure for converted speech.
 Beside the envelope, the pitch (evaluate.test_conversion_f0): f0 (YIN on the waveform, csrc/f0.hip; frame t is mel frame t),
-f0_distortion / f0_figures (F0 error in cents, voiced / unvoiced disagreement, log-F0 correlation along a dtw path).
+f0_distortion / f0_figures (F0 error in cents, voiced / unvoiced disagreement, log-F0 correlation along a dtw path);
+f0_candidates / f0_track (opt-in: each frame's strongest local minima of YIN's d', and a min-sum path over them that chooses
+one per frame or "unvoiced", csrc/f0_track.hip -- it repairs the octave errors and dropouts of a per-frame threshold).
 
 parity unpinned: librosa is absent (here, on the GPU box, and from the reference's own tree), and no file of the reference
 holds a waveform; tests compare with the numpy restatement in oracle/audio_oracle.py (same initial phases) and check the
@@ -287,21 +289,72 @@ def f0(wav, sample_rate=22050, hop_size=256, frame_length=1024, fmin=65.0, fmax=
     is d' at the chosen lag (the least d' of an unvoiced frame, 1.0 past the clip).  The waveform is zero outside the clip; a
     clip's frames are bit for bit what they are alone.  With inv_mel_spectrogram's hop_size * (T - 1) samples this gives T
     frames: mel frame t and F0 frame t are the same instant.  Every argument is checked before anything is launched."""
-    if isinstance(frame_length, bool) or not isinstance(frame_length, (int, np.integer)) or frame_length % 2 or not 64 <= frame_length <= 2048:
-        raise ValueError(f"f0: frame_length must be an even integer in [64, 2048], got {frame_length!r}")
-    if isinstance(hop_size, bool) or not isinstance(hop_size, (int, np.integer)) or hop_size < 1:
-        raise ValueError(f"f0: hop_size must be a positive integer, got {hop_size!r}")
-    if not 0 < threshold <= 1:
-        raise ValueError(f"f0: threshold must be in (0, 1], got {threshold!r}")
-    tau_min, tau_max = f0_lags(sample_rate, fmin, fmax)
-    as_numpy, B, L, lens = _clip_batch("f0", wav, lengths, 0)
-    if L < 1:
-        raise ValueError("f0: an empty waveform")
-    if B * (1 + L // hop_size) >= 2 ** 31:
-        raise ValueError(f"f0: {B} clips of {1 + L // hop_size} frames are 2^31 frames or more")
-    y = torch.from_numpy(np.ascontiguousarray(wav, dtype=np.float32)[None]).to(device) if as_numpy else wav
+    as_numpy, y, lens, tau_min, tau_max = _f0_args("f0", wav, sample_rate, hop_size, frame_length, fmin, fmax, lengths, device, threshold)
     freq, ap = ops.f0(y, int(frame_length), int(hop_size), tau_min, tau_max, float(threshold), float(sample_rate), lens)
     return (freq[0].cpu().numpy(), ap[0].cpu().numpy()) if as_numpy else (freq, ap)
+
+
+def _f0_args(fn, wav, sample_rate, hop_size, frame_length, fmin, fmax, lengths, device, threshold=None):
+    """The argument checks f0, f0_candidates and f0_track share (threshold: f0's alone), before anything is launched ->
+    (as_numpy, the (B, L) GPU batch, int32 host lengths or None, tau_min, tau_max)."""
+    if isinstance(frame_length, bool) or not isinstance(frame_length, (int, np.integer)) or frame_length % 2 or not 64 <= frame_length <= 2048:
+        raise ValueError(f"{fn}: frame_length must be an even integer in [64, 2048], got {frame_length!r}")
+    if isinstance(hop_size, bool) or not isinstance(hop_size, (int, np.integer)) or hop_size < 1:
+        raise ValueError(f"{fn}: hop_size must be a positive integer, got {hop_size!r}")
+    if threshold is not None and not 0 < threshold <= 1:
+        raise ValueError(f"{fn}: threshold must be in (0, 1], got {threshold!r}")
+    tau_min, tau_max = f0_lags(sample_rate, fmin, fmax)
+    as_numpy, B, L, lens = _clip_batch(fn, wav, lengths, 0)
+    if L < 1:
+        raise ValueError(f"{fn}: an empty waveform")
+    if B * (1 + L // hop_size) >= 2 ** 31:
+        raise ValueError(f"{fn}: {B} clips of {1 + L // hop_size} frames are 2^31 frames or more")
+    y = torch.from_numpy(np.ascontiguousarray(wav, dtype=np.float32)[None]).to(device) if as_numpy else wav
+    return as_numpy, y, lens, tau_min, tau_max
+
+
+def f0_candidates(wav, sample_rate=22050, hop_size=256, frame_length=1024, fmin=65.0, fmax=500.0, lengths=None, device="cuda:0"):
+    """The F0 candidates of every frame (include/nsg.h: nsg_audio_f0_candidates; csrc/f0.hip): the lags in f0_lags(sample_rate, fmin,
+    fmax) at which YIN's d' has a local minimum below 1 -- of them the 8 with the least d', by ascending lag -- each refined by
+    f0's parabola.  wav, lengths and the argument checks are f0's.  Returns (cand_f0 (T, 8) Hz, cand_ap (T, 8) = d' there, cand_logf
+    (T, 8) = log2 cand_f0, count (T,) int32) as numpy for a numpy waveform, GPU tensors (B, T, 8) / (B, T) for a batch; slots past
+    count hold (+0.0, 1.0, +0.0) and frames past a clip have count 0."""
+    as_numpy, y, lens, tau_min, tau_max = _f0_args("f0_candidates", wav, sample_rate, hop_size, frame_length, fmin, fmax, lengths, device)
+    out = ops.f0_candidates(y, int(frame_length), int(hop_size), tau_min, tau_max, float(sample_rate), lens)
+    return tuple(t[0].cpu().numpy() for t in out) if as_numpy else out
+
+
+# Praat's path-finder constants (Boersma 1993: octave cost, octave-jump cost, voiced / unvoiced cost) and, for the unvoiced state,
+# the middle of the window 0.2 .. 0.45 in which the prototype signal (tests/test_f0_track_host.py) is tracked without an error
+F0_TRACK_COSTS = dict(octave_cost=0.01, jump_cost=0.35, vuv_cost=0.14, unvoiced_cost=0.3)
+
+
+def f0_track(wav, sample_rate=22050, hop_size=256, frame_length=1024, fmin=65.0, fmax=500.0, lengths=None, device="cuda:0", octave_cost=0.01,
+             jump_cost=0.35, vuv_cost=0.14, unvoiced_cost=0.3, detail=False):
+    """Fundamental frequency by a path finder over YIN candidates (Boersma 1993, RAPT; include/nsg.h: nsg_audio_f0_candidates, then
+    nsg_f0_viterbi): instead of taking each frame's first lag under a threshold, keep the frame's 8 strongest local minima of d'
+    and let a dynamic programme choose one per frame, or "unvoiced".  A candidate costs its d' plus octave_cost per octave below
+    the top of the range (logf_top = log2(sample_rate / tau_min)); the unvoiced state costs unvoiced_cost; a step between two
+    candidates costs jump_cost per octave of the jump, a step between voiced and unvoiced vuv_cost.  This repairs f0's octave-up
+    picks and its dropouts where the period's d' sits just above the threshold.  wav, lengths and the argument checks are f0's;
+    a clip of `length` samples has 1 + length // hop_size frames.  Returns (f0, ap) in f0's shapes and conventions (ap of an
+    unvoiced frame: the least d' of its candidates, 1.0 if none), with detail=True (f0, ap, state, cost): state (T,) int32 is 0
+    for unvoiced, k for candidate slot k - 1 and -1 past the clip, cost the path's total.
+    The four defaults are Praat's path-finder constants and, for unvoiced_cost, a value from the window 0.2 .. 0.45 that tracks
+    the prototype signal without an error: a design choice, not a measurement on speech.  The costs are per frame step: they were
+    chosen at hop_size / sample_rate = 11.6 ms, and a caller who moves far from that should rescale jump_cost and vuv_cost
+    (a longer step allows a larger jump).  Every argument is checked before anything is launched."""
+    costs = dict(octave_cost=octave_cost, jump_cost=jump_cost, vuv_cost=vuv_cost, unvoiced_cost=unvoiced_cost)
+    for name, v in costs.items():
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0 <= v < float("inf"):
+            raise ValueError(f"f0_track: {name} must be a finite number >= 0, got {v!r}")
+    as_numpy, y, lens, tau_min, tau_max = _f0_args("f0_track", wav, sample_rate, hop_size, frame_length, fmin, fmax, lengths, device)
+    cf, ca, cl, cnt = ops.f0_candidates(y, int(frame_length), int(hop_size), tau_min, tau_max, float(sample_rate), lens)
+    frames = None if lens is None else 1 + lens // int(hop_size)
+    out = ops.f0_viterbi(cl, ca, cf, cnt, math.log2(float(sample_rate) / tau_min), *(float(v) for v in costs.values()), frames=frames)
+    state, cost, freq, ap = (t[0] for t in out) if as_numpy else out
+    res = (freq, ap, state, cost) if detail else (freq, ap)
+    return tuple(t.cpu().numpy() for t in res) if as_numpy else res
 
 
 def f0_figures(stats):

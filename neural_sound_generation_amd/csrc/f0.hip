@@ -1,5 +1,9 @@
-// F0 tracking (YIN) and F0 statistics along a warping path: the kernels behind audio.f0 and audio.f0_distortion
+// F0 tracking (YIN), the F0 candidates of a path finder, and F0 statistics along a warping path: the kernels behind audio.f0,
+// audio.f0_candidates (audio.f0_track; the path finder itself is csrc/f0_track.hip) and audio.f0_distortion
 // (evaluate.test_conversion_f0).  include/nsg.h states the arithmetic and its order; this file is how it is laid on the machine.
+// f0_kernel and f0_candidates_kernel share their front half as code -- f0_tile, f0_difference, f0_normalise: the spans, d, the
+// running sum, d' -- and the parabola (f0_refine); they differ in what they look for in d'.  f0_candidates_kernel's selection of
+// the 8 strongest minima is a rank count (the comment at the kernel says why).
 //
 // f0_kernel: the work is W * tau_max subtract-square-add triples a frame out of a span of W + tau_max samples, VALU work fed from
 // LDS.  A lane owns F0_RUN adjacent lags tau = F0_RUN g .. F0_RUN g + F0_RUN - 1 (lag 0 rides along: its d is 0 and is never
@@ -17,6 +21,8 @@
 //                             dl [F0_RUN G] d(tau), then d'(tau) in place
 //                             gt [NG4]     the totals of the groups of 8 lags (nsg.h: NSG_F0_LAG_GROUP)
 //                             ctl [2]      the first lag below the threshold; the bits of min d' (d' >= 0: its bits order as integers)
+//                                          (f0_candidates_kernel: ctl [18]: the 8 kept keys by rank, the count of minima, a pad;
+//                                          and the keys of all the frame's minima over sx, which is dead once d is formed)
 // The tail (running sum, d', the search) is a thread per group of 8 lags: its own chain over the group, then its own chain over
 // the earlier groups' totals (at most 127 adds); integer minima through LDS atomics (exact, order-free); the frame's first
 // thread advances to the local minimum, refines and stores.
@@ -45,13 +51,16 @@ struct F0Geom {
     int F;          // frames of a workgroup
     int tiles_t;    // workgroups of a clip
     int threads;
+    int ctl;        // control words of a frame (F0_CTL of f0_kernel, F0C_CTL of f0_candidates_kernel)
 };
-inline size_t f0_frame_floats(const F0Geom &q) { return (size_t)q.stride + q.RG + q.NG4 + 2; }
+constexpr int F0_CTL = 2;                          // the first lag below the threshold; the bits of min d'
+constexpr int F0C_CTL = 2 * NSG_F0_MAX_CANDIDATES + 2;   // the kept keys (64 bits each, by rank); the count of minima; a pad to 8 bytes
+inline size_t f0_frame_floats(const F0Geom &q) { return (size_t)q.stride + q.RG + q.NG4 + q.ctl; }
 
-inline F0Geom f0_geom(int W, int hop, int tau_min, int tau_max, int T)
+inline F0Geom f0_geom(int W, int hop, int tau_min, int tau_max, int T, int ctl)
 {
     F0Geom q;
-    q.W = W; q.hop = hop; q.tau_min = tau_min; q.tau_max = tau_max;
+    q.W = W; q.hop = hop; q.tau_min = tau_min; q.tau_max = tau_max; q.ctl = ctl;
     q.G = (tau_max + 1 + F0_RUN - 1) / F0_RUN;
     q.RG = F0_RUN * q.G;
     q.stride = (W + q.RG + 3) / 4 * 4 + 4;
@@ -80,45 +89,55 @@ __device__ __forceinline__ void f0_step(float (&acc)[F0_RUN], const float (&w)[F
         }
 }
 
+// ---- the front half both kernels run: a tile's place, its spans, d(tau), the running sum and d'(tau) -- stated here once ------
+// A workgroup's tile and its sections of LDS; thread (f, g) is run g of frame f (act: f < F), then group g of frame f
+struct F0Tile {
+    float *sx, *dl, *gt;        // [F][stride], [F][RG], [F][NG4]
+    int *ctl;                   // [F][q.ctl], 16-byte aligned (every section before it is a multiple of 4 floats a frame)
+    int tid, nthr, b, t0, len, Tb, nf, f, g;
+    bool act;
+};
+__device__ __forceinline__ F0Tile f0_tile(float *lds, const F0Geom &q, const int32_t *__restrict__ lengths, int L, int T)
+{
+    F0Tile m;
+    m.sx = lds;
+    m.dl = m.sx + q.F * q.stride;
+    m.gt = m.dl + q.F * q.RG;
+    m.ctl = reinterpret_cast<int *>(m.gt + q.F * q.NG4);
+    m.tid = threadIdx.x; m.nthr = blockDim.x;
+    m.b = blockIdx.x / q.tiles_t; m.t0 = (blockIdx.x - m.b * q.tiles_t) * q.F;
+    int len = lengths ? lengths[m.b] : L;
+    m.len = len < 0 ? 0 : (len > L ? L : len);         // the caller's to get right (nsg.h); clamped so that no read leaves wav
+    m.Tb = 1 + m.len / q.hop;
+    m.nf = T - m.t0 < q.F ? T - m.t0 : q.F;            // frames of this tile inside the tensor
+    m.f = m.tid / q.G; m.g = m.tid - m.f * q.G;
+    m.act = m.f < q.F;
+    return m;
+}
+
+// The spans, then d(tau) into dl; ends with the workgroup's barrier (which also publishes what the caller wrote to ctl before).
 // DIRECT (the diagnostics library's switch, for scripts/f0_timing.py): the loop the sliding window replaces -- a lane's lags are
 // g, g + G, ..., each pair reads its own x[s0 + j + tau] (consecutive lanes consecutive words) -- with the same chains, so the same bits.
 template <bool DIRECT>
-__global__ __launch_bounds__(F0_MAX_THREADS) void f0_kernel(const float *__restrict__ wav, const int32_t *__restrict__ lengths,
-                                                            float *__restrict__ f0, float *__restrict__ ap, int L, int T, F0Geom q,
-                                                            float threshold, float sample_rate)
+__device__ __forceinline__ void f0_difference(const F0Geom &q, const F0Tile &m, const float *__restrict__ wav, int L)
 {
-    extern __shared__ __attribute__((aligned(16))) float f0_lds[];
-    float *sx = f0_lds;                                // [F][stride]
-    float *dl = sx + q.F * q.stride;                   // [F][RG]
-    float *gt = dl + q.F * q.RG;                       // [F][NG4]
-    int *ctl = reinterpret_cast<int *>(gt + q.F * q.NG4);   // [F][2]
-    const int tid = threadIdx.x, nthr = blockDim.x;
-    const int b = blockIdx.x / q.tiles_t, t0 = (blockIdx.x - b * q.tiles_t) * q.F;
-    int len = lengths ? lengths[b] : L;
-    len = len < 0 ? 0 : (len > L ? L : len);           // the caller's to get right (nsg.h); clamped so that no read leaves wav
-    const int Tb = 1 + len / q.hop;
-    const int nf = T - t0 < q.F ? T - t0 : q.F;        // frames of this tile inside the tensor
-    float *of = f0 + (int64_t)b * T + t0, *oa = ap + (int64_t)b * T + t0;
-    if (t0 >= Tb) {                                    // the whole tile is past the clip (uniform over the workgroup)
-        for (int i = tid; i < nf; i += nthr) { of[i] = 0.f; oa[i] = 1.f; }
-        return;
-    }
-    const float *xb = wav + (int64_t)b * L;
+    float *sx = m.sx, *dl = m.dl;
+    const int tid = m.tid, nthr = m.nthr;
+    const float *xb = wav + (int64_t)m.b * L;
     const int S = q.W + q.RG;
     for (int f = 0; f < q.F; ++f) {                    // a frame's span, zero outside the clip and for frames past it
-        const bool livef = f < nf && t0 + f < Tb;
-        const int64_t s0 = (int64_t)(t0 + f) * q.hop - q.W / 2;
+        const bool livef = f < m.nf && m.t0 + f < m.Tb;
+        const int64_t s0 = (int64_t)(m.t0 + f) * q.hop - q.W / 2;
         for (int i = tid; i < q.stride; i += nthr) {
             const int64_t n = s0 + i;
-            const bool in = livef && i < S && n >= 0 && n < len;
+            const bool in = livef && i < S && n >= 0 && n < m.len;
             sx[f * q.stride + i] = in ? xb[in ? n : 0] : 0.f;
         }
     }
-    if (tid < q.F) { ctl[2 * tid] = 0x7fffffff; ctl[2 * tid + 1] = 0x7f800000; }
     __syncthreads();
 
-    const int f = tid / q.G, g = tid - f * q.G;
-    const bool act = f < q.F;
+    const int f = m.f, g = m.g;
+    const bool act = m.act;
     if (act && DIRECT) {
         const float *base = sx + f * q.stride, *win = base + g;
         float acc[F0_RUN];
@@ -172,12 +191,16 @@ __global__ __launch_bounds__(F0_MAX_THREADS) void f0_kernel(const float *__restr
         }
     }
     __syncthreads();
+}
 
-    // the running sum in nsg.h's order: thread (f, g) is group g of frame f, lags 8 g + 1 .. 8 g + 8
-    const bool grp = act && g < q.NG;
+// The running sum in nsg.h's order and d' over d in dl: thread (f, g), g < NG (grp), is group g of frame f, lags 8 g + 1 .. 8 g + 8,
+// and keeps its own d' in dpv (lags past tau_max: not set).  The caller puts a barrier before anybody reads another thread's d'.
+__device__ __forceinline__ void f0_normalise(const F0Geom &q, const F0Tile &m, bool grp, float (&dpv)[F0_GROUP])
+{
+    const int f = m.f, g = m.g;
     float dv[F0_GROUP], p[F0_GROUP];
     if (grp) {
-        const float *d = dl + f * q.RG + F0_GROUP * g + 1;
+        const float *d = m.dl + f * q.RG + F0_GROUP * g + 1;
         float run = 0.f;
 #pragma unroll
         for (int r = 0; r < F0_GROUP; ++r) {
@@ -186,16 +209,13 @@ __global__ __launch_bounds__(F0_MAX_THREADS) void f0_kernel(const float *__restr
             run = r == 0 ? dv[0] : run + dv[r];
             p[r] = run;
         }
-        gt[f * q.NG4 + g] = run;
+        m.gt[f * q.NG4 + g] = run;
     }
     __syncthreads();
     if (grp) {
         float G = 0.f;
-        for (int k = 0; k < g; ++k) G = G + gt[f * q.NG4 + k];
-        float *d = dl + f * q.RG + F0_GROUP * g + 1;
-        int first = 0x7fffffff;
-        float mn = __builtin_inff();
-        bool any = false;
+        for (int k = 0; k < g; ++k) G = G + m.gt[f * q.NG4 + k];
+        float *d = m.dl + f * q.RG + F0_GROUP * g + 1;
 #pragma unroll
         for (int r = 0; r < F0_GROUP; ++r) {
             const int tau = F0_GROUP * g + 1 + r;
@@ -204,11 +224,64 @@ __global__ __launch_bounds__(F0_MAX_THREADS) void f0_kernel(const float *__restr
                 const float num = dv[r] * (float)tau;
                 const float dp = c > 0.f ? num / c : 1.f;
                 d[r] = dp;
-                if (tau >= q.tau_min) {
-                    any = true;
-                    mn = dp < mn ? dp : mn;
-                    if (dp < threshold && first == 0x7fffffff) first = tau;
-                }
+                dpv[r] = dp;
+            }
+        }
+    }
+}
+
+// The parabola through d' at ts and its neighbours, under nsg.h's conditions and in its order: dp = the frame's d'(0 ..)
+__device__ __forceinline__ void f0_refine(const float *dp, int ts, int tau_max, float sample_rate, float &r_f0, float &r_ap)
+{
+    const float bb = dp[ts];
+    float delta = 0.f;
+    if (ts - 1 >= 1 && ts + 1 <= tau_max) {
+        const float a = dp[ts - 1], c = dp[ts + 1];
+        const float two_b = 2.f * bb;
+        const float den = (a - two_b) + c;
+        if (a >= bb && c >= bb && den > 0.f) {
+            const float diff = a - c;
+            const float half = 0.5f * diff;
+            delta = half / den;
+        }
+    }
+    const float period = (float)ts + delta;
+    r_f0 = sample_rate / period;
+    r_ap = bb;
+}
+
+template <bool DIRECT>
+__global__ __launch_bounds__(F0_MAX_THREADS) void f0_kernel(const float *__restrict__ wav, const int32_t *__restrict__ lengths,
+                                                            float *__restrict__ f0, float *__restrict__ ap, int L, int T, F0Geom q,
+                                                            float threshold, float sample_rate)
+{
+    extern __shared__ __attribute__((aligned(16))) float f0_lds[];
+    const F0Tile m = f0_tile(f0_lds, q, lengths, L, T);
+    int *ctl = m.ctl;                                  // [F][2]
+    const int tid = m.tid, f = m.f, g = m.g;
+    float *of = f0 + (int64_t)m.b * T + m.t0, *oa = ap + (int64_t)m.b * T + m.t0;
+    if (m.t0 >= m.Tb) {                                // the whole tile is past the clip (uniform over the workgroup)
+        for (int i = tid; i < m.nf; i += m.nthr) { of[i] = 0.f; oa[i] = 1.f; }
+        return;
+    }
+    if (tid < q.F) { ctl[2 * tid] = 0x7fffffff; ctl[2 * tid + 1] = 0x7f800000; }
+    f0_difference<DIRECT>(q, m, wav, L);
+
+    const bool grp = m.act && g < q.NG;
+    float dpv[F0_GROUP];
+    f0_normalise(q, m, grp, dpv);
+    if (grp) {
+        int first = 0x7fffffff;
+        float mn = __builtin_inff();
+        bool any = false;
+#pragma unroll
+        for (int r = 0; r < F0_GROUP; ++r) {
+            const int tau = F0_GROUP * g + 1 + r;
+            if (tau <= q.tau_max && tau >= q.tau_min) {
+                const float dp = dpv[r];
+                any = true;
+                mn = dp < mn ? dp : mn;
+                if (dp < threshold && first == 0x7fffffff) first = tau;
             }
         }
         if (first != 0x7fffffff) atomicMin(&ctl[2 * f], first);
@@ -216,34 +289,113 @@ __global__ __launch_bounds__(F0_MAX_THREADS) void f0_kernel(const float *__restr
     }
     __syncthreads();
 
-    if (act && g == 0 && f < nf) {
+    if (m.act && g == 0 && f < m.nf) {
         float r_f0 = 0.f, r_ap = 1.f;
-        if (t0 + f < Tb) {
-            const float *dp = dl + f * q.RG;
+        if (m.t0 + f < m.Tb) {
+            const float *dp = m.dl + f * q.RG;
             int ts = ctl[2 * f];
             if (ts == 0x7fffffff) {
                 r_ap = nsg_bitsf((unsigned)ctl[2 * f + 1]);
             } else {
                 while (ts + 1 <= q.tau_max && dp[ts + 1] < dp[ts]) ++ts;
-                const float bb = dp[ts];
-                float delta = 0.f;
-                if (ts - 1 >= 1 && ts + 1 <= q.tau_max) {
-                    const float a = dp[ts - 1], c = dp[ts + 1];
-                    const float two_b = 2.f * bb;
-                    const float den = (a - two_b) + c;
-                    if (a >= bb && c >= bb && den > 0.f) {
-                        const float diff = a - c;
-                        const float half = 0.5f * diff;
-                        delta = half / den;
-                    }
-                }
-                const float period = (float)ts + delta;
-                r_f0 = sample_rate / period;
-                r_ap = bb;
+                f0_refine(dp, ts, q.tau_max, sample_rate, r_f0, r_ap);
             }
         }
         of[f] = r_f0;
         oa[f] = r_ap;
+    }
+}
+
+// f0_candidates_kernel: the same front half, then the local minima of d' (nsg.h: nsg_audio_f0_candidates).  The top-8 selection is
+// a RANK COUNT, not eight rounds of a 64-bit atomicMin: a group's thread appends its minima's keys bits(d') << 32 | tau (d' >= 0: they
+// order as integers; a group of 8 lags holds at most 4) to the frame's list -- laid over the frame's span of samples, which is dead
+// once d is formed -- at slots one LDS atomic add hands out; after a barrier each minimum counts the keys below its own (one 8-byte
+// read a key, at an address the frame's threads share; a v_cmp_lt_u64 and an add), and the keys of rank < 8 go to slot rank.  A rank
+// is a property of the set, so the order in which the slots were handed out does not show.  In the ISA this is two barriers and one
+// returning atomic a thread; the eight rounds are sixteen barriers and eight ds_min_rtn_u64 that every holder of a minimum waits for.
+// Then thread k of the frame refines the key of rank k and stores it at the count of kept lags below its own: ascending lag.
+__global__ __launch_bounds__(F0_MAX_THREADS) void f0_candidates_kernel(const float *__restrict__ wav, const int32_t *__restrict__ lengths,
+                                                                       float *__restrict__ cand_f0, float *__restrict__ cand_ap,
+                                                                       float *__restrict__ cand_logf, int32_t *__restrict__ count, int L,
+                                                                       int T, F0Geom q, float sample_rate)
+{
+    constexpr int NC = NSG_F0_MAX_CANDIDATES;
+    extern __shared__ __attribute__((aligned(16))) float f0_lds[];
+    const F0Tile m = f0_tile(f0_lds, q, lengths, L, T);
+    const int tid = m.tid, f = m.f, g = m.g;
+    const int64_t row0 = (int64_t)m.b * T + m.t0;
+    if (m.t0 >= m.Tb) {                                // the whole tile is past the clip (uniform over the workgroup)
+        for (int i = tid; i < m.nf * NC; i += m.nthr) { cand_f0[row0 * NC + i] = 0.f; cand_ap[row0 * NC + i] = 1.f; cand_logf[row0 * NC + i] = 0.f; }
+        for (int i = tid; i < m.nf; i += m.nthr) count[row0 + i] = 0;
+        return;
+    }
+    if (tid < q.F) m.ctl[F0C_CTL * tid + 2 * NC] = 0;
+    f0_difference<false>(q, m, wav, L);
+
+    const bool grp = m.act && g < q.NG;
+    float dpv[F0_GROUP];
+    f0_normalise(q, m, grp, dpv);
+    __syncthreads();
+
+    const bool live = m.act && f < m.nf && m.t0 + f < m.Tb;
+    const float *dp = m.dl + (m.act ? f : 0) * q.RG;
+    unsigned long long *list = reinterpret_cast<unsigned long long *>(m.sx + (m.act ? f : 0) * q.stride);   // at most tau_max / 2 + 1 keys <= stride / 2
+    int *fctl = m.ctl + F0C_CTL * (m.act ? f : 0);
+    unsigned long long *sel = reinterpret_cast<unsigned long long *>(fctl);
+    unsigned mask = 0;                                 // bit r: lag 8 g + 1 + r is a candidate
+    if (grp && live) {
+        const int lo = q.tau_min > 2 ? q.tau_min : 2;
+#pragma unroll
+        for (int r = 0; r < F0_GROUP; ++r) {
+            const int tau = F0_GROUP * g + 1 + r;
+            if (tau >= lo && tau <= q.tau_max) {
+                const float v = dpv[r];
+                const bool right = tau == q.tau_max || v <= dp[tau < q.tau_max ? tau + 1 : tau];
+                if (v < dp[tau - 1] && right && v < 1.f) mask |= 1u << r;
+            }
+        }
+        if (mask) {
+            int slot = atomicAdd(&fctl[2 * NC], __popc(mask));
+#pragma unroll
+            for (int r = 0; r < F0_GROUP; ++r)
+                if (mask >> r & 1) list[slot++] = (unsigned long long)nsg_fbits(dpv[r]) << 32 | (unsigned)(F0_GROUP * g + 1 + r);
+        }
+    }
+    __syncthreads();
+    if (mask) {
+        const int n = fctl[2 * NC];
+#pragma unroll
+        for (int r = 0; r < F0_GROUP; ++r)
+            if (mask >> r & 1) {
+                const unsigned long long key = (unsigned long long)nsg_fbits(dpv[r]) << 32 | (unsigned)(F0_GROUP * g + 1 + r);
+                int rank = 0;
+                for (int i = 0; i < n; ++i) rank += list[i] < key ? 1 : 0;
+                if (rank < NC) sel[rank] = key;
+            }
+    }
+    __syncthreads();
+
+    if (m.act && f < m.nf) {
+        int n = live ? fctl[2 * NC] : 0;
+        n = n > NC ? NC : n;
+        const int64_t row = (row0 + f) * NC;
+        for (int k = g; k < NC; k += q.G) {
+            if (k < n) {
+                const int tau = (int)(unsigned)sel[k];
+                int pos = 0;
+                for (int j = 0; j < n; ++j) pos += (int)(unsigned)sel[j] < tau ? 1 : 0;
+                float r_f0, r_ap;
+                f0_refine(dp, tau, q.tau_max, sample_rate, r_f0, r_ap);
+                cand_f0[row + pos] = r_f0;
+                cand_ap[row + pos] = r_ap;
+                cand_logf[row + pos] = (float)log2((double)r_f0);
+            } else {
+                cand_f0[row + k] = 0.f;
+                cand_ap[row + k] = 1.f;
+                cand_logf[row + k] = 0.f;
+            }
+        }
+        if (g == 0) count[row0 + f] = n;
     }
 }
 
@@ -298,29 +450,53 @@ NSG_DIAG_SWITCH(int, g_f0_direct, 0)       // nsg_debug_set_f0_direct (diagnosti
 extern "C" NSG_API void nsg_debug_set_f0_direct(int on) { g_f0_direct = on; }
 #endif
 
+// The refusals nsg_audio_f0 and nsg_audio_f0_candidates share, in nsg_audio_f0's order; threshold: null where there is none
+static int f0_check(const char *fn, bool pointers, int B, int L, int frame_length, int hop, int tau_min, int tau_max, const float *threshold,
+                    float sample_rate)
+{
+    NSG_REQUIRE(pointers, NSG_E_INVALID, "%s: null pointer", fn);
+    NSG_REQUIRE(B >= 1 && L >= 1 && frame_length >= 1 && hop >= 1 && tau_min >= 1 && tau_max >= 1, NSG_E_INVALID,
+                "%s: non-positive size (B = %d, L = %d, frame_length = %d, hop = %d, tau_min = %d, tau_max = %d)", fn, B, L, frame_length,
+                hop, tau_min, tau_max);
+    NSG_REQUIRE(!threshold || (*threshold > 0.f && *threshold <= 1.f), NSG_E_INVALID, "%s: threshold = %g not in (0, 1]", fn,
+                threshold ? (double)*threshold : 0.0);
+    NSG_REQUIRE(sample_rate > 0.f && sample_rate <= 3.0e38f, NSG_E_INVALID, "%s: sample_rate = %g not positive and finite", fn, (double)sample_rate);
+    NSG_REQUIRE(frame_length % 2 == 0 && frame_length >= F0_MIN_W && frame_length <= F0_MAX_W, NSG_E_UNSUPPORTED,
+                "%s: frame_length = %d is odd or outside [%d, %d]", fn, frame_length, F0_MIN_W, F0_MAX_W);
+    NSG_REQUIRE(tau_min <= tau_max && tau_max <= F0_MAX_TAU, NSG_E_UNSUPPORTED, "%s: lags [%d, %d] outside 1 <= tau_min <= tau_max <= %d", fn,
+                tau_min, tau_max, F0_MAX_TAU);
+    NSG_REQUIRE((int64_t)B * (1 + L / hop) < 0x7fffffffLL, NSG_E_UNSUPPORTED, "%s: too many frames (B * T = %lld >= 2^31, outside the envelope)", fn,
+                (long long)B * (1 + L / hop));
+    return NSG_OK;
+}
+
 extern "C" {
 
 int nsg_audio_f0(const float *wav, const int32_t *lengths, float *f0, float *ap, int32_t B, int32_t L, int32_t frame_length, int32_t hop,
                  int32_t tau_min, int32_t tau_max, float threshold, float sample_rate, void *stream)
 {
-    NSG_REQUIRE(wav && f0 && ap, NSG_E_INVALID, "nsg_audio_f0: null pointer");
-    NSG_REQUIRE(B >= 1 && L >= 1 && frame_length >= 1 && hop >= 1 && tau_min >= 1 && tau_max >= 1, NSG_E_INVALID,
-                "nsg_audio_f0: non-positive size (B = %d, L = %d, frame_length = %d, hop = %d, tau_min = %d, tau_max = %d)", B, L, frame_length,
-                hop, tau_min, tau_max);
-    NSG_REQUIRE(threshold > 0.f && threshold <= 1.f, NSG_E_INVALID, "nsg_audio_f0: threshold = %g not in (0, 1]", (double)threshold);
-    NSG_REQUIRE(sample_rate > 0.f && sample_rate <= 3.0e38f, NSG_E_INVALID, "nsg_audio_f0: sample_rate = %g not positive and finite", (double)sample_rate);
-    NSG_REQUIRE(frame_length % 2 == 0 && frame_length >= F0_MIN_W && frame_length <= F0_MAX_W, NSG_E_UNSUPPORTED,
-                "nsg_audio_f0: frame_length = %d is odd or outside [%d, %d]", frame_length, F0_MIN_W, F0_MAX_W);
-    NSG_REQUIRE(tau_min <= tau_max && tau_max <= F0_MAX_TAU, NSG_E_UNSUPPORTED, "nsg_audio_f0: lags [%d, %d] outside 1 <= tau_min <= tau_max <= %d",
-                tau_min, tau_max, F0_MAX_TAU);
+    if (const int rc = f0_check("nsg_audio_f0", wav && f0 && ap, B, L, frame_length, hop, tau_min, tau_max, &threshold, sample_rate)) return rc;
     const int T = 1 + L / hop;
-    NSG_REQUIRE((int64_t)B * T < 0x7fffffffLL, NSG_E_UNSUPPORTED, "nsg_audio_f0: too many frames (B * T = %lld >= 2^31, outside the envelope)",
-                (long long)B * T);
-    const F0Geom q = f0_geom(frame_length, hop, tau_min, tau_max, T);
+    const F0Geom q = f0_geom(frame_length, hop, tau_min, tau_max, T, F0_CTL);
     const size_t lds = (size_t)q.F * f0_frame_floats(q) * sizeof(float);
     hipLaunchKernelGGL(g_f0_direct ? f0_kernel<true> : f0_kernel<false>, dim3((unsigned)(B * q.tiles_t)), dim3(q.threads), lds,
                        (hipStream_t)stream, wav, lengths, f0, ap, L, T, q, threshold, sample_rate);
     return nsg_check_launch("f0_kernel");
+}
+
+int nsg_audio_f0_candidates(const float *wav, const int32_t *lengths, float *cand_f0, float *cand_ap, float *cand_logf, int32_t *count,
+                            int32_t B, int32_t L, int32_t frame_length, int32_t hop, int32_t tau_min, int32_t tau_max, float sample_rate,
+                            void *stream)
+{
+    if (const int rc = f0_check("nsg_audio_f0_candidates", wav && cand_f0 && cand_ap && cand_logf && count, B, L, frame_length, hop, tau_min,
+                                tau_max, nullptr, sample_rate))
+        return rc;
+    const int T = 1 + L / hop;
+    const F0Geom q = f0_geom(frame_length, hop, tau_min, tau_max, T, F0C_CTL);
+    const size_t lds = (size_t)q.F * f0_frame_floats(q) * sizeof(float);
+    hipLaunchKernelGGL(f0_candidates_kernel, dim3((unsigned)(B * q.tiles_t)), dim3(q.threads), lds, (hipStream_t)stream, wav, lengths, cand_f0,
+                       cand_ap, cand_logf, count, L, T, q, sample_rate);
+    return nsg_check_launch("f0_candidates_kernel");
 }
 
 int nsg_f0_path_stats(const float *f0_a, const float *f0_b, const int32_t *path, const int32_t *steps, double *stats, int32_t B, int32_t Ta,

@@ -31,6 +31,7 @@ checkpoint layout, restated from the reference's src/test.py:73-106 and src/main
 """
 from __future__ import annotations
 
+import functools
 import os
 
 import numpy as np
@@ -297,7 +298,7 @@ def test_conversion(args, vqvae, pair_loader, device, epoch):
     return mcd_c, mcd_s
 
 
-def test_conversion_f0(args, vqvae, pair_loader, device, epoch, iters=None, angles0=None):
+def test_conversion_f0(args, vqvae, pair_loader, device, epoch, iters=None, angles0=None, *, tracker="yin", tracker_options=None):
     """The pitch figures of a speaker-conditioned VQ-VAE over parallel utterances, from waveforms: `pair_loader` yields
     (wav_src (B, Ls), len_src (B,), wav_tgt (B, Lt), len_tgt (B,), g_tgt (B,) int64) -- the same sentences by a source and a target
     speaker as zero-padded float32 waveforms at 22 050 Hz with their lengths in samples (host integers), and the target speakers'
@@ -311,8 +312,19 @@ def test_conversion_f0(args, vqvae, pair_loader, device, epoch, iters=None, angl
     each set pooled over all clips of the loader from the summed stats (audio.f0_figures of the sum, not a mean of per-clip
     ratios), "mcd" the mean over clips of the mel-cepstral distortion along the same paths in dB, "stats" the ten sums.  One host
     synchronisation, at the end.  ValueError, before anything of the batch is launched: a model without a speaker embedding, a
-    clip tensor of more than ops.DTW_MAX_FRAMES frames, a source clip of fewer than 4 frames; before anything at all: an empty loader."""
+    clip tensor of more than ops.DTW_MAX_FRAMES frames, a source clip of fewer than 4 frames; before anything at all: an empty loader.
+    tracker: "yin" (audio.f0, each frame on its own) or "viterbi" (audio.f0_track for all three waveforms: a path over each
+    frame's candidates, which repairs the octave-up picks and dropouts that a per-frame rule makes on a Griffin-Lim waveform and
+    that otherwise dominate the figures); tracker_options: audio.f0_track's costs (octave_cost, jump_cost, vuv_cost,
+    unvoiced_cost) for "viterbi".  Another tracker, or options that do not go with it, is a ValueError before anything is launched."""
     from . import audio
+    if tracker not in ("yin", "viterbi"):
+        raise ValueError(f"test_conversion_f0: tracker must be 'yin' or 'viterbi', got {tracker!r}")
+    options = dict(tracker_options or {})
+    if set(options) - (set(audio.F0_TRACK_COSTS) if tracker == "viterbi" else set()):
+        raise ValueError(f"test_conversion_f0: tracker_options {sorted(options)} do not go with tracker {tracker!r} "
+                         f"(viterbi takes {sorted(audio.F0_TRACK_COSTS)})")
+    track = audio.f0 if tracker == "yin" else functools.partial(audio.f0_track, **options)
     if getattr(vqvae, "n_speakers", None) is None:
         raise ValueError("test_conversion_f0: the model has no speaker embedding (VQVAE(..., n_speakers=N))")
     hop, fft = 256, 1024
@@ -336,9 +348,9 @@ def test_conversion_f0(args, vqvae, pair_loader, device, epoch, iters=None, angl
         _, converted = convert_voice(vqvae, mel_s[:, :, :Tc].contiguous(), g_tgt)
         a0 = angles0[k] if isinstance(angles0, (list, tuple)) else angles0
         wav_c = audio.inv_mel_spectrogram(converted.squeeze(1), fft_size=fft, hop_size=hop, iters=iters, angles0=a0)
-        f0_c, _ = audio.f0(wav_c, hop_size=hop, lengths=hop * (fc - 1))   # hop (Tc - 1) samples: Tc frames, fc of them the clip's
-        f0_t, _ = audio.f0(wav_tgt, hop_size=hop, lengths=lt)
-        f0_s, _ = audio.f0(wav_src, hop_size=hop, lengths=ls)
+        f0_c, _ = track(wav_c, hop_size=hop, lengths=hop * (fc - 1))   # hop (Tc - 1) samples: Tc frames, fc of them the clip's
+        f0_t, _ = track(wav_tgt, hop_size=hop, lengths=lt)
+        f0_s, _ = track(wav_src, hop_size=hop, lengths=ls)
         cep_t = audio.mel_cepstra(mel_t, ft)
         for row, (mel, frames, f0_x) in enumerate(((converted, fc, f0_c), (mel_s, fs, f0_s))):
             cost, steps, path = ops.dtw(audio.mel_cepstra(mel, frames), cep_t, frames, ft, want_path=True)

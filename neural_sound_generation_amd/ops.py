@@ -542,6 +542,72 @@ def f0(wav, frame_length, hop, tau_min, tau_max, threshold, sample_rate, lengths
     return f, ap
 
 
+F0_MAX_CANDIDATES = _lib.NSG_F0_MAX_CANDIDATES              # include/nsg.h: candidate slots of a frame
+F0_VITERBI_LDS_FRAMES = _lib.NSG_F0_VITERBI_LDS_FRAMES      # include/nsg.h: beyond it nsg_f0_viterbi wants a workspace
+
+
+def f0_candidates(wav, frame_length, hop, tau_min, tau_max, sample_rate, lengths=None, out=None):
+    """The F0 candidates of every frame (include/nsg.h: nsg_audio_f0_candidates): the local minima of YIN's d' below 1, the 8
+    strongest, by ascending lag.  wav (B, L) fp32 zero-padded clips; lengths as ops.f0 takes them -> (cand_f0, cand_ap, cand_logf
+    (B, T, 8) fp32, count (B, T) int32), T = 1 + L // hop; slots past count hold (+0.0, 1.0, +0.0).  out: the four tensors to
+    write instead of new ones."""
+    _chk(wav, "f0_candidates: wav")
+    if wav.dim() != 2 or wav.shape[0] < 1 or wav.shape[1] < 1:
+        raise _lib.NsgError(f"f0_candidates: wav {tuple(wav.shape)} is not (B, L) with B, L >= 1")
+    B, L = wav.shape
+    if int(hop) < 1:
+        raise _lib.NsgError(f"f0_candidates: hop = {hop} < 1")
+    T = 1 + L // int(hop)
+    lens = None if lengths is None else _lengths_on(lengths, "f0_candidates: lengths", B, 0, L, wav.device)
+    if out is None:
+        cf, ca, cl = (torch.empty(B, T, F0_MAX_CANDIDATES, dtype=torch.float32, device=wav.device) for _ in range(3))
+        cnt = torch.empty(B, T, dtype=torch.int32, device=wav.device)
+    else:
+        cf, ca, cl, cnt = out
+        for t, name, dtype, n in ((cf, "cand_f0", torch.float32, B * T * F0_MAX_CANDIDATES), (ca, "cand_ap", torch.float32, B * T * F0_MAX_CANDIDATES),
+                                  (cl, "cand_logf", torch.float32, B * T * F0_MAX_CANDIDATES), (cnt, "count", torch.int32, B * T)):
+            if _chk(t, f"f0_candidates: out {name}", dtype).numel() != n or t.device != wav.device:
+                raise _lib.NsgError(f"f0_candidates: out {name} {tuple(t.shape)} does not hold {n} elements")
+    _lib.call("nsg_audio_f0_candidates", _p(wav), _p(lens), _p(cf), _p(ca), _p(cl), _p(cnt), B, L, int(frame_length), int(hop), int(tau_min),
+              int(tau_max), float(sample_rate), _stream())
+    return cf, ca, cl, cnt
+
+
+def f0_viterbi(cand_logf, cand_ap, cand_f0, count, logf_top, octave_cost, jump_cost, vuv_cost, unvoiced_cost, frames=None, out=None):
+    """The min-sum path over candidate tensors (include/nsg.h: nsg_f0_viterbi).  cand_logf, cand_ap, cand_f0 (B, T, 8) fp32, count
+    (B, T) int32 (clamped into [0, 8] by the kernel); frames: None (all T), or (B,) frame counts in [0, T] (host: checked here and
+    uploaded; int32 on the device: the caller's) -> (state (B, T) int32, cost (B,) fp32, f0 (B, T), ap (B, T) fp32).  State 0 is
+    unvoiced, k >= 1 is slot k - 1, -1 is past the clip.  out: the four tensors to write instead of new ones."""
+    for t, name in ((cand_logf, "cand_logf"), (cand_ap, "cand_ap"), (cand_f0, "cand_f0")):
+        _chk(t, f"f0_viterbi: {name}")
+    _chk(count, "f0_viterbi: count", torch.int32)
+    if cand_logf.dim() != 3 or cand_logf.shape[0] < 1 or cand_logf.shape[1] < 1 or cand_logf.shape[2] != F0_MAX_CANDIDATES:
+        raise _lib.NsgError(f"f0_viterbi: cand_logf {tuple(cand_logf.shape)} is not (B, T, {F0_MAX_CANDIDATES}) with B, T >= 1")
+    B, T, _ = cand_logf.shape
+    if cand_ap.shape != cand_logf.shape or cand_f0.shape != cand_logf.shape or tuple(count.shape) != (B, T):
+        raise _lib.NsgError(f"f0_viterbi: cand_ap {tuple(cand_ap.shape)} / cand_f0 {tuple(cand_f0.shape)} / count {tuple(count.shape)} do not go "
+                            f"with cand_logf {tuple(cand_logf.shape)}")
+    if len({t.device for t in (cand_logf, cand_ap, cand_f0, count)}) != 1:
+        raise _lib.NsgError("f0_viterbi: the tensors are not on one device")
+    dev = cand_logf.device
+    fr = None if frames is None else _lengths_on(frames, "f0_viterbi: frames", B, 0, T, dev)
+    if out is None:
+        state = torch.empty(B, T, dtype=torch.int32, device=dev)
+        cost = torch.empty(B, dtype=torch.float32, device=dev)
+        f, ap = (torch.empty(B, T, dtype=torch.float32, device=dev) for _ in range(2))
+    else:
+        state, cost, f, ap = out
+        for t, name, dtype, n in ((state, "state", torch.int32, B * T), (cost, "cost", torch.float32, B), (f, "f0", torch.float32, B * T),
+                                  (ap, "ap", torch.float32, B * T)):
+            if _chk(t, f"f0_viterbi: out {name}", dtype).numel() != n or t.device != dev:
+                raise _lib.NsgError(f"f0_viterbi: out {name} {tuple(t.shape)} does not hold {n} elements")
+    nb = _lib.query("nsg_f0_viterbi_workspace_bytes", B, T)
+    ws = WS.get(nb, dev) if nb else None
+    _lib.call("nsg_f0_viterbi", _p(cand_logf), _p(cand_ap), _p(cand_f0), _p(count), _p(fr), _p(state), _p(cost), _p(f), _p(ap), B, T,
+              float(logf_top), float(octave_cost), float(jump_cost), float(vuv_cost), float(unvoiced_cost), _p(ws), nb, _stream())
+    return state, cost, f, ap
+
+
 def f0_path_stats(f0_a, f0_b, path, steps, out=None):
     """F0 statistics along warping paths (include/nsg.h: nsg_f0_path_stats).  f0_a (B, Ta), f0_b (B, Tb) fp32 (not > 0: unvoiced),
     path (B, Ta + Tb - 1, 2) int32 and steps (B,) int32 as ops.dtw returns them -> stats (B, 10) fp64:
