@@ -996,6 +996,70 @@ NSG_API int nsg_f0_viterbi(const float *cand_logf, const float *cand_ap, const f
                            float logf_top, float octave_cost, float jump_cost, float vuv_cost, float unvoiced_cost,
                            void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Augmenting a recording: tempo change without pitch change (waveform-similarity overlap-add, Verhelst & Roelands 1993), and
+ * gain plus noise at a level relative to the clip's RMS   src/util.py:106-134 (augment_audio_with_sox: `sox tempo ... gain ...`),
+ * src/util.py:164-196 (NoiseInjection).  parity unpinned: sox is absent; the contract is the one stated here, restated in fp32 and
+ * fp64 by tests/helpers/tempo_ref.py.  audio.tempo, audio.pitch_shift (tempo, then nsg_audio_resample), audio.mix_noise.
+ * ------------------------------------------------------------------------------------------- */
+
+/* S = segment length, O = overlap, W = search width, in samples; Ho = S - O, the output hop.  Per clip b: len = lengths[b]
+ * (lengths NULL: L), f = factor[b] (fp64; above 1 is faster), out_len = out_lengths[b], x = wav[b] read as zero outside [0, len)
+ * (samples past len are never read), M = ceil(out_len / Ho) segments:
+ *     q_0 = 0;   for m = 1 .. M - 1, in order:
+ *     n_m      = (int64) floor((double)(m Ho) * f)                      one fp64 product of an exact integer and f
+ *     d_m(dl)  = sum_{j=0}^{O-1} (x[q_{m-1} + Ho + j] - x[n_m + dl + j])^2      dl = 0 .. W - 1
+ *     q_m      = n_m + dl*,   dl* the SMALLEST dl that minimises d_m
+ * d_m is fp32: one chain per dl, the accumulator starts at +0.0 and takes fl(fl(a - c)^2) for j = 0, 1, ... in order; the
+ * subtraction, the product and the sum are each rounded and never contracted (nsg_audio_f0's rule).  Output sample k < out_len,
+ * with m = k / Ho and j = k mod Ho:
+ *     m >= 1 and j < O:   a = x[q_{m-1} + Ho + j],  b = x[q_m + j],  w = fl((float)j / (float)O):   out = fl(a + fl(w * fl(b - a)))
+ *     otherwise:          out = x[q_m + j]
+ * and +0.0 for out_len <= k < L_out.  (The cross-fade is written a + w (b - a): where the two segments agree the output is that
+ * value exactly, so f = 1 returns the input bit for bit -- dl = 0 gives d = +0.0, the first minimum -- and a signal with an
+ * integer period P <= W and small integer samples comes out as its own periodic continuation wherever every sample read lies
+ * inside the clip.)  positions (or NULL) [B][M_max] int32, M_max = ceil(L_out / Ho):  positions[b][m] = q_m for m < M, -1 beyond.
+ * A clip's output is a function of its own samples, length and factor: bit for bit independent of B, L, L_out, its row and any
+ * tiling.  wav [B][L] fp32; out [B][L_out] fp32, every element written exactly once.
+ * lengths, factor [B] fp64 and out_lengths [B] int32 are DEVICE memory.  PRECONDITION the entry point cannot check: factor finite
+ * and in [0.25, 4], 0 <= lengths[b] <= L, out_lengths[b] = floor((double)lengths[b] / factor[b]) <= L_out (under it every
+ * n_m < len); the caller checks it on the host copy it uploads.  The kernels clamp lengths into [0, L], out_lengths into
+ * [0, L_out] and take an n_m that is not in [0, len) as len (every sample read there is zero), so no access leaves a buffer.
+ * Two launches: a chain over the segments, one workgroup per clip -- tail and candidate window in LDS, lanes own runs of adjacent
+ * dl over a sliding register window, the minimum as an integer minimum of bits(d) << 32 | dl; the ranges of the next step are
+ * loaded while this one is searched -- and a sample-parallel pass that forms out from the positions (csrc/tsm.hip).  Without
+ * positions the q_m are kept in the workspace: nsg_audio_tempo_workspace_bytes(B, L_out, S, O) bytes ([B][M_max] int32); with
+ * positions no workspace is needed (it may be NULL).
+ * NSG_E_INVALID: a null wav / factor / out_lengths / out, B < 1, L < 1, L_out < 1;  NSG_E_UNSUPPORTED: O outside [1, 2048], S outside
+ * [2 O, 8192], W outside [1, 2048], B * L_out >= 2^31, L + S + W >= 2^31;  NSG_E_WORKSPACE: positions NULL and fewer workspace
+ * bytes than the query states. */
+NSG_API size_t nsg_audio_tempo_workspace_bytes(int32_t B, int32_t L_out, int32_t S, int32_t O);
+NSG_API int nsg_audio_tempo(const float *wav, const int32_t *lengths, const double *factor, const int32_t *out_lengths, float *out,
+                            int32_t *positions, int32_t B, int32_t L, int32_t L_out, int32_t S, int32_t O, int32_t W, void *workspace,
+                            size_t workspace_bytes, void *stream);
+
+/* Gain, and one noise recording added at a level relative to each clip's RMS (util.py:193-195 with sox's `gain` in front;
+ * data_energy / noise_energy there is sqrt(E_x / E_n): the two lengths cancel).  Per clip b of len = lengths[b] samples (lengths
+ * NULL: L), with v_i = noise[(offset[b] + i) mod Ln] -- one recording, read cyclically:
+ *     E_x = sum_{i < len} (double)x_i^2,   E_n = sum_{i < len} (double)v_i^2
+ *     s   = (float)((double)level[b] * sqrt(E_x / E_n))    in fp64, rounded once;  s = +0.0 where E_n = 0 or len = 0
+ *     out_i = fl(fl(gain[b] * x_i) + fl(s * v_i))   for i < len,   +0.0 for len <= i < L        (never contracted)
+ * The two sums are fp64 in this fixed order (csrc/nsg_reduce.h): the clip in partials of NSG_MIX_PARTIAL = 4096 samples; in
+ * partial p thread t of 256 adds the squares of samples 4096 p + t + 256 k, k = 0 .. 15, to 0.0 in that order, and the 256 thread
+ * sums are closed by the four-then-walk block sum (nsg_block_sum_four_walk); the partials are closed by the one-wave closer
+ * (nsg_wave_close_sum: lane l adds partials l, l + 64, ..., then lane 0 adds the 64 lane sums in lane order).  So a clip's result
+ * does not depend on B or on its row.  wav, out [B][L] fp32 (out may not alias wav); noise [Ln] fp32; gain, level [B] fp32 and
+ * offset [B] int32 in [0, Ln) are device memory (offset is clamped into that range, lengths into [0, L]); energy (or NULL)
+ * [B][2] fp64 receives (E_x, E_n).  Every element of out is written exactly once.  workspace:
+ * nsg_audio_mix_noise_workspace_bytes(B, L) bytes (the partials and s).
+ * NSG_E_INVALID: a null pointer other than lengths and energy, B < 1, L < 1, Ln < 1;  NSG_E_UNSUPPORTED: B * ceil(L / 1024) >= 2^31;
+ * NSG_E_WORKSPACE: fewer bytes than the query states. */
+#define NSG_MIX_PARTIAL 4096
+NSG_API size_t nsg_audio_mix_noise_workspace_bytes(int32_t B, int32_t L);
+NSG_API int nsg_audio_mix_noise(const float *wav, const int32_t *lengths, const float *noise, const float *gain, const float *level,
+                                const int32_t *offset, float *out, double *energy, int32_t B, int32_t L, int32_t Ln, void *workspace,
+                                size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

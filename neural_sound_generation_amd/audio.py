@@ -34,6 +34,12 @@ f0_distortion / f0_figures (F0 error in cents, voiced / unvoiced disagreement, l
 f0_candidates / f0_track (opt-in: each frame's strongest local minima of YIN's d', and a min-sum path over them that chooses
 one per frame or "unvoiced", csrc/f0_track.hip -- it repairs the octave errors and dropouts of a per-frame threshold).
 
+Augmenting a recording (the reference's src/util.py:106-196: `sox tempo ... gain ...` per utterance and NoiseInjection; sox is
+absent, so these are this project's definitions, include/nsg.h, not a parity claim): tempo (duration changed, pitch kept:
+waveform-similarity overlap-add, csrc/tsm.hip), pitch_shift (tempo, then resample: pitch changed, duration kept), mix_noise (gain,
+and a noise recording added at a level relative to the clip's RMS), random_augment (the reference's draws from a seeded CPU
+generator, then tempo and mix_noise); preprocess.process_utterances(augment_copies=n) writes augmented copies.  All opt-in.
+
 parity unpinned: librosa is absent (here, on the GPU box, and from the reference's own tree), and no file of the reference
 holds a waveform; tests compare with the numpy restatement in oracle/audio_oracle.py (same initial phases) and check the
 transform identities (istft(stft(y)) == y, the spectral error falls over the iterations).
@@ -541,6 +547,181 @@ def resample(wav, orig_sr, target_sr, lengths=None, device="cuda:0"):
 
 
 _resample = resample          # load_wav's flag has the function's name
+
+
+# The segment, search and overlap lengths of the tempo change, in milliseconds.  These are sox `tempo`'s defaults as recalled; sox
+# is not here to check them, so they are this project's constants, not a parity claim.
+TEMPO_SEGMENT_MS, TEMPO_SEARCH_MS, TEMPO_OVERLAP_MS = 82.0, 14.68, 12.0
+TEMPO_RANGE, GAIN_RANGE_DB, NOISE_LEVELS = (0.85, 1.15), (-6.0, 8.0), (0.0, 0.5)      # util.py:122-123, :168
+
+
+def tempo_sizes(sample_rate, segment_ms=TEMPO_SEGMENT_MS, search_ms=TEMPO_SEARCH_MS, overlap_ms=TEMPO_OVERLAP_MS):
+    """(S, O, W) in samples: segment, overlap and search width, each round(sample_rate * ms / 1000); (1808, 265, 324) at 22 050 Hz.
+    ValueError unless 1 <= O <= 2048, 2 O <= S <= 8192 and 1 <= W <= 2048 (include/nsg.h: nsg_audio_tempo's envelope)."""
+    vals = []
+    for nm, ms in (("segment_ms", segment_ms), ("overlap_ms", overlap_ms), ("search_ms", search_ms)):
+        if isinstance(ms, bool) or not isinstance(ms, (int, float, np.integer, np.floating)) or not 0 < ms < float("inf"):
+            raise ValueError(f"tempo: {nm} must be a positive finite number, got {ms!r}")
+        vals.append(ms)
+    if isinstance(sample_rate, bool) or not isinstance(sample_rate, (int, float, np.integer, np.floating)) or not 0 < sample_rate < float("inf"):
+        raise ValueError(f"tempo: sample_rate must be a positive finite number, got {sample_rate!r}")
+    S, O, W = (int(round(float(sample_rate) * float(ms) / 1000.0)) for ms in vals)
+    if not (1 <= O <= ops.TEMPO_MAX_OVERLAP and 2 * O <= S <= ops.TEMPO_MAX_SEGMENT and 1 <= W <= ops.TEMPO_MAX_SEARCH):
+        raise ValueError(f"tempo: {segment_ms} / {overlap_ms} / {search_ms} ms at {sample_rate} Hz are S = {S}, O = {O}, W = {W} samples; need "
+                         f"1 <= O <= {ops.TEMPO_MAX_OVERLAP}, 2 O <= S <= {ops.TEMPO_MAX_SEGMENT}, 1 <= W <= {ops.TEMPO_MAX_SEARCH}")
+    return S, O, W
+
+
+def _per_clip(fn, name, v, B, lo=None, hi=None, integer=False):
+    """`v`, a number or B numbers, as a (B,) array (float64, or int64 with integer=True), checked to be finite and in [lo, hi]."""
+    a = np.asarray(v)
+    if a.dtype == bool or not (np.issubdtype(a.dtype, np.integer) if integer else np.issubdtype(a.dtype, np.number)) or np.iscomplexobj(a):
+        raise ValueError(f"{fn}: {name} must be {'an integer' if integer else 'a number'} or {B} of them, got {v!r}")
+    a = a.astype(np.int64 if integer else np.float64)
+    a = np.broadcast_to(a, (B,)).copy() if a.ndim == 0 else a
+    if a.shape != (B,) or not np.isfinite(a).all() or (lo is not None and a.min() < lo) or (hi is not None and a.max() > hi):
+        raise ValueError(f"{fn}: {name} must be a finite number or {B} of them" + (f" in [{lo}, {hi}]" if lo is not None else "") + f", got {v!r}")
+    return a
+
+
+def _on_device(wav, as_numpy, device):
+    y = torch.from_numpy(np.ascontiguousarray(wav, dtype=np.float32)[None]).to(device) if as_numpy else wav
+    return _chk(y, "wav")
+
+
+def tempo(wav, factor, sample_rate=22050, segment_ms=TEMPO_SEGMENT_MS, search_ms=TEMPO_SEARCH_MS, overlap_ms=TEMPO_OVERLAP_MS, lengths=None,
+          device="cuda:0", detail=False):
+    """Tempo change without pitch change, what `sox tempo <factor>` is for (util.py:106-119), by waveform-similarity overlap-add
+    (include/nsg.h: nsg_audio_tempo states the arithmetic, csrc/tsm.hip runs it): the output is built from segments of S samples
+    that overlap by O; segment m is taken from the input near m (S - O) factor, at the one of W positions where it continues the
+    segment before it best (least sum of squared differences over the overlap), and cross-faded over the overlap.  (S, O, W) =
+    tempo_sizes(sample_rate, segment_ms, search_ms, overlap_ms).  factor: a number or one per clip, in [0.25, 4]; above 1 is
+    faster.  A clip of n samples gives floor(n / factor); factor 1 returns it bit for bit.  wav: a 1-D numpy waveform (returns
+    a float32 numpy waveform), or a float32 GPU tensor (B, L) of zero-padded clips with optional lengths (B,) integers in [0, L]
+    on the host (returns (tensor (B, max(1, max out_lengths)), out_lengths int32 numpy); the rest of a row is zeros).
+    detail=True also returns positions, int32: the input sample each segment starts at ((M,) numpy, or (B, M_max) on the
+    device with -1 past a clip's segments).  A clip's samples are bit for bit what they are alone.  Every argument is checked
+    before anything is launched."""
+    S, O, W = tempo_sizes(sample_rate, segment_ms, search_ms, overlap_ms)
+    as_numpy, B, L, lens = _clip_batch("tempo", wav, lengths, 0)
+    if L < 1:
+        raise ValueError("tempo: an empty waveform")
+    f = _per_clip("tempo", "factor", factor, B, ops.TEMPO_MIN_FACTOR, ops.TEMPO_MAX_FACTOR)
+    res = ops.tempo(_on_device(wav, as_numpy, device), f, S, O, W, lens, want_positions=detail)
+    if not as_numpy:
+        return res
+    n = int(res[1][0])
+    out = res[0][0, :n].cpu().numpy()
+    return (out, res[2][0, :-(-n // (S - O))].cpu().numpy()) if detail else out
+
+
+def pitch_shift(wav, num, den, sample_rate=22050, lengths=None, device="cuda:0"):
+    """Pitch times num / den with the duration kept: tempo(factor = den / num), which makes the clip num / den times as long at
+    its own pitch, then resample(orig_sr = num, target_sr = den), the existing kernel, which plays that back den / num times as
+    long: 196 / 185 is a semitone up.  num, den: positive integers with den / num in [0.25, 4] whose reduced ratio
+    resample_table accepts (its refusal is let through).  A clip of n samples gives ceil(floor(n num / den) P / Q) samples, (P, Q)
+    = resample_ratio(num, den) = (den, num) / gcd: n itself, or a sample or two off it.  wav and lengths as tempo takes them, every
+    clip at least den / num samples long; returns a numpy waveform, or (tensor, out_lengths int32 numpy).  Every argument is
+    checked before anything is launched."""
+    P, Q = resample_ratio(num, den)
+    if P != Q:
+        resample_table(P, Q)
+    as_numpy, B, L, lens = _clip_batch("pitch_shift", wav, lengths, 0)
+    factor = float(den) / float(num)
+    if not ops.TEMPO_MIN_FACTOR <= factor <= ops.TEMPO_MAX_FACTOR:
+        raise ValueError(f"pitch_shift: den / num = {factor} outside [{ops.TEMPO_MIN_FACTOR}, {ops.TEMPO_MAX_FACTOR}]")
+    src = lens if lens is not None else np.full(B, L, dtype=np.int32)
+    if L < 1 or ops.tempo_out_lengths(src, factor).min() < 1:
+        raise ValueError(f"pitch_shift: every clip must have at least den / num = {factor} samples")
+    y, mid = tempo(_on_device(wav, as_numpy, device), factor, sample_rate, lengths=lens)
+    out, out_lens = resample(y, int(num), int(den), lengths=mid)
+    return out[0, :int(out_lens[0])].cpu().numpy() if as_numpy else (out, out_lens)
+
+
+def mix_noise(wav, noise, level, offset, gain_db=0.0, lengths=None, device="cuda:0"):
+    """Gain, then a noise recording added at `level` relative to the clip's RMS: util.py:185-196 (NoiseInjection.inject_noise_sample)
+    with sox's `gain` (util.py:112-113) applied in front (include/nsg.h: nsg_audio_mix_noise):
+        out_i = gain x_i + level sqrt(E_x / E_n) v_i,   v_i = noise[(offset + i) mod len(noise)],   gain = (float)10^(gain_db / 20)
+    E_x, E_n the energies of the clip and of the noise under it (the gain does not enter the level: it is relative to the clip as
+    given).  noise: one recording, a 1-D numpy array or a 1-D float32 GPU tensor, read cyclically from `offset`.  level, gain_db:
+    a number or one per clip; offset: an integer or one per clip, in [0, len(noise)).  wav: a 1-D numpy waveform (returns numpy),
+    or a float32 GPU tensor (B, L) with optional lengths (B,) in [0, L] (returns a tensor (B, L), zeros past each length).  Every
+    argument is checked before anything is launched."""
+    as_numpy, B, L, lens = _clip_batch("mix_noise", wav, lengths, 0)
+    if L < 1:
+        raise ValueError("mix_noise: an empty waveform")
+    if isinstance(noise, np.ndarray):
+        if noise.ndim != 1 or len(noise) < 1 or not np.issubdtype(noise.dtype, np.floating):
+            raise TypeError(f"mix_noise: a numpy noise recording must be 1-D floating point and not empty, got {noise.dtype} {noise.shape}")
+    elif not torch.is_tensor(noise) or noise.dim() != 1 or noise.dtype != torch.float32 or noise.shape[0] < 1:
+        raise TypeError("mix_noise: noise must be a 1-D numpy array or a 1-D float32 tensor, not empty")
+    Ln = len(noise)
+    lv = _per_clip("mix_noise", "level", level, B)
+    off = _per_clip("mix_noise", "offset", offset, B, 0, Ln - 1, integer=True)
+    gain = 10.0 ** (_per_clip("mix_noise", "gain_db", gain_db, B) / 20.0)
+    if gain.max() > float(np.finfo(np.float32).max):
+        raise ValueError(f"mix_noise: gain_db = {gain_db!r} is not a finite fp32 gain")
+    y = _on_device(wav, as_numpy, device)
+    v = torch.from_numpy(np.ascontiguousarray(noise, dtype=np.float32)).to(y.device) if isinstance(noise, np.ndarray) else noise
+    out = ops.mix_noise(y, v, gain, lv, off, lens)
+    return out[0].cpu().numpy() if as_numpy else out
+
+
+def _range(fn, name, r):
+    if not (isinstance(r, (tuple, list)) and len(r) == 2 and all(isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) for v in r)
+            and np.isfinite(r[0]) and np.isfinite(r[1]) and r[0] <= r[1]):
+        raise ValueError(f"{fn}: {name} must be (low, high), finite, low <= high, got {r!r}")
+    return float(r[0]), float(r[1])
+
+
+def augment_draws(n, generator, tempo_range=TEMPO_RANGE, gain_range=GAIN_RANGE_DB, noise_len=None, noise_levels=NOISE_LEVELS):
+    """The reference's random augmentation parameters for n clips (util.py:128-131 tempo and gain, :182 the noise level, :188 where
+    the noise starts), from a CPU torch.Generator.  Per clip, in clip order, one fp64 u in [0, 1) per value (torch.rand(1,
+    dtype=float64, generator=generator)) in this order: tempo = low + (high - low) u; gain_db likewise; and, when noise_len is
+    given, level likewise and offset = min(floor(u noise_len), noise_len - 1).  -> dict of (n,) arrays: tempo, gain_db fp64, and
+    level fp64, offset int64 with noise.  Equal generator states give equal draws."""
+    if not isinstance(generator, torch.Generator) or generator.device.type != "cpu":
+        raise TypeError("augment: generator must be a CPU torch.Generator")
+    (t0, t1), (g0, g1), (l0, l1) = _range("augment", "tempo_range", tempo_range), _range("augment", "gain_range", gain_range), _range("augment", "noise_levels", noise_levels)
+    if not ops.TEMPO_MIN_FACTOR <= t0 <= t1 <= ops.TEMPO_MAX_FACTOR:
+        raise ValueError(f"augment: tempo_range {tempo_range!r} outside [{ops.TEMPO_MIN_FACTOR}, {ops.TEMPO_MAX_FACTOR}]")
+    if noise_len is not None and noise_len < 1:
+        raise ValueError("augment: an empty noise recording")
+
+    def u():
+        return float(torch.rand(1, dtype=torch.float64, generator=generator))
+
+    p = dict(tempo=np.empty(n), gain_db=np.empty(n))
+    if noise_len is not None:
+        p.update(level=np.empty(n), offset=np.empty(n, dtype=np.int64))
+    for i in range(n):
+        p["tempo"][i] = t0 + (t1 - t0) * u()
+        p["gain_db"][i] = g0 + (g1 - g0) * u()
+        if noise_len is not None:
+            p["level"][i] = l0 + (l1 - l0) * u()
+            p["offset"][i] = min(int(u() * noise_len), noise_len - 1)
+    return p
+
+
+def random_augment(wav, lengths, generator, tempo_range=TEMPO_RANGE, gain_range=GAIN_RANGE_DB, noise=None, noise_levels=NOISE_LEVELS,
+                   sample_rate=22050):
+    """util.py:122-134 (load_randomly_augmented_audio) and, with `noise`, :180-196 (NoiseInjection.inject_noise) for a batch: each clip
+    gets a tempo from tempo_range and a gain in dB from gain_range and, when noise (a 1-D recording, numpy or a float32 GPU tensor)
+    is given, that recording from a random offset at a level from noise_levels relative to the clip's RMS.  The values are
+    augment_draws(B, generator, ...): a CPU torch.Generator, a fixed order per clip (tempo, gain, level, offset), so equal seeds
+    give equal batches.  wav (B, L) float32 GPU tensor, lengths (B,) integers on the host or None.  Runs tempo, then mix_noise
+    (without noise: the gain alone) -> (out (B, max out_lengths), out_lengths int32 numpy, params: the draws)."""
+    as_numpy, B, L, lens = _clip_batch("random_augment", wav, lengths, 0)
+    if as_numpy:
+        raise TypeError("random_augment: expected a float32 tensor (B, L)")
+    Ln = None if noise is None else len(noise)
+    params = augment_draws(B, generator, tempo_range, gain_range, Ln, noise_levels)
+    y, out_lens = tempo(wav, params["tempo"], sample_rate, lengths=lens)
+    if noise is None:
+        out = mix_noise(y, torch.zeros(1, dtype=torch.float32, device=y.device), 0.0, 0, params["gain_db"], lengths=out_lens)
+    else:
+        out = mix_noise(y, noise, params["level"], params["offset"], params["gain_db"], lengths=out_lens)
+    return out, out_lens, params
 
 
 def trim_silence(wav, top_db=20.0, frame_length=2048, hop_length=512, lengths=None, device="cuda:0"):

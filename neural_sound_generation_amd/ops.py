@@ -630,6 +630,117 @@ def f0_path_stats(f0_a, f0_b, path, steps, out=None):
     return out
 
 
+TEMPO_MAX_OVERLAP, TEMPO_MAX_SEGMENT, TEMPO_MAX_SEARCH = 2048, 8192, 2048     # include/nsg.h: nsg_audio_tempo's envelope
+TEMPO_MIN_FACTOR, TEMPO_MAX_FACTOR = 0.25, 4.0
+
+
+def tempo_out_lengths(lengths, factor):
+    """out_lengths[b] = floor((double)lengths[b] / factor[b]) in fp64, as include/nsg.h states it (int64 numpy)."""
+    import numpy as np
+    return np.floor(np.asarray(lengths, dtype=np.float64) / np.asarray(factor, dtype=np.float64)).astype(np.int64)
+
+
+def tempo(wav, factor, S, O, W, lengths=None, want_positions=False, out=None):
+    """Waveform-similarity overlap-add (include/nsg.h: nsg_audio_tempo).  wav (B, L) fp32 zero-padded clips; factor: B finite
+    numbers in [0.25, 4] on the host (above 1 is faster); lengths: None (all L) or B integers in [0, L] on the host -- the
+    output lengths are formed from the host copies, which is why neither may be a device tensor -> (out (B, L_out) fp32 with
+    +0.0 past each clip, out_lengths (B,) int32 numpy = floor(lengths / factor), L_out = max(1, max out_lengths)) and, with
+    want_positions, positions (B, ceil(L_out / (S - O))) int32: each segment's start in the input, -1 past a clip's segments.
+    out: the tensor to write instead of a new one, (B, L_out') with L_out' >= every out_length (it fixes L_out).  The segment
+    sizes the kernel serves are the entry point's to state and refuse; everything the entry point cannot see is checked here."""
+    import numpy as np
+    _chk(wav, "tempo: wav")
+    if wav.dim() != 2 or wav.shape[0] < 1 or wav.shape[1] < 1:
+        raise _lib.NsgError(f"tempo: wav {tuple(wav.shape)} is not (B, L) with B, L >= 1")
+    B, L = wav.shape
+    S, O, W = int(S), int(O), int(W)
+    if O < 1 or S < 2 * O:
+        raise _lib.NsgError(f"tempo: need 1 <= O and 2 O <= S, got S = {S}, O = {O}")
+    f = np.asarray(factor, dtype=np.float64)
+    f = np.array(np.broadcast_to(f, (B,)) if f.ndim == 0 else f)                 # a writable, contiguous copy
+    if f.shape != (B,) or not np.isfinite(f).all() or f.min() < TEMPO_MIN_FACTOR or f.max() > TEMPO_MAX_FACTOR:
+        raise _lib.NsgError(f"tempo: factor must be {B} finite number(s) in [{TEMPO_MIN_FACTOR}, {TEMPO_MAX_FACTOR}], got {factor!r}")
+    if lengths is None:
+        lens_h = None
+    else:
+        if isinstance(lengths, torch.Tensor) and lengths.is_cuda:
+            raise _lib.NsgError("tempo: lengths must be on the host (the output lengths are formed from them)")
+        lens_h = lengths.numpy() if isinstance(lengths, torch.Tensor) else np.asarray(lengths)
+        if lens_h.shape != (B,) or not np.issubdtype(lens_h.dtype, np.integer):
+            raise _lib.NsgError(f"tempo: lengths: expected {B} integers, got {lens_h.dtype} {lens_h.shape}")
+        if lens_h.min() < 0 or lens_h.max() > L:
+            raise _lib.NsgError(f"tempo: lengths: every length must be in [0, {L}], got {int(lens_h.min())} .. {int(lens_h.max())}")
+    out_lens = tempo_out_lengths(np.full(B, L, dtype=np.int64) if lens_h is None else lens_h, f)
+    if out is None:
+        L_out = max(1, int(out_lens.max()))
+        if B * L_out >= 2 ** 31 - 1:
+            raise _lib.NsgError(f"tempo: {B} clips of {L_out} output samples are 2^31 or more")
+        out = torch.empty(B, L_out, dtype=torch.float32, device=wav.device)
+    else:
+        if _chk(out, "tempo: out").dim() != 2 or out.shape[0] != B or out.shape[1] < max(1, int(out_lens.max())) or out.device != wav.device:
+            raise _lib.NsgError(f"tempo: out {tuple(out.shape)} does not hold {B} clips of up to {int(out_lens.max())} samples")
+        L_out = out.shape[1]
+    packed = np.empty(4 * B, dtype=np.int32)            # one upload: factor (fp64, first: 8-byte aligned) | out_lengths | lengths
+    packed[:2 * B] = f.view(np.int32)
+    packed[2 * B:3 * B] = out_lens
+    packed[3 * B:] = 0 if lens_h is None else lens_h
+    packed = torch.from_numpy(packed).to(wav.device)
+    f_d, ol_d, lens_d = packed[:2 * B], packed[2 * B:3 * B], (None if lens_h is None else packed[3 * B:])
+    M_max = -(-L_out // (S - O))
+    pos = torch.empty(B, M_max, dtype=torch.int32, device=wav.device) if want_positions else None
+    ws, nb = (None, 0) if want_positions else _ws(wav.device, "nsg_audio_tempo_workspace_bytes", B, L_out, S, O)
+    _lib.call("nsg_audio_tempo", _p(wav), _p(lens_d), _p(f_d), _p(ol_d), _p(out), _p(pos), B, L, L_out, S, O, W, _p(ws), nb, _stream())
+    res = (out, out_lens.astype(np.int32))
+    return res + (pos,) if want_positions else res
+
+
+def mix_noise(wav, noise, gain, level, offset, lengths=None, out=None, want_energy=False):
+    """Gain and noise at a level relative to each clip's RMS (include/nsg.h: nsg_audio_mix_noise).  wav (B, L) fp32 zero-padded
+    clips, noise (Ln,) fp32 on the same device (one recording, read cyclically from offset[b]); gain, level: B numbers on the
+    host (rounded to fp32); offset: B integers in [0, Ln) on the host (checked here) -- or all three as (B,) fp32 / fp32 / int32
+    tensors already on the device, the caller's to have checked; lengths as ops.f0 takes them -> out (B, L) fp32,
+        out[b, i] = fl(fl(gain[b] x[b, i]) + fl(s_b noise[(offset[b] + i) mod Ln])),  s_b = (float)(level[b] sqrt(E_x / E_n)),
+    +0.0 past a clip's length; with want_energy also (B, 2) fp64 (E_x, E_n), the fp64 sums of squares s_b was formed from."""
+    import numpy as np
+    _chk(wav, "mix_noise: wav"); _chk(noise, "mix_noise: noise")
+    if wav.dim() != 2 or wav.shape[0] < 1 or wav.shape[1] < 1 or noise.dim() != 1 or noise.shape[0] < 1 or noise.device != wav.device:
+        raise _lib.NsgError(f"mix_noise: wav {tuple(wav.shape)} / noise {tuple(noise.shape)} are not (B, L) / (Ln,) on one device, B, L, Ln >= 1")
+    B, L = wav.shape
+    Ln = noise.shape[0]
+    on_device = [isinstance(v, torch.Tensor) and v.is_cuda for v in (gain, level, offset)]
+    if all(on_device):                                  # the caller's to have checked on the host copy they came from (the kernel clamps offset)
+        for name, v, dtype in (("gain", gain, torch.float32), ("level", level, torch.float32), ("offset", offset, torch.int32)):
+            if _chk(v, f"mix_noise: {name}", dtype).shape != (B,) or v.device != wav.device:
+                raise _lib.NsgError(f"mix_noise: {name} on the device must be a ({B},) tensor on wav's device, got {tuple(v.shape)}")
+        g_d, l_d, o_d = gain, level, offset
+    elif any(on_device):
+        raise _lib.NsgError("mix_noise: gain, level and offset must be all on the host or all on the device")
+    else:
+        packed = np.empty((3, B), dtype=np.int32)       # one upload for the three
+        for row, (name, v) in enumerate((("gain", gain), ("level", level))):
+            a = np.asarray(v, dtype=np.float64)
+            a = np.broadcast_to(a, (B,)) if a.ndim == 0 else a
+            if a.shape != (B,) or not np.isfinite(a).all():
+                raise _lib.NsgError(f"mix_noise: {name} must be {B} finite number(s), got {v!r}")
+            packed[row] = a.astype(np.float32).view(np.int32)
+        off = np.asarray(offset)
+        off = np.broadcast_to(off, (B,)) if off.ndim == 0 else off
+        if off.shape != (B,) or not np.issubdtype(off.dtype, np.integer) or off.min() < 0 or off.max() >= Ln:
+            raise _lib.NsgError(f"mix_noise: offset must be {B} integer(s) in [0, {Ln}), got {offset!r}")
+        packed[2] = off
+        packed = torch.from_numpy(packed).to(wav.device)
+        g_d, l_d, o_d = packed[0].view(torch.float32), packed[1].view(torch.float32), packed[2]
+    lens = None if lengths is None else _lengths_on(lengths, "mix_noise: lengths", B, 0, L, wav.device)
+    if out is None:
+        out = torch.empty_like(wav)
+    elif _chk(out, "mix_noise: out").numel() != B * L or out.device != wav.device or out.data_ptr() == wav.data_ptr():
+        raise _lib.NsgError(f"mix_noise: out {tuple(out.shape)} does not hold {B} x {L}, or is wav itself")
+    energy = torch.empty(B, 2, dtype=torch.float64, device=wav.device) if want_energy else None
+    ws, nb = _ws(wav.device, "nsg_audio_mix_noise_workspace_bytes", B, L)
+    _lib.call("nsg_audio_mix_noise", _p(wav), _p(lens), _p(noise), _p(g_d), _p(l_d), _p(o_d), _p(out), _p(energy), B, L, Ln, _p(ws), nb, _stream())
+    return (out, energy) if want_energy else out
+
+
 def vq_ema_update(codebook, ema_n, ema_s, n, s, decay=0.99, eps=1e-5):
     K, D = codebook.shape
     scratch = torch.empty(1, dtype=torch.float32, device=codebook.device)

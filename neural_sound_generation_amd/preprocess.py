@@ -91,21 +91,64 @@ def _resample_and_trim(wavs, rates, labels, sample_rate, trim_top_db, batch_clip
     return out
 
 
+def _augmented(clips, labels, copies, seed, tempo_range, noise, noise_levels, sample_rate, batch_clips, device):
+    """`copies` augmented versions of every clip, copy-major ([c * N + i] is copy c + 1 of clip i): a tempo change and, when noise
+    is given, that recording mixed in (audio.tempo, audio.mix_noise at 0 dB gain).  Every parameter is drawn before anything
+    runs, in that order, by audio.augment_draws from torch.Generator().manual_seed(seed) -- the gain is drawn too and not used,
+    so the other values are the ones audio.random_augment would draw -- and the kernels give a clip what they give it alone: the
+    result does not depend on batch_clips."""
+    N = len(clips)
+    if noise is not None:
+        noise = audio.load_wav(noise, sample_rate) if isinstance(noise, (str, os.PathLike)) else np.ascontiguousarray(noise, dtype=np.float32)
+        if noise.ndim != 1 or len(noise) < 1:
+            raise ValueError(f"process_utterances: noise must be a 1-D recording, got {noise.shape}")
+    params = audio.augment_draws(copies * N, torch.Generator().manual_seed(int(seed)), tempo_range, audio.GAIN_RANGE_DB,
+                                 None if noise is None else len(noise), noise_levels)
+    noise_d = None if noise is None else torch.from_numpy(noise).to(device)
+    out = [None] * (copies * N)
+    order = sorted(range(copies * N), key=lambda k: len(clips[k % N]))
+    for s in range(0, len(order), batch_clips):
+        idx = order[s:s + batch_clips]
+        lens = np.array([len(clips[k % N]) for k in idx], dtype=np.int32)
+        batch = np.zeros((len(idx), int(lens.max())), dtype=np.float32)
+        for r, k in enumerate(idx):
+            batch[r, :lens[r]] = clips[k % N]
+        y, out_lens = audio.tempo(torch.from_numpy(batch).to(device), params["tempo"][idx], sample_rate, lengths=lens)
+        if noise_d is not None:
+            y = audio.mix_noise(y, noise_d, params["level"][idx], params["offset"][idx], lengths=out_lens)
+        y = y.cpu().numpy()
+        for r, k in enumerate(idx):
+            out[k] = np.ascontiguousarray(y[r, :out_lens[r]])
+    return out, ["%s (augmented copy %d)" % (labels[k % N], k // N + 1) for k in range(copies * N)]
+
+
 def process_utterances(wavs, texts, out_dir, name="ljspeech", start_index=1, speaker_ids=None, sample_rate=22050, fft_size=1024,
-                       hop_size=256, n_mels=80, batch_clips=64, device="cuda:0", resample=False, trim_top_db=None):
+                       hop_size=256, n_mels=80, batch_clips=64, device="cuda:0", resample=False, trim_top_db=None, augment_copies=0,
+                       augment_seed=0, tempo_range=audio.TEMPO_RANGE, noise=None, noise_levels=audio.NOISE_LEVELS):
     """ljspeech._process_utterance over a list.  wavs: paths of PCM files (audio.load_wav) or 1-D float arrays; texts: one
     string each; speaker_ids: optional integers, appended as a fifth field.  Utterance i is written as
     `<name>-audio-%05d.npy` / `<name>-mel-%05d.npy` with number start_index + i.  Returns the metadata tuples
     (audio_filename, mel_filename, timesteps, text[, speaker]) in the order given.  The files do not depend on batch_clips.
     resample=True: a file at another rate is resampled to sample_rate instead of refused (arrays are taken to be at
     sample_rate).  trim_top_db: cut each clip to audio.trim_silence(clip, trim_top_db)'s span before the rescale, as
-    cmu_arctic._process_utterance does with 20.  With both off (the default) every step is the LJSpeech path's."""
+    cmu_arctic._process_utterance does with 20.  With both off (the default) every step is the LJSpeech path's.
+    augment_copies = n > 0: every utterance is also written n times augmented, as the reference augments what it loads
+    (util.py:122-134 and NoiseInjection): a tempo drawn from tempo_range and, when `noise` (a 1-D recording at sample_rate, or the
+    path of one) is given, that recording mixed in from a random offset at a level drawn from noise_levels relative to the
+    clip's RMS.  The augmentation runs after resample and trim and before the peak rescale; the reference's random gain is left
+    out on purpose, because the rescale to a peak of 0.999 cancels it.  Copy c = 1 .. n of utterance i is number
+    start_index + c * N + i (N utterances: the copies come after all the originals), with utterance i's text and speaker; the
+    returned metadata is in number order, N * (1 + n) rows.  The originals' files are bit for bit what they are without
+    augmentation.  All parameters are drawn up front from augment_seed (copy-major, then utterance order), so the files do not
+    depend on batch_clips.  augment_copies = 0 (the default) is the path without augmentation."""
     if len(texts) != len(wavs) or (speaker_ids is not None and len(speaker_ids) != len(wavs)):
         raise ValueError("process_utterances: wavs, texts and speaker_ids must have one entry per utterance")
     if batch_clips < 1:
         raise ValueError("process_utterances: batch_clips must be at least 1")
     if trim_top_db is not None and not trim_top_db > 0:
         raise ValueError(f"process_utterances: trim_top_db must be positive or None, got {trim_top_db!r}")
+    if isinstance(augment_copies, bool) or not isinstance(augment_copies, (int, np.integer)) or augment_copies < 0:
+        raise ValueError(f"process_utterances: augment_copies must be a non-negative integer, got {augment_copies!r}")
     os.makedirs(out_dir, exist_ok=True)
     prepare = bool(resample) or trim_top_db is not None
     clips, rates, labels = [], [], []
@@ -118,12 +161,21 @@ def process_utterances(wavs, texts, out_dir, name="ljspeech", start_index=1, spe
                 raise ValueError(f"{label}: sample rate {sr}, expected {sample_rate} (pass resample=True to resample it)")
         else:
             sr, wav = sample_rate, (audio.load_wav(w, sample_rate) if is_path else np.asarray(w, dtype=np.float32))
-        clips.append(wav if prepare else _rescaled(label, wav, fft_size))
+        clips.append(wav if prepare or augment_copies else _rescaled(label, wav, fft_size))
         rates.append(sr)
         labels.append(label)
     if prepare:
-        clips = [_rescaled(label, wav, fft_size)
-                 for label, wav in zip(labels, _resample_and_trim(clips, rates, labels, sample_rate, trim_top_db, batch_clips, device))]
+        clips = _resample_and_trim(clips, rates, labels, sample_rate, trim_top_db, batch_clips, device)
+    n_utt = len(clips)
+    if augment_copies:
+        for label, wav in zip(labels, clips):
+            if wav.ndim != 1 or len(wav) < 1:
+                raise ValueError(f"{label}: {wav.shape} samples; need a 1-D clip that is not empty")
+        more, more_labels = _augmented(clips, labels, int(augment_copies), augment_seed, tempo_range, noise, noise_levels, sample_rate,
+                                       batch_clips, device)
+        clips, labels = list(clips) + more, labels + more_labels
+    if prepare or augment_copies:
+        clips = [_rescaled(label, wav, fft_size) for label, wav in zip(labels, clips)]
     metadata = [None] * len(clips)
     order = sorted(range(len(clips)), key=lambda i: len(clips[i]))
     for s in range(0, len(order), batch_clips):
@@ -144,8 +196,8 @@ def process_utterances(wavs, texts, out_dir, name="ljspeech", start_index=1, spe
             audio_filename, mel_filename = "%s-audio-%05d.npy" % (name, start_index + i), "%s-mel-%05d.npy" % (name, start_index + i)
             np.save(join(out_dir, audio_filename), out.astype(np.float32), allow_pickle=False)
             np.save(join(out_dir, mel_filename), np.ascontiguousarray(mels[r, :N]), allow_pickle=False)
-            row = (audio_filename, mel_filename, len(out), texts[i])
-            metadata[i] = row + (int(speaker_ids[i]),) if speaker_ids is not None else row
+            row = (audio_filename, mel_filename, len(out), texts[i % n_utt])
+            metadata[i] = row + (int(speaker_ids[i % n_utt]),) if speaker_ids is not None else row
     return metadata
 
 
