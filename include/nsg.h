@@ -362,8 +362,10 @@ NSG_API int nsg_c1conv_bn_relu_forward(const float *img, const float *w, const f
  * moments (both calls; NULL allowed): NSG_C1_MOMENTS doubles = the image's tap moments S[t] = sum_p x[p][t] and
  * P[t][u] = sum_p x[p][t] x[p][u] over the 16 patch values of every output pixel (stored for values shifted by a constant,
  * the last entry: conditioning).  The bf16 layer takes its batch statistics
- * and its weight gradient from them (one pass over dy instead of two).  The training forward writes them when the pointer is
- * not NULL; the backward reads them when given and recomputes them from the image otherwise. */
+ * and its weight gradient from them (one pass over dy instead of two).  The bf16 training forward (y_dtype NSG_BF16,
+ * C = 32, 64, 96, 128 or 256: the widths of that path) writes them when the pointer is not NULL; the bf16 backward at those
+ * widths reads them when given and recomputes them from the image otherwise.  Every other form takes neither from them: the
+ * forward leaves the buffer as it was, the backward ignores it. */
 NSG_API int nsg_c1conv_bn_relu_backward(const float *img, const float *w, const float *bias, const float *gamma,
                                         const float *beta, const float *mean, const float *invstd, const void *dy,
                                         int32_t dy_dtype, float *dw, float *dbias, float *dgamma, float *dbeta, int32_t B,

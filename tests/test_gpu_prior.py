@@ -12,15 +12,9 @@ pytestmark = pytest.mark.gpu
 from neural_sound_generation_amd import ops  # noqa: E402
 from neural_sound_generation_amd.prior import GatedPixelCNN, GatedActivation  # noqa: E402
 from oracle import pixelcnn_oracle as P  # noqa: E402
+from tests.helpers.prior_ref import build  # noqa: E402,F401
 
 DEV = "cuda:0"
-
-
-def build(g):
-    input_dim, dim, n_layers, n_classes = (int(v) for v in g["cfg"])
-    m = GatedPixelCNN(input_dim, dim, n_layers, n_classes)
-    m.load_state_dict({k[4:]: torch.from_numpy(np.array(g[k])) for k in g.files if k.startswith("sd0.")})
-    return m.to(DEV), n_layers
 
 
 def test_gated_activation_and_cross_entropy_kernels():

@@ -14,6 +14,7 @@ pytestmark = pytest.mark.gpu
 from neural_sound_generation_amd import ops  # noqa: E402
 from neural_sound_generation_amd.prior import GatedPixelCNN  # noqa: E402
 from oracle import pixelcnn_oracle as P  # noqa: E402
+from tests.helpers.prior_ref import _ce64  # noqa: E402,F401
 
 DEV = "cuda:0"
 INPUT_DIM, DIM, N_LAYERS, N_CLASSES = 512, 64, 15, 10
@@ -193,29 +194,6 @@ def _ce_logits(regime, M, K, gen):
     elif regime == "constant":
         l = (torch.randn(M, 1, device=DEV, generator=gen) * 50).expand(M, K).contiguous()
     return l.contiguous(), t
-
-
-def _ce64(l, t, grad_scale):
-    """fp64 mean cross-entropy and its gradient on the fp32 logits, written so that nothing rounds at the scale of the row's
-    maximum mx = l[a]: with s = sum over k != a of exp(l[k] - mx), a row's loss is (mx - l[t]) + log1p(s), its softmax
-    exp(l[k] - mx) / (1 + s), and the gradient at a confident target -s / (1 + s).  (fp64 F.cross_entropy forms
-    mx + log(1 + s) - l[t]: on a row 30 above the rest that keeps a few digits of a 1e-13 loss.  It is held to this
-    closed form below, within its own rounding.)"""
-    l64 = l.double()
-    M, K = l64.shape
-    rows = torch.arange(M, device=l.device)
-    a = torch.argmax(l64, dim=1)                        # the first index of the maximum
-    mx = l64[rows, a]
-    e = torch.exp(l64 - mx[:, None])
-    e[rows, a] = 0.0
-    s = e.sum(dim=1)
-    loss = ((mx - l64[rows, t]) + torch.log1p(s)).mean()
-    e[rows, a] = 1.0
-    g = e / (1.0 + s)[:, None]
-    g[rows, t] -= 1.0
-    at = a == t
-    g[rows[at], t[at]] = -s[at] / (1.0 + s[at])
-    return loss, g * (grad_scale / M)
 
 
 def _ce_check(l, t, grad_scale, what):
