@@ -752,6 +752,37 @@ NSG_API size_t nsg_audio_griffin_lim_workspace_bytes(int32_t B, int32_t T, int32
 NSG_API int nsg_audio_griffin_lim(const float *S, const float *u, float *y, int32_t B, int32_t T, int32_t n_fft, int32_t hop,
                                   int32_t iters, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Griffin-Lim with momentum ("fast Griffin-Lim", Perraudin, Balazs, Sondergaard 2013; librosa.griffinlim's default since 0.7), an
+ * extension: the reference iterates without it.  Layouts, envelope and refusals are nsg_audio_griffin_lim's.  With X_0 = 0 and
+ * y_0 = istft(S exp(2 pi i u)), for i = 1 .. iters:
+ *     X_i = stft(y_{i-1})
+ *     t_i = X_i + momentum (X_i - X_{i-1})            per component, fp32
+ *     y_i = istft(S t_i / |t_i|)                      t_i = 0: phase 0, i.e. (S, 0), as np.angle(0) = 0
+ * and y = y_iters (librosa's angles = rebuilt - momentum / (1 + momentum) tprev up to a positive factor; t_1 = (1 + momentum) X_1
+ * has the phase of X_1).  c [B][T][F] complex (interleaved re, im), caller-owned, is the state X_{i-1}: its content on entry is
+ * never read (the first iteration uses X_0 = 0 without loading it, so it may hold NaN); with iters >= 1 it holds X_iters on
+ * return, with iters == 0 it is not written.  Each (frame, bin) of c is read and rewritten by the one thread that owns it.
+ * momentum == 0: c may be NULL and is not touched, and y is nsg_audio_griffin_lim's bit for bit (the same kernels).
+ * workspace: nsg_audio_griffin_lim_workspace_bytes(B, T, n_fft) bytes, the same two sections (the extra spectrum is the argument c).
+ * NSG_E_INVALID, before any launch: as nsg_audio_griffin_lim, momentum outside [0, 1] or NaN, c NULL with momentum > 0. */
+NSG_API int nsg_audio_griffin_lim_fast(const float *S, const float *u, float *y, float *c, int32_t B, int32_t T, int32_t n_fft,
+                                       int32_t hop, int32_t iters, float momentum, void *workspace, size_t workspace_bytes,
+                                       void *stream);
+
+/* The sums behind the spectral convergence || |stft(y)| - S || / || S || of waveforms y [B][hop*(T-1)] against magnitudes S [B][T][F],
+ * on Griffin-Lim's grid and reflect map (n_fft, hop, T as nsg_audio_griffin_lim takes them; a grid shorter than n_fft/2 is legal).
+ * With X = stft(y[b]) in fp32 and |X| = sqrtf(re^2 + im^2) as the phase kernels form it:
+ *     frame_sums[b][t] = { sum_f (double)(fl32(|X[t][f]| - S[t][f]))^2,  sum_f (double)S[t][f]^2 }       [B][T][2] fp64, may be NULL
+ *     clip_sums[b]     = the same pair summed over t                                                        [B][2] fp64
+ * Both sums are fp64 in one fixed order (csrc/nsg_reduce.h): over the bins of a frame, thread k of 256 adds the bins k, k + 256, ...
+ * to 0.0 in that order and the 256 thread sums are closed by the butterfly block sum (nsg_block_sum_butterfly); over the frames of a
+ * clip, thread k adds the frames k, k + 256, ... to 0.0 in that order, closed the same way.  Two launches give the same bits, and a
+ * clip's sums do not depend on B or on its row.  The spectrum is never stored and there is no workspace.  With frame_sums NULL the
+ * same adds run in one workgroup per clip, frame after frame: the same bits, without the parallelism over the frames.
+ * NSG_E_INVALID: a null y / S / clip_sums, B < 1, T < 2, hop < 1;  NSG_E_UNSUPPORTED: as nsg_audio_griffin_lim. */
+NSG_API int nsg_audio_spectral_convergence(const float *y, const float *S, double *frame_sums, double *clip_sums, int32_t B,
+                                           int32_t T, int32_t n_fft, int32_t hop, void *stream);
+
 /* X [B][1 + L/hop][F] complex (interleaved re, im) = librosa.stft(y[b], n_fft, hop): centred, reflect-padded, periodic Hann.
  * n_fft in {512, 1024, 2048}, L > n_fft/2 (as librosa requires), any hop > 0, B * (1 + L/hop) < 2^31. */
 NSG_API int nsg_audio_stft(const float *y, float *X, int32_t B, int32_t L, int32_t n_fft, int32_t hop, void *stream);

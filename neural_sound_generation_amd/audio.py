@@ -4,6 +4,10 @@ iterations), inverse pre-emphasis.  SURVEY.md section 8f row 4.
 
     inv_mel_spectrogram(mel_spectrogram, sample_rate, fft_size, hop_size, n_mel) -> waveform        (same signature)
 
+An extension, opt-in (the defaults are the reference's): griffin_lim / inv_mel_spectrogram(momentum=m) is Griffin-Lim with momentum
+("fast Griffin-Lim", Perraudin, Balazs, Sondergaard 2013: the phase of X + m (X - X_prev)), and spectral_convergence(y, S) reports
+how far |stft(y)| still is from the magnitudes asked for, || |stft(y)| - S || / || S || per clip.
+
 The arithmetic runs in libnsg.so (csrc/audio.hip: in-LDS FFT, fused STFT + phase update, overlap-add, recurrence); the mel
 filterbank and its pseudo-inverse are constants built once on the host with numpy (librosa.filters.mel restated: Slaney
 scale, area normalisation).  hparams are the reference's (src/hparams_tacotron.py:77-117: use_lws=False, power 1.5,
@@ -107,17 +111,57 @@ def mel_to_linear(mel: torch.Tensor, sample_rate=22050, fft_size=1024, n_mels=80
     return S
 
 
-def griffin_lim(S: torch.Tensor, fft_size=1024, hop_size=256, iters=GRIFFIN_LIM_ITERS, angles0: torch.Tensor | None = None) -> torch.Tensor:
-    """S (B, T, F) magnitudes -> y (B, hop*(T-1)).  angles0: uniform [0,1) numbers for the initial phases (drawn if None)."""
+def _momentum(fn, momentum):
+    """The momentum as the kernel gets it, rounded to fp32 (so a value that underflows to 0.f, 1e-50 say, is 0 here too and takes the
+    plain iteration with every check that goes with it)."""
+    if isinstance(momentum, bool) or not isinstance(momentum, (int, float, np.integer, np.floating)) or not 0.0 <= momentum <= 1.0:
+        raise ValueError(f"{fn}: momentum must be a number in [0, 1], got {momentum!r}")
+    return float(np.float32(momentum))
+
+
+def griffin_lim(S: torch.Tensor, fft_size=1024, hop_size=256, iters=GRIFFIN_LIM_ITERS, angles0: torch.Tensor | None = None, momentum=0.0,
+                state: torch.Tensor | None = None) -> torch.Tensor:
+    """S (B, T, F) magnitudes -> y (B, hop*(T-1)).  angles0: uniform [0,1) numbers for the initial phases (drawn if None).
+    momentum in [0, 1]: 0 is the reference's iteration y <- istft(S X / |X|), X = stft(y); above 0 it is fast Griffin-Lim
+    (Perraudin, Balazs, Sondergaard 2013; include/nsg.h: nsg_audio_griffin_lim_fast), which takes the phase of
+    X + momentum (X - X_prev) instead and keeps one more spectrum (0.99 is librosa's default).  state: a complex64 (B, T, F) GPU
+    tensor that receives X_iters, the last spectrum formed (momentum > 0 and iters >= 1; its content on entry is never read)."""
     _chk(S, "S")
+    momentum = _momentum("griffin_lim", momentum)
     B, T, F = S.shape
     if F != fft_size // 2 + 1:
         raise _lib.NsgError(f"griffin_lim: S has {F} bins, fft_size {fft_size} needs {fft_size // 2 + 1}")
+    if state is not None and (momentum == 0.0 or not torch.is_tensor(state) or state.dtype != torch.complex64 or tuple(state.shape) != (B, T, F)
+                              or state.device != S.device or not state.is_contiguous()):
+        raise ValueError(f"griffin_lim: state goes with momentum > 0 and is a contiguous complex64 tensor {(B, T, F)} on {S.device}")
     u = torch.rand(B, T, F, device=S.device) if angles0 is None else _chk(angles0.contiguous(), "angles0")
     y = torch.empty(B, hop_size * (T - 1), dtype=torch.float32, device=S.device)
     ws, nb = _ws(S.device, "nsg_audio_griffin_lim_workspace_bytes", B, T, fft_size)
-    _lib.call("nsg_audio_griffin_lim", _p(S), _p(u), _p(y), B, T, fft_size, hop_size, iters, _p(ws), nb, _stream())
+    if momentum == 0.0:
+        _lib.call("nsg_audio_griffin_lim", _p(S), _p(u), _p(y), B, T, fft_size, hop_size, iters, _p(ws), nb, _stream())
+    else:
+        c = torch.view_as_real(state) if state is not None else torch.empty(B, T, F, 2, dtype=torch.float32, device=S.device)
+        _lib.call("nsg_audio_griffin_lim_fast", _p(S), _p(u), _p(y), _p(c), B, T, fft_size, hop_size, iters, momentum, _p(ws), nb, _stream())
     return y
+
+
+def spectral_convergence(y: torch.Tensor, S: torch.Tensor, fft_size=1024, hop_size=256, per_frame=False):
+    """How far the waveforms y (B, hop*(T-1)) are from the magnitudes S (B, T, F) they were inverted from: the spectral
+    convergence || |stft(y)| - S || / || S || per clip (Sturmel & Daudet 2011), on griffin_lim's grid, as a float64 (B,) tensor
+    on the device: sqrt(num / den) of include/nsg.h's nsg_audio_spectral_convergence sums, 0 where both are 0 and inf where only
+    den is 0.  per_frame=True also returns the (B, T, 2) sums {num, den} of every frame.  Nothing synchronises."""
+    _chk(y, "y")
+    _chk(S, "S")
+    B, T, F = S.shape
+    if F != fft_size // 2 + 1 or tuple(y.shape) != (B, hop_size * (T - 1)):
+        raise _lib.NsgError(f"spectral_convergence: S {tuple(S.shape)} at fft_size {fft_size}, hop_size {hop_size} goes with y "
+                            f"{(B, hop_size * (T - 1))} and {fft_size // 2 + 1} bins, got y {tuple(y.shape)}")
+    frames = torch.empty(B, T, 2, dtype=torch.float64, device=S.device)
+    clips = torch.empty(B, 2, dtype=torch.float64, device=S.device)
+    _lib.call("nsg_audio_spectral_convergence", _p(y), _p(S), _p(frames), _p(clips), B, T, fft_size, hop_size, _stream())
+    num, den = clips.unbind(1)
+    sc = torch.where(num == 0, torch.zeros_like(num), torch.sqrt(num / den))
+    return (sc, frames) if per_frame else sc
 
 
 def stft(y: torch.Tensor, fft_size=1024, hop_size=256) -> torch.Tensor:
@@ -395,19 +439,25 @@ def inv_preemphasis(y: torch.Tensor, k=PREEMPHASIS) -> torch.Tensor:
 
 
 def inv_mel_spectrogram(mel_spectrogram, sample_rate=22050, fft_size=1024, hop_size=256, n_mel=80, iters=GRIFFIN_LIM_ITERS,
-                        angles0=None, device="cuda:0"):
+                        angles0=None, device="cuda:0", momentum=0.0):
     """audio_tacotron.py:99-116.  mel_spectrogram: numpy (n_mel, T) as in the reference (returns a float32 numpy waveform), or a
-    GPU tensor (B, n_mel, T) (returns a (B, hop*(T-1)) tensor)."""
+    GPU tensor (B, n_mel, T) (returns a (B, hop*(T-1)) tensor).  momentum: griffin_lim's (0, the default, is the reference's)."""
     as_numpy = isinstance(mel_spectrogram, np.ndarray)
     mel = torch.from_numpy(np.ascontiguousarray(mel_spectrogram, dtype=np.float32)).to(device) if as_numpy else mel_spectrogram
+    y = _invert_mel(mel, sample_rate, fft_size, hop_size, n_mel, iters, angles0, momentum)[2]
+    return y[0].cpu().numpy() if as_numpy else y
+
+
+def _invert_mel(mel, sample_rate, fft_size, hop_size, n_mel, iters, angles0, momentum):
+    """inv_mel_spectrogram's steps on a GPU tensor -> (S, Griffin-Lim's waveform, the waveform after inverse pre-emphasis)."""
     if mel.dim() == 2:
         mel = mel.unsqueeze(0)
     mel = mel.contiguous().float()
     S = mel_to_linear(mel, sample_rate, fft_size, n_mel)
     if angles0 is not None and not torch.is_tensor(angles0):
         angles0 = torch.from_numpy(np.ascontiguousarray(angles0, dtype=np.float32)).to(mel.device)
-    y = inv_preemphasis(griffin_lim(S, fft_size, hop_size, iters, angles0))
-    return y[0].cpu().numpy() if as_numpy else y
+    y = griffin_lim(S, fft_size, hop_size, iters, angles0, momentum)
+    return S, y, inv_preemphasis(y)
 
 
 def save_wav(wav, path, sample_rate=22050):

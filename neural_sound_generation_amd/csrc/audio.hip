@@ -4,7 +4,8 @@
 // their published algorithms are restated here as HIP kernels (and in numpy in oracle/audio_oracle.py):
 //   * radix-2 Stockham FFT of one frame per 256-thread workgroup, entirely in LDS (ping-pong buffers, twiddle table);
 //   * stft: centred frames with reflect padding x periodic Hann window -> FFT -> keep 1 + N/2 bins; fused with the
-//     Griffin-Lim phase update  spec = |S| * X / |X|;
+//     Griffin-Lim phase update  spec = |S| * X / |X|  (with momentum: the phase of X + momentum (X - X_prev), X_prev updated in place);
+//   * spectral convergence: the same transform with || |X| - S ||^2 and || S ||^2 summed in fp64 out of LDS (the spectrum is not stored);
 //   * istft: Hermitian extension -> inverse FFT -> x window -> frame buffer; overlap-add as a gather (deterministic)
 //     divided by the window's sum of squares, centre-trimmed;
 //   * inverse pre-emphasis y[n] = x[n] + k y[n-1]: chunked, each chunk re-running a discarded warm-up (k^W < 1e-9).
@@ -12,6 +13,7 @@
 // reflect-mapped index, Hann, two frames per complex FFT, |X| in LDS, the filterbank as a band matrix, dB, normalise, clip.
 // fp32 throughout (complex as float2).  These are LDS- / HBM-bound kernels; nothing here touches the matrix pipe.
 #include "nsg_common.h"
+#include "nsg_reduce.h"
 #include <math.h>
 
 namespace {
@@ -169,6 +171,124 @@ __global__ __launch_bounds__(256) void stft_phase_kernel(const float *__restrict
     }
 }
 
+// The windowed, reflect-padded frame t of clip yb (L samples) into b0, then its FFT: stft_phase_kernel's load and transform,
+// statement by statement, for the kernels below (which therefore form the X that nsg_audio_stft returns).
+template <int LOG2N>
+__device__ __forceinline__ v2f *stft_frame_lds(const float *__restrict__ yb, int t, int hop, int L, v2f *b0, v2f *b1, const v2f *tw, int tid)
+{
+    constexpr int N = 1 << LOG2N;
+    const int period = 2 * (L - 1);
+    for (int n = tid; n < N; n += 256) {
+        int idx = (t * hop + n - N / 2) % period;
+        if (idx < 0) idx += period;
+        if (idx >= L) idx = period - idx;
+        b0[n] = v2f{yb[idx] * hann_sin2(n, N), 0.f};
+    }
+    return fft_lds<LOG2N>(b0, b1, tw, tid, false);
+}
+
+// Fast Griffin-Lim's phase update (Perraudin, Balazs, Sondergaard 2013), one frame per workgroup as stft_phase_kernel:
+//     X = rfft(hann * frame of y);  t = X + momentum (X - prev);  prev <- X;  spec = S t / |t|   (t = 0 -> (S, 0))
+// prev [B][T][F] is the caller's state buffer.  Each (frame, bin) is read and rewritten by the one thread that owns it, so the
+// update is in place.  FIRST: prev is taken as 0 and is not loaded (it may hold anything, NaN included), only stored.
+template <int LOG2N, bool FIRST>
+__global__ __launch_bounds__(256) void stft_phase_momentum_kernel(const float *__restrict__ y, const float *__restrict__ S, v2f *__restrict__ spec,
+                                                                  v2f *__restrict__ prev, int T, int hop, int L, int F, float momentum)
+{
+    constexpr int N = 1 << LOG2N;
+    __shared__ v2f b0[N], b1[N], tw[N / 2];
+    const int tid = threadIdx.x;
+    const size_t fr = blockIdx.x;
+    const int b = (int)(fr / T), t = (int)(fr - (size_t)b * T);
+    fill_twiddles<LOG2N>(tw, tid);
+    v2f *r = stft_frame_lds<LOG2N>(y + (size_t)b * L, t, hop, L, b0, b1, tw, tid);
+    for (int f = tid; f < F; f += 256) {
+        const size_t i = fr * F + f;
+        const v2f X = r[f];
+        const v2f P = FIRST ? v2f{0.f, 0.f} : prev[i];
+        prev[i] = X;
+        const float tx = X.x + momentum * (X.x - P.x), ty = X.y + momentum * (X.y - P.y);
+        const float mag = sqrtf(tx * tx + ty * ty);
+        const float s = S[i];
+        spec[i] = mag > 0.f ? v2f{s * tx / mag, s * ty / mag} : v2f{s, 0.f};   // np.angle(0) = 0
+    }
+}
+
+// The two sums of frame t of clip b behind the spectral convergence, in every thread: { sum_f (|X[f]| - S[f])^2, sum_f S[f]^2 } with
+// |X| and the difference in fp32 (|X| as the phase kernels form it) and the squares and sums in fp64.  Order: thread tid adds its
+// bins tid, tid + 256, ... to 0.0 in that order; the 256 thread sums are closed by nsg_block_sum_butterfly.  Barriers inside:
+// called by all 256 threads from uniform control flow.  The spectrum never leaves LDS.
+template <int LOG2N>
+__device__ __forceinline__ void frame_convergence_sums(const float *__restrict__ yb, const float *__restrict__ Sf, int t, int hop, int L, int F,
+                                                       v2f *b0, v2f *b1, const v2f *tw, double *red, int tid, double &num, double &den)
+{
+    v2f *r = stft_frame_lds<LOG2N>(yb, t, hop, L, b0, b1, tw, tid);
+    double a = 0.0, d = 0.0;
+    for (int f = tid; f < F; f += 256) {
+        const v2f X = r[f];
+        const float s = Sf[f];
+        const float e = sqrtf(X.x * X.x + X.y * X.y) - s;
+        a += (double)e * (double)e;
+        d += (double)s * (double)s;
+    }
+    num = nsg_block_sum_butterfly(a, red, tid);
+    den = nsg_block_sum_butterfly(d, red, tid);
+}
+
+// one frame per workgroup: frame_sums[b][t] = frame_convergence_sums
+template <int LOG2N>
+__global__ __launch_bounds__(256) void convergence_frames_kernel(const float *__restrict__ y, const float *__restrict__ S, double *__restrict__ frame_sums,
+                                                                 int T, int hop, int L, int F)
+{
+    constexpr int N = 1 << LOG2N;
+    __shared__ v2f b0[N], b1[N], tw[N / 2];
+    __shared__ double red[4];
+    const int tid = threadIdx.x;
+    const size_t fr = blockIdx.x;
+    const int b = (int)(fr / T), t = (int)(fr - (size_t)b * T);
+    fill_twiddles<LOG2N>(tw, tid);
+    double num, den;
+    frame_convergence_sums<LOG2N>(y + (size_t)b * L, S + fr * F, t, hop, L, F, b0, b1, tw, red, tid, num, den);
+    if (tid == 0) { frame_sums[2 * fr] = num; frame_sums[2 * fr + 1] = den; }
+}
+
+// one clip per workgroup: clip_sums[b] = the frames' pairs summed over t.  Order: thread tid adds the frames tid, tid + 256, ... to
+// 0.0 in that order; the 256 thread sums are closed by nsg_block_sum_butterfly.
+__global__ __launch_bounds__(256) void convergence_clips_kernel(const double *__restrict__ frame_sums, double *__restrict__ clip_sums, int T)
+{
+    __shared__ double red[4];
+    const int tid = threadIdx.x;
+    const double *fs = frame_sums + (size_t)blockIdx.x * T * 2;
+    double a = 0.0, d = 0.0;
+    for (int t = tid; t < T; t += 256) { a += fs[2 * t]; d += fs[2 * t + 1]; }
+    a = nsg_block_sum_butterfly(a, red, tid);
+    d = nsg_block_sum_butterfly(d, red, tid);
+    if (tid == 0) { clip_sums[2 * blockIdx.x] = a; clip_sums[2 * blockIdx.x + 1] = d; }
+}
+
+// The same clip sums without a frame_sums buffer: one clip per workgroup, its frames one after another, frame t's pair added by
+// thread t % 256 -- the adds and their order are convergence_clips_kernel's, only the parallelism over the frames is lost.
+template <int LOG2N>
+__global__ __launch_bounds__(256) void convergence_serial_kernel(const float *__restrict__ y, const float *__restrict__ S, double *__restrict__ clip_sums,
+                                                                 int T, int hop, int L, int F)
+{
+    constexpr int N = 1 << LOG2N;
+    __shared__ v2f b0[N], b1[N], tw[N / 2];
+    __shared__ double red[4];
+    const int tid = threadIdx.x;
+    const int b = blockIdx.x;
+    fill_twiddles<LOG2N>(tw, tid);
+    double a = 0.0, d = 0.0;
+    for (int t = 0; t < T; ++t) {
+        double num, den;                                      // (the sums' barriers stand between a frame's last read of b0 / b1 and the next load)
+        frame_convergence_sums<LOG2N>(y + (size_t)b * L, S + ((size_t)b * T + t) * F, t, hop, L, F, b0, b1, tw, red, tid, num, den);
+        if ((t & 255) == tid) { a += num; d += den; }
+    }
+    a = nsg_block_sum_butterfly(a, red, tid);
+    d = nsg_block_sum_butterfly(d, red, tid);
+    if (tid == 0) { clip_sums[2 * b] = a; clip_sums[2 * b + 1] = d; }
+}
+
 // y[n] = x[n] + k y[n-1] is a decaying recurrence: the influence of y[n-W] on y[n] is k^W.  Each thread owns a chunk of
 // CH samples and starts the recurrence W samples earlier from zero, W chosen so that k^W < 1e-9 (605 samples for
 // k = 0.97): the discarded warm-up makes the chunks independent to far below fp32 rounding.  out-of-place.
@@ -285,6 +405,44 @@ inline GriffinLimLayout griffin_lim_layout(void *ws, int B, int T, int n_fft)
 }
 inline int log2_of(int n) { int l = 0; while ((1 << l) < n) ++l; return (1 << l) == n ? l : -1; }
 
+template <int LOG2N>
+void phase_launch(unsigned nfr, hipStream_t s, const float *y, const float *S, v2f *spec, v2f *prev, int T, int hop, int L, int F, float momentum, bool first)
+{
+    if (momentum == 0.f) hipLaunchKernelGGL((stft_phase_kernel<LOG2N>), dim3(nfr), dim3(256), 0, s, y, S, spec, T, hop, L, F, 0);
+    else if (first)      hipLaunchKernelGGL((stft_phase_momentum_kernel<LOG2N, true>), dim3(nfr), dim3(256), 0, s, y, S, spec, prev, T, hop, L, F, momentum);
+    else                 hipLaunchKernelGGL((stft_phase_momentum_kernel<LOG2N, false>), dim3(nfr), dim3(256), 0, s, y, S, spec, prev, T, hop, L, F, momentum);
+}
+
+// The launches of both Griffin-Lim entry points, whose checks have passed: y_0 = istft(S exp(2 pi i u)), then per iteration the
+// phase kernel and the istft.  momentum == 0 is the plain phase kernel, and c is not touched; otherwise c [B][T][F] complex is the
+// state X_{i-1}, taken as 0 (and not loaded) in the first iteration.
+void griffin_lim_launch(const float *S, const float *u, float *y, float *c, float momentum, int B, int T, int lg, int hop, int iters,
+                        const GriffinLimLayout &G, hipStream_t s)
+{
+    const int n_fft = 1 << lg;
+    const int F = n_fft / 2 + 1;
+    const int L = hop * (T - 1);
+    v2f *spec = G.spec;
+    float *frames = G.frames;
+    v2f *prev = reinterpret_cast<v2f *>(c);
+    const int64_t nspec = (int64_t)B * T * F;
+    const unsigned nfr = (unsigned)(B * T);
+    hipLaunchKernelGGL(init_phase_kernel, dim3(ew_blocks(nspec)), dim3(256), 0, s, S, u, spec, nspec);
+    auto istft = [&]() {
+        if (lg == 9)       hipLaunchKernelGGL((istft_frames_kernel<9>), dim3(nfr), dim3(256), 0, s, spec, frames, F);
+        else if (lg == 10) hipLaunchKernelGGL((istft_frames_kernel<10>), dim3(nfr), dim3(256), 0, s, spec, frames, F);
+        else               hipLaunchKernelGGL((istft_frames_kernel<11>), dim3(nfr), dim3(256), 0, s, spec, frames, F);
+        hipLaunchKernelGGL(overlap_add_kernel, dim3(ew_blocks((int64_t)B * L)), dim3(256), 0, s, frames, y, B, T, n_fft, hop, L);
+    };
+    istft();
+    for (int it = 0; it < iters; ++it) {
+        if (lg == 9)       phase_launch<9>(nfr, s, y, S, spec, prev, T, hop, L, F, momentum, it == 0);
+        else if (lg == 10) phase_launch<10>(nfr, s, y, S, spec, prev, T, hop, L, F, momentum, it == 0);
+        else               phase_launch<11>(nfr, s, y, S, spec, prev, T, hop, L, F, momentum, it == 0);
+        istft();
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -318,28 +476,55 @@ int nsg_audio_griffin_lim(const float *S, const float *u, float *y, int32_t B, i
     const GriffinLimLayout G = griffin_lim_layout(workspace, B, T, n_fft);
     NSG_REQUIRE(workspace && workspace_bytes >= G.bytes, NSG_E_WORKSPACE, "nsg_audio_griffin_lim: workspace too small");
     NSG_REQUIRE((int64_t)B * T < 0x7fffffff, NSG_E_UNSUPPORTED, "nsg_audio_griffin_lim: too many frames");
+    griffin_lim_launch(S, u, y, nullptr, 0.f, B, T, lg, hop, iters, G, (hipStream_t)stream);
+    return nsg_check_launch("griffin_lim");
+}
+
+// Griffin-Lim with momentum; the state X_{i-1} lives in the caller's c, the workspace is nsg_audio_griffin_lim's
+int nsg_audio_griffin_lim_fast(const float *S, const float *u, float *y, float *c, int32_t B, int32_t T, int32_t n_fft, int32_t hop, int32_t iters,
+                               float momentum, void *workspace, size_t workspace_bytes, void *stream)
+{
+    NSG_REQUIRE(S && u && y && B > 0 && T > 1 && hop > 0 && iters >= 0, NSG_E_INVALID, "nsg_audio_griffin_lim_fast: bad argument");
+    NSG_REQUIRE(momentum >= 0.f && momentum <= 1.f, NSG_E_INVALID, "nsg_audio_griffin_lim_fast: momentum must be in [0, 1]");      // (NaN fails both)
+    NSG_REQUIRE(c || momentum == 0.f, NSG_E_INVALID, "nsg_audio_griffin_lim_fast: momentum > 0 needs the state buffer c");
+    const int lg = log2_of(n_fft);
+    NSG_REQUIRE(lg >= 9 && lg <= 11, NSG_E_UNSUPPORTED, "nsg_audio_griffin_lim_fast: n_fft must be 512, 1024 or 2048");
+    NSG_REQUIRE(n_fft % hop == 0, NSG_E_UNSUPPORTED, "nsg_audio_griffin_lim_fast: hop must divide n_fft");
+    NSG_REQUIRE((int64_t)hop * (T - 1) < 0x7fffffff, NSG_E_UNSUPPORTED, "nsg_audio_griffin_lim_fast: too many samples (hop * (T - 1) >= 2^31)");
+    NSG_REQUIRE((int64_t)hop * (T - 1) >= 2, NSG_E_UNSUPPORTED, "nsg_audio_griffin_lim_fast: hop * (T - 1) must be at least 2 samples (a one-sample grid has no reflect padding)");
+    const GriffinLimLayout G = griffin_lim_layout(workspace, B, T, n_fft);
+    NSG_REQUIRE(workspace && workspace_bytes >= G.bytes, NSG_E_WORKSPACE, "nsg_audio_griffin_lim_fast: workspace too small");
+    NSG_REQUIRE((int64_t)B * T < 0x7fffffff, NSG_E_UNSUPPORTED, "nsg_audio_griffin_lim_fast: too many frames");
+    griffin_lim_launch(S, u, y, c, momentum, B, T, lg, hop, iters, G, (hipStream_t)stream);
+    return nsg_check_launch("griffin_lim_fast");
+}
+
+// frame_sums [B][T][2] (may be NULL), clip_sums [B][2] fp64: the sums behind ||  |stft(y)| - S || / || S ||
+int nsg_audio_spectral_convergence(const float *y, const float *S, double *frame_sums, double *clip_sums, int32_t B, int32_t T, int32_t n_fft,
+                                   int32_t hop, void *stream)
+{
+    NSG_REQUIRE(y && S && clip_sums && B > 0 && T > 1 && hop > 0, NSG_E_INVALID, "nsg_audio_spectral_convergence: bad argument");
+    const int lg = log2_of(n_fft);
+    NSG_REQUIRE(lg >= 9 && lg <= 11, NSG_E_UNSUPPORTED, "nsg_audio_spectral_convergence: n_fft must be 512, 1024 or 2048");
+    NSG_REQUIRE(n_fft % hop == 0, NSG_E_UNSUPPORTED, "nsg_audio_spectral_convergence: hop must divide n_fft");
+    NSG_REQUIRE((int64_t)hop * (T - 1) < 0x7fffffff, NSG_E_UNSUPPORTED, "nsg_audio_spectral_convergence: too many samples (hop * (T - 1) >= 2^31)");
+    NSG_REQUIRE((int64_t)hop * (T - 1) >= 2, NSG_E_UNSUPPORTED, "nsg_audio_spectral_convergence: hop * (T - 1) must be at least 2 samples (a one-sample grid has no reflect padding)");
+    NSG_REQUIRE((int64_t)B * T < 0x7fffffff, NSG_E_UNSUPPORTED, "nsg_audio_spectral_convergence: too many frames");
     hipStream_t s = (hipStream_t)stream;
     const int F = n_fft / 2 + 1;
     const int L = hop * (T - 1);
-    v2f *spec = G.spec;
-    float *frames = G.frames;
-    const int64_t nspec = (int64_t)B * T * F;
-    const unsigned nfr = (unsigned)(B * T);
-    hipLaunchKernelGGL(init_phase_kernel, dim3(ew_blocks(nspec)), dim3(256), 0, s, S, u, spec, nspec);
-    auto istft = [&]() {
-        if (lg == 9)       hipLaunchKernelGGL((istft_frames_kernel<9>), dim3(nfr), dim3(256), 0, s, spec, frames, F);
-        else if (lg == 10) hipLaunchKernelGGL((istft_frames_kernel<10>), dim3(nfr), dim3(256), 0, s, spec, frames, F);
-        else               hipLaunchKernelGGL((istft_frames_kernel<11>), dim3(nfr), dim3(256), 0, s, spec, frames, F);
-        hipLaunchKernelGGL(overlap_add_kernel, dim3(ew_blocks((int64_t)B * L)), dim3(256), 0, s, frames, y, B, T, n_fft, hop, L);
-    };
-    istft();
-    for (int it = 0; it < iters; ++it) {
-        if (lg == 9)       hipLaunchKernelGGL((stft_phase_kernel<9>), dim3(nfr), dim3(256), 0, s, y, S, spec, T, hop, L, F, 0);
-        else if (lg == 10) hipLaunchKernelGGL((stft_phase_kernel<10>), dim3(nfr), dim3(256), 0, s, y, S, spec, T, hop, L, F, 0);
-        else               hipLaunchKernelGGL((stft_phase_kernel<11>), dim3(nfr), dim3(256), 0, s, y, S, spec, T, hop, L, F, 0);
-        istft();
+    if (frame_sums) {
+        const unsigned nfr = (unsigned)(B * T);
+        if (lg == 9)       hipLaunchKernelGGL((convergence_frames_kernel<9>), dim3(nfr), dim3(256), 0, s, y, S, frame_sums, T, hop, L, F);
+        else if (lg == 10) hipLaunchKernelGGL((convergence_frames_kernel<10>), dim3(nfr), dim3(256), 0, s, y, S, frame_sums, T, hop, L, F);
+        else               hipLaunchKernelGGL((convergence_frames_kernel<11>), dim3(nfr), dim3(256), 0, s, y, S, frame_sums, T, hop, L, F);
+        hipLaunchKernelGGL(convergence_clips_kernel, dim3((unsigned)B), dim3(256), 0, s, frame_sums, clip_sums, T);
+    } else {
+        if (lg == 9)       hipLaunchKernelGGL((convergence_serial_kernel<9>), dim3((unsigned)B), dim3(256), 0, s, y, S, clip_sums, T, hop, L, F);
+        else if (lg == 10) hipLaunchKernelGGL((convergence_serial_kernel<10>), dim3((unsigned)B), dim3(256), 0, s, y, S, clip_sums, T, hop, L, F);
+        else               hipLaunchKernelGGL((convergence_serial_kernel<11>), dim3((unsigned)B), dim3(256), 0, s, y, S, clip_sums, T, hop, L, F);
     }
-    return nsg_check_launch("griffin_lim");
+    return nsg_check_launch("spectral_convergence");
 }
 
 // X [B][T][F] complex (interleaved re, im) = stft(y [B][L]) with T = 1 + L / hop frames (librosa.stft, centred, reflect, Hann)

@@ -298,7 +298,7 @@ def test_conversion(args, vqvae, pair_loader, device, epoch):
     return mcd_c, mcd_s
 
 
-def test_conversion_f0(args, vqvae, pair_loader, device, epoch, iters=None, angles0=None, *, tracker="yin", tracker_options=None):
+def test_conversion_f0(args, vqvae, pair_loader, device, epoch, iters=None, angles0=None, *, tracker="yin", tracker_options=None, momentum=0.0):
     """The pitch figures of a speaker-conditioned VQ-VAE over parallel utterances, from waveforms: `pair_loader` yields
     (wav_src (B, Ls), len_src (B,), wav_tgt (B, Lt), len_tgt (B,), g_tgt (B,) int64) -- the same sentences by a source and a target
     speaker as zero-padded float32 waveforms at 22 050 Hz with their lengths in samples (host integers), and the target speakers'
@@ -309,6 +309,9 @@ def test_conversion_f0(args, vqvae, pair_loader, device, epoch, iters=None, angl
     converted, the target and the source waveforms (F0 frame t is mel frame t); mel cepstra and ops.dtw with the path of converted
     against target and of source against target; ops.f0_path_stats along each path.  Returns
         {"converted": figures, "source": figures, "clips": n},   figures = {"f0_rmse_cents", "vuv_error", "f0_corr", "mcd", "stats"}
+    and, in "converted" alone, "spectral_convergence": the mean over clips of audio.spectral_convergence of Griffin-Lim's waveform
+    (before the inverse pre-emphasis) against the magnitudes it was inverted from, i.e. how far the inversion behind the converted
+    figures still is from the spectrum asked for; momentum is audio.griffin_lim's (0, the default, is the reference's iteration);
     each set pooled over all clips of the loader from the summed stats (audio.f0_figures of the sum, not a mean of per-clip
     ratios), "mcd" the mean over clips of the mel-cepstral distortion along the same paths in dB, "stats" the ten sums.  One host
     synchronisation, at the end.  ValueError, before anything of the batch is launched: a model without a speaker embedding, a
@@ -316,8 +319,10 @@ def test_conversion_f0(args, vqvae, pair_loader, device, epoch, iters=None, angl
     tracker: "yin" (audio.f0, each frame on its own) or "viterbi" (audio.f0_track for all three waveforms: a path over each
     frame's candidates, which repairs the octave-up picks and dropouts that a per-frame rule makes on a Griffin-Lim waveform and
     that otherwise dominate the figures); tracker_options: audio.f0_track's costs (octave_cost, jump_cost, vuv_cost,
-    unvoiced_cost) for "viterbi".  Another tracker, or options that do not go with it, is a ValueError before anything is launched."""
+    unvoiced_cost) for "viterbi".  Another tracker, options that do not go with it, or a momentum outside [0, 1] is a ValueError
+    before anything is launched."""
     from . import audio
+    momentum = audio._momentum("test_conversion_f0", momentum)
     if tracker not in ("yin", "viterbi"):
         raise ValueError(f"test_conversion_f0: tracker must be 'yin' or 'viterbi', got {tracker!r}")
     options = dict(tracker_options or {})
@@ -329,7 +334,7 @@ def test_conversion_f0(args, vqvae, pair_loader, device, epoch, iters=None, angl
         raise ValueError("test_conversion_f0: the model has no speaker embedding (VQVAE(..., n_speakers=N))")
     hop, fft = 256, 1024
     iters = audio.GRIFFIN_LIM_ITERS if iters is None else int(iters)
-    total = torch.zeros(2, 11, dtype=torch.float64, device=device)          # per set: the ten sums, the sum of the clips' MCD
+    total = torch.zeros(2, 12, dtype=torch.float64, device=device)          # per set: the ten sums, the sums of the clips' MCD and convergence
     n = 0
     for k, (wav_src, len_src, wav_tgt, len_tgt, g_tgt) in enumerate(pair_loader):
         ls = np.asarray(len_src.cpu() if torch.is_tensor(len_src) else len_src).astype(np.int64)
@@ -347,7 +352,8 @@ def test_conversion_f0(args, vqvae, pair_loader, device, epoch, iters=None, angl
         mel_t = audio.melspectrogram(wav_tgt, fft_size=fft, hop_size=hop, lengths=lt)
         _, converted = convert_voice(vqvae, mel_s[:, :, :Tc].contiguous(), g_tgt)
         a0 = angles0[k] if isinstance(angles0, (list, tuple)) else angles0
-        wav_c = audio.inv_mel_spectrogram(converted.squeeze(1), fft_size=fft, hop_size=hop, iters=iters, angles0=a0)
+        S_c, y_c, wav_c = audio._invert_mel(converted.squeeze(1), 22050, fft, hop, 80, iters, a0, momentum)      # inv_mel_spectrogram's steps
+        total[0, 11] += audio.spectral_convergence(y_c, S_c, fft, hop).sum()
         f0_c, _ = track(wav_c, hop_size=hop, lengths=hop * (fc - 1))   # hop (Tc - 1) samples: Tc frames, fc of them the clip's
         f0_t, _ = track(wav_tgt, hop_size=hop, lengths=lt)
         f0_s, _ = track(wav_src, hop_size=hop, lengths=ls)
@@ -364,12 +370,15 @@ def test_conversion_f0(args, vqvae, pair_loader, device, epoch, iters=None, angl
     sums = torch.cat((total, torch.stack(audio.f0_figures(total[:, :10]), dim=1)), dim=1).tolist()      # the one read-back
     out = {"clips": n}
     for row, name in enumerate(("converted", "source")):
-        rmse, vuv, corr = sums[row][11:]
+        rmse, vuv, corr = sums[row][12:]
         out[name] = {"f0_rmse_cents": rmse, "vuv_error": vuv, "f0_corr": corr, "mcd": sums[row][10] / n, "stats": sums[row][:10]}
+    out["converted"]["spectral_convergence"] = sums[0][11] / n
     print('====> Conversion test set: F0 RMSE {:.2f} cents, V/UV error {:.4f}, log-F0 correlation {:.4f}, MCD {:.4f} dB converted; '
           '{:.2f} cents, {:.4f}, {:.4f}, {:.4f} dB source against target ({} clips)'.format(
               *(out["converted"][k] for k in ("f0_rmse_cents", "vuv_error", "f0_corr", "mcd")),
               *(out["source"][k] for k in ("f0_rmse_cents", "vuv_error", "f0_corr", "mcd")), n))
+    print('====> Conversion test set: spectral convergence of the inversion {:.4f} ({} Griffin-Lim iterations, momentum {:g})'.format(
+        out["converted"]["spectral_convergence"], iters, momentum))
     return out
 
 
@@ -391,13 +400,15 @@ def continue_mels(vqvae, prior, mel: torch.Tensor, label: torch.Tensor, keep_fra
 
 @torch.no_grad()
 def continue_audio(vqvae, prior, wav: torch.Tensor, label: torch.Tensor, keep_frames: int, frames: int, g=None, generator=None,
-                   sample_rate=22050, fft_size=1024, hop_size=256, angles0=None, **controls):
+                   sample_rate=22050, fft_size=1024, hop_size=256, angles0=None, iters=None, momentum=0.0, **controls):
     """Continue recordings in time: wav (B, L) float32 on the GPU -> its mel (audio.melspectrogram, 1 + L // hop_size frames)
     -> continue_mels (the first keep_frames held, the grid sampled out to frames) -> waveform (audio.inv_mel_spectrogram;
-    angles0 (B, frames, 1 + fft_size / 2) fixes Griffin-Lim's initial phases).  Returns codes (B, 20, frames // 4), mels
+    angles0 (B, frames, 1 + fft_size / 2) fixes Griffin-Lim's initial phases; iters, default audio.GRIFFIN_LIM_ITERS, and momentum
+    are audio.griffin_lim's).  Returns codes (B, 20, frames // 4), mels
     (B, 1, 80, frames) and waveforms (B, hop_size * (frames - 1))."""
     from . import audio
     mel = audio.melspectrogram(wav, sample_rate, fft_size, hop_size, 80)
     codes, out = continue_mels(vqvae, prior, mel.unsqueeze(1), label, keep_frames, frames, g=g, generator=generator, **controls)
-    y = audio.inv_mel_spectrogram(out.squeeze(1), sample_rate, fft_size, hop_size, 80, angles0=angles0)
+    y = audio.inv_mel_spectrogram(out.squeeze(1), sample_rate, fft_size, hop_size, 80, audio.GRIFFIN_LIM_ITERS if iters is None else int(iters),
+                                  angles0=angles0, momentum=momentum)
     return codes, out, y
