@@ -769,6 +769,38 @@ NSG_API int nsg_audio_griffin_lim_fast(const float *S, const float *u, float *y,
                                        int32_t hop, int32_t iters, float momentum, void *workspace, size_t workspace_bytes,
                                        void *stream);
 
+/* Initial phases for Griffin-Lim by single-pass spectrogram inversion (SPSI; Beauregard, Harish, Wyse 2015), an extension: the
+ * reference starts from random phases.  A spectral peak at the fractional bin j + p advances its phase by hop (j + p) / n_fft
+ * turns a frame, and the bins of its main lobe are locked to it.  This is this project's own definition, with no parity claim.
+ *   S [B][T][F] fp32 magnitudes, frame-major, F = n_fft/2 + 1  ->  angles [B][T][F] fp32, in turns in [0, 1): what
+ *   nsg_audio_griffin_lim / _fast take as u.
+ * All phase arithmetic is fp64, in turns, reduced mod 1 after every frame (radians accumulated in fp32 over ~900 frames lose the
+ * phase); frac(x) = x - floor(x).  Per clip the state is phi[F], the centre phase last assigned to each bin, zero before frame 0.
+ * With r = hop / n_fft (a power of two, so every product by it is exact), for t = 0 .. T-1 and m = S[b][t]:
+ *   peaks     bin j in 1 .. F-2 is a peak iff m[j] > m[j-1] && m[j] > m[j+1], strict, on the fp32 values: a plateau is not a
+ *             peak, a NaN is never one.
+ *   offset    for a peak, with a, b, c = m[j-1], m[j], m[j+1] widened to fp64:  p = 0.5 * (a - c) / ((a - 2*b) + c), in that
+ *             order; the denominator is strictly negative and |p| < 0.5.
+ *   phase     val_j = phi[j] + (j + p) * r.
+ *   regions   between consecutive peaks j < j' the boundary v is the FIRST index of the minimum of m[j .. j']; bins <= v belong to
+ *             j, the rest to j'; bins below the first peak belong to it, bins above the last to the last.
+ *   update    every bin k owned by j gets phi[k] = frac(val_j) (identity phase locking);
+ *             a frame with no peak: phi[k] = frac(phi[k] + k * r) for every k.
+ *   output    angles[b][t][k] = (float) frac(phi[k] + 0.5 * k); a result that rounds to 1.0f is written as 0.0f.  (0.5 k is the
+ *             (-1)^k of a centred symmetric window's transform: adjacent main-lobe bins alternate in sign.)
+ * Every operation is a correctly rounded IEEE operation or an exact product by a power of two, so angles is a function of S
+ * alone, bit for bit: two calls agree, and a clip's angles do not depend on B or on its row.  The contract covers finite
+ * magnitudes; non-finite ones give unspecified angles (and touch no memory outside the arguments).
+ * Envelope: nsg_audio_griffin_lim's, except that T >= 1 (a single frame is legal, and hop * (T - 1) has no lower bound): n_fft in
+ * {512, 1024, 2048}, hop divides n_fft, B * T < 2^31.  angles must not overlap the workspace.
+ * workspace: nsg_audio_griffin_lim_workspace_bytes(B, T, n_fft) bytes (no query of its own); it holds, per (frame, bin), the fp64
+ * advance and the uint16 owner: 10 F bytes a frame of that workspace's 16 F - 8.  A first launch, parallel over the B T frames, writes them; a second,
+ * one workgroup per clip, walks the frames.  No atomics.
+ * NSG_E_INVALID, before any launch: a null S / angles, B < 1, T < 1, hop < 1;  NSG_E_UNSUPPORTED: another n_fft, a hop that does not
+ * divide it, too many frames or samples;  NSG_E_WORKSPACE: a null workspace or fewer bytes than the query's. */
+NSG_API int nsg_audio_spsi_phases(const float *S, float *angles, int32_t B, int32_t T, int32_t n_fft, int32_t hop, void *workspace,
+                                  size_t workspace_bytes, void *stream);
+
 /* The sums behind the spectral convergence || |stft(y)| - S || / || S || of waveforms y [B][hop*(T-1)] against magnitudes S [B][T][F],
  * on Griffin-Lim's grid and reflect map (n_fft, hop, T as nsg_audio_griffin_lim takes them; a grid shorter than n_fft/2 is legal).
  * With X = stft(y[b]) in fp32 and |X| = sqrtf(re^2 + im^2) as the phase kernels form it:

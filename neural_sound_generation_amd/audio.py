@@ -8,6 +8,12 @@ An extension, opt-in (the defaults are the reference's): griffin_lim / inv_mel_s
 ("fast Griffin-Lim", Perraudin, Balazs, Sondergaard 2013: the phase of X + m (X - X_prev)), and spectral_convergence(y, S) reports
 how far |stft(y)| still is from the magnitudes asked for, || |stft(y)| - S || / || S || per clip.
 
+Another, opt-in too: spsi_phases(S) / inv_mel_spectrogram(init="spsi") starts Griffin-Lim from the phases of a single-pass
+spectrogram inversion (Beauregard, Harish, Wyse 2015) instead of random ones: every spectral peak's phase advances by
+hop (j + p) / n_fft turns a frame, j + p its parabola-refined bin, and the bins of its lobe are locked to it (include/nsg.h states
+it; fp64 turns on the device, no FFT).  It buys the first iterations, not a better fixed point: on the export's mel magnitudes
+the random start ends slightly lower at 60 iterations.
+
 The arithmetic runs in libnsg.so (csrc/audio.hip: in-LDS FFT, fused STFT + phase update, overlap-add, recurrence); the mel
 filterbank and its pseudo-inverse are constants built once on the host with numpy (librosa.filters.mel restated: Slaney
 scale, area normalisation).  hparams are the reference's (src/hparams_tacotron.py:77-117: use_lws=False, power 1.5,
@@ -143,6 +149,41 @@ def griffin_lim(S: torch.Tensor, fft_size=1024, hop_size=256, iters=GRIFFIN_LIM_
         c = torch.view_as_real(state) if state is not None else torch.empty(B, T, F, 2, dtype=torch.float32, device=S.device)
         _lib.call("nsg_audio_griffin_lim_fast", _p(S), _p(u), _p(y), _p(c), B, T, fft_size, hop_size, iters, momentum, _p(ws), nb, _stream())
     return y
+
+
+def spsi_phases(S: torch.Tensor, fft_size=1024, hop_size=256) -> torch.Tensor:
+    """Initial phases for griffin_lim by single-pass spectrogram inversion (Beauregard, Harish, Wyse 2015; include/nsg.h:
+    nsg_audio_spsi_phases states the arithmetic): S (B, T, F) float32 magnitudes on the GPU -> (B, T, F) float32 on S's device, in
+    turns in [0, 1), what griffin_lim takes as angles0.  Each spectral peak's phase advances by hop (j + p) / n_fft turns a frame, j + p
+    its parabola-refined bin, and the bins around it are locked to it; fp64 on the device, a function of S alone bit for bit.
+    fft_size in {512, 1024, 2048}, hop_size a divisor of it, T >= 1.  Every argument is checked before anything is launched."""
+    if isinstance(fft_size, bool) or not isinstance(fft_size, (int, np.integer)) or fft_size not in (512, 1024, 2048):
+        raise ValueError(f"spsi_phases: fft_size must be 512, 1024 or 2048, got {fft_size!r}")
+    if isinstance(hop_size, bool) or not isinstance(hop_size, (int, np.integer)) or hop_size < 1 or fft_size % hop_size:
+        raise ValueError(f"spsi_phases: hop_size must be a positive integer that divides fft_size = {fft_size}, got {hop_size!r}")
+    if not torch.is_tensor(S) or S.dim() != 3 or S.shape[2] != fft_size // 2 + 1 or S.shape[0] < 1 or S.shape[1] < 1:
+        raise ValueError(f"spsi_phases: expected magnitudes (B, T, {fft_size // 2 + 1}) with B, T >= 1 for fft_size {fft_size}, got "
+                         f"{tuple(S.shape) if torch.is_tensor(S) else type(S).__name__}")
+    _chk(S, "S")
+    B, T, F = S.shape
+    if B * T >= 2 ** 31:
+        raise ValueError(f"spsi_phases: {B} clips of {T} frames are 2^31 frames or more")
+    angles = torch.empty(B, T, F, dtype=torch.float32, device=S.device)
+    ws, nb = _ws(S.device, "nsg_audio_griffin_lim_workspace_bytes", B, T, int(fft_size))
+    _lib.call("nsg_audio_spsi_phases", _p(S), _p(angles), B, T, int(fft_size), int(hop_size), _p(ws), nb, _stream())
+    return angles
+
+
+INITS = ("random", "spsi")
+
+
+def _init(fn, init, angles0):
+    """inv_mel_spectrogram's `init` checked against its angles0, before anything is launched."""
+    if not isinstance(init, str) or init not in INITS:
+        raise ValueError(f"{fn}: init must be one of {INITS}, got {init!r}")
+    if init == "spsi" and angles0 is not None:
+        raise ValueError(f"{fn}: init='spsi' computes the initial phases itself; it does not go with angles0")
+    return init
 
 
 def spectral_convergence(y: torch.Tensor, S: torch.Tensor, fft_size=1024, hop_size=256, per_frame=False):
@@ -439,23 +480,30 @@ def inv_preemphasis(y: torch.Tensor, k=PREEMPHASIS) -> torch.Tensor:
 
 
 def inv_mel_spectrogram(mel_spectrogram, sample_rate=22050, fft_size=1024, hop_size=256, n_mel=80, iters=GRIFFIN_LIM_ITERS,
-                        angles0=None, device="cuda:0", momentum=0.0):
+                        angles0=None, device="cuda:0", momentum=0.0, init="random"):
     """audio_tacotron.py:99-116.  mel_spectrogram: numpy (n_mel, T) as in the reference (returns a float32 numpy waveform), or a
-    GPU tensor (B, n_mel, T) (returns a (B, hop*(T-1)) tensor).  momentum: griffin_lim's (0, the default, is the reference's)."""
+    GPU tensor (B, n_mel, T) (returns a (B, hop*(T-1)) tensor).  momentum: griffin_lim's (0, the default, is the reference's).
+    init: "random" (the default and the reference's: angles0, drawn if None) or "spsi": Griffin-Lim starts from
+    spsi_phases(S) instead, which reaches a given spectral convergence in fewer iterations (not a better fixed point: DESIGN.md
+    5k).  init="spsi" with an explicit angles0, or any other string, is a ValueError before anything is launched."""
+    _init("inv_mel_spectrogram", init, angles0)
     as_numpy = isinstance(mel_spectrogram, np.ndarray)
     mel = torch.from_numpy(np.ascontiguousarray(mel_spectrogram, dtype=np.float32)).to(device) if as_numpy else mel_spectrogram
-    y = _invert_mel(mel, sample_rate, fft_size, hop_size, n_mel, iters, angles0, momentum)[2]
+    y = _invert_mel(mel, sample_rate, fft_size, hop_size, n_mel, iters, angles0, momentum, init)[2]
     return y[0].cpu().numpy() if as_numpy else y
 
 
-def _invert_mel(mel, sample_rate, fft_size, hop_size, n_mel, iters, angles0, momentum):
+def _invert_mel(mel, sample_rate, fft_size, hop_size, n_mel, iters, angles0, momentum, init="random"):
     """inv_mel_spectrogram's steps on a GPU tensor -> (S, Griffin-Lim's waveform, the waveform after inverse pre-emphasis)."""
+    _init("inv_mel_spectrogram", init, angles0)
     if mel.dim() == 2:
         mel = mel.unsqueeze(0)
     mel = mel.contiguous().float()
     S = mel_to_linear(mel, sample_rate, fft_size, n_mel)
     if angles0 is not None and not torch.is_tensor(angles0):
         angles0 = torch.from_numpy(np.ascontiguousarray(angles0, dtype=np.float32)).to(mel.device)
+    if init == "spsi":
+        angles0 = spsi_phases(S, fft_size, hop_size)
     y = griffin_lim(S, fft_size, hop_size, iters, angles0, momentum)
     return S, y, inv_preemphasis(y)
 

@@ -443,6 +443,149 @@ void griffin_lim_launch(const float *S, const float *u, float *y, float *c, floa
     }
 }
 
+// ---- single-pass spectrogram inversion phases (include/nsg.h: nsg_audio_spsi_phases) ----
+// Two launches.  spsi_frames_kernel, one workgroup per (clip, frame), does everything that does not depend on the frame before:
+// peaks, their parabolic offsets, and for every bin the peak that owns it and that peak's advance (own + p) r.  spsi_walk_kernel,
+// one workgroup per clip, is the sequential rest: phi_t[k] = frac(phi_{t-1}[own_t[k]] + adv_t[k]), one LDS gather and one add per
+// bin and one barrier per frame, its operands loaded SPSI_AHEAD frames ahead.
+//
+// Ownership by two segmented scans over the bins, run together (Hillis-Steele in LDS, ceil(log2 F) steps whatever the frame holds,
+// so the frame whose only peaks are bins 1 and F-2 costs what every other costs): forward, each bin learns the nearest peak at or
+// below it and the least magnitude from that peak up to itself; backward, the nearest peak at or above and the least magnitude
+// from itself up to that peak.  A bin k strictly between the peaks j < j' lies at or below the FIRST minimum of m[j .. j'] iff
+// every magnitude in [j, k-1] is greater than the least of [k, j']:  min m[j .. k-1] > min m[k .. j'].
+struct SpsiEl { int idx; float v; };      // the nearest peak seen so far (-1: none yet) and the least magnitude up to it
+
+// nsg_audio_spsi_phases' workspace: the advances [B][T][F] fp64 | the owners [B][T][F] uint16.  It is carved from a workspace of
+// nsg_audio_griffin_lim_workspace_bytes(B, T, n_fft) bytes, whose two sections are each at least as long as these two
+// (8 F = 8 F and 4 n_fft = 8 F - 8 >= 2 F bytes per frame); the entry point checks it.
+struct SpsiLayout { double *adv; uint16_t *own; size_t bytes; };
+inline SpsiLayout spsi_layout(void *ws, int B, int T, int n_fft)
+{
+    const size_t F = (size_t)n_fft / 2 + 1;
+    NsgCarver c(ws);
+    return {c.take<double>(nsg_align_up((size_t)B * T * F * sizeof(double), 256)),
+            c.take<uint16_t>(nsg_align_up((size_t)B * T * F * sizeof(uint16_t), 256)), c.off};
+}
+
+template <int LOG2N>
+__global__ __launch_bounds__(256) void spsi_frames_kernel(const float *__restrict__ S, double *__restrict__ adv, uint16_t *__restrict__ own, double r)
+{
+    constexpr int F = (1 << LOG2N) / 2 + 1;
+    __shared__ float m[F];
+    __shared__ SpsiEl fw[2][F], bw[2][F];
+    const int tid = threadIdx.x;
+    const size_t row = (size_t)blockIdx.x * F;
+    for (int k = tid; k < F; k += 256) m[k] = S[row + k];
+    __syncthreads();
+    for (int k = tid; k < F; k += 256) {
+        const bool peak = k >= 1 && k <= F - 2 && m[k] > m[k - 1] && m[k] > m[k + 1];      // strict: a plateau, a NaN is no peak
+        const SpsiEl e = {peak ? k : -1, m[k]};
+        fw[0][k] = e;
+        bw[0][k] = e;
+    }
+    __syncthreads();
+    int cur = 0;
+#pragma unroll 1
+    for (int d = 1; d < F; d <<= 1) {
+        for (int k = tid; k < F; k += 256) {
+            SpsiEl a = fw[cur][k];
+            if (a.idx < 0 && k >= d) { const SpsiEl l = fw[cur][k - d]; a.idx = l.idx; a.v = fminf(l.v, a.v); }
+            fw[cur ^ 1][k] = a;
+            SpsiEl b = bw[cur][k];
+            if (b.idx < 0 && k + d < F) { const SpsiEl h = bw[cur][k + d]; b.idx = h.idx; b.v = fminf(b.v, h.v); }
+            bw[cur ^ 1][k] = b;
+        }
+        __syncthreads();
+        cur ^= 1;
+    }
+    const SpsiEl *L = fw[cur], *R = bw[cur];
+    double *p = reinterpret_cast<double *>(fw[cur ^ 1]);      // the scans are done: their other buffer holds the peaks' offsets
+    const bool any = L[F - 1].idx >= 0;
+    for (int k = tid; k < F; k += 256)
+        if (L[k].idx == k) {
+            const double a = (double)m[k - 1], b = (double)m[k], c = (double)m[k + 1];
+            p[k] = 0.5 * (a - c) / ((a - 2.0 * b) + c);
+        }
+    __syncthreads();
+    for (int k = tid; k < F; k += 256) {
+        int o = k;
+        double a = (double)k * r;                               // a frame with no peak: every bin advances at its centre
+        if (any) {
+            const int lo = L[k].idx, hi = R[k].idx;
+            if (lo == k || hi < 0) o = lo;
+            else if (lo < 0) o = hi;
+            else o = L[k - 1].v > R[k].v ? lo : hi;            // k - 1 >= lo: L[k - 1].v = min m[lo .. k - 1]
+            a = ((double)o + p[o]) * r;
+        }
+        adv[row + k] = a;
+        own[row + k] = (uint16_t)o;
+    }
+}
+
+// Frames whose operands are in flight while one is applied.  The walk's loop body holds no branch: a bin index past F - 1 is
+// clamped to F - 1 and a frame index past T - 1 to T - 1 (such lanes and loads repeat the last one's work, value for value), so the
+// compiler can wait for exactly the oldest frame's loads (a counted vmcnt) and leave the younger ones in flight.  With a branch round
+// a load it waits for all of them, and every frame then costs a trip to memory (1.42 us measured, against 0.35 us).
+constexpr int SPSI_AHEAD = 8;
+
+template <int LOG2N>
+__global__ __launch_bounds__(256) void spsi_walk_kernel(const double *__restrict__ adv, const uint16_t *__restrict__ own, float *__restrict__ angles, int T)
+{
+    constexpr int F = (1 << LOG2N) / 2 + 1;
+    constexpr int NB = (F + 255) / 256;                        // bins per thread: k = min(tid + 256 i, F - 1)
+    __shared__ double phi[2][F];
+    const int tid = threadIdx.x;
+    const size_t base = (size_t)blockIdx.x * T * F;
+    double a[SPSI_AHEAD][NB];
+    int o[SPSI_AHEAD][NB];
+    auto fetch = [&](int slot, int t) {
+        const size_t at = base + (size_t)(t < T ? t : T - 1) * F;
+#pragma unroll
+        for (int i = 0; i < NB; ++i) {
+            const int k = tid + 256 * i < F ? tid + 256 * i : F - 1;
+            a[slot][i] = adv[at + k];
+            o[slot][i] = own[at + k];
+        }
+    };
+    auto apply = [&](int slot, int t) {                        // frame t, whose operands are in `slot`; t and slot have one parity
+        const double *in = phi[slot & 1];
+        double *out = phi[(slot & 1) ^ 1];
+        float *dst = angles + base + (size_t)t * F;
+#pragma unroll
+        for (int i = 0; i < NB; ++i) {
+            const int k = tid + 256 * i < F ? tid + 256 * i : F - 1;
+            double v = in[o[slot][i]] + a[slot][i];
+            v -= floor(v);
+            out[k] = v;
+            double w = v + 0.5 * (double)k;                     // (-1)^k of a centred symmetric window's transform
+            w -= floor(w);
+            const float f = (float)w;
+            dst[k] = f == 1.0f ? 0.0f : f;
+        }
+    };
+#pragma unroll
+    for (int d = 0; d < SPSI_AHEAD; ++d) fetch(d, d);
+    for (int k = tid; k < F; k += 256) phi[0][k] = 0.0;
+    __syncthreads();
+    int t0 = 0;
+    for (; t0 + SPSI_AHEAD <= T; t0 += SPSI_AHEAD) {
+#pragma unroll
+        for (int d = 0; d < SPSI_AHEAD; ++d) {
+            apply(d, t0 + d);
+            fetch(d, t0 + d + SPSI_AHEAD);
+            __syncthreads();
+        }
+    }
+#pragma unroll
+    for (int d = 0; d < SPSI_AHEAD; ++d) {                      // the last T mod SPSI_AHEAD frames: their operands are already here
+        if (t0 + d >= T) break;
+        apply(d, t0 + d);
+        __syncthreads();
+    }
+}
+static_assert(SPSI_AHEAD % 2 == 0, "spsi_walk_kernel: the ping-pong parity of frame t0 + d is d's");
+
 }  // namespace
 
 extern "C" {
@@ -497,6 +640,36 @@ int nsg_audio_griffin_lim_fast(const float *S, const float *u, float *y, float *
     NSG_REQUIRE((int64_t)B * T < 0x7fffffff, NSG_E_UNSUPPORTED, "nsg_audio_griffin_lim_fast: too many frames");
     griffin_lim_launch(S, u, y, c, momentum, B, T, lg, hop, iters, G, (hipStream_t)stream);
     return nsg_check_launch("griffin_lim_fast");
+}
+
+// S [B][T][F] magnitudes -> angles [B][T][F] in turns, what both Griffin-Lim entry points take as u
+int nsg_audio_spsi_phases(const float *S, float *angles, int32_t B, int32_t T, int32_t n_fft, int32_t hop, void *workspace, size_t workspace_bytes,
+                          void *stream)
+{
+    NSG_REQUIRE(S && angles && B > 0 && T > 0 && hop > 0, NSG_E_INVALID, "nsg_audio_spsi_phases: bad argument");
+    const int lg = log2_of(n_fft);
+    NSG_REQUIRE(lg >= 9 && lg <= 11, NSG_E_UNSUPPORTED, "nsg_audio_spsi_phases: n_fft must be 512, 1024 or 2048");
+    NSG_REQUIRE(n_fft % hop == 0, NSG_E_UNSUPPORTED, "nsg_audio_spsi_phases: hop must divide n_fft");
+    NSG_REQUIRE((int64_t)hop * (T - 1) < 0x7fffffff, NSG_E_UNSUPPORTED, "nsg_audio_spsi_phases: too many samples (hop * (T - 1) >= 2^31)");
+    NSG_REQUIRE((int64_t)B * T < 0x7fffffff, NSG_E_UNSUPPORTED, "nsg_audio_spsi_phases: too many frames");
+    const size_t need = griffin_lim_layout(nullptr, B, T, n_fft).bytes;
+    NSG_REQUIRE(workspace && workspace_bytes >= need, NSG_E_WORKSPACE, "nsg_audio_spsi_phases: workspace too small");
+    const SpsiLayout P = spsi_layout(workspace, B, T, n_fft);
+    NSG_REQUIRE(P.bytes <= need, NSG_E_UNSUPPORTED, "nsg_audio_spsi_phases: the layout does not fit nsg_audio_griffin_lim's workspace");
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned nfr = (unsigned)(B * T);
+    const double r = (double)hop / (double)n_fft;      // a power of two: exact
+    if (lg == 9) {
+        hipLaunchKernelGGL((spsi_frames_kernel<9>), dim3(nfr), dim3(256), 0, s, S, P.adv, P.own, r);
+        hipLaunchKernelGGL((spsi_walk_kernel<9>), dim3((unsigned)B), dim3(256), 0, s, P.adv, P.own, angles, T);
+    } else if (lg == 10) {
+        hipLaunchKernelGGL((spsi_frames_kernel<10>), dim3(nfr), dim3(256), 0, s, S, P.adv, P.own, r);
+        hipLaunchKernelGGL((spsi_walk_kernel<10>), dim3((unsigned)B), dim3(256), 0, s, P.adv, P.own, angles, T);
+    } else {
+        hipLaunchKernelGGL((spsi_frames_kernel<11>), dim3(nfr), dim3(256), 0, s, S, P.adv, P.own, r);
+        hipLaunchKernelGGL((spsi_walk_kernel<11>), dim3((unsigned)B), dim3(256), 0, s, P.adv, P.own, angles, T);
+    }
+    return nsg_check_launch("spsi_phases");
 }
 
 // frame_sums [B][T][2] (may be NULL), clip_sums [B][2] fp64: the sums behind ||  |stft(y)| - S || / || S ||

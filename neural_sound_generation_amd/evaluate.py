@@ -298,7 +298,7 @@ def test_conversion(args, vqvae, pair_loader, device, epoch):
     return mcd_c, mcd_s
 
 
-def test_conversion_f0(args, vqvae, pair_loader, device, epoch, iters=None, angles0=None, *, tracker="yin", tracker_options=None, momentum=0.0):
+def test_conversion_f0(args, vqvae, pair_loader, device, epoch, iters=None, angles0=None, *, tracker="yin", tracker_options=None, momentum=0.0, init="random"):
     """The pitch figures of a speaker-conditioned VQ-VAE over parallel utterances, from waveforms: `pair_loader` yields
     (wav_src (B, Ls), len_src (B,), wav_tgt (B, Lt), len_tgt (B,), g_tgt (B,) int64) -- the same sentences by a source and a target
     speaker as zero-padded float32 waveforms at 22 050 Hz with their lengths in samples (host integers), and the target speakers'
@@ -311,7 +311,8 @@ def test_conversion_f0(args, vqvae, pair_loader, device, epoch, iters=None, angl
         {"converted": figures, "source": figures, "clips": n},   figures = {"f0_rmse_cents", "vuv_error", "f0_corr", "mcd", "stats"}
     and, in "converted" alone, "spectral_convergence": the mean over clips of audio.spectral_convergence of Griffin-Lim's waveform
     (before the inverse pre-emphasis) against the magnitudes it was inverted from, i.e. how far the inversion behind the converted
-    figures still is from the spectrum asked for; momentum is audio.griffin_lim's (0, the default, is the reference's iteration);
+    figures still is from the spectrum asked for; momentum is audio.griffin_lim's (0, the default, is the reference's iteration) and
+    init audio.inv_mel_spectrogram's ("random", the default, or "spsi": Griffin-Lim starts from audio.spsi_phases, without angles0);
     each set pooled over all clips of the loader from the summed stats (audio.f0_figures of the sum, not a mean of per-clip
     ratios), "mcd" the mean over clips of the mel-cepstral distortion along the same paths in dB, "stats" the ten sums.  One host
     synchronisation, at the end.  ValueError, before anything of the batch is launched: a model without a speaker embedding, a
@@ -319,10 +320,11 @@ def test_conversion_f0(args, vqvae, pair_loader, device, epoch, iters=None, angl
     tracker: "yin" (audio.f0, each frame on its own) or "viterbi" (audio.f0_track for all three waveforms: a path over each
     frame's candidates, which repairs the octave-up picks and dropouts that a per-frame rule makes on a Griffin-Lim waveform and
     that otherwise dominate the figures); tracker_options: audio.f0_track's costs (octave_cost, jump_cost, vuv_cost,
-    unvoiced_cost) for "viterbi".  Another tracker, options that do not go with it, or a momentum outside [0, 1] is a ValueError
-    before anything is launched."""
+    unvoiced_cost) for "viterbi".  Another tracker, options that do not go with it, a momentum outside [0, 1], or an init that is
+    neither or that comes with angles0 is a ValueError before anything is launched."""
     from . import audio
     momentum = audio._momentum("test_conversion_f0", momentum)
+    audio._init("test_conversion_f0", init, angles0)
     if tracker not in ("yin", "viterbi"):
         raise ValueError(f"test_conversion_f0: tracker must be 'yin' or 'viterbi', got {tracker!r}")
     options = dict(tracker_options or {})
@@ -352,7 +354,7 @@ def test_conversion_f0(args, vqvae, pair_loader, device, epoch, iters=None, angl
         mel_t = audio.melspectrogram(wav_tgt, fft_size=fft, hop_size=hop, lengths=lt)
         _, converted = convert_voice(vqvae, mel_s[:, :, :Tc].contiguous(), g_tgt)
         a0 = angles0[k] if isinstance(angles0, (list, tuple)) else angles0
-        S_c, y_c, wav_c = audio._invert_mel(converted.squeeze(1), 22050, fft, hop, 80, iters, a0, momentum)      # inv_mel_spectrogram's steps
+        S_c, y_c, wav_c = audio._invert_mel(converted.squeeze(1), 22050, fft, hop, 80, iters, a0, momentum, init)      # inv_mel_spectrogram's steps
         total[0, 11] += audio.spectral_convergence(y_c, S_c, fft, hop).sum()
         f0_c, _ = track(wav_c, hop_size=hop, lengths=hop * (fc - 1))   # hop (Tc - 1) samples: Tc frames, fc of them the clip's
         f0_t, _ = track(wav_tgt, hop_size=hop, lengths=lt)
@@ -377,8 +379,8 @@ def test_conversion_f0(args, vqvae, pair_loader, device, epoch, iters=None, angl
           '{:.2f} cents, {:.4f}, {:.4f}, {:.4f} dB source against target ({} clips)'.format(
               *(out["converted"][k] for k in ("f0_rmse_cents", "vuv_error", "f0_corr", "mcd")),
               *(out["source"][k] for k in ("f0_rmse_cents", "vuv_error", "f0_corr", "mcd")), n))
-    print('====> Conversion test set: spectral convergence of the inversion {:.4f} ({} Griffin-Lim iterations, momentum {:g})'.format(
-        out["converted"]["spectral_convergence"], iters, momentum))
+    print('====> Conversion test set: spectral convergence of the inversion {:.4f} ({} Griffin-Lim iterations, momentum {:g}, init {})'.format(
+        out["converted"]["spectral_convergence"], iters, momentum, init))
     return out
 
 
@@ -400,15 +402,16 @@ def continue_mels(vqvae, prior, mel: torch.Tensor, label: torch.Tensor, keep_fra
 
 @torch.no_grad()
 def continue_audio(vqvae, prior, wav: torch.Tensor, label: torch.Tensor, keep_frames: int, frames: int, g=None, generator=None,
-                   sample_rate=22050, fft_size=1024, hop_size=256, angles0=None, iters=None, momentum=0.0, **controls):
+                   sample_rate=22050, fft_size=1024, hop_size=256, angles0=None, iters=None, momentum=0.0, init="random", **controls):
     """Continue recordings in time: wav (B, L) float32 on the GPU -> its mel (audio.melspectrogram, 1 + L // hop_size frames)
     -> continue_mels (the first keep_frames held, the grid sampled out to frames) -> waveform (audio.inv_mel_spectrogram;
     angles0 (B, frames, 1 + fft_size / 2) fixes Griffin-Lim's initial phases; iters, default audio.GRIFFIN_LIM_ITERS, and momentum
-    are audio.griffin_lim's).  Returns codes (B, 20, frames // 4), mels
+    are audio.griffin_lim's, init audio.inv_mel_spectrogram's).  Returns codes (B, 20, frames // 4), mels
     (B, 1, 80, frames) and waveforms (B, hop_size * (frames - 1))."""
     from . import audio
+    audio._init("continue_audio", init, angles0)
     mel = audio.melspectrogram(wav, sample_rate, fft_size, hop_size, 80)
     codes, out = continue_mels(vqvae, prior, mel.unsqueeze(1), label, keep_frames, frames, g=g, generator=generator, **controls)
     y = audio.inv_mel_spectrogram(out.squeeze(1), sample_rate, fft_size, hop_size, 80, audio.GRIFFIN_LIM_ITERS if iters is None else int(iters),
-                                  angles0=angles0, momentum=momentum)
+                                  angles0=angles0, momentum=momentum, init=init)
     return codes, out, y
