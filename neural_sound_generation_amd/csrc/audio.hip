@@ -2,10 +2,11 @@
 // with use_lws=False): denormalise, dB -> amplitude, pseudo-inverse mel basis, power, Griffin-Lim, inverse pre-emphasis.
 // SURVEY.md section 8f row 4.  The reference delegates the transforms to librosa (stft / istft) and scipy (lfilter);
 // their published algorithms are restated here as HIP kernels (and in numpy in oracle/audio_oracle.py):
-//   * radix-2 Stockham FFT of one frame per 256-thread workgroup, entirely in LDS (ping-pong buffers, twiddle table);
-//   * stft: centred frames with reflect padding x periodic Hann window -> FFT -> keep 1 + N/2 bins; fused with the
-//     Griffin-Lim phase update  spec = |S| * X / |X|  (with momentum: the phase of X + momentum (X - X_prev), X_prev updated in place);
-//   * spectral convergence: the same transform with || |X| - S ||^2 and || S ||^2 summed in fp64 out of LDS (the spectrum is not stored);
+//   * radix-2 Stockham FFT of one frame per 256-thread workgroup, entirely in LDS (FftLds: ping-pong buffers, twiddle table);
+//   * stft: centred frames with reflect padding x periodic Hann window -> FFT (stft_frame_lds, the one place that forms such a
+//     frame) -> keep 1 + N/2 bins; stft_kernel<LOG2N, OUT> stores them raw or fused with the Griffin-Lim phase update
+//     spec = |S| * X / |X|  (with momentum: the phase of X + momentum (X - X_prev), X_prev updated in place);
+//   * spectral convergence: the same frame with || |X| - S ||^2 and || S ||^2 summed in fp64 out of LDS (the spectrum is not stored);
 //   * istft: Hermitian extension -> inverse FFT -> x window -> frame buffer; overlap-add as a gather (deterministic)
 //     divided by the window's sum of squares, centre-trimmed;
 //   * inverse pre-emphasis y[n] = x[n] + k y[n-1]: chunked, each chunk re-running a discarded warm-up (k^W < 1e-9).
@@ -15,6 +16,7 @@
 #include "nsg_common.h"
 #include "nsg_reduce.h"
 #include <math.h>
+#include <type_traits>
 
 namespace {
 
@@ -22,32 +24,46 @@ typedef float v2f __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ v2f cmul(v2f a, v2f b) { return v2f{a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
 
-// In-LDS radix-2 Stockham FFT of N = 2^LOG2N points by 256 threads.  buf0 holds the input; returns the buffer holding the
-// result.  tw[t] = exp(-2 pi i t / N), t < N/2.  inverse: conjugated twiddles (no 1/N scaling).
+// The LDS of a radix-2 Stockham FFT of N = 2^LOG2N points by 256 threads: declared __shared__ once per kernel, then
+// fill_twiddles(tid) by all threads before the first transform (whose first barrier orders the fill).
 template <int LOG2N>
-__device__ v2f *fft_lds(v2f *buf0, v2f *buf1, const v2f *tw, int tid, bool inverse)
-{
-    constexpr int N = 1 << LOG2N;
-    v2f *in = buf0, *out = buf1;
-#pragma unroll 1
-    for (int s = 0; s < LOG2N; ++s) {
-        const int Ns = 1 << s;
-        __syncthreads();
-        for (int j = tid; j < N / 2; j += 256) {
-            const int k = j & (Ns - 1);
-            v2f w = tw[k << (LOG2N - 1 - s)];
-            if (inverse) w.y = -w.y;
-            const v2f a = in[j];
-            const v2f b = cmul(w, in[j + N / 2]);
-            const int j0 = ((j >> s) << (s + 1)) + k;
-            out[j0] = a + b;
-            out[j0 + Ns] = a - b;
+struct FftLds {
+    static constexpr int N = 1 << LOG2N;
+    v2f b0[N], b1[N], tw[N / 2];      // the input, then ping-pong | tw[t] = exp(-2 pi i t / N), t < N/2
+
+    __device__ __forceinline__ void fill_twiddles(int tid)
+    {
+        for (int t = tid; t < N / 2; t += 256) {
+            float sn, cs;
+            sincospif(-2.0f * (float)t / (float)N, &sn, &cs);
+            tw[t] = v2f{cs, sn};
         }
-        v2f *t = in; in = out; out = t;
     }
-    __syncthreads();
-    return in;
-}
+
+    // Transforms b0; returns the buffer holding the result.  inverse: conjugated twiddles (no 1/N scaling).
+    __device__ v2f *transform(int tid, bool inverse)
+    {
+        v2f *in = b0, *out = b1;
+#pragma unroll 1
+        for (int s = 0; s < LOG2N; ++s) {
+            const int Ns = 1 << s;
+            __syncthreads();
+            for (int j = tid; j < N / 2; j += 256) {
+                const int k = j & (Ns - 1);
+                v2f w = tw[k << (LOG2N - 1 - s)];
+                if (inverse) w.y = -w.y;
+                const v2f a = in[j];
+                const v2f b = cmul(w, in[j + N / 2]);
+                const int j0 = ((j >> s) << (s + 1)) + k;
+                out[j0] = a + b;
+                out[j0 + Ns] = a - b;
+            }
+            v2f *t = in; in = out; out = t;
+        }
+        __syncthreads();
+        return in;
+    }
+};
 
 // Periodic Hann window 0.5 - 0.5 cos(2 pi n / N) as sin^2(pi n / N): no cancellation at the window's ends, where the cosine form
 // is wrong by eps / w (8e-4 of w at n = 1, N = 512).  Griffin-Lim needs the accurate form: overlap-add divides by the sum of
@@ -55,17 +71,6 @@ __device__ v2f *fft_lds(v2f *buf0, v2f *buf1, const v2f *tw, int tid, bool inver
 // next STFT multiplies those same samples (y = frame / w there) by w again.  (melspectrogram_kernel keeps the cosine form:
 // it only multiplies by w, where the error is 3e-8 of the window's peak, and its outputs are pinned bit for bit.)
 __device__ __forceinline__ float hann_sin2(int n, int N) { const float s = sinpif((float)n / (float)N); return s * s; }
-
-template <int LOG2N>
-__device__ __forceinline__ void fill_twiddles(v2f *tw, int tid)
-{
-    constexpr int N = 1 << LOG2N;
-    for (int t = tid; t < N / 2; t += 256) {
-        float sn, cs;
-        sincospif(-2.0f * (float)t / (float)N, &sn, &cs);
-        tw[t] = v2f{cs, sn};
-    }
-}
 
 // S[b][t][f] = max(1e-10, sum_m inv[f][m] * amp(mel[b][m][t]))^power,  amp = 10^((clip(mel,0,max_abs)*(-min_db)/max_abs + min_db + ref_db)/20)
 __global__ __launch_bounds__(256) void mel_to_linear_kernel(const float *__restrict__ mel, const float *__restrict__ inv, float *__restrict__ S,
@@ -102,18 +107,18 @@ template <int LOG2N>
 __global__ __launch_bounds__(256) void istft_frames_kernel(const v2f *__restrict__ spec, float *__restrict__ frames, int F)
 {
     constexpr int N = 1 << LOG2N;
-    __shared__ v2f b0[N], b1[N], tw[N / 2];
+    __shared__ FftLds<LOG2N> fft;
     const int tid = threadIdx.x;
     const size_t fr = blockIdx.x;
-    fill_twiddles<LOG2N>(tw, tid);
+    fft.fill_twiddles(tid);
     const v2f *sp = spec + fr * F;
     for (int k = tid; k < N; k += 256) {
         v2f v;
         if (k <= N / 2) { v = sp[k]; if (k == 0 || k == N / 2) v.y = 0.f; }     // irfft ignores the imaginary part of DC / Nyquist
         else { v = sp[N - k]; v.y = -v.y; }
-        b0[k] = v;
+        fft.b0[k] = v;
     }
-    v2f *r = fft_lds<LOG2N>(b0, b1, tw, tid, true);
+    v2f *r = fft.transform(tid, true);
     float *dst = frames + fr * N;
     for (int n = tid; n < N; n += 256) dst[n] = r[n].x * (1.0f / (float)N) * hann_sin2(n, N);
 }
@@ -140,77 +145,59 @@ __global__ __launch_bounds__(256) void overlap_add_kernel(const float *__restric
     }
 }
 
-// one frame per workgroup: X = rfft(hann * reflect-padded frame of y);  spec[b][t][f] = S[b][t][f] * X[f] / |X[f]|
-// The padded index is numpy's reflect map for every L >= 2, however short the signal is against N/2 (Griffin-Lim's grid is
-// hop (T - 1) samples, a quarter of N/2 at T = 2 and hop = N/8).  L = 1 has no reflection (period 0): both launchers refuse it.
+// X = rfft(hann * reflect-padded frame t of clip yb (L samples)): the frame into fft.b0, then its FFT.  The only place that forms
+// such a frame, so every kernel that calls it forms the X that nsg_audio_stft returns.  The padded index is numpy's reflect map
+// for every L >= 2, however short the signal is against N/2 (Griffin-Lim's grid is hop (T - 1) samples, a quarter of N/2 at
+// T = 2 and hop = N/8).  L = 1 has no reflection (period 0): every launcher refuses it.
 template <int LOG2N>
-__global__ __launch_bounds__(256) void stft_phase_kernel(const float *__restrict__ y, const float *__restrict__ S, v2f *__restrict__ spec,
-                                                         int T, int hop, int L, int F, int want_raw)
+__device__ __forceinline__ v2f *stft_frame_lds(const float *__restrict__ yb, int t, int hop, int L, FftLds<LOG2N> &fft, int tid)
 {
     constexpr int N = 1 << LOG2N;
-    __shared__ v2f b0[N], b1[N], tw[N / 2];
-    const int tid = threadIdx.x;
-    const size_t fr = blockIdx.x;
-    const int b = (int)(fr / T), t = (int)(fr - (size_t)b * T);
-    fill_twiddles<LOG2N>(tw, tid);
-    const float *yb = y + (size_t)b * L;
     const int period = 2 * (L - 1);
     for (int n = tid; n < N; n += 256) {
         int idx = (t * hop + n - N / 2) % period;             // np.pad(mode="reflect"): the reflection has period 2 (L - 1) and
         if (idx < 0) idx += period;                           // folds as often as the padding needs (a grid shorter than N/2
         if (idx >= L) idx = period - idx;                     // folds more than once); the launchers guarantee L >= 2
-        b0[n] = v2f{yb[idx] * hann_sin2(n, N), 0.f};
+        fft.b0[n] = v2f{yb[idx] * hann_sin2(n, N), 0.f};
     }
-    v2f *r = fft_lds<LOG2N>(b0, b1, tw, tid, false);
-    for (int f = tid; f < F; f += 256) {
-        const v2f X = r[f];
-        if (want_raw) { spec[fr * F + f] = X; continue; }
-        const float mag = sqrtf(X.x * X.x + X.y * X.y);
-        const float s = S[fr * F + f];
-        spec[fr * F + f] = mag > 0.f ? v2f{s * X.x / mag, s * X.y / mag} : v2f{s, 0.f};   // np.angle(0) = 0
-    }
+    return fft.transform(tid, false);
 }
 
-// The windowed, reflect-padded frame t of clip yb (L samples) into b0, then its FFT: stft_phase_kernel's load and transform,
-// statement by statement, for the kernels below (which therefore form the X that nsg_audio_stft returns).
-template <int LOG2N>
-__device__ __forceinline__ v2f *stft_frame_lds(const float *__restrict__ yb, int t, int hop, int L, v2f *b0, v2f *b1, const v2f *tw, int tid)
-{
-    constexpr int N = 1 << LOG2N;
-    const int period = 2 * (L - 1);
-    for (int n = tid; n < N; n += 256) {
-        int idx = (t * hop + n - N / 2) % period;
-        if (idx < 0) idx += period;
-        if (idx >= L) idx = period - idx;
-        b0[n] = v2f{yb[idx] * hann_sin2(n, N), 0.f};
-    }
-    return fft_lds<LOG2N>(b0, b1, tw, tid, false);
-}
+// What stft_kernel stores of X, one frame per workgroup:
+//   STFT_RAW             spec = X                                           (nsg_audio_stft; S and prev are not read)
+//   STFT_PHASE           spec = S X / |X|                                   (Griffin-Lim's phase update; X = 0 -> (S, 0))
+//   STFT_MOMENTUM        t = X + momentum (X - prev);  prev <- X;  spec = S t / |t|   (fast Griffin-Lim: Perraudin, Balazs,
+//                        Sondergaard 2013).  prev [B][T][F] is the caller's state buffer; each (frame, bin) is read and rewritten by
+//                        the one thread that owns it, so the update is in place.
+//   STFT_MOMENTUM_FIRST  the same with prev taken as 0 and not loaded (it may hold anything, NaN included), only stored.
+enum StftOut { STFT_RAW, STFT_PHASE, STFT_MOMENTUM_FIRST, STFT_MOMENTUM };
 
-// Fast Griffin-Lim's phase update (Perraudin, Balazs, Sondergaard 2013), one frame per workgroup as stft_phase_kernel:
-//     X = rfft(hann * frame of y);  t = X + momentum (X - prev);  prev <- X;  spec = S t / |t|   (t = 0 -> (S, 0))
-// prev [B][T][F] is the caller's state buffer.  Each (frame, bin) is read and rewritten by the one thread that owns it, so the
-// update is in place.  FIRST: prev is taken as 0 and is not loaded (it may hold anything, NaN included), only stored.
-template <int LOG2N, bool FIRST>
-__global__ __launch_bounds__(256) void stft_phase_momentum_kernel(const float *__restrict__ y, const float *__restrict__ S, v2f *__restrict__ spec,
-                                                                  v2f *__restrict__ prev, int T, int hop, int L, int F, float momentum)
+template <int LOG2N, StftOut OUT>
+__global__ __launch_bounds__(256) void stft_kernel(const float *__restrict__ y, const float *__restrict__ S, v2f *__restrict__ spec,
+                                                   v2f *__restrict__ prev, int T, int hop, int L, int F, float momentum)
 {
-    constexpr int N = 1 << LOG2N;
-    __shared__ v2f b0[N], b1[N], tw[N / 2];
+    __shared__ FftLds<LOG2N> fft;
     const int tid = threadIdx.x;
     const size_t fr = blockIdx.x;
     const int b = (int)(fr / T), t = (int)(fr - (size_t)b * T);
-    fill_twiddles<LOG2N>(tw, tid);
-    v2f *r = stft_frame_lds<LOG2N>(y + (size_t)b * L, t, hop, L, b0, b1, tw, tid);
+    fft.fill_twiddles(tid);
+    v2f *r = stft_frame_lds<LOG2N>(y + (size_t)b * L, t, hop, L, fft, tid);
     for (int f = tid; f < F; f += 256) {
         const size_t i = fr * F + f;
         const v2f X = r[f];
-        const v2f P = FIRST ? v2f{0.f, 0.f} : prev[i];
-        prev[i] = X;
-        const float tx = X.x + momentum * (X.x - P.x), ty = X.y + momentum * (X.y - P.y);
-        const float mag = sqrtf(tx * tx + ty * ty);
-        const float s = S[i];
-        spec[i] = mag > 0.f ? v2f{s * tx / mag, s * ty / mag} : v2f{s, 0.f};   // np.angle(0) = 0
+        if constexpr (OUT == STFT_RAW) {
+            spec[i] = X;
+        } else {
+            float tx = X.x, ty = X.y;
+            if constexpr (OUT != STFT_PHASE) {
+                const v2f P = OUT == STFT_MOMENTUM_FIRST ? v2f{0.f, 0.f} : prev[i];
+                prev[i] = X;
+                tx = X.x + momentum * (X.x - P.x), ty = X.y + momentum * (X.y - P.y);
+            }
+            const float mag = sqrtf(tx * tx + ty * ty);
+            const float s = S[i];
+            spec[i] = mag > 0.f ? v2f{s * tx / mag, s * ty / mag} : v2f{s, 0.f};   // np.angle(0) = 0
+        }
     }
 }
 
@@ -220,9 +207,9 @@ __global__ __launch_bounds__(256) void stft_phase_momentum_kernel(const float *_
 // called by all 256 threads from uniform control flow.  The spectrum never leaves LDS.
 template <int LOG2N>
 __device__ __forceinline__ void frame_convergence_sums(const float *__restrict__ yb, const float *__restrict__ Sf, int t, int hop, int L, int F,
-                                                       v2f *b0, v2f *b1, const v2f *tw, double *red, int tid, double &num, double &den)
+                                                       FftLds<LOG2N> &fft, double *red, int tid, double &num, double &den)
 {
-    v2f *r = stft_frame_lds<LOG2N>(yb, t, hop, L, b0, b1, tw, tid);
+    v2f *r = stft_frame_lds<LOG2N>(yb, t, hop, L, fft, tid);
     double a = 0.0, d = 0.0;
     for (int f = tid; f < F; f += 256) {
         const v2f X = r[f];
@@ -240,15 +227,14 @@ template <int LOG2N>
 __global__ __launch_bounds__(256) void convergence_frames_kernel(const float *__restrict__ y, const float *__restrict__ S, double *__restrict__ frame_sums,
                                                                  int T, int hop, int L, int F)
 {
-    constexpr int N = 1 << LOG2N;
-    __shared__ v2f b0[N], b1[N], tw[N / 2];
+    __shared__ FftLds<LOG2N> fft;
     __shared__ double red[4];
     const int tid = threadIdx.x;
     const size_t fr = blockIdx.x;
     const int b = (int)(fr / T), t = (int)(fr - (size_t)b * T);
-    fill_twiddles<LOG2N>(tw, tid);
+    fft.fill_twiddles(tid);
     double num, den;
-    frame_convergence_sums<LOG2N>(y + (size_t)b * L, S + fr * F, t, hop, L, F, b0, b1, tw, red, tid, num, den);
+    frame_convergence_sums<LOG2N>(y + (size_t)b * L, S + fr * F, t, hop, L, F, fft, red, tid, num, den);
     if (tid == 0) { frame_sums[2 * fr] = num; frame_sums[2 * fr + 1] = den; }
 }
 
@@ -272,16 +258,15 @@ template <int LOG2N>
 __global__ __launch_bounds__(256) void convergence_serial_kernel(const float *__restrict__ y, const float *__restrict__ S, double *__restrict__ clip_sums,
                                                                  int T, int hop, int L, int F)
 {
-    constexpr int N = 1 << LOG2N;
-    __shared__ v2f b0[N], b1[N], tw[N / 2];
+    __shared__ FftLds<LOG2N> fft;
     __shared__ double red[4];
     const int tid = threadIdx.x;
     const int b = blockIdx.x;
-    fill_twiddles<LOG2N>(tw, tid);
+    fft.fill_twiddles(tid);
     double a = 0.0, d = 0.0;
     for (int t = 0; t < T; ++t) {
-        double num, den;                                      // (the sums' barriers stand between a frame's last read of b0 / b1 and the next load)
-        frame_convergence_sums<LOG2N>(y + (size_t)b * L, S + ((size_t)b * T + t) * F, t, hop, L, F, b0, b1, tw, red, tid, num, den);
+        double num, den;                                      // (the sums' barriers stand between a frame's last read of the FFT's buffers and the next load)
+        frame_convergence_sums<LOG2N>(y + (size_t)b * L, S + ((size_t)b * T + t) * F, t, hop, L, F, fft, red, tid, num, den);
         if ((t & 255) == tid) { a += num; d += den; }
     }
     a = nsg_block_sum_butterfly(a, red, tid);
@@ -329,7 +314,7 @@ __global__ __launch_bounds__(256) void melspectrogram_kernel(const float *__rest
                                                              float ref_db, float max_abs, int frame_major)
 {
     constexpr int N = 1 << LOG2N, F = N / 2 + 1;
-    __shared__ v2f b0[N], b1[N], tw[N / 2];
+    __shared__ FftLds<LOG2N> fft;
     __shared__ float mag[2][F];
     const int tid = threadIdx.x;
     const int b = (int)(blockIdx.x / (unsigned)pairs), t0 = 2 * (int)(blockIdx.x - (unsigned)b * pairs);
@@ -344,7 +329,7 @@ __global__ __launch_bounds__(256) void melspectrogram_kernel(const float *__rest
         if (owns) ob[(t0 + j) * t_stride + m * m_stride] = 0.f;
         return;
     }
-    fill_twiddles<LOG2N>(tw, tid);
+    fft.fill_twiddles(tid);
     const float *x = wav + (size_t)b * L;
     const bool two = t0 + 1 < Tb;
     for (int n = tid; n < N; n += 256) {
@@ -355,16 +340,16 @@ __global__ __launch_bounds__(256) void melspectrogram_kernel(const float *__rest
             if (q == 1 && !two) break;
             // Precondition len > N/2 (checked by the launcher for L and by the caller for lengths[]): the padding is N/2 on each
             // side, so one fold is the exact reflect map and the clamp below is never taken.  Shorter clips would need the
-            // periodic map of stft_phase_kernel.
+            // periodic map of stft_frame_lds.
             int idx = (t0 + q) * hop + n - N / 2;
             if (idx < 0) idx = -idx;                          // np.pad(mode="reflect") of the pre-emphasised clip
             if (idx >= len) idx = 2 * (len - 1) - idx;
             idx = idx < 0 ? 0 : (idx >= len ? len - 1 : idx);
             p[q] = idx > 0 ? x[idx] - k * x[idx - 1] : x[0];
         }
-        b0[n] = v2f{p[0] * w, p[1] * w};
+        fft.b0[n] = v2f{p[0] * w, p[1] * w};
     }
-    v2f *r = fft_lds<LOG2N>(b0, b1, tw, tid, false);
+    v2f *r = fft.transform(tid, false);
     for (int f = tid; f < F; f += 256) {
         const v2f Z = r[f], C = r[(N - f) & (N - 1)];
         const float ar = Z.x + C.x, ai = Z.y - C.y;           // 2 X0[f]
@@ -405,42 +390,91 @@ inline GriffinLimLayout griffin_lim_layout(void *ws, int B, int T, int n_fft)
 }
 inline int log2_of(int n) { int l = 0; while ((1 << l) < n) ++l; return (1 << l) == n ? l : -1; }
 
-template <int LOG2N>
-void phase_launch(unsigned nfr, hipStream_t s, const float *y, const float *S, v2f *spec, v2f *prev, int T, int hop, int L, int F, float momentum, bool first)
+// The FFT sizes, n_fft in {512, 1024, 2048}, are enumerated here and nowhere else.  fft_size_log2 checks an entry point's n_fft and
+// returns lg = log2(n_fft), or the refusal's (negative) code; with_fft_size(lg, fn) calls fn(std::integral_constant<int, lg>{}), whose
+// type carries lg to a kernel's template argument.
+int fft_size_log2(const char *name, int n_fft)
 {
-    if (momentum == 0.f) hipLaunchKernelGGL((stft_phase_kernel<LOG2N>), dim3(nfr), dim3(256), 0, s, y, S, spec, T, hop, L, F, 0);
-    else if (first)      hipLaunchKernelGGL((stft_phase_momentum_kernel<LOG2N, true>), dim3(nfr), dim3(256), 0, s, y, S, spec, prev, T, hop, L, F, momentum);
-    else                 hipLaunchKernelGGL((stft_phase_momentum_kernel<LOG2N, false>), dim3(nfr), dim3(256), 0, s, y, S, spec, prev, T, hop, L, F, momentum);
+    const int lg = log2_of(n_fft);
+    NSG_REQUIRE(lg >= 9 && lg <= 11, NSG_E_UNSUPPORTED, "%s: n_fft must be 512, 1024 or 2048", name);
+    return lg;
+}
+template <class Fn>
+void with_fft_size(int lg, Fn &&fn)
+{
+    if (lg == 9)       fn(std::integral_constant<int, 9>{});
+    else if (lg == 10) fn(std::integral_constant<int, 10>{});
+    else               fn(std::integral_constant<int, 11>{});
 }
 
-// The launches of both Griffin-Lim entry points, whose checks have passed: y_0 = istft(S exp(2 pi i u)), then per iteration the
-// phase kernel and the istft.  momentum == 0 is the plain phase kernel, and c is not touched; otherwise c [B][T][F] complex is the
-// state X_{i-1}, taken as 0 (and not loaded) in the first iteration.
-void griffin_lim_launch(const float *S, const float *u, float *y, float *c, float momentum, int B, int T, int lg, int hop, int iters,
-                        const GriffinLimLayout &G, hipStream_t s)
+// one workgroup per frame (or pair of frames): B * T is a grid dimension
+int frames_fit(const char *name, int B, int T)
 {
-    const int n_fft = 1 << lg;
+    NSG_REQUIRE((int64_t)B * T < 0x7fffffff, NSG_E_UNSUPPORTED, "%s: too many frames (B * T >= 2^31)", name);
+    return 0;
+}
+
+// The grid of nsg_audio_stft and nsg_audio_melspectrogram, T = 1 + L / hop frames of clips longer than the padding: lg, or the
+// refusal's code.
+int stft_grid(const char *name, int B, int L, int n_fft, int hop)
+{
+    const int lg = fft_size_log2(name, n_fft);
+    if (lg < 0) return lg;
+    NSG_REQUIRE(L > n_fft / 2, NSG_E_UNSUPPORTED, "%s: reflect padding needs more than n_fft/2 samples", name);
+    const int rc = frames_fit(name, B, 1 + L / hop);
+    return rc ? rc : lg;
+}
+
+// Griffin-Lim's grid, T frames over hop (T - 1) samples, as the four entry points on it take it (their pointer and sign checks
+// have passed): lg, or the refusal's code.  reflects: the caller forms reflect-padded frames of the samples, so there must be two
+// of them (SPSI forms none, and takes a single frame).  has_workspace: the caller takes nsg_audio_griffin_lim's workspace.
+int griffin_lim_grid(const char *name, int B, int T, int n_fft, int hop, bool reflects, bool has_workspace, const void *workspace, size_t workspace_bytes)
+{
+    const int lg = fft_size_log2(name, n_fft);
+    if (lg < 0) return lg;
+    const int64_t L = (int64_t)hop * (T - 1);
+    NSG_REQUIRE(n_fft % hop == 0, NSG_E_UNSUPPORTED, "%s: hop must divide n_fft", name);
+    NSG_REQUIRE(L < 0x7fffffff, NSG_E_UNSUPPORTED, "%s: too many samples (hop * (T - 1) >= 2^31)", name);
+    NSG_REQUIRE(!reflects || L >= 2, NSG_E_UNSUPPORTED, "%s: hop * (T - 1) must be at least 2 samples (a one-sample grid has no reflect padding)", name);
+    if (const int rc = frames_fit(name, B, T)) return rc;
+    NSG_REQUIRE(!has_workspace || (workspace && workspace_bytes >= griffin_lim_layout(nullptr, B, T, n_fft).bytes), NSG_E_WORKSPACE,
+                "%s: workspace too small", name);
+    return lg;
+}
+
+// Both Griffin-Lim entry points, under the caller's name: y_0 = istft(S exp(2 pi i u)), then per iteration the phase kernel and the
+// istft.  momentum == 0 is the plain phase update, and c is not touched; otherwise c [B][T][F] complex is the state X_{i-1}, taken as
+// 0 (and not loaded) in the first iteration.
+int griffin_lim_run(const char *name, const float *S, const float *u, float *y, float *c, float momentum, int B, int T, int n_fft, int hop, int iters,
+                    void *workspace, size_t workspace_bytes, hipStream_t s)
+{
+    NSG_REQUIRE(S && u && y && B > 0 && T > 1 && hop > 0 && iters >= 0, NSG_E_INVALID, "%s: bad argument", name);
+    NSG_REQUIRE(momentum >= 0.f && momentum <= 1.f, NSG_E_INVALID, "%s: momentum must be in [0, 1]", name);      // (NaN fails both)
+    NSG_REQUIRE(c || momentum == 0.f, NSG_E_INVALID, "%s: momentum > 0 needs the state buffer c", name);
+    const int lg = griffin_lim_grid(name, B, T, n_fft, hop, true, true, workspace, workspace_bytes);
+    if (lg < 0) return lg;
+    const GriffinLimLayout G = griffin_lim_layout(workspace, B, T, n_fft);
     const int F = n_fft / 2 + 1;
     const int L = hop * (T - 1);
-    v2f *spec = G.spec;
-    float *frames = G.frames;
     v2f *prev = reinterpret_cast<v2f *>(c);
     const int64_t nspec = (int64_t)B * T * F;
     const unsigned nfr = (unsigned)(B * T);
-    hipLaunchKernelGGL(init_phase_kernel, dim3(ew_blocks(nspec)), dim3(256), 0, s, S, u, spec, nspec);
-    auto istft = [&]() {
-        if (lg == 9)       hipLaunchKernelGGL((istft_frames_kernel<9>), dim3(nfr), dim3(256), 0, s, spec, frames, F);
-        else if (lg == 10) hipLaunchKernelGGL((istft_frames_kernel<10>), dim3(nfr), dim3(256), 0, s, spec, frames, F);
-        else               hipLaunchKernelGGL((istft_frames_kernel<11>), dim3(nfr), dim3(256), 0, s, spec, frames, F);
-        hipLaunchKernelGGL(overlap_add_kernel, dim3(ew_blocks((int64_t)B * L)), dim3(256), 0, s, frames, y, B, T, n_fft, hop, L);
-    };
-    istft();
-    for (int it = 0; it < iters; ++it) {
-        if (lg == 9)       phase_launch<9>(nfr, s, y, S, spec, prev, T, hop, L, F, momentum, it == 0);
-        else if (lg == 10) phase_launch<10>(nfr, s, y, S, spec, prev, T, hop, L, F, momentum, it == 0);
-        else               phase_launch<11>(nfr, s, y, S, spec, prev, T, hop, L, F, momentum, it == 0);
+    hipLaunchKernelGGL(init_phase_kernel, dim3(ew_blocks(nspec)), dim3(256), 0, s, S, u, G.spec, nspec);
+    with_fft_size(lg, [&](auto lgc) {
+        constexpr int LG = decltype(lgc)::value;
+        auto istft = [&]() {
+            hipLaunchKernelGGL((istft_frames_kernel<LG>), dim3(nfr), dim3(256), 0, s, G.spec, G.frames, F);
+            hipLaunchKernelGGL(overlap_add_kernel, dim3(ew_blocks((int64_t)B * L)), dim3(256), 0, s, G.frames, y, B, T, n_fft, hop, L);
+        };
         istft();
-    }
+        for (int it = 0; it < iters; ++it) {
+            if (momentum == 0.f) hipLaunchKernelGGL((stft_kernel<LG, STFT_PHASE>), dim3(nfr), dim3(256), 0, s, y, S, G.spec, prev, T, hop, L, F, momentum);
+            else if (it == 0)    hipLaunchKernelGGL((stft_kernel<LG, STFT_MOMENTUM_FIRST>), dim3(nfr), dim3(256), 0, s, y, S, G.spec, prev, T, hop, L, F, momentum);
+            else                 hipLaunchKernelGGL((stft_kernel<LG, STFT_MOMENTUM>), dim3(nfr), dim3(256), 0, s, y, S, G.spec, prev, T, hop, L, F, momentum);
+            istft();
+        }
+    });
+    return nsg_check_launch(name);
 }
 
 // ---- single-pass spectrogram inversion phases (include/nsg.h: nsg_audio_spsi_phases) ----
@@ -610,36 +644,14 @@ size_t nsg_audio_griffin_lim_workspace_bytes(int32_t B, int32_t T, int32_t n_fft
 int nsg_audio_griffin_lim(const float *S, const float *u, float *y, int32_t B, int32_t T, int32_t n_fft, int32_t hop, int32_t iters,
                           void *workspace, size_t workspace_bytes, void *stream)
 {
-    NSG_REQUIRE(S && u && y && B > 0 && T > 1 && hop > 0 && iters >= 0, NSG_E_INVALID, "nsg_audio_griffin_lim: bad argument");
-    const int lg = log2_of(n_fft);
-    NSG_REQUIRE(lg >= 9 && lg <= 11, NSG_E_UNSUPPORTED, "nsg_audio_griffin_lim: n_fft must be 512, 1024 or 2048");
-    NSG_REQUIRE(n_fft % hop == 0, NSG_E_UNSUPPORTED, "nsg_audio_griffin_lim: hop must divide n_fft");
-    NSG_REQUIRE((int64_t)hop * (T - 1) < 0x7fffffff, NSG_E_UNSUPPORTED, "nsg_audio_griffin_lim: too many samples (hop * (T - 1) >= 2^31)");
-    NSG_REQUIRE((int64_t)hop * (T - 1) >= 2, NSG_E_UNSUPPORTED, "nsg_audio_griffin_lim: hop * (T - 1) must be at least 2 samples (a one-sample grid has no reflect padding)");
-    const GriffinLimLayout G = griffin_lim_layout(workspace, B, T, n_fft);
-    NSG_REQUIRE(workspace && workspace_bytes >= G.bytes, NSG_E_WORKSPACE, "nsg_audio_griffin_lim: workspace too small");
-    NSG_REQUIRE((int64_t)B * T < 0x7fffffff, NSG_E_UNSUPPORTED, "nsg_audio_griffin_lim: too many frames");
-    griffin_lim_launch(S, u, y, nullptr, 0.f, B, T, lg, hop, iters, G, (hipStream_t)stream);
-    return nsg_check_launch("griffin_lim");
+    return griffin_lim_run("nsg_audio_griffin_lim", S, u, y, nullptr, 0.f, B, T, n_fft, hop, iters, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 // Griffin-Lim with momentum; the state X_{i-1} lives in the caller's c, the workspace is nsg_audio_griffin_lim's
 int nsg_audio_griffin_lim_fast(const float *S, const float *u, float *y, float *c, int32_t B, int32_t T, int32_t n_fft, int32_t hop, int32_t iters,
                                float momentum, void *workspace, size_t workspace_bytes, void *stream)
 {
-    NSG_REQUIRE(S && u && y && B > 0 && T > 1 && hop > 0 && iters >= 0, NSG_E_INVALID, "nsg_audio_griffin_lim_fast: bad argument");
-    NSG_REQUIRE(momentum >= 0.f && momentum <= 1.f, NSG_E_INVALID, "nsg_audio_griffin_lim_fast: momentum must be in [0, 1]");      // (NaN fails both)
-    NSG_REQUIRE(c || momentum == 0.f, NSG_E_INVALID, "nsg_audio_griffin_lim_fast: momentum > 0 needs the state buffer c");
-    const int lg = log2_of(n_fft);
-    NSG_REQUIRE(lg >= 9 && lg <= 11, NSG_E_UNSUPPORTED, "nsg_audio_griffin_lim_fast: n_fft must be 512, 1024 or 2048");
-    NSG_REQUIRE(n_fft % hop == 0, NSG_E_UNSUPPORTED, "nsg_audio_griffin_lim_fast: hop must divide n_fft");
-    NSG_REQUIRE((int64_t)hop * (T - 1) < 0x7fffffff, NSG_E_UNSUPPORTED, "nsg_audio_griffin_lim_fast: too many samples (hop * (T - 1) >= 2^31)");
-    NSG_REQUIRE((int64_t)hop * (T - 1) >= 2, NSG_E_UNSUPPORTED, "nsg_audio_griffin_lim_fast: hop * (T - 1) must be at least 2 samples (a one-sample grid has no reflect padding)");
-    const GriffinLimLayout G = griffin_lim_layout(workspace, B, T, n_fft);
-    NSG_REQUIRE(workspace && workspace_bytes >= G.bytes, NSG_E_WORKSPACE, "nsg_audio_griffin_lim_fast: workspace too small");
-    NSG_REQUIRE((int64_t)B * T < 0x7fffffff, NSG_E_UNSUPPORTED, "nsg_audio_griffin_lim_fast: too many frames");
-    griffin_lim_launch(S, u, y, c, momentum, B, T, lg, hop, iters, G, (hipStream_t)stream);
-    return nsg_check_launch("griffin_lim_fast");
+    return griffin_lim_run("nsg_audio_griffin_lim_fast", S, u, y, c, momentum, B, T, n_fft, hop, iters, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 // S [B][T][F] magnitudes -> angles [B][T][F] in turns, what both Griffin-Lim entry points take as u
@@ -647,28 +659,18 @@ int nsg_audio_spsi_phases(const float *S, float *angles, int32_t B, int32_t T, i
                           void *stream)
 {
     NSG_REQUIRE(S && angles && B > 0 && T > 0 && hop > 0, NSG_E_INVALID, "nsg_audio_spsi_phases: bad argument");
-    const int lg = log2_of(n_fft);
-    NSG_REQUIRE(lg >= 9 && lg <= 11, NSG_E_UNSUPPORTED, "nsg_audio_spsi_phases: n_fft must be 512, 1024 or 2048");
-    NSG_REQUIRE(n_fft % hop == 0, NSG_E_UNSUPPORTED, "nsg_audio_spsi_phases: hop must divide n_fft");
-    NSG_REQUIRE((int64_t)hop * (T - 1) < 0x7fffffff, NSG_E_UNSUPPORTED, "nsg_audio_spsi_phases: too many samples (hop * (T - 1) >= 2^31)");
-    NSG_REQUIRE((int64_t)B * T < 0x7fffffff, NSG_E_UNSUPPORTED, "nsg_audio_spsi_phases: too many frames");
-    const size_t need = griffin_lim_layout(nullptr, B, T, n_fft).bytes;
-    NSG_REQUIRE(workspace && workspace_bytes >= need, NSG_E_WORKSPACE, "nsg_audio_spsi_phases: workspace too small");
+    const int lg = griffin_lim_grid("nsg_audio_spsi_phases", B, T, n_fft, hop, false, true, workspace, workspace_bytes);
+    if (lg < 0) return lg;
     const SpsiLayout P = spsi_layout(workspace, B, T, n_fft);
-    NSG_REQUIRE(P.bytes <= need, NSG_E_UNSUPPORTED, "nsg_audio_spsi_phases: the layout does not fit nsg_audio_griffin_lim's workspace");
+    NSG_REQUIRE(P.bytes <= griffin_lim_layout(nullptr, B, T, n_fft).bytes, NSG_E_UNSUPPORTED,
+                "nsg_audio_spsi_phases: the layout does not fit nsg_audio_griffin_lim's workspace");
     hipStream_t s = (hipStream_t)stream;
-    const unsigned nfr = (unsigned)(B * T);
     const double r = (double)hop / (double)n_fft;      // a power of two: exact
-    if (lg == 9) {
-        hipLaunchKernelGGL((spsi_frames_kernel<9>), dim3(nfr), dim3(256), 0, s, S, P.adv, P.own, r);
-        hipLaunchKernelGGL((spsi_walk_kernel<9>), dim3((unsigned)B), dim3(256), 0, s, P.adv, P.own, angles, T);
-    } else if (lg == 10) {
-        hipLaunchKernelGGL((spsi_frames_kernel<10>), dim3(nfr), dim3(256), 0, s, S, P.adv, P.own, r);
-        hipLaunchKernelGGL((spsi_walk_kernel<10>), dim3((unsigned)B), dim3(256), 0, s, P.adv, P.own, angles, T);
-    } else {
-        hipLaunchKernelGGL((spsi_frames_kernel<11>), dim3(nfr), dim3(256), 0, s, S, P.adv, P.own, r);
-        hipLaunchKernelGGL((spsi_walk_kernel<11>), dim3((unsigned)B), dim3(256), 0, s, P.adv, P.own, angles, T);
-    }
+    with_fft_size(lg, [&](auto lgc) {
+        constexpr int LG = decltype(lgc)::value;
+        hipLaunchKernelGGL((spsi_frames_kernel<LG>), dim3((unsigned)(B * T)), dim3(256), 0, s, S, P.adv, P.own, r);
+        hipLaunchKernelGGL((spsi_walk_kernel<LG>), dim3((unsigned)B), dim3(256), 0, s, P.adv, P.own, angles, T);
+    });
     return nsg_check_launch("spsi_phases");
 }
 
@@ -677,26 +679,20 @@ int nsg_audio_spectral_convergence(const float *y, const float *S, double *frame
                                    int32_t hop, void *stream)
 {
     NSG_REQUIRE(y && S && clip_sums && B > 0 && T > 1 && hop > 0, NSG_E_INVALID, "nsg_audio_spectral_convergence: bad argument");
-    const int lg = log2_of(n_fft);
-    NSG_REQUIRE(lg >= 9 && lg <= 11, NSG_E_UNSUPPORTED, "nsg_audio_spectral_convergence: n_fft must be 512, 1024 or 2048");
-    NSG_REQUIRE(n_fft % hop == 0, NSG_E_UNSUPPORTED, "nsg_audio_spectral_convergence: hop must divide n_fft");
-    NSG_REQUIRE((int64_t)hop * (T - 1) < 0x7fffffff, NSG_E_UNSUPPORTED, "nsg_audio_spectral_convergence: too many samples (hop * (T - 1) >= 2^31)");
-    NSG_REQUIRE((int64_t)hop * (T - 1) >= 2, NSG_E_UNSUPPORTED, "nsg_audio_spectral_convergence: hop * (T - 1) must be at least 2 samples (a one-sample grid has no reflect padding)");
-    NSG_REQUIRE((int64_t)B * T < 0x7fffffff, NSG_E_UNSUPPORTED, "nsg_audio_spectral_convergence: too many frames");
+    const int lg = griffin_lim_grid("nsg_audio_spectral_convergence", B, T, n_fft, hop, true, false, nullptr, 0);
+    if (lg < 0) return lg;
     hipStream_t s = (hipStream_t)stream;
     const int F = n_fft / 2 + 1;
     const int L = hop * (T - 1);
-    if (frame_sums) {
-        const unsigned nfr = (unsigned)(B * T);
-        if (lg == 9)       hipLaunchKernelGGL((convergence_frames_kernel<9>), dim3(nfr), dim3(256), 0, s, y, S, frame_sums, T, hop, L, F);
-        else if (lg == 10) hipLaunchKernelGGL((convergence_frames_kernel<10>), dim3(nfr), dim3(256), 0, s, y, S, frame_sums, T, hop, L, F);
-        else               hipLaunchKernelGGL((convergence_frames_kernel<11>), dim3(nfr), dim3(256), 0, s, y, S, frame_sums, T, hop, L, F);
-        hipLaunchKernelGGL(convergence_clips_kernel, dim3((unsigned)B), dim3(256), 0, s, frame_sums, clip_sums, T);
-    } else {
-        if (lg == 9)       hipLaunchKernelGGL((convergence_serial_kernel<9>), dim3((unsigned)B), dim3(256), 0, s, y, S, clip_sums, T, hop, L, F);
-        else if (lg == 10) hipLaunchKernelGGL((convergence_serial_kernel<10>), dim3((unsigned)B), dim3(256), 0, s, y, S, clip_sums, T, hop, L, F);
-        else               hipLaunchKernelGGL((convergence_serial_kernel<11>), dim3((unsigned)B), dim3(256), 0, s, y, S, clip_sums, T, hop, L, F);
-    }
+    with_fft_size(lg, [&](auto lgc) {
+        constexpr int LG = decltype(lgc)::value;
+        if (frame_sums) {
+            hipLaunchKernelGGL((convergence_frames_kernel<LG>), dim3((unsigned)(B * T)), dim3(256), 0, s, y, S, frame_sums, T, hop, L, F);
+            hipLaunchKernelGGL(convergence_clips_kernel, dim3((unsigned)B), dim3(256), 0, s, frame_sums, clip_sums, T);
+        } else {
+            hipLaunchKernelGGL((convergence_serial_kernel<LG>), dim3((unsigned)B), dim3(256), 0, s, y, S, clip_sums, T, hop, L, F);
+        }
+    });
     return nsg_check_launch("spectral_convergence");
 }
 
@@ -704,17 +700,13 @@ int nsg_audio_spectral_convergence(const float *y, const float *S, double *frame
 int nsg_audio_stft(const float *y, float *X, int32_t B, int32_t L, int32_t n_fft, int32_t hop, void *stream)
 {
     NSG_REQUIRE(y && X && B > 0 && L > 0 && hop > 0, NSG_E_INVALID, "nsg_audio_stft: bad argument");
-    const int lg = log2_of(n_fft);
-    NSG_REQUIRE(lg >= 9 && lg <= 11, NSG_E_UNSUPPORTED, "nsg_audio_stft: n_fft must be 512, 1024 or 2048");
-    NSG_REQUIRE(L > n_fft / 2, NSG_E_UNSUPPORTED, "nsg_audio_stft: reflect padding needs more than n_fft/2 samples");
+    const int lg = stft_grid("nsg_audio_stft", B, L, n_fft, hop);
+    if (lg < 0) return lg;
     const int T = 1 + L / hop, F = n_fft / 2 + 1;
-    hipStream_t s = (hipStream_t)stream;
-    NSG_REQUIRE((int64_t)B * T < 0x7fffffff, NSG_E_UNSUPPORTED, "nsg_audio_stft: too many frames (B * T >= 2^31)");
-    const unsigned nfr = (unsigned)(B * T);
-    v2f *spec = reinterpret_cast<v2f *>(X);
-    if (lg == 9)       hipLaunchKernelGGL((stft_phase_kernel<9>), dim3(nfr), dim3(256), 0, s, y, nullptr, spec, T, hop, L, F, 1);
-    else if (lg == 10) hipLaunchKernelGGL((stft_phase_kernel<10>), dim3(nfr), dim3(256), 0, s, y, nullptr, spec, T, hop, L, F, 1);
-    else               hipLaunchKernelGGL((stft_phase_kernel<11>), dim3(nfr), dim3(256), 0, s, y, nullptr, spec, T, hop, L, F, 1);
+    with_fft_size(lg, [&](auto lgc) {
+        hipLaunchKernelGGL((stft_kernel<decltype(lgc)::value, STFT_RAW>), dim3((unsigned)(B * T)), dim3(256), 0, (hipStream_t)stream, y, (const float *)nullptr,
+                           reinterpret_cast<v2f *>(X), (v2f *)nullptr, T, hop, L, F, 0.f);
+    });
     return nsg_check_launch("stft");
 }
 
@@ -747,12 +739,10 @@ int nsg_audio_melspectrogram(const float *wav, const int32_t *lengths, const flo
     NSG_REQUIRE(wav && basis && bands && out && B > 0 && L > 0 && hop > 0 && n_mels > 0, NSG_E_INVALID, "nsg_audio_melspectrogram: bad argument");
     NSG_REQUIRE(max_abs_value > 0.f && min_level_db < 0.f && (frame_major == 0 || frame_major == 1), NSG_E_INVALID,
                 "nsg_audio_melspectrogram: bad argument (max_abs_value > 0, min_level_db < 0, frame_major 0 or 1)");
-    const int lg = log2_of(n_fft);
-    NSG_REQUIRE(lg >= 9 && lg <= 11, NSG_E_UNSUPPORTED, "nsg_audio_melspectrogram: n_fft must be 512, 1024 or 2048");
+    const int lg = stft_grid("nsg_audio_melspectrogram", B, L, n_fft, hop);
+    if (lg < 0) return lg;
     NSG_REQUIRE(n_mels <= MEL_MAX_ROWS, NSG_E_UNSUPPORTED, "nsg_audio_melspectrogram: at most 128 mel bins");
-    NSG_REQUIRE(L > n_fft / 2, NSG_E_UNSUPPORTED, "nsg_audio_melspectrogram: reflect padding needs more than n_fft/2 samples");
     const int T = 1 + L / hop, F = n_fft / 2 + 1;
-    NSG_REQUIRE((int64_t)B * T < 0x7fffffff, NSG_E_UNSUPPORTED, "nsg_audio_melspectrogram: too many frames (B * T >= 2^31)");
     MelBands mb;
     for (int m = 0; m < n_mels; ++m) {
         const int32_t f0 = bands[2 * m], f1 = bands[2 * m + 1];
@@ -765,12 +755,10 @@ int nsg_audio_melspectrogram(const float *wav, const int32_t *lengths, const flo
     hipStream_t s = (hipStream_t)stream;
     const int pairs = (T + 1) / 2;                 // a workgroup owns two frames of a clip
     const unsigned nwg = (unsigned)(B * pairs);
-#define NSG_MEL_LAUNCH(LG) hipLaunchKernelGGL((melspectrogram_kernel<LG>), dim3(nwg), dim3(256), 0, s, wav, lengths, basis, mb, out, T, pairs, hop, L, n_mels, \
-                                              preemphasis, min_amp, min_level_db, ref_level_db, max_abs_value, frame_major)
-    if (lg == 9)       NSG_MEL_LAUNCH(9);
-    else if (lg == 10) NSG_MEL_LAUNCH(10);
-    else               NSG_MEL_LAUNCH(11);
-#undef NSG_MEL_LAUNCH
+    with_fft_size(lg, [&](auto lgc) {
+        hipLaunchKernelGGL((melspectrogram_kernel<decltype(lgc)::value>), dim3(nwg), dim3(256), 0, s, wav, lengths, basis, mb, out, T, pairs, hop, L, n_mels,
+                           preemphasis, min_amp, min_level_db, ref_level_db, max_abs_value, frame_major);
+    });
     return nsg_check_launch("melspectrogram_kernel");
 }
 

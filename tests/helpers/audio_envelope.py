@@ -20,7 +20,7 @@ def c_rem(a, b):
 
 
 def reflect_index_fixed(i, L):
-    """stft_phase_kernel's padded index, statement by statement (i = t hop + n - N/2, any sign)."""
+    """stft_frame_lds's padded index, statement by statement (i = t hop + n - N/2, any sign)."""
     period = 2 * (L - 1)
     idx = c_rem(i, period)
     if idx < 0:

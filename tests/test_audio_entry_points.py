@@ -1,5 +1,5 @@
 """CPU tests of the mel -> waveform entry points of csrc/audio.hip: what they refuse before any launch (pointers that are
-never dereferenced, as in tests/test_preprocess.py), the reflect map of stft_phase_kernel restated in Python against
+never dereferenced, as in tests/test_preprocess.py), the reflect map of stft_frame_lds restated in Python against
 np.pad(mode="reflect"), and what the derived bounds of tests/helpers/audio_envelope.py assume about their inputs."""
 import ctypes
 
@@ -88,6 +88,51 @@ def test_griffin_lim_refuses_bad_arguments_before_any_launch():
     # the smallest grids the entry point accepts are refused for nothing but the workspace here (so the checks above it passed)
     for change in (dict(hop=2, T=2), dict(hop=1, T=3), dict(hop=1024, T=2), dict(hop=128, T=2)):
         assert _refused(lib, name, gl(ws=NULL, **change), WORKSPACE), change
+
+
+def _grid_entry_points(lib):
+    """name -> (call(B, T, n_fft, hop, ws, ws_bytes), takes a workspace) for the four entry points on Griffin-Lim's grid, every
+    other argument good."""
+    return {
+        "nsg_audio_griffin_lim":
+            (lambda B, T, n, h, ws, nb: lib.nsg_audio_griffin_lim(P(OK), P(OK), P(OK), B, T, n, h, 3, P(ws), nb, None), True),
+        "nsg_audio_griffin_lim_fast":
+            (lambda B, T, n, h, ws, nb: lib.nsg_audio_griffin_lim_fast(P(OK), P(OK), P(OK), P(OK), B, T, n, h, 3, 0.99, P(ws), nb, None), True),
+        "nsg_audio_spsi_phases":
+            (lambda B, T, n, h, ws, nb: lib.nsg_audio_spsi_phases(P(OK), P(OK), B, T, n, h, P(ws), nb, None), True),
+        "nsg_audio_spectral_convergence":
+            (lambda B, T, n, h, ws, nb: lib.nsg_audio_spectral_convergence(P(OK), P(OK), P(OK), P(OK), B, T, n, h, None), False),
+    }
+
+
+@pytest.mark.parametrize("name", ["nsg_audio_griffin_lim", "nsg_audio_griffin_lim_fast", "nsg_audio_spsi_phases", "nsg_audio_spectral_convergence"])
+def test_the_four_entry_points_on_griffin_lims_grid_refuse_the_same_grids(name):
+    """The bad grids of test_griffin_lim_refuses_bad_arguments_before_any_launch, fed to every entry point that takes that grid:
+    the same code, under the entry point's own name, with a workspace that would do (so the grid alone is refused) and with none
+    (the grid is judged before the workspace).  The two stated differences: SPSI takes a single frame and the one-sample grid,
+    which it reflects nowhere, as far as its workspace check."""
+    lib = _lib.load()
+    call, has_ws = _grid_entry_points(lib)[name]
+    good = dict(B=2, T=24, n_fft=1024, hop=256)
+    spsi = name == "nsg_audio_spsi_phases"
+
+    def run(ws=OK, ws_bytes=1 << 62, **change):
+        a = dict(good, **change)
+        return call(a["B"], a["T"], a["n_fft"], a["hop"], ws, ws_bytes)
+
+    for change in (dict(n_fft=1000), dict(n_fft=256), dict(n_fft=4096), dict(n_fft=0), dict(hop=200), dict(hop=384), dict(hop=2048),
+                   dict(B=1 << 16, T=1 << 15)):                            # B * T = 2^31 frames
+        assert _refused(lib, name, run(**change), UNSUPPORTED), change
+        assert _refused(lib, name, run(ws=NULL, ws_bytes=0, **change), UNSUPPORTED), change
+    assert b"too many frames" in lib.nsg_last_error_string()
+    # a one-sample grid has no reflection, a single frame no samples at all: only SPSI, which forms no frame of samples, takes them
+    assert _refused(lib, name, run(ws=NULL, hop=1, T=2), WORKSPACE if spsi else UNSUPPORTED)
+    assert _refused(lib, name, run(ws=NULL, T=1), WORKSPACE if spsi else INVALID)
+    if has_ws:
+        need = lib.nsg_audio_griffin_lim_workspace_bytes(2, 24, 1024)
+        for ws, nb in ((NULL, need), (OK, need - 1), (OK, 0)):
+            assert _refused(lib, name, run(ws=ws, ws_bytes=nb), WORKSPACE), (ws, nb)
+            assert b"workspace too small" in lib.nsg_last_error_string()
 
 
 def test_griffin_lim_workspace_bytes():

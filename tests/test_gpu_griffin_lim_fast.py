@@ -1,4 +1,4 @@
-"""GPU tests of fast Griffin-Lim and the spectral-convergence figure (csrc/audio.hip: stft_phase_momentum_kernel, the
+"""GPU tests of fast Griffin-Lim and the spectral-convergence figure (csrc/audio.hip: stft_kernel's momentum outputs, the
 convergence_* kernels; include/nsg.h: nsg_audio_griffin_lim_fast, nsg_audio_spectral_convergence) and of their wiring through
 audio.py and evaluate.py.
 
