@@ -1125,6 +1125,67 @@ NSG_API int nsg_audio_mix_noise(const float *wav, const int32_t *lengths, const 
                                 const int32_t *offset, float *out, double *energy, int32_t B, int32_t L, int32_t Ln, void *workspace,
                                 size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Judging a reconstructed waveform against the recording: short-time objective intelligibility, STOI (Taal, Hendriks, Heusdens,
+ * Jensen 2011) and extended STOI (Jensen, Taal 2016).  An extension: the reference has no figure in the waveform domain.  parity
+ * unpinned: pystoi is absent; the definition is this project's own, written from the two papers and stated here in full,
+ * restated in fp64 by tests/helpers/stoi_ref.py.  audio.stoi_envelopes, audio.stoi (csrc/stoi.hip).
+ * ------------------------------------------------------------------------------------------- */
+
+/* Everything is at 10 000 Hz (the caller resamples).  x [B][L] fp32 is the clean batch, y [B][L] the processed one, aligned sample
+ * for sample; clip b has len = lengths[b] samples of its row (lengths NULL: L; int32 DEVICE memory).
+ *   window     w[n] = 0.5 - 0.5 cos(2 pi (n + 1) / 257), n = 0 .. 255 (MATLAB's hanning(256)), evaluated in fp64.
+ *   candidates frame t = 0 .. T_b - 1, T_b = (len - 256) / 128 + 1, is samples 128 t .. 128 t + 255 of x, with the energy
+ *                  energy[b][t] = sum_n ((double)w[n] * (double)x[128 t + n])^2                          [B][Tmax] fp64
+ *              products, squares and sum in fp64 in one fixed order: with n = 4 l + i, lane l of 64 adds its squares i = 0 .. 3 to
+ *              0.0 in that order, and the 64 lane sums are closed by xor-butterflies over the offsets 32, 16, .., 1
+ *              (csrc/nsg_reduce.h: nsg_wave_sum_butterfly).  Tmax = (L - 256) / 128 + 1; energy[b][t] = 0.0 for t >= T_b.
+ *   selection  frame t is kept iff energy[b][t] > 1e-4 * max_t energy[b][t]: a strict comparison in fp64 against the exact maximum
+ *              (the 40 dB range); an all-zero clip keeps nothing.  The decision comes from x alone.  src[b][k] = the k-th kept
+ *              frame, ascending, for k < C = kept[b], and -1 for C <= k < Tmax.                          [B][Tmax], [B] int32
+ *   compaction xs[128 k + n] += w[n] x[128 src[k] + n], k < C, n < 256, and ys the same with the same src: a sample of xs is the
+ *              sum of at most two windowed source samples.  It is formed where it is used and never stored.
+ *   spectrum   frame m = 0 .. C - 1 is w[n] xs[128 m + n], n < 256, in fp32 with the window rounded to fp32:
+ *                  fl(w[n] * fl(fl(w[n'] x[128 src[m'] + n']) + fl(w[n''] x[128 src[m''] + n''])))   the two (m', n'), m' < m'', with
+ *              128 m' + n' = 128 m + n, or the one product when there is one; zero-padded to 512; X = its 512-point DFT; |X[f]|^2 on
+ *              f = 0 .. 256.  x's and y's frame are the real and the imaginary part of one complex radix-2 FFT in fp32, split by
+ *              Hermitian symmetry.
+ *   bands      j = 0 .. 14: the bins [band_lo[j], band_hi[j]).  audio.stoi_bands() builds the third-octave table: with f[i] = i
+ *              10000 / 512, band_lo[j] = argmin_i |f[i] - 150 * 2^((2 j - 1) / 6)|, band_hi[j] = argmin_i |f[i] - 150 * 2^((2 j + 1) / 6)|
+ *              (band 0 is bins 7 .. 8; band 14 ends below bin 257).
+ *                  env[0][b][m][j] = sqrtf(sum_{f in band j} |X[m][f]|^2),  env[1][b][m][j] the same for y   [2][B][Tmax][15] fp32
+ *              the sum in fp32 added to 0.f in index order; rows m >= C are written as zeros.
+ * A clip's five outputs depend on its own samples and length alone: bit for bit independent of B, L and its row.  Every element of
+ * energy, src, kept and env is written exactly once.  No workspace, no atomics, three launches: energies (one wave per frame),
+ * selection (one workgroup per clip: exact maximum, keep mask, exclusive block scan), envelopes (one workgroup per (clip, m) on a
+ * grid of B * Tmax; those with m >= C write their zeros and leave).  band_lo, band_hi [15] int32 are HOST memory, read and checked
+ * before the first launch.
+ * NSG_E_INVALID: a null pointer other than lengths, B < 1, bands that are not 15 ascending non-empty runs inside 0 .. 256
+ * (0 <= lo_0, lo_j < hi_j, hi_j <= lo_{j+1}, hi_14 <= 257);  NSG_E_UNSUPPORTED: L < 256, B * Tmax >= 2^31.
+ * A lengths[b] below 256 or above L cannot be refused on the host: such a clip has T_b = 0, kept[b] = 0 and a NaN figure. */
+NSG_API int nsg_audio_stoi_envelopes(const float *x, const float *y, const int32_t *lengths, const int32_t *band_lo,
+                                     const int32_t *band_hi, double *energy, int32_t *src, int32_t *kept, float *env, int32_t B,
+                                     int32_t L, void *stream);
+
+/* The figure from the envelopes: env [2][B][Tmax][15] fp32 and kept [B] int32 as nsg_audio_stoi_envelopes writes them (kept is
+ * clamped to Tmax) -> d [B] fp64.  All arithmetic is fp64 on the widened envelopes; eps = 2^-52.  With C = kept[b], a segment is the
+ * 30 frames m - 29 .. m for m = 29 .. C - 1; x_j, y_j are the 30-vectors of band j of env[0], env[1]; every sum below runs over its
+ * index ascending from 0.0.
+ *   extended = 0, STOI:   alpha = sqrt(sum x_j^2 / (sum y_j^2 + eps));   y'_j = min(alpha y_j, (1 + 10^(15/20)) x_j) element-wise;
+ *       d[m][j] = sum (x_j - mean x_j)(y'_j - mean y'_j) / (sqrt(sum (x_j - mean x_j)^2) * sqrt(sum (y'_j - mean y'_j)^2) + eps)
+ *       with mean v = (sum v) / 30;  d[b] = the mean of d[m][j] over all 15 (C - 29) pairs.
+ *   extended = 1, ESTOI:  on the 15 x 30 segment matrices of X and of Y separately, subtract each row's mean and multiply each row by
+ *       1 / (its norm + eps); then subtract each column's mean (over the 15 bands) and divide each column by (its norm + eps);
+ *       d[m] = (1 / 30) sum_n sum_j X~[j][n] Y~[j][n];  d[b] = the mean of d[m] over the C - 29 segments.
+ * The per-item figures are added in one fixed order (csrc/nsg_reduce.h): thread k of 256 adds its items k, k + 256, ... to 0.0 in
+ * that order (item i of STOI is the segment ending at 29 + i / 15, band i mod 15; item i of ESTOI the segment ending at 29 + i), the
+ * 256 thread sums are closed by the butterfly block sum (nsg_block_sum_butterfly), and the total is divided by the item count.  Two
+ * calls give the same bits, and a clip's figure does not depend on B or on its row.  d[b] = NaN where kept[b] < 30.  One
+ * workgroup per clip, one launch, no workspace.
+ * NSG_E_INVALID: a null pointer, B < 1, Tmax < 1, extended not 0 or 1;  NSG_E_UNSUPPORTED: B * Tmax >= 2^31. */
+NSG_API int nsg_audio_stoi_score(const float *env, const int32_t *kept, double *d, int32_t B, int32_t Tmax, int32_t extended,
+                                 void *stream);
+
 #ifdef __cplusplus
 }
 #endif

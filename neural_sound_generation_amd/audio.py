@@ -50,6 +50,12 @@ waveform-similarity overlap-add, csrc/tsm.hip), pitch_shift (tempo, then resampl
 and a noise recording added at a level relative to the clip's RMS), random_augment (the reference's draws from a seeded CPU
 generator, then tempo and mix_noise); preprocess.process_utterances(augment_copies=n) writes augmented copies.  All opt-in.
 
+Judging a reconstruction against the recording it came from (evaluate.test_reconstruction_audio): stoi (STOI and, extended, ESTOI:
+the short-time objective intelligibility of a processed waveform against the clean one, aligned sample for sample, at 10 kHz through
+resample; csrc/stoi.hip), in two stages that can be called alone, stoi_envelopes and stoi_score; stoi_bands is the third-octave
+table.  An extension: the reference has no figure in the waveform domain.  parity unpinned: pystoi is absent (here and on the GPU
+box); the definition is this project's own, from the two papers, stated in include/nsg.h.
+
 parity unpinned: librosa is absent (here, on the GPU box, and from the reference's own tree), and no file of the reference
 holds a waveform; tests compare with the numpy restatement in oracle/audio_oracle.py (same initial phases) and check the
 transform identities (istft(stft(y)) == y, the spectral error falls over the iterations).
@@ -858,3 +864,121 @@ def load_wav(path, sample_rate=22050, resample=False, device="cuda:0") -> np.nda
             raise ValueError(f"{path}: sample rate {sr}, expected {sample_rate} (pass resample=True to resample it)")
         wav = _resample(wav, sr, sample_rate, device=device)
     return wav
+
+
+STOI_RATE, STOI_FRAME, STOI_HOP, STOI_FFT, STOI_BANDS, STOI_SEGMENT = 10000, 256, 128, 512, 15, 30     # include/nsg.h: nsg_audio_stoi_envelopes
+
+
+@functools.lru_cache(maxsize=1)
+def stoi_bands() -> np.ndarray:
+    """The 15 third-octave bands of STOI as runs of the 512-point spectrum's bins at 10 kHz, (15, 2) int32 rows [lo, hi): with
+    f[i] = i 10000 / 512, lo_j = argmin_i |f[i] - 150 * 2^((2 j - 1) / 6)| and hi_j = argmin_i |f[i] - 150 * 2^((2 j + 1) / 6)| (centre
+    frequencies 150 * 2^(j / 3) Hz).  Band 0 is bins 7 .. 8, and hi_j = lo_{j+1}."""
+    f = np.arange(STOI_FFT // 2 + 1, dtype=np.float64) * STOI_RATE / STOI_FFT
+    j = np.arange(STOI_BANDS, dtype=np.float64)
+    lo = np.argmin(np.abs(f[None, :] - (150.0 * 2.0 ** ((2.0 * j - 1.0) / 6.0))[:, None]), axis=1)
+    hi = np.argmin(np.abs(f[None, :] - (150.0 * 2.0 ** ((2.0 * j + 1.0) / 6.0))[:, None]), axis=1)
+    bands = np.ascontiguousarray(np.stack((lo, hi), axis=1), dtype=np.int32)
+    bands.setflags(write=False)
+    return bands
+
+
+def _stoi_pair(fn, x, y, lengths):
+    """The checks stoi_envelopes and stoi share, before anything is launched -> (B, L, host lengths or the device tensor or None)."""
+    for nm, t in (("x", x), ("y", y)):
+        if not torch.is_tensor(t) or t.dim() != 2 or t.dtype != torch.float32:
+            raise TypeError(f"{fn}: {nm} must be a float32 tensor (B, L), got {tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+    if x.shape != y.shape or x.device != y.device:
+        raise ValueError(f"{fn}: x {tuple(x.shape)} on {x.device} and y {tuple(y.shape)} on {y.device} are not one aligned batch")
+    B, L = x.shape
+    if B < 1:
+        raise ValueError(f"{fn}: an empty batch")
+    if lengths is not None and not (torch.is_tensor(lengths) and lengths.is_cuda):
+        host = lengths.numpy() if torch.is_tensor(lengths) else np.asarray(lengths)
+        if host.shape != (B,) or not np.issubdtype(host.dtype, np.integer):
+            raise ValueError(f"{fn}: lengths must be {B} integers, got {host.dtype} {host.shape}")
+        if host.min() < 0 or host.max() > L:
+            raise ValueError(f"{fn}: every length must be in [0, {L}], got {int(host.min())} .. {int(host.max())}")
+        lengths = np.ascontiguousarray(host, dtype=np.int32)
+    return B, L, lengths
+
+
+def stoi_envelopes(x, y, lengths=None):
+    """The first stage of stoi, at 10 kHz (include/nsg.h: nsg_audio_stoi_envelopes states it; csrc/stoi.hip): x the clean clips, y the
+    processed ones, float32 GPU tensors (B, L) aligned sample for sample, L >= 256; lengths (B,) integers in [0, L] on the host, or
+    an int32 tensor on the device (None: all L).  Frames of 256 samples every 128 under a Hann window; those whose energy in x is
+    within 40 dB of the clip's loudest are kept, the kept frames of both signals are overlap-added into compacted signals, and
+    those are analysed again (512-point FFT, 15 third-octave bands).  Returns (env (2, B, Tmax, 15) float32: the band envelopes
+    of x and of y, zeros past each clip's kept frames; kept (B,) int32; src (B, Tmax) int32: the candidate frame behind each kept
+    one, -1 beyond; energy (B, Tmax) float64: the candidates' energies), Tmax = (L - 256) // 128 + 1.  A clip shorter than 256
+    samples keeps nothing.  A clip's outputs are bit for bit what they are alone.  parity unpinned: pystoi is absent, the
+    definition is this project's, from the papers.  Every argument is checked before anything is launched; nothing synchronises."""
+    B, L, lens = _stoi_pair("stoi_envelopes", x, y, lengths)
+    if L < STOI_FRAME:
+        raise ValueError(f"stoi_envelopes: {L} samples; a frame needs {STOI_FRAME}")
+    Tmax = (L - STOI_FRAME) // STOI_HOP + 1
+    if B * Tmax >= 2 ** 31:
+        raise ValueError(f"stoi_envelopes: {B} clips of {Tmax} frames are 2^31 frames or more")
+    _chk(x, "x")
+    _chk(y, "y")
+    lens_d = None if lens is None else ops._lengths_on(lens, "stoi_envelopes: lengths", B, 0, L, x.device)
+    bands = stoi_bands()
+    lo, hi = np.ascontiguousarray(bands[:, 0]), np.ascontiguousarray(bands[:, 1])
+    energy = torch.empty(B, Tmax, dtype=torch.float64, device=x.device)
+    src = torch.empty(B, Tmax, dtype=torch.int32, device=x.device)
+    kept = torch.empty(B, dtype=torch.int32, device=x.device)
+    env = torch.empty(2, B, Tmax, STOI_BANDS, dtype=torch.float32, device=x.device)
+    _lib.call("nsg_audio_stoi_envelopes", _p(x), _p(y), _p(lens_d), c_void_p(lo.ctypes.data), c_void_p(hi.ctypes.data), _p(energy), _p(src), _p(kept),
+              _p(env), B, L, _stream())
+    return env, kept, src, energy
+
+
+def stoi_score(env, kept, extended=False):
+    """The second stage of stoi (include/nsg.h: nsg_audio_stoi_score): env (2, B, Tmax, 15) float32 and kept (B,) int32 as
+    stoi_envelopes returns them -> d (B,) float64 on the device, NaN where kept < 30.  fp64 throughout."""
+    if not isinstance(extended, (bool, np.bool_)):
+        raise ValueError(f"stoi_score: extended must be a bool, got {extended!r}")
+    if not torch.is_tensor(env) or env.dim() != 4 or env.shape[0] != 2 or env.shape[3] != STOI_BANDS or env.shape[1] < 1 or env.shape[2] < 1:
+        raise ValueError(f"stoi_score: env must be (2, B, Tmax, {STOI_BANDS}) with B, Tmax >= 1")
+    _, B, Tmax, _ = env.shape
+    if not torch.is_tensor(kept) or tuple(kept.shape) != (B,) or kept.device != env.device:
+        raise ValueError(f"stoi_score: kept must be an int32 tensor ({B},) on env's device")
+    if B * Tmax >= 2 ** 31:
+        raise ValueError(f"stoi_score: {B} clips of {Tmax} frames are 2^31 frames or more")
+    _chk(env, "env")
+    _chk(kept, "kept", torch.int32)
+    d = torch.empty(B, dtype=torch.float64, device=env.device)
+    _lib.call("nsg_audio_stoi_score", _p(env), _p(kept), _p(d), B, Tmax, int(bool(extended)), _stream())
+    return d
+
+
+def stoi(x, y, sample_rate=22050, lengths=None, extended=False):
+    """Short-time objective intelligibility of processed clips y against the clean clips x (STOI: Taal, Hendriks, Heusdens, Jensen
+    2011; extended=True: ESTOI, Jensen and Taal 2016), the waveform-domain figure for a reconstruction against its recording:
+    insensitive to level and phase, it needs only a time-aligned pair.  x, y: float32 GPU tensors (B, L) at sample_rate, aligned
+    sample for sample; lengths (B,) integers on the host (None: all L).  With sample_rate != 10000 both go through
+    resample(., sample_rate, 10000, lengths) first (22 050 -> 10 000 is 200 / 441, a table of 200 x 284); at 10 000 lengths may
+    also be an int32 device tensor.  Then stoi_envelopes and stoi_score (include/nsg.h states both): the correlation of the two
+    signals' third-octave band envelopes over segments of 30 frames (384 ms), after the frames more than 40 dB below the clean
+    clip's loudest are removed -- per band with the processed envelope scaled and clipped (STOI), or per segment after row and
+    column normalisation (ESTOI).  Returns (d (B,) float64 on the device: about 1 for y = x, lower for worse, NaN where fewer
+    than 30 frames are kept; kept (B,) int32 on the device).  parity unpinned: pystoi is absent (here and on the GPU box); the
+    definition is this project's own, from the two papers, and tests compare with its numpy restatement.  Every argument is
+    checked before anything is launched; nothing synchronises."""
+    if not isinstance(extended, (bool, np.bool_)):
+        raise ValueError(f"stoi: extended must be a bool, got {extended!r}")
+    P, Q = resample_ratio(sample_rate, STOI_RATE)
+    B, L, lens = _stoi_pair("stoi", x, y, lengths)
+    if -(-L * P // Q) < STOI_FRAME:
+        raise ValueError(f"stoi: {L} samples at {sample_rate} Hz are {-(-L * P // Q)} at {STOI_RATE} Hz; a frame needs {STOI_FRAME}")
+    if P != Q:
+        if lens is not None and not isinstance(lens, np.ndarray):
+            raise ValueError("stoi: lengths on the device go with sample_rate = 10000 (the resampler takes them on the host)")
+        if lens is not None and lens.min() < 1:
+            raise ValueError(f"stoi: every length must be in [1, {L}] to be resampled, got {int(lens.min())}")
+        resample_table(P, Q)
+        x, lens10 = resample(x, sample_rate, STOI_RATE, lengths=lens)
+        y, _ = resample(y, sample_rate, STOI_RATE, lengths=lens)
+        lens = None if lens is None else lens10
+    env, kept, _, _ = stoi_envelopes(x, y, lens)
+    return stoi_score(env, kept, extended), kept

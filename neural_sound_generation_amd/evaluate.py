@@ -27,6 +27,9 @@ checkpoint layout, restated from the reference's src/test.py:73-106 and src/main
     target for context; `test_conversion_f0(args, vqvae, pair_loader, device, epoch)` -- the same pairs as waveforms, judged by
     pitch: the converted mel inverted to a waveform, F0 by YIN (audio.f0), and along the same warping paths the F0 error in
     cents, the voiced / unvoiced disagreement and the log-F0 correlation (audio.f0_figures), pooled over all clips.
+  * `test_reconstruction_audio(args, vqvae, wav_loader, device, epoch)` -- the reconstruction judged as audio against the
+    recording: wav -> mel -> model -> waveform, and the mel inverted without the model beside it, each scored by STOI and ESTOI
+    (audio.stoi) against the wav it came from.
   * `codebook_usage(model, loader, device)` -- how much of the codebook a dataset uses: per-code counts and their perplexity.
 """
 from __future__ import annotations
@@ -382,6 +385,72 @@ def test_conversion_f0(args, vqvae, pair_loader, device, epoch, iters=None, angl
     print('====> Conversion test set: spectral convergence of the inversion {:.4f} ({} Griffin-Lim iterations, momentum {:g}, init {})'.format(
         out["converted"]["spectral_convergence"], iters, momentum, init))
     return out
+
+
+def test_reconstruction_audio(args, vqvae, wav_loader, device, epoch, iters=None, angles0=None, *, momentum=0.0, init="random"):
+    """The audio figure of a VQ-VAE's reconstructions, against the recordings themselves: `wav_loader` yields (wav (B, L) float32
+    zero-padded at 22 050 Hz, lengths (B,) host integers) or (wav, lengths, g (B,) int64 speaker ids).  Per batch:
+    audio.melspectrogram(wav, lengths=...) (T = 1 + L // 256 frames); Tc = T // 4 * 4; the model in eval mode (its mode is restored)
+    on mel[:, None, :, :Tc], with g if the model has speakers; then two waveforms of 256 (Tc - 1) samples from inv_mel_spectrogram's
+    steps -- "analysis_synthesis", from the mel itself: the ceiling the mel inversion sets, whatever the model does -- and
+    "reconstruction", from the model's output.  Each is scored against wav[:, :256 (Tc - 1)] with the lengths min(len, 256 (Tc - 1))
+    by audio.stoi, both STOI and ESTOI (at 10 kHz, through audio.resample).  iters (default audio.GRIFFIN_LIM_ITERS), angles0 (the
+    initial phases (B, Tc, 513) for every batch, or a sequence of them, one per batch; None draws them), momentum and init are
+    audio.inv_mel_spectrogram's, and serve both inversions.  Returns
+        {"analysis_synthesis": {"stoi", "estoi"}, "reconstruction": {"stoi", "estoi"}, "clips": n, "scored": n_finite}
+    each figure the mean over the clips of the loader on which it is finite (a clip that keeps fewer than 30 frames at 10 kHz,
+    about 0.4 s of speech, has none: NaN if there is no such clip at all), "scored" the clips on which all four are.  The sums and
+    counts stay on the device: one host synchronisation, at the end.  ValueError before anything is launched: a momentum outside
+    [0, 1], an init that is neither "random" nor "spsi" or that comes with angles0; an empty loader."""
+    from . import audio
+    momentum = audio._momentum("test_reconstruction_audio", momentum)
+    audio._init("test_reconstruction_audio", init, angles0)
+    hop, fft = 256, 1024
+    iters = audio.GRIFFIN_LIM_ITERS if iters is None else int(iters)
+    total = torch.zeros(2, 5, dtype=torch.float64, device=device)           # per figure: the sum and the count of the finite ones | [0, 4]: clips with all four
+    n = 0
+    was_training = vqvae.training
+    vqvae.eval()
+    try:
+        for k, batch in enumerate(wav_loader):
+            wav, lengths = batch[0], batch[1]
+            g = batch[2] if len(batch) > 2 else None
+            ls = np.asarray(lengths.cpu() if torch.is_tensor(lengths) else lengths).astype(np.int64)
+            wav = wav.to(device).contiguous()
+            Tc = (1 + wav.shape[1] // hop) // 4 * 4
+            if Tc < 4:
+                raise ValueError("test_reconstruction_audio: the batch needs at least 4 frames (one latent column)")
+            mel = audio.melspectrogram(wav, fft_size=fft, hop_size=hop, lengths=ls)[:, :, :Tc].contiguous()
+            with torch.no_grad():
+                g_d = g.to(device) if g is not None and getattr(vqvae, "n_speakers", None) is not None else None
+                out = vqvae(mel.unsqueeze(1), g_d)[0].squeeze(1)
+            if out.shape[2] != Tc:
+                out = F.pad(out, (0, Tc - out.shape[2])) if out.shape[2] < Tc else out[:, :, :Tc]
+            a0 = angles0[k] if isinstance(angles0, (list, tuple)) else angles0
+            n_out = hop * (Tc - 1)
+            clean = wav[:, :n_out].contiguous()
+            lc = np.minimum(ls, n_out)
+            figures = []
+            for m in (mel, out.contiguous()):
+                y = audio._invert_mel(m, 22050, fft, hop, 80, iters, a0, momentum, init)[2]
+                figures += [audio.stoi(clean, y, 22050, lc, extended=ext)[0] for ext in (False, True)]
+            d = torch.stack(figures)                                        # (4, B): a/s stoi, a/s estoi, reconstruction stoi, estoi
+            ok = torch.isfinite(d)
+            total[0, :4] += torch.where(ok, d, torch.zeros_like(d)).sum(1)
+            total[1, :4] += ok.sum(1)
+            total[0, 4] += ok.all(0).sum()
+            n += len(wav)
+    finally:
+        vqvae.train(was_training)
+    if n == 0:
+        raise ValueError("test_reconstruction_audio: empty loader")
+    sums, counts = total.tolist()                                           # the one read-back
+    mean = [s / c if c else float("nan") for s, c in zip(sums[:4], counts[:4])]
+    res = {"analysis_synthesis": {"stoi": mean[0], "estoi": mean[1]}, "reconstruction": {"stoi": mean[2], "estoi": mean[3]},
+           "clips": n, "scored": int(sums[4])}
+    print('====> Reconstruction test set: STOI {:.4f}, ESTOI {:.4f} reconstructed; {:.4f}, {:.4f} analysis-synthesis ({} of {} clips scored, '
+          '{} Griffin-Lim iterations, momentum {:g}, init {})'.format(mean[2], mean[3], mean[0], mean[1], res["scored"], n, iters, momentum, init))
+    return res
 
 
 @torch.no_grad()
