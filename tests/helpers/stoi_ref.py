@@ -8,6 +8,10 @@ csrc/stoi.hip.  parity unpinned: pystoi is absent, so this is the project's own 
     stoi64(x, y, length, extended)   both
     env32_paired(x, y, length, Tmax) the KERNEL'S METHOD in fp32 on the CPU, as frontend_ref64.mel32_paired does for the mel front
                                      end: x's and y's frame through one complex64 FFT, split, band sums, root
+    score64_ordered(env, kept, ext)  score64 again with every sum in the kernel's stated order: the reference's own rounding
+
+envelopes64, env32_paired and check_env take bands= (a (15, 2) table of runs [lo, hi); None: audio.stoi_bands()).  The second half
+of the file holds the cases of tests/test_gpu_stoi_envelope.py: envelope_batch, band_batch, scale_batch, score_case, exact_case.
 """
 from __future__ import annotations
 
@@ -27,6 +31,9 @@ CLIP = 1.0 + 10.0 ** (15.0 / 20.0)               # the -15 dB signal-to-distorti
 # and rounded up.  The steady tone sets it: its envelopes hardly move over a segment, so the correlation divides one rounding
 # residue by another (the clips with pauses give 2e-9 .. 4e-6).  The factor allows for the kernel's FFT (radix-2 Stockham,
 # sincospif twiddles) not being the CPU library's algorithm: its error is of the same order, log2(N) 2^-24 of the spectrum's peak.
+# The long ragged batch of tests/test_gpu_stoi_envelope.py (envelope_batch("ragged"): clips of 513, 257, 256 and 30 frames) gives
+#     python -c "from tests.helpers import stoi_ref as R; print(R.measure_delta(R.envelope_batch('ragged')[:3]))"   -> 5.12e-05 (STOI 5.12e-05, ESTOI 3.48e-05)
+# which is below DELTA, so that batch is held to the same TOL_FACTOR * DELTA (its steady tones set it, too).
 DELTA = 9e-5
 TOL_FACTOR = 8.0
 
@@ -59,18 +66,24 @@ def select(e):
     return mask, np.flatnonzero(mask).astype(np.int32), margin
 
 
-def _band_env(P):
+def _bands(bands=None):
+    """The band table a caller passed, (15, 2) rows [lo, hi), or the third-octave one."""
+    return audio.stoi_bands() if bands is None else np.asarray(bands, dtype=np.int32).reshape(BANDS, 2)
+
+
+def _band_env(P, bands=None):
     """P (C, 257) powers -> (C, 15) envelopes"""
-    b = audio.stoi_bands()
+    b = _bands(bands)
     return np.sqrt(np.stack([P[:, lo:hi].sum(axis=1) for lo, hi in b], axis=1))
 
 
-def check_env(env_got, r, tag=""):
+def check_env(env_got, r, tag="", bands=None):
     """|env_got - env_ref| <= REL (sqrt(n_j) peak + env_ref) on the kept frames of the clip whose envelopes64 is r, zeros beyond:
     REL is the project's STFT bound relative to the spectrum's peak (x's and y's frame share one FFT, so leakage scales with the
-    pair's peak), a band adds n_j bins in quadrature at worst, and the norm is 1-Lipschitz.  Returns the worst error / bound."""
+    pair's peak), a band adds n_j bins in quadrature at worst, and the norm is 1-Lipschitz.  `bands` is the table r was computed
+    with (None: the third-octave one).  Returns the worst error / bound."""
     from tests.helpers.mel_forward64 import REL
-    n = np.diff(audio.stoi_bands(), axis=1)[:, 0].astype(np.float64)
+    n = np.diff(_bands(bands), axis=1)[:, 0].astype(np.float64)
     C = r["kept"]
     got = np.asarray(env_got, dtype=np.float64)
     assert got.shape == r["env"].shape, (tag, got.shape, r["env"].shape)
@@ -85,7 +98,7 @@ def check_env(env_got, r, tag=""):
     return worst
 
 
-def envelopes64(x, y, length, Tmax=None):
+def envelopes64(x, y, length, Tmax=None, bands=None):
     """The first stage for one clip in fp64 -> dict(energy (Tmax,), mask, src (Tmax,) with the -1 tail, kept, env (2, Tmax, 15),
     peak (Tmax,): the largest of |X[f]| and |Y[f]| over each spectral frame's bins, margin_db)."""
     T = n_frames(length)
@@ -105,7 +118,7 @@ def envelopes64(x, y, length, Tmax=None):
             comp[HOP * k:HOP * k + FRAME] += w * sig[HOP * src[k]:HOP * src[k] + FRAME]
         fr = np.stack([w * comp[HOP * m:HOP * m + FRAME] for m in range(C)])
         mag = np.abs(np.fft.rfft(fr, n=FFT, axis=1))
-        env[s, :C] = _band_env(mag ** 2)
+        env[s, :C] = _band_env(mag ** 2, bands)
         peak[:C] = np.maximum(peak[:C], mag.max(axis=1))
     energy = np.zeros(Tmax)
     energy[:T] = e
@@ -114,7 +127,7 @@ def envelopes64(x, y, length, Tmax=None):
     return dict(energy=energy, mask=mask, src=src_full, kept=C, env=env, peak=peak, margin_db=margin)
 
 
-def env32_paired(x, y, length, Tmax=None):
+def env32_paired(x, y, length, Tmax=None, bands=None):
     """The kernel's method in fp32 on the CPU (given the fp64 selection): the compacted frames in float32, x's and y's frame as the
     real and the imaginary part of ONE complex64 torch.fft.fft of 512 points, split by Hermitian symmetry, |.|^2, band sums and
     root in float32 -> env (2, Tmax, 15) float32."""
@@ -142,7 +155,7 @@ def env32_paired(x, y, length, Tmax=None):
     for s, V in enumerate((f32(0.5) * (Z + Cj), f32(0.5) * (Z - Cj))):
         V = V[:, :F]
         P = (V.real * V.real + V.imag * V.imag).numpy().astype(f32)
-        b = audio.stoi_bands()
+        b = _bands(bands)
         env[s, :C] = np.sqrt(np.stack([P[:, lo:hi].sum(axis=1, dtype=f32) for lo, hi in b], axis=1)).astype(f32)
     return env
 
@@ -235,9 +248,10 @@ def gpu_batch():
     return x, y, np.asarray(GPU_LENGTHS, dtype=np.int32)
 
 
-def measure_delta():
-    """DELTA's measurement (reference against reference): (the maximum, STOI's, ESTOI's)."""
-    x, y, lens = gpu_batch()
+def measure_delta(batch=None):
+    """DELTA's measurement (reference against reference) on batch = (x, y, lengths), gpu_batch() by default: (the maximum, STOI's,
+    ESTOI's)."""
+    x, y, lens = gpu_batch() if batch is None else batch
     worst = [0.0, 0.0]
     for b, n in enumerate(lens):
         r = envelopes64(x[b], y[b], int(n))
@@ -247,3 +261,202 @@ def measure_delta():
             if np.isfinite(c):
                 worst[ext] = max(worst[ext], abs(a - c))
     return max(worst), worst[0], worst[1]
+
+
+# ---- the cases of tests/test_gpu_stoi_envelope.py; tests/test_stoi_envelope_host.py checks their conditions on the CPU -----------
+ROUND = 256                                      # frames a round of stoi_select_kernel's scan takes, segments a round of ESTOI's tile
+
+
+def row_len(T, r=0):
+    """The samples of T frames and r more (r < 128 leaves T as it is)."""
+    return FRAME + HOP * (T - 1) + r
+
+
+def gap3():
+    """512 samples of the tone with samples 128 .. 383 zero: frame 1 is silent, so kept = 2 and src = [0, 2]."""
+    x = tone(512)
+    x[HOP:HOP + FRAME] = 0.0
+    return x
+
+
+# name -> (L, clips); a clip is (kind, length, seed): 'tone' keeps every frame (kept = T exactly), 'speech' is speechlike(length,
+# seed) whose pauses drop frames, 'gap' is gap3(), 'zero' is silence under a noisy y.  The seeds were chosen on the CPU so that
+# every clip is at least 0.01 dB from the threshold and every speech clip of more than 256 frames drops a frame before frame 256
+# and keeps one at or after it (the one of 513 frames keeps frame 512, the only frame of the third round).  A tone of Tmax frames
+# never lies in the last row: the frame after its last kept one is then the next clip's first, not a guard.
+ENVELOPE_CASES = {
+    "T1": (row_len(1), [("tone", row_len(1), 0)]),
+    "T2_T3": (row_len(3, 77), [("tone", row_len(3, 77), 0), ("tone", row_len(2, 77), 0), ("gap", row_len(3), 0)]),
+    "T256": (row_len(256), [("tone", row_len(256), 0), ("speech", row_len(256), 300)]),
+    "T257": (row_len(257), [("tone", row_len(257), 0), ("speech", row_len(257), 302)]),
+    "T512": (row_len(512), [("tone", row_len(512), 0), ("speech", row_len(512), 302)]),
+    "T513": (row_len(513), [("tone", row_len(513), 0), ("speech", row_len(513), 300)]),
+    "ragged": (row_len(513), [("speech", row_len(513), 301), ("speech", row_len(257), 300), ("tone", row_len(256, 77), 0),
+                              ("tone", row_len(30), 0), ("speech", 255, 360), ("zero", row_len(513), 370)]),
+}
+
+
+def envelope_batch(name):
+    """(x, y (B, L) float32, zero past each length; lengths int32; the clips' kinds).  y = x + white noise at 5 dB SNR."""
+    L, clips = ENVELOPE_CASES[name]
+    x = np.zeros((len(clips), L), np.float32)
+    y = np.zeros_like(x)
+    for b, (kind, n, seed) in enumerate(clips):
+        if kind == "zero":
+            y[b, :n] = (0.01 * np.random.default_rng(seed).standard_normal(n)).astype(np.float32)
+            continue
+        x[b, :n] = tone(n) if kind == "tone" else gap3() if kind == "gap" else speechlike(n, seed)
+        y[b, :n] = add_noise(x[b, :n], 5.0, 5000 + seed + b)
+    return x, y, np.asarray([c[1] for c in clips], dtype=np.int32), [c[0] for c in clips]
+
+
+def straddles(r, T):
+    """Of a clip's envelopes64 r: a frame before 256 is dropped and one at or after 256 is kept (T = 513: frame 512)."""
+    src = r["src"][:r["kept"]]
+    return bool((~r["mask"][:ROUND]).any() and (src >= ROUND).any() and (T != 2 * ROUND + 1 or src[-1] == 2 * ROUND))
+
+
+# Band tables that reach the spectrum's ends: 15 one-bin bands with bins 0 and 256 among them (each of X[0], X[256], Y[0], Y[256] is
+# then held alone), and 15 runs that cover all of [0, 257), one-bin runs at both ends.
+ONE_BIN_BANDS = np.asarray([[f, f + 1] for f in (0, 1, 2, 7, 19, 40, 64, 100, 127, 128, 129, 200, 254, 255, 256)], dtype=np.int32)
+_EDGES = (0, 1, 3, 8, 20, 33, 64, 65, 100, 128, 129, 180, 230, 255, 256, 257)
+FULL_BANDS = np.asarray(list(zip(_EDGES[:-1], _EDGES[1:])), dtype=np.int32)
+BAND_L = row_len(40)
+BAND_LENGTHS = (row_len(3), row_len(40))
+
+
+def band_batch():
+    """(x, y (2, 5248), lengths): clips of 3 and of 40 frames with a DC offset and a component at 5 kHz, so bins 0 and 256 are not
+    near zero; y = x + white noise at 5 dB SNR."""
+    x = np.zeros((2, BAND_L), np.float32)
+    y = np.zeros_like(x)
+    for b, n in enumerate(BAND_LENGTHS):
+        x[b, :n] = speechlike(n, 400 + b) + np.float32(0.05) + np.float32(0.05) * (1.0 - 2.0 * (np.arange(n) % 2)).astype(np.float32)
+        y[b, :n] = add_noise(x[b, :n], 5.0, 410 + b)
+    return x, y, np.asarray(BAND_LENGTHS, dtype=np.int32)
+
+
+SCALE_L = row_len(40, 77)
+SCALE_LENGTHS = (row_len(40, 77), row_len(30))
+SCALE_POWERS = (-8, 8)
+
+
+def scale_batch():
+    """(x, y (2, 5325), lengths) for the power-of-two probe: a clip of 40 frames with pauses and the tone of 30 frames."""
+    x = np.zeros((2, SCALE_L), np.float32)
+    y = np.zeros_like(x)
+    for b, n in enumerate(SCALE_LENGTHS):
+        x[b, :n] = speechlike(n, 420) if b == 0 else tone(n)
+        y[b, :n] = add_noise(x[b, :n], 5.0, 430 + b)
+    return x, y, np.asarray(SCALE_LENGTHS, dtype=np.int32)
+
+
+# ---- the score stage on synthetic envelopes ------------------------------------------------------------------------------------
+SCORE_TMAX = 600
+SCORE_KEPT = (29, 30, 31, 46, 47, 285, 286, 541, 542, 600, 700, -3)
+SCORE_SEED = 154                                 # chosen on the CPU: the clip binds in at least one (segment, band) of every scored clip
+SCORE_TOL = 1e-10                                # fp64 against fp64 on a quantity in [-1, 1] (tests/test_gpu_stoi.py's)
+MIN_SPREAD = 0.05                                # every 30-vector's standard deviation / mean: the correlations are well conditioned
+
+
+def clamp_kept(kept, Tmax):
+    return max(0, min(int(kept), Tmax))
+
+
+def score_case():
+    """(env (2, 12, 600, 15) float32, kept): x uniform in [0.1, 1], y = x (1 + 0.3 u) with u uniform in [-1, 1], y = 10 x in about a
+    tenth of the frames (there min(alpha y, clip x) can take the clip), NaN past each clip's kept frames."""
+    rng = np.random.default_rng(SCORE_SEED)
+    B = len(SCORE_KEPT)
+    x = rng.uniform(0.1, 1.0, (B, SCORE_TMAX, BANDS))
+    y = x * (1.0 + 0.3 * rng.uniform(-1.0, 1.0, x.shape))
+    loud = rng.random((B, SCORE_TMAX)) < 0.1
+    y[loud] = 10.0 * x[loud]
+    env = np.stack([x, y]).astype(np.float32)
+    for b, k in enumerate(SCORE_KEPT):
+        env[:, b, clamp_kept(k, SCORE_TMAX):] = np.nan
+    return env, np.asarray(SCORE_KEPT, dtype=np.int32)
+
+
+EXACT_TMAX = 300
+EXACT_KEPT = (290, 290)                          # past ESTOI's first tile
+
+
+def exact_case():
+    """(env (2, 2, 300, 15) float32, kept).  Clip 0: env_x = 1.0 everywhere under a random env_y.  Clip 1: env_y == env_x, uniform
+    in [0.1, 1].  NaN past kept."""
+    rng = np.random.default_rng(1)
+    env = rng.uniform(0.1, 1.0, (2, 2, EXACT_TMAX, BANDS)).astype(np.float32)
+    env[0, 0] = 1.0
+    env[1, 1] = env[0, 1]
+    for b, k in enumerate(EXACT_KEPT):
+        env[:, b, k:] = np.nan
+    return env, np.asarray(EXACT_KEPT, dtype=np.int32)
+
+
+def segments(env_b, C):
+    """env_b (2, >= C, 15) -> X, Y (C - 29, 15, 30) fp64: band j's 30-vector of the segment of frames s .. s + 29 is [s, j]."""
+    win = np.lib.stride_tricks.sliding_window_view(np.asarray(env_b, dtype=np.float64)[:, :C], SEG, axis=1)      # (2, segs, 15, 30)
+    return win[0], win[1]
+
+
+def clip_binds(env_b, C):
+    """In how many (segment, band) pairs of a clip STOI's min(alpha y, clip x) takes clip x in at least one frame."""
+    X, Y = segments(env_b, C)
+    alpha = np.sqrt(np.sum(X ** 2, axis=2, keepdims=True) / (np.sum(Y ** 2, axis=2, keepdims=True) + EPS))
+    return int((alpha * Y > CLIP * X).any(axis=2).sum())
+
+
+def spread(env_b, C):
+    """The least standard deviation / mean over every band's 30-vector of every segment, of x and of y."""
+    return float(min((V.std(axis=2) / V.mean(axis=2)).min() for V in segments(env_b, C)))
+
+
+def score64_ordered(env_b, kept, extended):
+    """score64 with every sum taken in the kernel's order as include/nsg.h states it (nsg_audio_stoi_score): each item's sums over
+    their index ascending from 0.0, thread k of 256 adding its items k, k + 256, ... to 0.0, the xor-butterflies over the offsets
+    32 .. 1 inside each wave of 64 and ((w0 + w1) + w2) + w3.  A second fp64 evaluation: what the two differ by is the
+    reference's own rounding."""
+    C = clamp_kept(kept, np.shape(env_b)[1])
+    if C < SEG:
+        return float("nan")
+    X, Y = segments(env_b, C)
+    segs = C - SEG + 1
+
+    def run(V, axis_len, take):                                    # sum_i take(i) for i ascending, from 0.0
+        s = np.zeros_like(take(0))
+        for i in range(axis_len):
+            s = s + take(i)
+        return s
+
+    if extended:
+        stat = []
+        for V in (X, Y):
+            mean = run(V, SEG, lambda n: V[:, :, n]) / SEG                                          # (segs, 15)
+            nrm = run(V, SEG, lambda n: (V[:, :, n] - mean) ** 2)
+            stat.append((mean, 1.0 / (np.sqrt(nrm) + EPS)))
+        d = np.zeros(segs)
+        for n in range(SEG):
+            xc, yc = ((V[:, :, n] - m) * sc for V, (m, sc) in zip((X, Y), stat))                      # (segs, 15)
+            a = xc - (run(xc, BANDS, lambda j: xc[:, j]) / BANDS)[:, None]
+            c = yc - (run(yc, BANDS, lambda j: yc[:, j]) / BANDS)[:, None]
+            num, nx, ny = (run(a, BANDS, lambda j, p=p, q=q: p[:, j] * q[:, j]) for p, q in ((a, c), (a, a), (c, c)))
+            d = d + num / ((np.sqrt(nx) + EPS) * (np.sqrt(ny) + EPS))
+        items = d / SEG
+    else:
+        X, Y = X.reshape(segs * BANDS, SEG), Y.reshape(segs * BANDS, SEG)                          # item i: segment i / 15, band i % 15
+        sx2, sy2, sx = (run(X, SEG, lambda n, V=V, W=W: V[:, n] * W[:, n]) for V, W in ((X, X), (Y, Y), (X, np.ones_like(X))))
+        alpha = np.sqrt(sx2 / (sy2 + EPS))
+        Yp = np.minimum(alpha[:, None] * Y, CLIP * X)
+        a, c = X - (sx / SEG)[:, None], Yp - (run(Yp, SEG, lambda n: Yp[:, n]) / SEG)[:, None]
+        num, nx, ny = (run(a, SEG, lambda n, p=p, q=q: p[:, n] * q[:, n]) for p, q in ((a, c), (a, a), (c, c)))
+        items = num / (np.sqrt(nx) * np.sqrt(ny) + EPS)
+    part = np.zeros(256)
+    for i0 in range(0, len(items), 256):
+        chunk = items[i0:i0 + 256]
+        part[:len(chunk)] = part[:len(chunk)] + chunk
+    v = part.reshape(4, 64)
+    lane = np.arange(64)
+    for off in (32, 16, 8, 4, 2, 1):
+        v = v + v[:, lane ^ off]
+    return float((((v[0, 0] + v[1, 0]) + v[2, 0]) + v[3, 0]) / len(items))
