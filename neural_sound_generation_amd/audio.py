@@ -251,6 +251,13 @@ def preemphasis(y: torch.Tensor, k=PREEMPHASIS) -> torch.Tensor:
 LAYOUTS = {"mel_major": 0, "frame_major": 1}
 
 
+def _on_device(wav, as_numpy, device):
+    """The (B, L) float32 GPU batch the waveform kernels take: a numpy waveform uploaded to `device` as one clip, a tensor as it
+    is -- on the GPU, float32 and contiguous, or an NsgError."""
+    y = torch.from_numpy(np.ascontiguousarray(wav, dtype=np.float32)[None]).to(device) if as_numpy else wav
+    return _chk(y, "wav")
+
+
 def melspectrogram(wav, sample_rate=22050, fft_size=1024, hop_size=256, n_mels=80, lengths=None, layout="mel_major", device="cuda:0"):
     """audio_tacotron.py:70-78 with hparams_tacotron.py's settings.  wav: a 1-D numpy waveform as in the reference (returns a
     float32 numpy (n_mels, T), T = 1 + len // hop_size), or a float32 GPU tensor (B, L) of zero-padded clips (returns a GPU
@@ -282,8 +289,7 @@ def melspectrogram(wav, sample_rate=22050, fft_size=1024, hop_size=256, n_mels=8
             raise ValueError(f"melspectrogram: every length must be in ({fft_size // 2}, {L}], got {int(host.min())} .. {int(host.max())}")
         lens = np.ascontiguousarray(host, dtype=np.int32)
     bands = _mel_bands(sample_rate, fft_size, n_mels)
-    y = torch.from_numpy(np.ascontiguousarray(wav, dtype=np.float32)[None]).to(device) if as_numpy else wav
-    _chk(y, "wav")
+    y = _on_device(wav, as_numpy, device)
     T = 1 + L // hop_size
     basis = _mel_basis_on(sample_rate, fft_size, n_mels, y.device)
     lens_d = torch.from_numpy(lens).to(y.device) if lens is not None else None
@@ -406,8 +412,7 @@ def _f0_args(fn, wav, sample_rate, hop_size, frame_length, fmin, fmax, lengths, 
         raise ValueError(f"{fn}: an empty waveform")
     if B * (1 + L // hop_size) >= 2 ** 31:
         raise ValueError(f"{fn}: {B} clips of {1 + L // hop_size} frames are 2^31 frames or more")
-    y = torch.from_numpy(np.ascontiguousarray(wav, dtype=np.float32)[None]).to(device) if as_numpy else wav
-    return as_numpy, y, lens, tau_min, tau_max
+    return as_numpy, _on_device(wav, as_numpy, device), lens, tau_min, tau_max
 
 
 def f0_candidates(wav, sample_rate=22050, hop_size=256, frame_length=1024, fmin=65.0, fmax=500.0, lengths=None, device="cuda:0"):
@@ -638,9 +643,8 @@ def resample(wav, orig_sr, target_sr, lengths=None, device="cuda:0"):
     L_out = -(-L * P // Q)
     if L_out >= 2 ** 31:
         raise ValueError(f"resample: {L} samples at {P} / {Q} give {L_out} samples, 2^31 or more")
-    y = torch.from_numpy(np.ascontiguousarray(wav, dtype=np.float32)[None]).to(device) if as_numpy else wav
-    _chk(y, "wav")
-    table = _resample_table_on(P, Q, str(y.device))
+    y = _on_device(wav, as_numpy, device)
+    table =_resample_table_on(P, Q, str(y.device))
     lens_d = torch.from_numpy(lens).to(y.device) if lens is not None else None
     out = torch.empty(B, L_out, dtype=torch.float32, device=y.device)
     _lib.call("nsg_audio_resample", _p(y), _p(lens_d), _p(table), _p(out), B, L, P, Q, W, _stream())
@@ -686,11 +690,6 @@ def _per_clip(fn, name, v, B, lo=None, hi=None, integer=False):
     if a.shape != (B,) or not np.isfinite(a).all() or (lo is not None and a.min() < lo) or (hi is not None and a.max() > hi):
         raise ValueError(f"{fn}: {name} must be a finite number or {B} of them" + (f" in [{lo}, {hi}]" if lo is not None else "") + f", got {v!r}")
     return a
-
-
-def _on_device(wav, as_numpy, device):
-    y = torch.from_numpy(np.ascontiguousarray(wav, dtype=np.float32)[None]).to(device) if as_numpy else wav
-    return _chk(y, "wav")
 
 
 def tempo(wav, factor, sample_rate=22050, segment_ms=TEMPO_SEGMENT_MS, search_ms=TEMPO_SEARCH_MS, overlap_ms=TEMPO_OVERLAP_MS, lengths=None,
@@ -843,10 +842,9 @@ def trim_silence(wav, top_db=20.0, frame_length=2048, hop_length=512, lengths=No
     if not top_db > 0:
         raise ValueError(f"trim_silence: top_db must be positive, got {top_db!r}")
     as_numpy, B, L, lens = _clip_batch("trim_silence", wav, lengths, frame_length // 2 + 1)
-    y = torch.from_numpy(np.ascontiguousarray(wav, dtype=np.float32)[None]).to(device) if as_numpy else wav
-    _chk(y, "wav")
+    y = _on_device(wav, as_numpy, device)
     lens_d = torch.from_numpy(lens).to(y.device) if lens is not None else None
-    bounds = torch.empty(B, 2, dtype=torch.int32, device=y.device)
+    bounds =torch.empty(B, 2, dtype=torch.int32, device=y.device)
     ws, nb = _ws(y.device, "nsg_audio_trim_workspace_bytes", B, L, hop_length)
     _lib.call("nsg_audio_trim_bounds", _p(y), _p(lens_d), _p(bounds), B, L, frame_length, hop_length, top_db, _p(ws), nb, _stream())
     if not as_numpy:

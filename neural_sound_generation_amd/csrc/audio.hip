@@ -16,6 +16,7 @@
 #include "nsg_common.h"
 #include "nsg_reduce.h"
 #include "nsg_fft.h"
+#include "nsg_wave.h"
 #include <math.h>
 #include <type_traits>
 
@@ -274,8 +275,7 @@ __global__ __launch_bounds__(256) void melspectrogram_kernel(const float *__rest
     __shared__ float mag[2][F];
     const int tid = threadIdx.x;
     const int b = (int)(blockIdx.x / (unsigned)pairs), t0 = 2 * (int)(blockIdx.x - (unsigned)b * pairs);
-    int len = lengths ? lengths[b] : L;
-    len = len < 1 ? 1 : (len > L ? L : len);                  // (the caller checked N/2 < len <= L on its host copy)
+    const int len = nsg_clip_len_reflect(lengths, b, L);      // (the caller checked N/2 < len <= L on its host copy)
     const int Tb = 1 + len / hop;                             // the clip's own frame count
     float *ob = out + (size_t)b * n_mels * T;
     const size_t m_stride = frame_major ? 1 : (size_t)T, t_stride = frame_major ? (size_t)n_mels : 1;
@@ -294,13 +294,9 @@ __global__ __launch_bounds__(256) void melspectrogram_kernel(const float *__rest
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             if (q == 1 && !two) break;
-            // Precondition len > N/2 (checked by the launcher for L and by the caller for lengths[]): the padding is N/2 on each
-            // side, so one fold is the exact reflect map and the clamp below is never taken.  Shorter clips would need the
-            // periodic map of stft_frame_lds.
-            int idx = (t0 + q) * hop + n - N / 2;
-            if (idx < 0) idx = -idx;                          // np.pad(mode="reflect") of the pre-emphasised clip
-            if (idx >= len) idx = 2 * (len - 1) - idx;
-            idx = idx < 0 ? 0 : (idx >= len ? len - 1 : idx);
+            // np.pad(mode="reflect") of the pre-emphasised clip.  len > N/2 (checked by the launcher for L and by the caller for
+            // lengths[]) and the padding is N/2 on each side: nsg_reflect_once's precondition.
+            const int idx = nsg_reflect_once((t0 + q) * hop + n - N / 2, len);
             p[q] = idx > 0 ? x[idx] - k * x[idx - 1] : x[0];
         }
         fft.b0[n] = v2f{p[0] * w, p[1] * w};

@@ -7,12 +7,12 @@
 //
 // f0_kernel: the work is W * tau_max subtract-square-add triples a frame out of a span of W + tau_max samples, VALU work fed from
 // LDS.  A lane owns F0_RUN adjacent lags tau = F0_RUN g .. F0_RUN g + F0_RUN - 1 (lag 0 rides along: its d is 0 and is never
-// read) and keeps the F0_RUN + 3 samples x[s0 + j + tau] that four consecutive j need in registers: a step of four j costs one
-// 16-byte read of the next four samples (consecutive lanes 16 bytes apart, conflict-free) and one 16-byte read of x[s0 + j .. j + 3]
-// at an address the frame's lanes share (a broadcast), for 4 * F0_RUN triples; the one-read-per-pair loop would pay 4 * F0_RUN
-// reads.  One fp32 chain per lag over j in order, so a lag's sum does not know which lane or workgroup formed it.  The loop is
-// bound by the VALU issue rate (three uncontracted instructions a pair); build.py compiles this file with -fno-slp-vectorize:
-// packed into v_pk_add_f32 / v_pk_mul_f32 the triples pay for the register shuffles and the launch is 1.3 x slower.
+// read) and forms their sums with nsg_ssd_run (nsg_wave.h), the sliding register window tsm.hip's search calls too: a step of
+// four j costs one 16-byte read of the next four samples (consecutive lanes 16 bytes apart, conflict-free) and one 16-byte read of
+// x[s0 + j .. j + 3] at an address the frame's lanes share (a broadcast), for 4 * F0_RUN triples.  One fp32 chain per lag over j in
+// order, so a lag's sum does not know which lane or workgroup formed it.  W is even, so of the loop's tails only {0, 2} are
+// instantiated (F0_TAILS).  The loop is bound by the VALU issue rate (three uncontracted instructions a pair); build.py compiles
+// this file with -fno-slp-vectorize, as nsg_wave.h asks.
 // G = ceil((tau_max + 1) / F0_RUN) lanes serve a frame; a workgroup takes F = 256 / G adjacent frames of one clip (as many as
 // F0_LDS_BUDGET holds), lane = (frame, run), so that few lanes idle (3 frames of 85 runs at tau_max = 339).  Each frame has its
 // own span in LDS: frames with gaps between them (hop > W + tau_max) cost no more than adjacent ones.
@@ -30,10 +30,12 @@
 // f0_path_stats_kernel: one wave per pair, lane l the cells l, l + 64, ..., then nsg_wave_sum_butterfly (nsg_reduce.h).
 #include "nsg_common.h"
 #include "nsg_reduce.h"
+#include "nsg_wave.h"
 
 namespace {
 
 constexpr int F0_RUN = 4;                          // adjacent lags a lane owns
+constexpr unsigned F0_TAILS = 0b0101;              // W mod 4 is 0 or 2: f0_check refuses an odd frame_length
 constexpr int F0_THREADS = 256;                    // lanes a workgroup shares among its frames (one frame may need more: F0_MAX_THREADS)
 constexpr int F0_MAX_THREADS = 320;                // ceil((1024 + 1) / 4) = 257 runs, rounded up to whole waves
 constexpr int F0_MIN_W = 64, F0_MAX_W = 2048, F0_MAX_TAU = 1024;
@@ -75,20 +77,6 @@ inline F0Geom f0_geom(int W, int hop, int tau_min, int tau_max, int T, int ctl)
     return q;
 }
 
-// NJ consecutive j from j0 for a lane's F0_RUN lags: w[0 .. F0_RUN + NJ - 1) holds x[s0 + j0 + tau0 ...], u the NJ samples x[s0 + j0 ...]
-template <int NJ>
-__device__ __forceinline__ void f0_step(float (&acc)[F0_RUN], const float (&w)[F0_RUN + 4], const float (&u)[4])
-{
-#pragma unroll
-    for (int jj = 0; jj < NJ; ++jj)
-#pragma unroll
-        for (int r = 0; r < F0_RUN; ++r) {
-            const float t = u[jj] - w[jj + r];
-            const float sq = t * t;
-            acc[r] = acc[r] + sq;
-        }
-}
-
 // ---- the front half both kernels run: a tile's place, its spans, d(tau), the running sum and d'(tau) -- stated here once ------
 // A workgroup's tile and its sections of LDS; thread (f, g) is run g of frame f (act: f < F), then group g of frame f
 struct F0Tile {
@@ -106,8 +94,7 @@ __device__ __forceinline__ F0Tile f0_tile(float *lds, const F0Geom &q, const int
     m.ctl = reinterpret_cast<int *>(m.gt + q.F * q.NG4);
     m.tid = threadIdx.x; m.nthr = blockDim.x;
     m.b = blockIdx.x / q.tiles_t; m.t0 = (blockIdx.x - m.b * q.tiles_t) * q.F;
-    int len = lengths ? lengths[m.b] : L;
-    m.len = len < 0 ? 0 : (len > L ? L : len);         // the caller's to get right (nsg.h); clamped so that no read leaves wav
+    m.len = nsg_clip_len(lengths, m.b, L);
     m.Tb = 1 + m.len / q.hop;
     m.nf = T - m.t0 < q.F ? T - m.t0 : q.F;            // frames of this tile inside the tensor
     m.f = m.tid / q.G; m.g = m.tid - m.f * q.G;
@@ -128,11 +115,7 @@ __device__ __forceinline__ void f0_difference(const F0Geom &q, const F0Tile &m, 
     for (int f = 0; f < q.F; ++f) {                    // a frame's span, zero outside the clip and for frames past it
         const bool livef = f < m.nf && m.t0 + f < m.Tb;
         const int64_t s0 = (int64_t)(m.t0 + f) * q.hop - q.W / 2;
-        for (int i = tid; i < q.stride; i += nthr) {
-            const int64_t n = s0 + i;
-            const bool in = livef && i < S && n >= 0 && n < m.len;
-            sx[f * q.stride + i] = in ? xb[in ? n : 0] : 0.f;
-        }
+        for (int i = tid; i < q.stride; i += nthr) sx[f * q.stride + i] = nsg_clip_at(xb, s0 + i, m.len, livef && i < S);
     }
     __syncthreads();
 
@@ -158,31 +141,8 @@ __device__ __forceinline__ void f0_difference(const F0Geom &q, const F0Tile &m, 
     } else if (act) {
         const float *base = sx + f * q.stride;         // x[s0 + j] at base[j]: the frame's lanes read it at one address
         const float *win = base + F0_RUN * g;          // x[s0 + j + tau0] at win[j], tau0 = F0_RUN g
-        float acc[F0_RUN], w[F0_RUN + 4], u[4];
-#pragma unroll
-        for (int r = 0; r < F0_RUN; ++r) acc[r] = 0.f;
-#pragma unroll
-        for (int r = 0; r < F0_RUN; r += 4) {
-            const v4f v = *reinterpret_cast<const v4f *>(win + r);
-            w[r] = v.x; w[r + 1] = v.y; w[r + 2] = v.z; w[r + 3] = v.w;
-        }
-        int j0 = 0;
-        for (; j0 + 4 <= q.W; j0 += 4) {
-            const v4f uv = *reinterpret_cast<const v4f *>(base + j0);
-            const v4f nv = *reinterpret_cast<const v4f *>(win + j0 + F0_RUN);
-            u[0] = uv.x; u[1] = uv.y; u[2] = uv.z; u[3] = uv.w;
-            w[F0_RUN] = nv.x; w[F0_RUN + 1] = nv.y; w[F0_RUN + 2] = nv.z; w[F0_RUN + 3] = nv.w;
-            f0_step<4>(acc, w, u);
-#pragma unroll
-            for (int r = 0; r < F0_RUN; ++r) w[r] = w[r + 4];
-        }
-        if (j0 < q.W) {                                // W = 2 mod 4: the last two j (the rows are long enough for these reads)
-            const v4f uv = *reinterpret_cast<const v4f *>(base + j0);
-            const v4f nv = *reinterpret_cast<const v4f *>(win + j0 + F0_RUN);
-            u[0] = uv.x; u[1] = uv.y; u[2] = uv.z; u[3] = uv.w;
-            w[F0_RUN] = nv.x; w[F0_RUN + 1] = nv.y; w[F0_RUN + 2] = nv.z; w[F0_RUN + 3] = nv.w;
-            f0_step<2>(acc, w, u);
-        }
+        float acc[F0_RUN];                             // (W = 2 mod 4: the rows are long enough for the tail's reads)
+        nsg_ssd_run<F0_RUN, F0_TAILS>(acc, win, base, q.W);
         float *dst = dl + f * q.RG + F0_RUN * g;
 #pragma unroll
         for (int r = 0; r < F0_RUN; r += 4) {

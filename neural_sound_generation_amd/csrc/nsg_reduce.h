@@ -71,14 +71,19 @@ __device__ __forceinline__ void nsg_block_sum_walk256(double part, Done done)
     }
 }
 
-// The butterfly's wave stage.  Order: xor-butterflies over the 64 lanes (offsets 32, 16, ..., 1).  The result is in every lane.
-// No barrier, no LDS.
-__device__ __forceinline__ double nsg_wave_sum_butterfly(double v)
+// The xor-butterfly over the 64 lanes of a wave: for off = 32, 16, ..., 1, v = op(v, the v of lane ^ off).  The result is in every
+// lane.  No barrier, no LDS.
+template <typename T, typename Op>
+__device__ __forceinline__ T nsg_wave_butterfly(T v, Op op)
 {
 #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    for (int off = 32; off >= 1; off >>= 1) v = op(v, __shfl_xor(v, off, 64));
     return v;
 }
+
+// The butterfly's wave stage.  Order: nsg_wave_butterfly's, v + the other lane's (offsets 32, 16, ..., 1), in v's own precision.
+__device__ __forceinline__ double nsg_wave_sum_butterfly(double v) { return nsg_wave_butterfly(v, [](double a, double b) { return a + b; }); }
+__device__ __forceinline__ float nsg_wave_sum_butterfly(float v) { return nsg_wave_butterfly(v, [](float a, float b) { return a + b; }); }
 
 // Butterfly.  Order: nsg_wave_sum_butterfly inside each wave, then the 4 wave totals through
 // red[0..3] as ((w0 + w1) + w2) + w3.  The result is in every thread.  Two barriers (the second frees red for the next call).
@@ -90,6 +95,20 @@ __device__ __forceinline__ double nsg_block_sum_butterfly(double v, double *red,
     const double r = ((red[0] + red[1]) + red[2]) + red[3];
     __syncthreads();
     return r;
+}
+
+// ---- exact, order-free wave reductions ----------------------------------------------------------------------------------------
+
+// The maximum / the minimum of the 64 lanes' values, in every lane (nsg_wave_butterfly: no barrier, no LDS).  A maximum or a
+// minimum is the same number in any order, so these have no order to state; lanes with nothing to offer pass the identity.  The
+// floating-point maxima are fmaxf / fmax: a NaN loses to any number.
+__device__ __forceinline__ float nsg_wave_max(float v) { return nsg_wave_butterfly(v, [](float a, float b) { return fmaxf(a, b); }); }
+__device__ __forceinline__ double nsg_wave_max(double v) { return nsg_wave_butterfly(v, [](double a, double b) { return fmax(a, b); }); }
+__device__ __forceinline__ int nsg_wave_max(int v) { return nsg_wave_butterfly(v, [](int a, int b) { return b > a ? b : a; }); }
+__device__ __forceinline__ int nsg_wave_min(int v) { return nsg_wave_butterfly(v, [](int a, int b) { return b < a ? b : a; }); }
+__device__ __forceinline__ unsigned long long nsg_wave_min(unsigned long long v)
+{
+    return nsg_wave_butterfly(v, [](unsigned long long a, unsigned long long b) { return b < a ? b : a; });
 }
 
 // ---- closing sums over block or slab partials ---------------------------------------------------------------------------------

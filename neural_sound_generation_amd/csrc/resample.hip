@@ -6,8 +6,12 @@
 //     do not depend on the batch, the row or the tiling.
 //   * trim bounds: librosa.effects.trim's frame energies (centred, reflect-padded frames), the clip's loudest frame as the
 //     reference, and the first and last frame within top_db of it.
-// fp32, ragged batches as melspectrogram_kernel takes them.  HBM- / L2-bound kernels; nothing here touches the matrix pipe.
+// fp32, ragged batches as melspectrogram_kernel takes them: a clip's length, the zero-padded read and the reflect map are
+// nsg_wave.h's, the wave stages of the frame sums and of the bounds nsg_reduce.h's.  HBM- / L2-bound kernels; nothing here
+// touches the matrix pipe.
 #include "nsg_common.h"
+#include "nsg_reduce.h"
+#include "nsg_wave.h"
 #include <math.h>
 
 namespace {
@@ -27,8 +31,7 @@ __global__ __launch_bounds__(RS_TILE) void resample_kernel(const float *__restri
     const int tid = threadIdx.x;
     const int b = (int)(blockIdx.x / (unsigned)tiles);
     const int64_t m0 = (int64_t)(blockIdx.x - (unsigned)b * tiles) * RS_TILE, m = m0 + tid;
-    int len = lengths ? lengths[b] : L_in;
-    len = len < 0 ? 0 : (len > L_in ? L_in : len);                      // no read leaves wav, whatever lengths holds
+    const int len = nsg_clip_len(lengths, b, L_in);
     const int64_t len_out = ((int64_t)len * P + Q - 1) / Q;             // <= L_out
     float *ob = out + (size_t)b * L_out;
     if (m0 >= len_out) {                                                // the whole tile is past the clip's end
@@ -38,10 +41,7 @@ __global__ __launch_bounds__(RS_TILE) void resample_kernel(const float *__restri
     const int64_t m_last = m0 + RS_TILE - 1 < L_out - 1 ? m0 + RS_TILE - 1 : L_out - 1;
     const int64_t lo = m0 * Q / P - W + 1, hi = m_last * Q / P + W;     // inclusive; hi - lo + 1 <= (RS_TILE - 1) Q / P + 2 W + 1
     const float *x = wav + (size_t)b * L_in;
-    for (int i = tid; i <= (int)(hi - lo); i += RS_TILE) {
-        const int64_t n = lo + i;
-        xs[i] = n >= 0 && n < len ? x[n] : 0.f;
-    }
+    for (int i = tid; i <= (int)(hi - lo); i += RS_TILE) xs[i] = nsg_clip_at(x, lo + i, len);
     __syncthreads();
     if (m >= L_out) return;
     float acc = 0.f;
@@ -55,74 +55,60 @@ __global__ __launch_bounds__(RS_TILE) void resample_kernel(const float *__restri
 }
 
 // mse[b][t] = mean over the frame of p^2, p = reflect_pad(x_b[0:len_b], N/2)[t hop : t hop + N]; one wave per frame: lane l adds
-// samples l, l + 64, ... in that order, then the 64 lane sums meet in a fixed butterfly.  Frames past the clip's own count are
-// left unwritten (trim_bounds_kernel never reads them).
+// samples l, l + 64, ... in that order, then the 64 lane sums meet in nsg_wave_sum_butterfly.  Frames past the clip's own count
+// are left unwritten (trim_bounds_kernel never reads them).
 __global__ __launch_bounds__(256) void frame_energy_kernel(const float *__restrict__ wav, const int32_t *__restrict__ lengths,
                                                            float *__restrict__ mse, int L, int T, int groups, int N, int hop)
 {
     const int b = (int)(blockIdx.x / (unsigned)groups);
     const int t = (int)(blockIdx.x - (unsigned)b * groups) * 4 + (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    int len = lengths ? lengths[b] : L;
-    len = len < 1 ? 1 : (len > L ? L : len);                            // (the caller checked N/2 < len <= L on its host copy)
+    const int len = nsg_clip_len_reflect(lengths, b, L);                // (the caller checked N/2 < len <= L on its host copy)
     if (t >= 1 + len / hop) return;                                     // wave-uniform
     const float *x = wav + (size_t)b * L;
     const int64_t start = (int64_t)t * hop - N / 2;
     float s = 0.f;
     for (int i = lane; i < N; i += 64) {
-        int64_t idx = start + i;                                        // one fold is the exact reflect map for len > N/2
-        if (idx < 0) idx = -idx;
-        if (idx >= len) idx = 2 * ((int64_t)len - 1) - idx;
-        idx = idx < 0 ? 0 : (idx >= len ? len - 1 : idx);
-        const float v = x[idx];
+        const float v = x[nsg_reflect_once(start + i, len)];            // the padding N/2 < len: one fold is the exact map
         s = fmaf(v, v, s);
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, 64);
+    s = nsg_wave_sum_butterfly(s);
     if (lane == 0) mse[(size_t)b * T + t] = s / (float)N;
 }
 
 // One workgroup per clip: ref = max_t mse[t]; frame t is non-silent iff 10 log10(max(1e-10, mse[t])) - 10 log10(max(1e-10, ref))
-// > -top_db; bounds = (first hop, min(len, (last + 1) hop)), or (0, 0) when no frame qualifies.  max / min / max reductions: exact
-// in any order.
+// > -top_db; bounds = (first hop, min(len, (last + 1) hop)), or (0, 0) when no frame qualifies.  max / min / max reductions, exact
+// in any order: nsg_reduce.h's wave stage, then the four wave results through LDS (as stoi_select_kernel's maximum).  A thread
+// -- or a whole wave -- that owns no frame offers the identity: 0.f, INT_MAX, -1.
 __global__ __launch_bounds__(256) void trim_bounds_kernel(const float *__restrict__ mse, const int32_t *__restrict__ lengths,
                                                           int32_t *__restrict__ bounds, int L, int T, int hop, float top_db)
 {
-    __shared__ float red_f[256];
-    __shared__ int red_lo[256], red_hi[256];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    int len = lengths ? lengths[b] : L;
-    len = len < 1 ? 1 : (len > L ? L : len);
+    __shared__ float wmax[4];
+    __shared__ int wlo[4], whi[4];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int len = nsg_clip_len_reflect(lengths, b, L);
     const int Tb = 1 + len / hop;
     const float *e = mse + (size_t)b * T;
     float mx = 0.f;                                                     // energies are >= 0
     for (int t = tid; t < Tb; t += 256) mx = fmaxf(mx, e[t]);
-    red_f[tid] = mx;
+    mx = nsg_wave_max(mx);
+    if (lane == 0) wmax[wave] = mx;
     __syncthreads();
-    for (int d = 128; d >= 1; d >>= 1) {
-        if (tid < d) red_f[tid] = fmaxf(red_f[tid], red_f[tid + d]);
-        __syncthreads();
-    }
-    const float ref_db = 10.f * log10f(fmaxf(1e-10f, red_f[0]));
+    const float ref_db = 10.f * log10f(fmaxf(1e-10f, fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]))));
     int first = 0x7fffffff, last = -1;
     for (int t = tid; t < Tb; t += 256)
         if (10.f * log10f(fmaxf(1e-10f, e[t])) - ref_db > -top_db) {
             first = t < first ? t : first;
             last = t;
         }
-    red_lo[tid] = first;
-    red_hi[tid] = last;
+    first = nsg_wave_min(first);
+    last = nsg_wave_max(last);
+    if (lane == 0) { wlo[wave] = first; whi[wave] = last; }
     __syncthreads();
-    for (int d = 128; d >= 1; d >>= 1) {
-        if (tid < d) {
-            red_lo[tid] = red_lo[tid] < red_lo[tid + d] ? red_lo[tid] : red_lo[tid + d];
-            red_hi[tid] = red_hi[tid] > red_hi[tid + d] ? red_hi[tid] : red_hi[tid + d];
-        }
-        __syncthreads();
-    }
     if (tid == 0) {
-        const int64_t end = ((int64_t)red_hi[0] + 1) * hop;
-        bounds[2 * b] = red_hi[0] < 0 ? 0 : (int32_t)((int64_t)red_lo[0] * hop);
-        bounds[2 * b + 1] = red_hi[0] < 0 ? 0 : (int32_t)(end < len ? end : len);
+        const int lo = min(min(wlo[0], wlo[1]), min(wlo[2], wlo[3])), hi = max(max(whi[0], whi[1]), max(whi[2], whi[3]));
+        const int64_t end = ((int64_t)hi + 1) * hop;
+        bounds[2 * b] = hi < 0 ? 0 : (int32_t)((int64_t)lo * hop);
+        bounds[2 * b + 1] = hi < 0 ? 0 : (int32_t)(end < len ? end : len);
     }
 }
 

@@ -71,8 +71,7 @@ __global__ __launch_bounds__(256) void stoi_select_kernel(const double *__restri
     int32_t *sb = src + (size_t)b * Tmax;
     double mx = 0.0;                                           // (energies are >= 0)
     for (int t = tid; t < Tb; t += 256) mx = fmax(mx, e[t]);
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) mx = fmax(mx, __shfl_xor(mx, off, 64));
+    mx = nsg_wave_max(mx);
     if (lane == 0) wmax[wave] = mx;
     __syncthreads();
     const double thr = STOI_RANGE * fmax(fmax(wmax[0], wmax[1]), fmax(wmax[2], wmax[3]));

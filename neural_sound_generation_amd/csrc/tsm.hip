@@ -4,13 +4,14 @@
 //
 // tsm_chain_kernel (nsg_audio_tempo, first launch): one workgroup of 256 lanes per clip walks the segments m = 1 .. M - 1 in
 // order.  A step compares the O tail samples behind the previous segment with the W candidate positions of this one: W * O
-// subtract-square-add triples out of W + O - 1 samples, VALU work fed from LDS -- f0_difference's loop (csrc/f0.hip).  A lane
-// owns RUN adjacent candidates delta = RUN g .. RUN g + RUN - 1 (RUN = 2, 4 or 8: the least that lets 256 lanes cover W, so that
-// the four SIMDs share the work) and keeps the RUN + 3 window samples that four consecutive j need in registers: four j cost one
-// read of the next four window samples (consecutive lanes RUN floats apart) and one 16-byte read of the tail at an address all
-// lanes share (a broadcast), for 4 RUN triples.  One fp32 chain per candidate over j in order.  The argmin is the integer minimum
-// of bits(d) << 32 | delta (d >= 0: its bits order as integers; equal d: the smallest delta): a butterfly inside each wave, then
-// one LDS atomic per wave -- exact and order-free.
+// subtract-square-add triples out of W + O - 1 samples, VALU work fed from LDS.  The loop is nsg_ssd_run (nsg_wave.h), the
+// function f0_difference (csrc/f0.hip) calls too, here with every tail (O mod 4 is anything) and compiled with -fno-slp-vectorize
+// as that header asks.  A lane owns RUN adjacent candidates delta = RUN g .. RUN g + RUN - 1 (RUN = 2, 4 or 8: the
+// least that lets 256 lanes cover W, so that the four SIMDs share the work): four j cost one read of the next four window samples
+// (consecutive lanes RUN floats apart) and one 16-byte read of the tail at an address all lanes share (a broadcast), for 4 RUN
+// triples.  One fp32 chain per candidate over j in order.  The argmin is the integer minimum of bits(d) << 32 | delta (d >= 0: its
+// bits order as integers; equal d: the smallest delta): nsg_wave_min (nsg_reduce.h) inside each wave, then one LDS atomic per wave
+// -- exact and order-free.
 //   The chain over m runs only through delta*: the window x[n_m .. n_m + W + O - 1) does not depend on earlier steps, and the tail
 // x[q_{m-1} + Ho ..) lies inside x[n_{m-1} + Ho .. n_{m-1} + Ho + W + O - 1), which does not either.  So both ranges of step
 // m + 1 are loaded from global memory into registers BEFORE step m's search and stored to LDS after it: no global load waits on
@@ -29,6 +30,7 @@
 // mix_apply_kernel (two reads and one write a sample, four consecutive samples a thread, 16-byte accesses where they are aligned).
 #include "nsg_common.h"
 #include "nsg_reduce.h"
+#include "nsg_wave.h"
 
 namespace {
 
@@ -38,7 +40,6 @@ constexpr int TSM_MAX_RUN = 8;
 constexpr int TSM_MAX_STRIDE = (TSM_MAX_W + TSM_MAX_O + 2 * TSM_MAX_RUN + 8 + 3) / 4 * 4;
 constexpr int TSM_NPF = (TSM_MAX_STRIDE + TSM_THREADS - 1) / TSM_THREADS;     // floats of a range a lane carries in registers
 constexpr int TSM_TILE = 1024;                                                // output samples of a render block
-typedef float v2f __attribute__((ext_vector_type(2)));
 
 inline int tsm_run(int W) { return W <= 2 * TSM_THREADS ? 2 : (W <= 4 * TSM_THREADS ? 4 : 8); }
 // floats of win / twin: an active lane (RUN g < W) reads up to win[RUN g + O4 + RUN + 3], O4 <= O + 3
@@ -54,8 +55,7 @@ __device__ __forceinline__ TsmClip tsm_clip(const int32_t *lengths, const double
                                             int Ho)
 {
     TsmClip c;
-    const int len = lengths ? lengths[b] : L;
-    c.len = len < 0 ? 0 : (len > L ? L : len);
+    c.len = nsg_clip_len(lengths, b, L);
     const int ol = out_lengths[b];
     c.out_len = ol < 0 ? 0 : (ol > L_out ? L_out : ol);
     c.M = (c.out_len + Ho - 1) / Ho;
@@ -77,9 +77,7 @@ __device__ __forceinline__ void tsm_fetch(float (&r)[TSM_NPF], const float *__re
     for (int k = 0; k < TSM_NPF; ++k) {
         if (k < npf) {
             const int i = k * TSM_THREADS + tid;
-            const int64_t at = base + i;
-            const bool in = i < n && at >= 0 && at < len;
-            r[k] = in ? xb[in ? at : 0] : 0.f;
+            r[k] = nsg_clip_at(xb, base + i, len, i < n);
         }
     }
 }
@@ -95,63 +93,12 @@ __device__ __forceinline__ void tsm_commit(float *dst, const float (&r)[TSM_NPF]
     }
 }
 
-template <int RUN>
-__device__ __forceinline__ void tsm_load4(const float *p, float *o)
-{
-    if (RUN % 4 == 0) {
-        const v4f v = *reinterpret_cast<const v4f *>(p);
-        o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
-    } else {                                           // RUN = 2: the lane's window is 8-byte aligned
-        const v2f a = *reinterpret_cast<const v2f *>(p), b = *reinterpret_cast<const v2f *>(p + 2);
-        o[0] = a.x; o[1] = a.y; o[2] = b.x; o[3] = b.y;
-    }
-}
-
-// NJ consecutive j from j0 for a lane's RUN candidates: w[0 .. RUN + NJ - 1) holds win[delta0 + j0 ...], u the NJ tail samples
-template <int RUN, int NJ>
-__device__ __forceinline__ void tsm_step(float (&acc)[RUN], const float (&w)[RUN + 4], const float (&u)[4])
-{
-#pragma unroll
-    for (int jj = 0; jj < NJ; ++jj)
-#pragma unroll
-        for (int r = 0; r < RUN; ++r) {
-            const float t = u[jj] - w[jj + r];
-            const float sq = t * t;
-            acc[r] = acc[r] + sq;
-        }
-}
-
 // d(delta) of the lane's run, folded to the lane's least key bits(d) << 32 | delta over delta < W
 template <int RUN>
 __device__ __forceinline__ unsigned long long tsm_search(const float *win, const float *tail, int O, int W, int g)
 {
-    const float *p = win + RUN * g;
-    float acc[RUN], w[RUN + 4], u[4];
-#pragma unroll
-    for (int r = 0; r < RUN; ++r) acc[r] = 0.f;
-#pragma unroll
-    for (int r = 0; r < RUN; r += 2) {
-        const v2f v = *reinterpret_cast<const v2f *>(p + r);
-        w[r] = v.x; w[r + 1] = v.y;
-    }
-    int j0 = 0;
-    for (; j0 + 4 <= O; j0 += 4) {
-        const v4f uv = *reinterpret_cast<const v4f *>(tail + j0);
-        u[0] = uv.x; u[1] = uv.y; u[2] = uv.z; u[3] = uv.w;
-        tsm_load4<RUN>(p + j0 + RUN, &w[RUN]);
-        tsm_step<RUN, 4>(acc, w, u);
-#pragma unroll
-        for (int r = 0; r < RUN; ++r) w[r] = w[r + 4];
-    }
-    if (j0 < O) {                                      // the last O mod 4 samples (both rows are long enough for these reads)
-        const v4f uv = *reinterpret_cast<const v4f *>(tail + j0);
-        u[0] = uv.x; u[1] = uv.y; u[2] = uv.z; u[3] = uv.w;
-        tsm_load4<RUN>(p + j0 + RUN, &w[RUN]);
-        const int rem = O - j0;
-        if (rem == 1) tsm_step<RUN, 1>(acc, w, u);
-        else if (rem == 2) tsm_step<RUN, 2>(acc, w, u);
-        else tsm_step<RUN, 3>(acc, w, u);
-    }
+    float acc[RUN];                                    // (O mod 4 != 0: both rows are long enough for the tail's reads)
+    nsg_ssd_run<RUN, 0b1111>(acc, win + RUN * g, tail, O);
     unsigned long long best = ~0ull;
 #pragma unroll
     for (int r = 0; r < RUN; ++r) {
@@ -203,12 +150,7 @@ __global__ __launch_bounds__(TSM_THREADS) void tsm_chain_kernel(const float *__r
             tsm_fetch(rw, xb, tsm_nominal(m + 1, Ho, c), n, c.len, npf, tid);
             tsm_fetch(rt, xb, nm + Ho, n, c.len, npf, tid);
         }
-        unsigned long long best = act ? tsm_search<RUN>(win, tail, O, W, g) : ~0ull;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const unsigned long long o = __shfl_xor(best, off, 64);
-            best = o < best ? o : best;
-        }
+        const unsigned long long best = nsg_wave_min(act ? tsm_search<RUN>(win, tail, O, W, g) : ~0ull);
         if ((tid & 63) == 0) atomicMin(key, best);
         __syncthreads();
         dprev = (int)(unsigned)*key;
@@ -238,13 +180,9 @@ __global__ __launch_bounds__(256) void tsm_render_kernel(const float *__restrict
         float v = 0.f;
         if (k < c.out_len) {
             const int m = nsg_div(k, div_ho), j = k - m * Ho;
-            const int64_t at = (int64_t)qb[m] + j;
-            const bool in = at >= 0 && at < c.len;
-            v = in ? xb[in ? at : 0] : 0.f;
+            v = nsg_clip_at(xb, (int64_t)qb[m] + j, c.len);
             if (m >= 1 && j < O) {
-                const int64_t pa = (int64_t)qb[m - 1] + Ho + j;
-                const bool ina = pa >= 0 && pa < c.len;
-                const float a = ina ? xb[ina ? pa : 0] : 0.f;
+                const float a = nsg_clip_at(xb, (int64_t)qb[m - 1] + Ho + j, c.len);
                 const float w = (float)j / fO;
                 const float diff = v - a;
                 const float sc = w * diff;
@@ -266,8 +204,7 @@ struct MixClip {
 __device__ __forceinline__ MixClip mix_clip(const int32_t *lengths, const int32_t *offset, int b, int L, int Ln)
 {
     MixClip c;
-    const int len = lengths ? lengths[b] : L;
-    c.len = len < 0 ? 0 : (len > L ? L : len);
+    c.len = nsg_clip_len(lengths, b, L);
     const int o = offset[b];
     c.off = (unsigned)(o < 0 ? 0 : (o > Ln - 1 ? Ln - 1 : o));      // the caller's to get right (nsg.h); clamped so that no read leaves noise
     return c;
@@ -314,8 +251,7 @@ __global__ __launch_bounds__(64) void mix_scale_kernel(const double *__restrict_
     nsg_wave_close_sum(pb + (int64_t)gridDim.x * NP, NP, [&](double t) { tot[1] = t; });
     if (threadIdx.x == 0) {
         const double ex = tot[0], en = tot[1];
-        int len = lengths ? lengths[b] : L;
-        len = len < 0 ? 0 : (len > L ? L : len);
+        const int len = nsg_clip_len(lengths, b, L);
         float s = 0.f;
         if (len > 0 && en != 0.0) {
             const double ratio = ex / en;
@@ -349,10 +285,7 @@ __global__ __launch_bounds__(256) void mix_apply_kernel(const float *__restrict_
         x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
     } else {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const bool in = i0 + e < c.len;
-            x[e] = in ? xb[in ? i0 + e : 0] : 0.f;
-        }
+        for (int e = 0; e < 4; ++e) x[e] = nsg_clip_at(xb, i0 + e, c.len);
     }
     unsigned r = (c.off + (unsigned)i0) % uLn;
 #pragma unroll

@@ -119,11 +119,12 @@ def trim_clips():
     return clips
 
 
-@pytest.mark.parametrize("frame_length,hop", [(2048, 512), (512, 128)])
+@pytest.mark.parametrize("frame_length,hop", [(2048, 512), (512, 128), (64, 8)])
 def test_trim_bounds_are_the_fp64_formulas(frame_length, hop):
     """Exact equality with trim64, asserted only after the condition that makes it derivable: every frame is at least 0.01 dB
     from the threshold, and fp32 summation of a frame of <= 2048 squares moves its level by at most
-    10 log10(1 + 2 * 2050 * 2^-24) = 1.1e-3 dB."""
+    10 log10(1 + 2 * 2050 * 2^-24) = 1.1e-3 dB.  The bounds kernel takes 256 frames a round, a wave 64 of them: at (2048, 512)
+    every clip has fewer than 64 frames (3 .. 41: whole waves own none), at (64, 8) four of the five more than 256 (129 .. 2561)."""
     clips = trim_clips()
     want = []
     for y, (_, _, _, table) in zip(clips, TRIM_CASES):

@@ -1,7 +1,7 @@
 """GPU: nsg_audio_tempo equals the fp32 restatement of its contract (tests/helpers/tempo_ref.py: wsola_f32) bit for bit -- the
 positions exactly, the output by bit pattern, the rows' padding included -- across the envelope: the smallest and the largest
 sizes, an odd overlap and a search width that is no multiple of a lane's run, every search width class (a lane's run of 2, 4 and
-8 candidates), an overlap as long as the hop, a search of one position, the factors 0.25 .. 4, ragged lengths down to none, a clip
+8 candidates) with every overlap mod 4, an overlap as long as the hop, a search of one position, the factors 0.25 .. 4, ragged lengths down to none, a clip
 alone and as a row of a larger batch.  Inputs and outputs sit in guarded buffers, with NaN past each clip's length: a read past a
 length or a row's end would reach the result, a store outside the outputs would reach the guards.  Then audio.tempo,
 audio.pitch_shift, audio.random_augment and preprocess's augmented copies end to end."""
@@ -103,6 +103,15 @@ def test_kernel_equals_the_restatement(name):
     assert np.array_equal(bits(out[2, :L]), bits(host[2]))                                  # factor 1
     if W > 1:
         assert len(np.unique((pos[1, 1:] - np.floor(np.arange(1, pos.shape[1]) * (S - O) * 0.85))[pos[1, 1:] >= 0])) > 1   # the search moved
+
+
+@pytest.mark.parametrize("O", [4, 5, 6, 7])
+@pytest.mark.parametrize("W", [20, 513, 1025])
+def test_every_run_with_every_tail_of_the_overlap(W, O):
+    """The search is one template over (a lane's run, O mod 4): W = 20, 513, 1025 are runs of 2, 4 and 8 candidates, O = 4 .. 7 the
+    four remainders, so each of the twelve instantiations runs here."""
+    host = np.stack([clip(2500, 7 * W + O + b, f0=110.0 + 35.0 * b) for b in range(len(FACTORS))])
+    check(host, FACTORS, 64, O, W)
 
 
 def test_the_defaults_on_a_second_of_audio():
