@@ -734,6 +734,27 @@ NSG_API int nsg_prior_walk_ctl(const float *w, const float *emb, const float *co
                                float *logits, int32_t B, int32_t H, int32_t W, int32_t dim, int32_t n_layers, int32_t input_dim,
                                int32_t row, float temperature, int32_t top_k, float top_p, void *stream);
 
+/* The controlled walk under classifier-free guidance.  B is the number of clips and is even: clips 2p and 2p + 1 are pair p,
+ * the conditional branch (its cond and vh rows come from the real label) and the unconditional branch (from the null label).
+ * u, x_in, keep and codes are indexed by pair, [B / 2][H][W]; cond, vh and e_row stay per clip (the next row pass needs both
+ * branches' embeddings); logits (optional) stays [B][H][W][K] and receives each branch's RAW logits, before they are combined.
+ * Per position, with the head's fp32 logits l_c (clip 2p) and l_u (clip 2p + 1) and guidance g:
+ *     l_k = l_c,k + g * (l_c,k - l_u,k)        three separately rounded fp32 operations: subtract, multiply, add (never fused),
+ * then steps 1-5 of nsg_prior_walk_ctl's rule run on l.  The chosen code goes to codes[p][row][j], and its embedding to the
+ * e_row of BOTH clips of the pair: the branches walk the same codes.  With g == 0, or where l_c == l_u, l is l_c and the pair's
+ * codes are those nsg_prior_walk_ctl gives clip 2p under the same u, bit for bit.
+ * One workgroup per 4 clips = 2 pairs (a trailing one serves one pair); a pair never straddles workgroups.  The partition of
+ * the work and every summation order are nsg_prior_walk's: a pair's arithmetic does not depend on the other pairs of the batch,
+ * and each branch's logits are those the teacher-forced walk computes for that clip on the chosen codes.
+ * Same envelope, alignment and extent checks as nsg_prior_walk_ctl and the same refusals; in addition NSG_E_INVALID for an odd
+ * B and for a guidance that is not finite, < 0 or > 1024.  (The cap keeps l finite: |l| <= 1025 |l_c| + 1024 |l_u|, below FLT_MAX
+ * for every pair of logits under FLT_MAX / 2049 ~ 1.6e35 in magnitude, which any head with finite weights of ordinary size
+ * produces.) */
+NSG_API int nsg_prior_walk_cfg(const float *w, const float *emb, const float *cond, const float *vh, const float *u,
+                               const int64_t *x_in, const uint8_t *keep, int64_t *codes, float *e_row, int64_t e_clip_stride,
+                               float *logits, int32_t B, int32_t H, int32_t W, int32_t dim, int32_t n_layers, int32_t input_dim,
+                               int32_t row, float temperature, int32_t top_k, float top_p, float guidance, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Mel -> waveform inversion (the epoch loop's audio export)   src/main.py:164-197, src/audio_tacotron.py:99-116,142-153
  * librosa's stft / istft / filters.mel and scipy's lfilter restated; fp32; frame-major spectrograms [B][T][F], F = n_fft/2+1.

@@ -45,6 +45,10 @@ struct WalkCtlArgs : WalkArgs {   // nsg_prior_walk_ctl: u and codes are set; x_
     float top_p;             // 1 = off
 };
 
+struct WalkCfgArgs : WalkCtlArgs {   // nsg_prior_walk_cfg: B even, clips 2p (conditional) and 2p + 1 (unconditional) are pair p;
+    float guidance;                  // u, x_in, keep and codes are [B / 2][H][W], one entry per pair
+};
+
 // Partial sums of y[c][n] for n < N (N % 4 == 0), k < Kd, into red[(s * NC + c) * N + n], s = the thread's k-slice
 // (S <= SMAX slices of consecutive k, each summed in k order).
 // x[c][k] is read from up to three LDS segments of `seglen` floats each (segment k / seglen), clip c at +c * cs.
@@ -232,9 +236,13 @@ __device__ __noinline__ int pick_ctl(const float *l, int K, int lane, float u, f
 }
 
 // CTL: the instantiation of nsg_prior_walk_ctl (temperature, top-k, top-p, kept codes); the plain one is nsg_prior_walk's.
-template <bool CTL>
-__global__ __launch_bounds__(THREADS) void prior_walk_kernel(std::conditional_t<CTL, WalkCtlArgs, WalkArgs> a)
+// CFG (with CTL): the instantiation of nsg_prior_walk_cfg.  The clips of a pair run the same chain on their own cond and vh
+// rows; their logits are combined in LDS, one wave picks the pair's code, and both clips take its embedding.
+template <bool CTL, bool CFG = false>
+__global__ __launch_bounds__(THREADS) void prior_walk_kernel(std::conditional_t<CFG, WalkCfgArgs, std::conditional_t<CTL, WalkCtlArgs, WalkArgs>> a)
 {
+    static_assert(CTL || !CFG, "the guided walk picks with the controlled pick");
+    static_assert(NC % 2 == 0, "a pair never straddles workgroups");
     extern __shared__ float lds[];
     const int dim = a.dim, D2 = 2 * dim, L = a.L, Kp = a.Kp;
     const int b0 = blockIdx.x * NC;
@@ -330,10 +338,19 @@ __global__ __launch_bounds__(THREADS) void prior_walk_kernel(std::conditional_t<
             if (a.logits && c < nc && n < a.K) a.logits[(((size_t)(b0 + c) * a.H + i) * a.W + j) * a.K + n] = v;
         }
         __syncthreads();
-        // 5. the code: teacher-forced, or the inverse CDF of the softmax against u (one wave per clip)
-        if (wave < nc) {
-            const int c = wave, b = b0 + c;
-            const size_t pos = ((size_t)b * a.H + i) * a.W + j;
+        if constexpr (CFG) {
+            // 4b. l = l_c + guidance * (l_c - l_u), three separately rounded operations, over the conditional branch's row
+            for (int t = threadIdx.x; t < (NC / 2) * Kp; t += THREADS) {
+                const int p = t / Kp, n = t - p * Kp;
+                const float lc = lg[2 * p * Kp + n], lu = lg[(2 * p + 1) * Kp + n];
+                lg[2 * p * Kp + n] = __fadd_rn(lc, __fmul_rn(a.guidance, __fsub_rn(lc, lu)));
+            }
+            __syncthreads();
+        }
+        // 5. the code: teacher-forced, or the inverse CDF of the softmax against u (one wave per clip; per pair under CFG)
+        if (wave < (CFG ? nc / 2 : nc)) {
+            const int c = CFG ? 2 * wave : wave, b = b0 + c;
+            const size_t pos = ((size_t)(CFG ? b / 2 : b) * a.H + i) * a.W + j;
             int code;
             if constexpr (CTL) {
                 if (a.keep && a.keep[pos]) code = (int)a.x_in[pos];
@@ -383,6 +400,7 @@ __global__ __launch_bounds__(THREADS) void prior_walk_kernel(std::conditional_t<
             code = min(max(code, 0), a.K - 1);
             if (lane == 0) {
                 code_sh[c] = code;
+                if constexpr (CFG) code_sh[c + 1] = code;      // both branches continue from the pair's code
                 if (a.codes) a.codes[pos] = code;
             }
         }
@@ -425,7 +443,7 @@ size_t nsg_prior_walk_weight_floats(int32_t dim, int32_t n_layers, int32_t input
     return layer0 + (size_t)(n_layers - 1) * layerN + (size_t)dim * HEAD + HEAD + HEAD * Kp + Kp;
 }
 
-// The checks nsg_prior_walk and nsg_prior_walk_ctl share (fn: the entry point's name for the error string)
+// The checks every walk shares (fn: the entry point's name for the error string)
 static int walk_checks(const char *fn, const float *w, const float *emb, const float *cond, const float *vh, const float *e_row,
                        int64_t e_clip_stride, int32_t B, int32_t H, int32_t W, int32_t dim, int32_t n_layers, int32_t input_dim, int32_t row)
 {
@@ -485,6 +503,31 @@ int nsg_prior_walk_ctl(const float *w, const float *emb, const float *cond, cons
     hipLaunchKernelGGL(prior_walk_kernel<true>, dim3((unsigned)nsg_cdiv(B, NC)), dim3(THREADS), walk_lds_bytes(dim, n_layers, a.Kp),
                        (hipStream_t)stream, a);
     return nsg_check_launch("prior_walk_ctl_kernel");
+}
+
+int nsg_prior_walk_cfg(const float *w, const float *emb, const float *cond, const float *vh, const float *u, const int64_t *x_in,
+                       const uint8_t *keep, int64_t *codes, float *e_row, int64_t e_clip_stride, float *logits, int32_t B, int32_t H,
+                       int32_t W, int32_t dim, int32_t n_layers, int32_t input_dim, int32_t row, float temperature, int32_t top_k,
+                       float top_p, float guidance, void *stream)
+{
+    NSG_REQUIRE(u && codes, NSG_E_INVALID, "nsg_prior_walk_cfg: u and codes are required");
+    NSG_REQUIRE((x_in != nullptr) == (keep != nullptr), NSG_E_INVALID, "nsg_prior_walk_cfg: x_in and keep come together");
+    NSG_REQUIRE(isfinite(temperature) && temperature > 0.f && isfinite(1.0f / temperature), NSG_E_INVALID,
+                "nsg_prior_walk_cfg: temperature must be finite and > 0, and so must 1 / temperature in fp32");
+    NSG_REQUIRE(top_k >= 0, NSG_E_INVALID, "nsg_prior_walk_cfg: top_k=%d must be >= 0 (0 = off)", top_k);
+    NSG_REQUIRE(top_p > 0.f && top_p <= 1.f, NSG_E_INVALID, "nsg_prior_walk_cfg: top_p must be in (0, 1] (1 = off)");
+    NSG_REQUIRE(B % 2 == 0, NSG_E_INVALID, "nsg_prior_walk_cfg: B=%d must be even (clips 2p and 2p + 1 are pair p)", B);
+    NSG_REQUIRE(isfinite(guidance) && guidance >= 0.f && guidance <= 1024.f, NSG_E_INVALID,
+                "nsg_prior_walk_cfg: guidance must be finite and in [0, 1024]");
+    if (const int rc = walk_checks("nsg_prior_walk_cfg", w, emb, cond, vh, e_row, e_clip_stride, B, H, W, dim, n_layers, input_dim, row)) return rc;
+    static LdsOptIn once;
+    if (const int rc = nsg_lds_opt_in(once, {reinterpret_cast<const void *>(&prior_walk_kernel<true, true>)}, LDS_MAX, "nsg_prior_walk_cfg")) return rc;
+    WalkCfgArgs a;
+    walk_fill(a, w, emb, cond, vh, u, x_in, codes, e_row, e_clip_stride, logits, B, H, W, dim, n_layers, input_dim, row);
+    a.keep = keep; a.inv_t = 1.0f / temperature; a.top_k = top_k; a.top_p = top_p; a.guidance = guidance;
+    hipLaunchKernelGGL((prior_walk_kernel<true, true>), dim3((unsigned)nsg_cdiv(B, NC)), dim3(THREADS), walk_lds_bytes(dim, n_layers, a.Kp),
+                       (hipStream_t)stream, a);
+    return nsg_check_launch("prior_walk_cfg_kernel");
 }
 
 }  // extern "C"

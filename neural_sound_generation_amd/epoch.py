@@ -106,11 +106,12 @@ def run_vae_epoch(args, model, step_or_optimizer, train_loader, test_loader, dev
 
 
 def run_prior_epoch(args, vqvae, prior, step_or_optimizer, train_loader, test_loader, device, epoch, checkpoint_path=None,
-                    sample_label=None, sample_frames=64, generator=None, eval_with_ema=False):
+                    sample_label=None, sample_frames=64, generator=None, eval_with_ema=False, sample_controls=None):
     """Stage two's epoch: train_prior -> test_prior -> checkpoint ({'epoch', 'arch': 'pixelcnn', 'state_dict', 'optimizer'}, the
     layout of run_epoch's; evaluate.load_checkpoint into the prior and the step's optimiser resumes bit-identically) -> with
     sample_label (B,) int64: evaluate.sample_mels of those classes, sample_frames frames each, saved as a .npy of mels
-    (B, 80, sample_frames).  step_or_optimizer: a PriorTrainStep or a torch optimiser (train_prior).  The VQ-VAE is only read.
+    (B, 80, sample_frames); sample_controls: a dict of GatedPixelCNN.sample's controls forwarded to sample_mels (temperature,
+    top_k, top_p, guidance, null_label).  step_or_optimizer: a PriorTrainStep or a torch optimiser (train_prior).  The VQ-VAE is only read.
     eval_with_ema: test_prior and the samples (nothing else) see the prior's averaged weights (FlatAdam(weight_ema_decay=));
     the checkpoint always holds the raw weights, and the averaged ones inside the optimiser's state.
     Returns a dict with the numbers and the files written."""
@@ -131,7 +132,8 @@ def run_prior_epoch(args, vqvae, prior, step_or_optimizer, train_loader, test_lo
         vqvae.eval()
         try:
             with _averaged(optimizer, eval_with_ema):
-                codes, mels = sample_mels(vqvae, prior, sample_label.to(device), sample_frames, generator=generator)
+                codes, mels = sample_mels(vqvae, prior, sample_label.to(device), sample_frames, generator=generator,
+                                          **(sample_controls or {}))
         finally:
             vqvae.train(was_training)
         out["sample_codes"] = codes

@@ -35,6 +35,7 @@ checkpoint layout, restated from the reference's src/test.py:73-106 and src/main
 from __future__ import annotations
 
 import functools
+import numbers
 import os
 
 import numpy as np
@@ -179,7 +180,7 @@ LATENT_ROWS = 20   # the VQ-VAE's latent grid of an 80-band mel: two stride-2 co
 def sample_mels(vqvae, prior, label: torch.Tensor, frames: int, g=None, generator=None, **controls):
     """Codes (B, 20, frames // 4) sampled from the prior for the class labels (B,), and their decoded mels (B, 1, 80, frames)
     (vqvae.decode; put the VQ-VAE in eval mode for its running BatchNorm statistics).  controls: GatedPixelCNN.sample's
-    temperature, top_k and top_p."""
+    temperature, top_k and top_p.  guidance= and null_label= (classifier-free guidance) pass through to it as well."""
     if frames < 4:
         raise ValueError("sample_mels: frames must be at least 4 (one latent column)")
     codes = prior.sample(label, shape=(LATENT_ROWS, frames // 4), batch_size=label.shape[0], generator=generator, **controls)
@@ -240,6 +241,38 @@ def test_prior(args, vqvae, prior, test_loader, device, epoch):
     nats = float(nll / count)
     print('====> Prior test set: {:.4f} nats per code ({:.4f} bits)'.format(nats, nats / float(np.log(2.0))))
     return nats
+
+
+def label_information(args, vqvae, prior, test_loader, device, null_label):
+    """How much the label tells the prior, the quantity classifier-free guidance extrapolates: one pass over the loader, each
+    batch scored twice by prior.nll, under its own labels and under null_label for every clip, pooled over codes as test_prior
+    pools.  Returns {"nats_conditional", "nats_unconditional", "gain"}, gain = unconditional - conditional in nats per code.
+    Roughly zero for a prior trained without label dropout on a null class it never saw as such."""
+    from .prior_train import prior_labels
+    n_classes = prior.layers[0].class_cond_embedding.num_embeddings
+    if isinstance(null_label, bool) or not isinstance(null_label, numbers.Integral) or not 0 <= null_label < n_classes:
+        raise ValueError(f"label_information: null_label must be an integer in [0, {n_classes})")
+    nll = torch.zeros(2, dtype=torch.float64, device=device)
+    count = torch.zeros((), dtype=torch.int64, device=device)
+    n = 0
+    for x, y, c, g, input_lengths in test_loader:
+        c = c.to(device).unsqueeze(1)
+        codes, lengths = codes_from_mels(vqvae, c, input_lengths)
+        label = prior_labels(prior, g, len(c))
+        cond_nll, clip_count = prior.nll(codes, label, lengths)
+        null_nll, _ = prior.nll(codes, torch.full_like(label, int(null_label)), lengths)
+        nll[0] += cond_nll.double().sum()
+        nll[1] += null_nll.double().sum()
+        count += clip_count.sum()
+        n += 1
+    if n == 0:
+        raise ValueError("label_information: empty loader")
+    if int(count) == 0:
+        raise ValueError("label_information: no clip of the loader is long enough for one latent column")
+    cond, uncond = float(nll[0] / count), float(nll[1] / count)
+    print('====> Prior label information: {:.4f} nats per code conditional, {:.4f} under the null label, gain {:.4f}'.format(
+        cond, uncond, uncond - cond))
+    return {"nats_conditional": cond, "nats_unconditional": uncond, "gain": uncond - cond}
 
 
 def convert_voice(vqvae, mel: torch.Tensor, g_target: torch.Tensor):
@@ -458,7 +491,7 @@ def continue_mels(vqvae, prior, mel: torch.Tensor, label: torch.Tensor, keep_fra
     """Continue mels in time: mel (B, 1, 80, T) is encoded to its codes, the first keep_frames // 4 latent columns are kept
     and the prior samples the grid out to frames // 4 columns (GatedPixelCNN.continue_codes, which says what the sampled codes
     are conditioned on; controls: temperature, top_k, top_p), then the grid is decoded.  Returns codes (B, 20, frames // 4)
-    and mels (B, 1, 80, frames)."""
+    and mels (B, 1, 80, frames).  guidance= and null_label= (classifier-free guidance) pass through to sample as well."""
     if frames < 4:
         raise ValueError("continue_mels: frames must be at least 4 (one latent column)")
     known = vqvae.encode(mel)
@@ -476,7 +509,8 @@ def continue_audio(vqvae, prior, wav: torch.Tensor, label: torch.Tensor, keep_fr
     -> continue_mels (the first keep_frames held, the grid sampled out to frames) -> waveform (audio.inv_mel_spectrogram;
     angles0 (B, frames, 1 + fft_size / 2) fixes Griffin-Lim's initial phases; iters, default audio.GRIFFIN_LIM_ITERS, and momentum
     are audio.griffin_lim's, init audio.inv_mel_spectrogram's).  Returns codes (B, 20, frames // 4), mels
-    (B, 1, 80, frames) and waveforms (B, hop_size * (frames - 1))."""
+    (B, 1, 80, frames) and waveforms (B, hop_size * (frames - 1)).  guidance= and null_label= (classifier-free guidance) pass
+    through to GatedPixelCNN.sample with the other controls."""
     from . import audio
     audio._init("continue_audio", init, angles0)
     mel = audio.melspectrogram(wav, sample_rate, fft_size, hop_size, 80)

@@ -1574,11 +1574,11 @@ def _prior_walk_extents(fn, w, emb, cond, vh, e_row, H, row, tensors):
         raise _lib.NsgError(f"{fn}: weight blob of {w.numel()} floats, expected {prior_walk_weight_floats(dim, L, K)}")
     if not e_row.is_cuda or e_row.dtype != torch.float32 or tuple(e_row.shape) != (B, W, dim) or e_row.stride()[1:] != (dim, 1):
         raise _lib.NsgError(f"{fn}: e_row must be fp32 (B, W, dim) = {(B, W, dim)} with rows of dim contiguous floats")
-    for t, nm, dt, tail in tensors:
+    for t, nm, dt, tail, *lead in tensors:          # lead: the leading extent where it is not B (prior_walk_cfg's pairs)
         if t is not None:
             _chk(t, nm, dt)
-            if tuple(t.shape) != (B, H, W) + tail:
-                raise _lib.NsgError(f"{fn}: {nm} {tuple(t.shape)}, expected {(B, H, W) + tail}")
+            if tuple(t.shape) != (lead[0] if lead else B, H, W) + tail:
+                raise _lib.NsgError(f"{fn}: {nm} {tuple(t.shape)}, expected {(lead[0] if lead else B, H, W) + tail}")
     if not 0 <= row < H:
         raise _lib.NsgError(f"{fn}: row {row} outside 0 .. {H - 1}")
     return B, W, dim, L, K
@@ -1621,6 +1621,35 @@ def prior_walk_ctl(w, emb, cond, vh, e_row, H, row, u, codes, x_in=None, keep=No
         (logits, "logits", torch.float32, (K,))))
     _lib.call("nsg_prior_walk_ctl", _p(w), _p(emb), _p(cond), _p(vh), _p(u), _p(x_in), _p(keep), _p(codes), _p(e_row), e_row.stride(0), _p(logits), B,
               H, W, dim, L, K, row, temperature, min(int(top_k), 2 ** 31 - 1), top_p, _stream())
+
+
+def prior_walk_cfg(w, emb, cond, vh, e_row, H, row, u, codes, guidance, x_in=None, keep=None, logits=None, temperature=1.0, top_k=0,
+                   top_p=1.0):
+    """prior_walk_ctl under classifier-free guidance (nsg_prior_walk_cfg; the rule is in include/nsg.h).  cond, vh and e_row
+    hold B = 2P clips: clips 2p and 2p + 1 are pair p, the conditional branch (the real label's rows) and the unconditional
+    one (the null label's).  u (P, H, W) fp32, codes (P, H, W) int64 and the optional x_in / keep (P, H, W) are per pair;
+    logits (B, H, W, K) optional receives each branch's raw logits.  The pick runs on l_c + guidance * (l_c - l_u), guidance
+    in [0, 1024], and both clips of a pair continue from the pair's code."""
+    if u is None or codes is None:
+        raise _lib.NsgError("prior_walk_cfg: u and codes are required")
+    if (x_in is None) != (keep is None):
+        raise _lib.NsgError("prior_walk_cfg: x_in and keep come together")
+    if keep is not None and keep.dtype not in (torch.bool, torch.uint8):
+        raise _lib.NsgError(f"prior_walk_cfg: keep must be bool or uint8, got {keep.dtype}")
+    temperature, top_p, guidance = float(temperature), float(top_p), float(guidance)
+    if not (math.isfinite(temperature) and temperature > 0 and 0 < top_p <= 1) or int(top_k) != top_k or top_k < 0:
+        raise _lib.NsgError(f"prior_walk_cfg: temperature {temperature} (finite, > 0), top_k {top_k} (integer >= 0) or top_p {top_p} "
+                            "(in (0, 1]) out of range")
+    if not 0 <= guidance <= 1024:                   # NaN fails both comparisons
+        raise _lib.NsgError(f"prior_walk_cfg: guidance {guidance} outside [0, 1024]")
+    if cond.dim() != 3 or cond.shape[1] % 2 != 0:
+        raise _lib.NsgError(f"prior_walk_cfg: cond {tuple(cond.shape)} must hold an even number of clips (pairs of branches)")
+    K, P = emb.shape[0], cond.shape[1] // 2
+    B, W, dim, L, K = _prior_walk_extents("prior_walk_cfg", w, emb, cond, vh, e_row, H, row, (
+        (u, "u", torch.float32, (), P), (x_in, "x_in", torch.int64, (), P), (keep, "keep", None, (), P),
+        (codes, "codes", torch.int64, (), P), (logits, "logits", torch.float32, (K,))))
+    _lib.call("nsg_prior_walk_cfg", _p(w), _p(emb), _p(cond), _p(vh), _p(u), _p(x_in), _p(keep), _p(codes), _p(e_row), e_row.stride(0), _p(logits), B,
+              H, W, dim, L, K, row, temperature, min(int(top_k), 2 ** 31 - 1), top_p, guidance, _stream())
 
 
 def prepared_conv_forward(d: ConvDesc, x, w_fwd, bias, y, flags=0):

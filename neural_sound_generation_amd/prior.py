@@ -262,7 +262,7 @@ class GatedPixelCNN(nn.Module):
     # ------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def sample(self, label, shape=(8, 8), batch_size=64, u=None, generator=None, *, temperature=1.0, top_k=0, top_p=1.0,
-               given=None, keep=None):
+               given=None, keep=None, guidance=0.0, null_label=None):
         """Ancestral sampling in raster order with nothing recomputed: int64 codes (batch_size, H, W).  Each code is the
         inverse CDF of its softmax against u[b, i, j] (include/nsg.h, nsg_prior_walk); u is drawn with torch.rand on the
         model's device when not given.  The same distribution as `generate`, O(H W) work instead of O((H W)^2).
@@ -276,12 +276,20 @@ class GatedPixelCNN(nn.Module):
         and only the other positions are sampled.  This is not posterior inference: each sampled code is drawn from the
         prior's conditional given everything BEFORE it in raster order, kept or sampled, and kept codes later in raster order
         do not influence it.  Keeping whole leading rows is exact conditional sampling; keeping the first columns of every
-        row is the usual "hold the known, sample the rest"."""
+        row is the usual "hold the known, sample the rest".
+
+        Classifier-free guidance (include/nsg.h, nsg_prior_walk_cfg): with guidance > 0, a real number up to 1024, every
+        clip is walked twice, under its label and under null_label (an integer in [0, n_classes), required then and refused
+        otherwise), and each code is picked -- by the controls above, against the same u -- from the logits
+        l_c + guidance * (l_c - l_u); both branches continue from that code.  It pushes a sample towards what its label
+        adds over the null class, which is something only for a prior trained with label dropout on that null class
+        (prior_train.drop_labels).  guidance == 0 is the sampler without it: the same launches, the same bits."""
         H, W = self._grid(shape)
         B = int(batch_size)
         label = self._labels(label, B)
         dev = label.device
         ctl = self._controls(temperature, top_k, top_p)
+        guided = self._guidance(guidance, null_label)
         if (given is None) != (keep is None):
             raise ValueError("sample: given and keep come together")
         if given is not None:
@@ -300,7 +308,11 @@ class GatedPixelCNN(nn.Module):
         elif not isinstance(u, torch.Tensor) or tuple(u.shape) != (B, H, W) or u.dtype != torch.float32:
             raise ValueError(f"sample: u must be a float32 tensor of shape {(B, H, W)}")
         codes = torch.empty((B, H, W), dtype=torch.int64, device=dev)
-        if ctl is None and given is None:
+        if guided is not None:                       # 2B clips: [label[0], null, label[1], null, ...]; u, given, keep and codes per pair
+            pairs = torch.stack([label, torch.full_like(label, guided[1])], 1).reshape(-1)
+            self._walk_rows(pairs, 2 * B, H, W, u=u.to(dev).contiguous(), codes=codes, x_in=given, keep=keep, ctl=ctl or (1.0, 0, 1.0),
+                            guidance=guided[0])
+        elif ctl is None and given is None:
             self._walk_rows(label, B, H, W, u=u.to(dev).contiguous(), codes=codes)
         else:
             self._walk_rows(label, B, H, W, u=u.to(dev).contiguous(), codes=codes, x_in=given, keep=keep, ctl=ctl or (1.0, 0, 1.0))
@@ -310,7 +322,7 @@ class GatedPixelCNN(nn.Module):
     def continue_codes(self, prefix, label, width, **controls):
         """Continue a grid of codes in time: prefix int64 (B, H, W0) with W0 <= width -> int64 (B, H, width) whose columns
         < W0 are the prefix and whose other columns are sampled (`sample` with the first W0 columns of every row kept;
-        controls: sample's u, generator, temperature, top_k, top_p).  Not posterior inference: a sampled code is conditioned
+        controls: sample's u, generator, temperature, top_k, top_p, guidance, null_label).  Not posterior inference: a sampled code is conditioned
         on what precedes it in raster order -- the rows above, prefix and continuation, and its own row to its left -- and
         not on the prefix columns of the rows below it."""
         if not isinstance(prefix, torch.Tensor) or prefix.dim() != 3 or prefix.dtype != torch.int64:
@@ -342,6 +354,23 @@ class GatedPixelCNN(nn.Module):
         if float(temperature) == 1.0 and top_k == 0 and float(top_p) == 1.0:
             return None
         return float(temperature), top_k, float(top_p)
+
+    def _guidance(self, guidance, null_label):
+        """Validates sample's guidance and null_label; None without guidance, else (guidance, null_label)."""
+        if isinstance(guidance, bool) or not isinstance(guidance, numbers.Real):
+            raise ValueError("sample: guidance must be a number")
+        if not 0 <= guidance <= 1024:                # NaN fails both comparisons
+            raise ValueError("sample: guidance must be in [0, 1024] (0: off)")
+        if guidance == 0:
+            if null_label is not None:
+                raise ValueError("sample: null_label is given without guidance")
+            return None
+        n_classes = self.layers[0].class_cond_embedding.num_embeddings
+        if null_label is None or isinstance(null_label, bool) or not isinstance(null_label, numbers.Integral):
+            raise ValueError("sample: guidance > 0 needs null_label, an integer class")
+        if not 0 <= null_label < n_classes:
+            raise ValueError(f"sample: null_label outside [0, {n_classes})")
+        return float(guidance), int(null_label)
 
     @torch.no_grad()
     def incremental_logits(self, x, label):
@@ -405,13 +434,16 @@ class GatedPixelCNN(nn.Module):
         parts += [w0.weight.detach()[:, :, 0, 0].t().reshape(-1), w0.bias.detach(), w2t.reshape(-1), b2]
         return torch.cat([p.reshape(-1).float() for p in parts]).contiguous()
 
-    def _walk_rows(self, label, B, H, W, u=None, codes=None, x_in=None, logits=None, times=None, ctl=None, keep=None):
+    def _walk_rows(self, label, B, H, W, u=None, codes=None, x_in=None, logits=None, times=None, ctl=None, keep=None, guidance=None):
         """Row i: the row pass (vertical stacks, their gates and the v2h 1x1s of every layer, all W columns, on the conv
         kernels), then the column walk.  Layer 0 reads rows i-3 .. i of e (row i is masked: zeros until the walk writes it),
         the others rows i-1, i of their vertical input; rows above the grid are zero, as the conv's padding is.
         times: optional dict that collects the row passes' and walks' GPU milliseconds (scripts/prior_sample_timing.py).
         ctl: None for the plain walk (nsg_prior_walk), or (temperature, top_k, top_p) for the controlled one
-        (nsg_prior_walk_ctl), which also takes keep (B, H, W) with x_in as the kept codes."""
+        (nsg_prior_walk_ctl), which also takes keep (B, H, W) with x_in as the kept codes.
+        guidance: None, or with ctl the guided walk (nsg_prior_walk_cfg): B = 2P clips whose labels interleave each pair's
+        real and null label, while u, codes, x_in and keep are (P, H, W); logits stays (B, H, W, K).  The row pass is the
+        same one on the 2P clips."""
         self._check_walk()
         self.layers[0].make_causal()
         dim, L, K = self.dim, len(self.layers), self.embedding.num_embeddings
@@ -458,7 +490,10 @@ class GatedPixelCNN(nn.Module):
                 v2h[l]()
             if ev:
                 ev[1].record()
-            if ctl is None:
+            if guidance is not None:
+                ops.prior_walk_cfg(blob, emb, cond, vh, e_grid[:, i + 3], H, i, u, codes, guidance, x_in=x_in, keep=keep, logits=logits,
+                                   temperature=ctl[0], top_k=ctl[1], top_p=ctl[2])
+            elif ctl is None:
                 ops.prior_walk(blob, emb, cond, vh, e_grid[:, i + 3], H, i, u=u, x_in=x_in, codes=codes, logits=logits)
             else:
                 ops.prior_walk_ctl(blob, emb, cond, vh, e_grid[:, i + 3], H, i, u, codes, x_in=x_in, keep=keep, logits=logits,

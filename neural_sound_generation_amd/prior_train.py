@@ -16,8 +16,12 @@
     The gradients lie in one flat bucket (`opt.flat_grad`), so data parallelism is one all-reduce of it (not wired here).
   * `train_prior(args, vqvae, prior, step_or_optimizer, train_loader, device, epoch)` -- one epoch over a loader of
     (x, y, c, g, input_lengths): codes from the frozen VQ-VAE (evaluate.codes_from_mels), label = g (zeros without speakers).
+  * `drop_labels(label, p, null_label, generator)` -- label dropout, the training half of classifier-free guidance; train_prior
+    applies it before either kind of step when args.label_dropout > 0.  PriorTrainStep knows nothing of it.
 """
 from __future__ import annotations
+
+import numbers
 
 import torch
 
@@ -190,13 +194,59 @@ def prior_labels(prior: GatedPixelCNN, g, B: int):
     return g
 
 
+def drop_labels(label, p, null_label, generator):
+    """Label dropout for classifier-free guidance: label int64 (B,) with label[b] replaced by null_label where a uniform draw
+    from the CPU `generator` is < p.  The B draws are made on the host in clip order (one torch.rand(B) call); the replacement
+    is a torch.where on the label's own device.  p == 0 draws nothing and returns `label` itself."""
+    if isinstance(p, bool) or not isinstance(p, numbers.Real) or not 0 <= p <= 1:
+        raise ValueError("drop_labels: p must be a number in [0, 1]")
+    if not isinstance(label, torch.Tensor) or label.dim() != 1 or label.dtype != torch.int64:
+        raise ValueError("drop_labels: label must be an int64 tensor (B,)")
+    if p == 0:
+        return label
+    if isinstance(null_label, bool) or not isinstance(null_label, numbers.Integral) or null_label < 0:
+        raise ValueError("drop_labels: null_label must be an integer >= 0")
+    if not isinstance(generator, torch.Generator) or generator.device.type != "cpu":
+        raise ValueError("drop_labels: generator must be a CPU torch.Generator")
+    drop = torch.rand(label.shape[0], generator=generator) < p
+    return torch.where(drop.to(label.device), torch.full_like(label, int(null_label)), label)
+
+
+def _label_dropout(args, prior, epoch):
+    """train_prior's label dropout from args (label_dropout, null_label, label_dropout_seed), validated: None when off, else
+    (p, null_label, the epoch's CPU generator, seeded from (seed, epoch))."""
+    p = getattr(args, "label_dropout", 0.0)
+    null_label = getattr(args, "null_label", None)
+    seed = getattr(args, "label_dropout_seed", 0)
+    n_classes = prior.layers[0].class_cond_embedding.num_embeddings
+    if isinstance(p, bool) or not isinstance(p, numbers.Real) or not 0 <= p <= 1:
+        raise ValueError("train_prior: label_dropout must be a number in [0, 1]")
+    if null_label is not None and (isinstance(null_label, bool) or not isinstance(null_label, numbers.Integral) or not 0 <= null_label < n_classes):
+        raise ValueError(f"train_prior: null_label must be an integer in [0, {n_classes})")
+    if p == 0:
+        return None
+    if null_label is None:
+        raise ValueError("train_prior: label_dropout > 0 needs a null_label")
+    if isinstance(seed, bool) or not isinstance(seed, numbers.Integral) or isinstance(epoch, bool) or not isinstance(epoch, numbers.Integral):
+        raise ValueError("train_prior: label_dropout_seed and epoch must be integers")
+    # one stream per (seed, epoch): the pair packed into the generator's 64-bit seed, 32 bits each
+    generator = torch.Generator().manual_seed(((int(seed) & 0xFFFFFFFF) << 32) | (int(epoch) & 0xFFFFFFFF))
+    return float(p), int(null_label), generator
+
+
 def train_prior(args, vqvae, prior, step_or_optimizer, train_loader, device, epoch):
     """One epoch of the prior on the codes of the (frozen, never updated) VQ-VAE.  `train_loader` yields
     (x, y, c, g, input_lengths) with c (B, 80, T) mel frames, T a multiple of 4.  step_or_optimizer: a PriorTrainStep (the fused
     step) or a torch optimiser over prior.parameters() (the autograd path: parity / fallback form).  The padded columns of each
-    clip are left out of the loss.  Returns the mean of the batches' losses."""
+    clip are left out of the loss.  Returns the mean of the batches' losses.
+    Label dropout (training for classifier-free guidance, GatedPixelCNN.sample(guidance=)): with args.label_dropout = p > 0 each
+    clip's label is replaced by args.null_label with probability p before the step (drop_labels), from one CPU generator per
+    epoch seeded from (args.label_dropout_seed, epoch).  The three attributes are optional; without them, or with p == 0, the
+    epoch is the one without dropout, bit for bit.  A p outside [0, 1], a null_label outside the prior's classes and dropout
+    without a null label are a ValueError before the first batch."""
     from .evaluate import codes_from_mels
     fused = isinstance(step_or_optimizer, PriorTrainStep)
+    dropout = _label_dropout(args, prior, epoch)
     prior.train()
     total = torch.zeros((), dtype=torch.float64, device=device)
     n_batches = 0
@@ -204,6 +254,8 @@ def train_prior(args, vqvae, prior, step_or_optimizer, train_loader, device, epo
         c = c.to(device).unsqueeze(1)
         codes, lengths = codes_from_mels(vqvae, c, input_lengths)
         label = prior_labels(prior, g, len(c)).to(device)
+        if dropout is not None:
+            label = drop_labels(label, *dropout)
         lengths = lengths.to(device)                    # (validated on the host by codes_from_mels: clipped to [0, W])
         if fused:
             loss = step_or_optimizer.step(codes, label, lengths, check=False)
