@@ -1207,6 +1207,55 @@ NSG_API int nsg_audio_stoi_envelopes(const float *x, const float *y, const int32
 NSG_API int nsg_audio_stoi_score(const float *env, const int32_t *kept, double *d, int32_t B, int32_t Tmax, int32_t extended,
                                  void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * F0-conditioned decoder (extension, beside the speaker-conditioned one; not in the reference): the decoder input also gets one
+ * row of an F0 table per latent COLUMN, chosen by the quantised log-F0 of the four mel frames the column covers, so the codes
+ * need not carry pitch.  parity unpinned: the definitions are this project's own, stated here in full and restated in numpy by
+ * tests/helpers/f0_cond_ref.py.  models.VQVAE(n_f0_bins=), train.FusedTrainStep, audio.f0_bins (csrc/f0_cond.hip).
+ * None of the three entry points takes a workspace; every launcher checks all of its arguments before it launches anything.
+ * ------------------------------------------------------------------------------------------- */
+
+/* The decoder input in one pass, for the latent grid [B][H][W] of C channels:
+ *     y[b][h][w][:] = act( (src(b,h,w)[:] + clip_rows[b][:]) + table[bins[b][w]][:] ),     row = (b H + h) W + w
+ *   src       idx == NULL: x is the fp32 rows themselves, src = x[row][:]  ([B H W][C]);
+ *             idx != NULL: x is a [K][C] fp32 table and src = x[idx[row]][:], idx [B H W] int64 -- a gather (the bf16 training
+ *             step never materialises an fp32 z_q);
+ *   clip_rows [B][C] fp32 or NULL (then src + table[..]: one add);  table [n_rows][C] fp32;  bins [B][W] int64;
+ *   act       identity (relu == 0) or max(., 0);  y [B H W][C] of y_dtype, fp32 or bf16 (round to nearest even).
+ * The two adds are fp32 additions in exactly the order written.  A bins value outside [0, n_rows) and an idx value outside [0, K)
+ * are CLAMPED into range (compared as the 64-bit values they are), so caller-made bins can never read outside the tables; the
+ * Python layers check their ranges on the host where they are given on the module paths.
+ * NSG_E_INVALID (message names the entry point): a null x, table, bins or y;  B, H, W, C, n_rows (K with idx) not positive;  an
+ * unknown y_dtype;  C not a multiple of 4 (fp32 y) or 8 (bf16 y);  x, clip_rows, table or y not 16-byte aligned, idx or bins not
+ * 8-byte aligned;  B H W C, n_rows C or K C not below 2^31. */
+NSG_API int nsg_add_cond(const float *x, const int64_t *idx, const float *clip_rows, const float *table, const int64_t *bins, void *y,
+                         int32_t B, int32_t H, int32_t W, int32_t C, int32_t K, int32_t n_rows, int32_t relu, int32_t y_dtype,
+                         void *stream);
+
+/* The first stage of that add's gradients: out[b][w][:] = sum over h of x[b][h][w][:], x [B][H][W][C] fp32 or bf16, out [B][W][C]
+ * fp32.  One thread owns a (b, w, 16-byte channel vector) triple and adds its H values to 0.f in ascending h in fp32: the result
+ * is fixed by construction and the same on every call.  The table's gradient is then nsg_index_add_rows* over bins, the clip
+ * rows' gradient nsg_clip_colsum of out with rows_per_clip = W.
+ * NSG_E_INVALID: a null pointer;  B, H, W or C not positive;  an unknown dtype;  C not a multiple of 4 (fp32) or 8 (bf16);  x or
+ * out not 16-byte aligned;  B H W C not below 2^31. */
+NSG_API int nsg_column_sum(const void *x, int32_t dtype, int32_t B, int32_t H, int32_t W, int32_t C, float *out, void *stream);
+
+/* An F0 track at the mel frame rate -> one bin per latent column.  f0 [B][T] fp32 Hz, +0.0 on unvoiced frames (as nsg_audio_f0 and
+ * nsg_f0_viterbi write it);  frames [B] int32 DEVICE memory or NULL (then T; clamped into [0, T]);  affine [B][3] fp32 rows of
+ * (mu_src, ratio, mu_tgt) or NULL;  bins [B][W] int64;  logf [B][W] fp32 or NULL.
+ * Latent column w covers frames 4w .. 4w + 3 (the encoder's two stride-2 stages).  Over those of them that are < frames[b] and
+ * voiced (f0 > 0), in frame order:  n = their number,  l = (sum of fl32(log2((double)f0)) added to 0.f in fp32) / (float)n.
+ *     l' = mu_tgt + (l - mu_src) * ratio      (fp32: the difference, the product, then the sum; l' = l without affine)
+ *     u  = ((l' - lo) * (float)n_bins) / span (fp32: the difference, the product, then the quotient), with the launch constants
+ *          lo = fl32(log2((double)fmin)), span = fl32(log2((double)fmax)) - lo (an fp32 difference)
+ *     the column is voiced iff n >= 2:  bin = 1 + min(max(floor(u), 0), n_bins - 1), logf = l';  otherwise bin = 0, logf = +0.0.
+ * (A column needs two voiced frames: a lone voiced frame beside three unvoiced ones is a tracker's onset or octave slip more often
+ * than a pitch.)  Every element of bins (and logf) is written; a clip's row depends on its own track and length alone.
+ * NSG_E_INVALID: a null f0 or bins;  B, T or W not positive;  T < 4 W;  n_bins < 1;  not 0 < fmin < fmax < inf, or a range whose
+ * fp32 span is not positive;  a pointer not aligned to its element (4 bytes; bins 8);  B T not below 2^31. */
+NSG_API int nsg_f0_bins(const float *f0, const int32_t *frames, const float *affine, int64_t *bins, float *logf, int32_t B, int32_t T,
+                        int32_t W, int32_t n_bins, float fmin, float fmax, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

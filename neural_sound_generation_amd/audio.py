@@ -482,6 +482,75 @@ def f0_distortion(f0_a, f0_b, path, steps):
     return (*f0_figures(stats), stats)
 
 
+def _f0_batch(fn, f0):
+    if not isinstance(f0, torch.Tensor) or f0.dim() != 2 or f0.dtype != torch.float32 or f0.shape[0] < 1 or f0.shape[1] < 1:
+        raise ValueError(f"{fn}: f0 must be a float32 tensor (B, T) with B, T >= 1, as f0 / f0_track return it for a batch")
+    return f0.shape
+
+
+def f0_bins(f0, frames=None, n_bins=32, fmin=65.0, fmax=500.0, affine=None, detail=False):
+    """An F0 track at the mel frame rate as the F0-conditioned decoder takes it: one bin per latent column (include/nsg.h:
+    nsg_f0_bins states the arithmetic, csrc/f0_cond.hip runs it).  f0 (B, T) fp32 GPU tensor in Hz, +0.0 where unvoiced (f0 /
+    f0_track); frames: None (all T), or (B,) valid frame counts in [0, T].  Latent column w of the T // 4 covers frames 4w .. 4w + 3;
+    with at least two of them voiced and inside the clip its value is the mean of their log2 F0 -- moved by affine (B, 3) fp32 rows
+    (mu_src, ratio, mu_tgt) to mu_tgt + (l - mu_src) ratio when given (f0_affine) -- and its bin 1 + the index of the n_bins equal
+    log-frequency steps of [fmin, fmax] it falls into (clamped to the ends); otherwise the column is unvoiced, bin 0.
+    Returns bins (B, T // 4) int64; with detail=True (bins, logf (B, T // 4) fp32: the moved mean log2 F0, +0.0 where unvoiced).
+    ValueError before anything is launched: fewer than 4 frames, n_bins < 1, not 0 < fmin < fmax."""
+    B, T = _f0_batch("f0_bins", f0)
+    if T < 4:
+        raise ValueError(f"f0_bins: {T} frames hold no latent column (4 frames each)")
+    if isinstance(n_bins, bool) or not isinstance(n_bins, (int, np.integer)) or n_bins < 1:
+        raise ValueError(f"f0_bins: n_bins must be a positive integer, got {n_bins!r}")
+    if not 0 < fmin < fmax < float("inf"):
+        raise ValueError(f"f0_bins: need 0 < fmin < fmax, got {fmin!r}, {fmax!r}")
+    return ops.f0_bins(f0.contiguous(), T // 4, int(n_bins), float(fmin), float(fmax), frames=frames, affine=affine, want_logf=detail)
+
+
+def logf0_sums(f0, frames=None):
+    """The moments of a clip's voiced log-F0: f0 (B, T) fp32 (+0.0: unvoiced), frames None or (B,) valid frame counts (a device
+    tensor, or host integers) -> (B, 3) fp64 on f0's device: (n_voiced, sum log2 f0, sum (log2 f0)^2) over the frames t <
+    frames[b] with f0 > 0, logarithms and sums in fp64.  Rows add: pooled over clips they give a speaker's statistics
+    (evaluate.speaker_f0_stats).  Nothing synchronises."""
+    B, T = _f0_batch("logf0_sums", f0)
+    voiced = f0 > 0
+    if frames is not None:
+        fr = frames if isinstance(frames, torch.Tensor) else torch.as_tensor(np.asarray(frames).astype(np.int64))
+        if tuple(fr.shape) != (B,):
+            raise ValueError(f"logf0_sums: frames must hold {B} counts, got {tuple(fr.shape)}")
+        voiced = voiced & (torch.arange(T, device=f0.device).unsqueeze(0) < fr.to(f0.device).unsqueeze(1))
+    l = torch.where(voiced, torch.log2(torch.where(voiced, f0, torch.ones_like(f0)).double()), torch.zeros((), dtype=torch.float64, device=f0.device))
+    return torch.stack((voiced.sum(1).double(), l.sum(1), (l * l).sum(1)), dim=1)
+
+
+F0_AFFINE_MIN_VAR = 1e-12             # octaves^2: below it a source's spread is the rounding of its moments' difference -- "zero"
+
+
+def f0_affine(sums_src, target_mean, target_std):
+    """The move of a source contour to a target speaker's log-F0 statistics, as f0_bins takes it: sums_src (B, 3) fp64 rows of
+    logf0_sums (each source clip's own moments), target_mean and target_std (B,) (tensors, or numbers for all clips) in log2 Hz
+    -> (B, 3) fp32 rows (mu_src, ratio, mu_tgt) on sums_src's device:
+        mu_src = sum / n,  var_src = sumsq / n - mu_src^2,  ratio = target_std / sqrt(var_src),  mu_tgt = target_mean
+    with ratio = 1 where the source has fewer than 2 voiced frames or zero spread (var_src <= F0_AFFINE_MIN_VAR), and mu_src =
+    mu_tgt where it has no voiced frame (nothing moves: such a clip has no voiced column either).  fp64 until the final rounding;
+    nothing synchronises."""
+    if not isinstance(sums_src, torch.Tensor) or sums_src.dim() != 2 or sums_src.shape[1] != 3 or sums_src.dtype != torch.float64:
+        raise ValueError("f0_affine: sums_src must be (B, 3) fp64 rows of logf0_sums")
+    B, dev = sums_src.shape[0], sums_src.device
+    mt, st = (torch.as_tensor(v, dtype=torch.float64, device=dev).expand(B) if not isinstance(v, torch.Tensor) or v.dim() == 0
+              else v.to(device=dev, dtype=torch.float64) for v in (target_mean, target_std))
+    if tuple(mt.shape) != (B,) or tuple(st.shape) != (B,):
+        raise ValueError(f"f0_affine: target_mean and target_std must be numbers or hold {B} values")
+    n, s1, s2 = sums_src.unbind(1)
+    some = n > 0
+    n1 = torch.where(some, n, torch.ones_like(n))
+    mu = torch.where(some, s1 / n1, mt)
+    var = torch.where(some, s2 / n1 - (s1 / n1) ** 2, torch.zeros_like(n))
+    spread = (n >= 2) & (var > F0_AFFINE_MIN_VAR)
+    ratio = torch.where(spread, st / torch.sqrt(torch.where(spread, var, torch.ones_like(var))), torch.ones_like(var))
+    return torch.stack((mu, ratio, mt), dim=1).to(torch.float32).contiguous()
+
+
 def inv_preemphasis(y: torch.Tensor, k=PREEMPHASIS) -> torch.Tensor:
     _chk(y, "y")
     B, L = y.shape

@@ -26,7 +26,10 @@ checkpoint layout, restated from the reference's src/test.py:73-106 and src/main
     distortion after dynamic time warping (audio.mel_cepstral_distortion) of converted against target, and of source against
     target for context; `test_conversion_f0(args, vqvae, pair_loader, device, epoch)` -- the same pairs as waveforms, judged by
     pitch: the converted mel inverted to a waveform, F0 by YIN (audio.f0), and along the same warping paths the F0 error in
-    cents, the voiced / unvoiced disagreement and the log-F0 correlation (audio.f0_figures), pooled over all clips.
+    cents, the voiced / unvoiced disagreement and the log-F0 correlation (audio.f0_figures), pooled over all clips.  A model with an
+    F0 table (VQVAE(n_f0_bins=)) takes the pitch as an input: `convert_voice(..., f0_bins=)`, `test_conversion_f0(..., f0_stats=)`
+    feed the source's contour moved to the target speaker's log-F0 statistics; `speaker_f0_stats(wav_loader, n_speakers, device)`
+    pools those statistics per speaker.
   * `test_reconstruction_audio(args, vqvae, wav_loader, device, epoch)` -- the reconstruction judged as audio against the
     recording: wav -> mel -> model -> waveform, and the mel inverted without the model beside it, each scored by STOI and ESTOI
     (audio.stoi) against the wav it came from.
@@ -275,13 +278,21 @@ def label_information(args, vqvae, prior, test_loader, device, null_label):
     return {"nats_conditional": cond, "nats_unconditional": uncond, "gain": uncond - cond}
 
 
-def convert_voice(vqvae, mel: torch.Tensor, g_target: torch.Tensor):
+def convert_voice(vqvae, mel: torch.Tensor, g_target: torch.Tensor, f0_bins: torch.Tensor | None = None):
     """Re-voice clips as other speakers: mel (B, 1, 80, T) (or (B, 80, T)) on the GPU, T a multiple of 4, is encoded to its
     codes and decoded under the speaker ids g_target (B,) int64 -> (codes (B, 20, T // 4) int64, mels (B, 1, 80, T)).  The
     VQ-VAE runs in eval mode (its mode is restored) and is not changed.  ValueError: a model without a speaker embedding, or a
-    g_target that is not (B,) int64 within [0, n_speakers) -- checked on the host before anything is launched."""
+    g_target that is not (B,) int64 within [0, n_speakers) -- checked on the host before anything is launched.
+    f0_bins (B, T // 4) int64 in [0, n_f0_bins]: the pitch contour the decoder of an F0-conditioned model (VQVAE(n_f0_bins=)) is
+    to follow -- for conversion the source's contour moved to the target speaker's statistics (audio.f0_affine, audio.f0_bins).
+    Such a model requires it, a model without an F0 table refuses it: ValueError either way, as for a wrong shape, dtype or range."""
     if getattr(vqvae, "n_speakers", None) is None:
         raise ValueError("convert_voice: the model has no speaker embedding (VQVAE(..., n_speakers=N))")
+    has_f0 = getattr(vqvae, "n_f0_bins", None) is not None
+    if has_f0 and f0_bins is None:
+        raise ValueError("convert_voice: the model's decoder is F0-conditioned (n_f0_bins): give f0_bins (audio.f0_bins)")
+    if not has_f0 and f0_bins is not None:
+        raise ValueError("convert_voice: f0_bins given to a model without an F0 table (VQVAE(..., n_f0_bins=N))")
     if mel.dim() == 3:
         mel = mel.unsqueeze(1)
     if mel.dim() != 4 or mel.shape[1] != 1:
@@ -291,12 +302,15 @@ def convert_voice(vqvae, mel: torch.Tensor, g_target: torch.Tensor):
         raise ValueError(f"convert_voice: g_target must be an int64 tensor of shape ({B},)")
     if B and (int(g_target.min()) < 0 or int(g_target.max()) >= vqvae.n_speakers):
         raise ValueError(f"convert_voice: g_target must lie in [0, {vqvae.n_speakers}), got {int(g_target.min())} .. {int(g_target.max())}")
+    if f0_bins is not None:
+        vqvae.check_f0_bins(f0_bins, B, mel.shape[3] // 4, "convert_voice")
     was_training = vqvae.training
     vqvae.eval()
     try:
         with torch.no_grad():
             codes = vqvae.encode(mel).contiguous()
-            mels = vqvae.decode(codes, g_target.to(mel.device))
+            g_dev = g_target.to(mel.device)
+            mels = vqvae.decode(codes, g_dev) if f0_bins is None else vqvae.decode(codes, g_dev, f0_bins.to(mel.device))
     finally:
         vqvae.train(was_training)
     return codes, mels
@@ -334,7 +348,49 @@ def test_conversion(args, vqvae, pair_loader, device, epoch):
     return mcd_c, mcd_s
 
 
-def test_conversion_f0(args, vqvae, pair_loader, device, epoch, iters=None, angles0=None, *, tracker="yin", tracker_options=None, momentum=0.0, init="random"):
+def _f0_tracker(fn, tracker, tracker_options):
+    """audio.f0 or audio.f0_track with its costs, as test_conversion_f0, speaker_f0_stats and train.train_conditioned name them."""
+    from . import audio
+    if tracker not in ("yin", "viterbi"):
+        raise ValueError(f"{fn}: tracker must be 'yin' or 'viterbi', got {tracker!r}")
+    options = dict(tracker_options or {})
+    if set(options) - (set(audio.F0_TRACK_COSTS) if tracker == "viterbi" else set()):
+        raise ValueError(f"{fn}: tracker_options {sorted(options)} do not go with tracker {tracker!r} "
+                         f"(viterbi takes {sorted(audio.F0_TRACK_COSTS)})")
+    return audio.f0 if tracker == "yin" else functools.partial(audio.f0_track, **options)
+
+
+def speaker_f0_stats(wav_loader, n_speakers, device, tracker="yin", tracker_options=None):
+    """Every speaker's log-F0 statistics, the target side of pitch-transforming conversion: `wav_loader` yields (wav (B, L) float32
+    zero-padded at 22 050 Hz, lengths (B,) host integers, g (B,) int64 speaker ids).  Per batch the F0 track (tracker,
+    tracker_options: test_conversion_f0's) and audio.logf0_sums of its 1 + length // 256 frames, added to the speaker's row on the
+    device.  Returns (stats (n_speakers, 2) fp64: mean and standard deviation (of the population: / n) of log2 F0 over all voiced
+    frames of the speaker, NaN for a speaker without one; counts (n_speakers,) int64 voiced frames) on the host, read back once."""
+    from . import audio
+    track = _f0_tracker("speaker_f0_stats", tracker, tracker_options)
+    if isinstance(n_speakers, bool) or not isinstance(n_speakers, numbers.Integral) or n_speakers < 1:
+        raise ValueError(f"speaker_f0_stats: n_speakers must be a positive integer, got {n_speakers!r}")
+    hop = 256
+    total = torch.zeros(n_speakers, 3, dtype=torch.float64, device=device)
+    seen = False
+    for wav, lengths, g in wav_loader:
+        ls = np.asarray(lengths.cpu() if torch.is_tensor(lengths) else lengths).astype(np.int64)
+        g = torch.as_tensor(g, dtype=torch.int64)
+        if tuple(g.shape) != (len(wav),) or (len(wav) and (int(g.min()) < 0 or int(g.max()) >= n_speakers)):
+            raise ValueError(f"speaker_f0_stats: g must hold {len(wav)} speaker ids in [0, {n_speakers})")
+        f0, _ = track(wav.to(device).contiguous(), hop_size=hop, lengths=ls)
+        total.index_add_(0, g.to(device), audio.logf0_sums(f0, 1 + ls // hop))
+        seen = True
+    if not seen:
+        raise ValueError("speaker_f0_stats: empty loader")
+    n, s1, s2 = total.cpu().unbind(1)                                       # the one read-back
+    mean = s1 / n                                                           # (0 / 0: NaN for a speaker without a voiced frame)
+    std = torch.sqrt(torch.clamp(s2 / n - mean * mean, min=0.0))
+    return torch.stack((mean, std), dim=1), n.to(torch.int64)
+
+
+def test_conversion_f0(args, vqvae, pair_loader, device, epoch, iters=None, angles0=None, *, tracker="yin", tracker_options=None, momentum=0.0, init="random",
+                       f0_stats=None):
     """The pitch figures of a speaker-conditioned VQ-VAE over parallel utterances, from waveforms: `pair_loader` yields
     (wav_src (B, Ls), len_src (B,), wav_tgt (B, Lt), len_tgt (B,), g_tgt (B,) int64) -- the same sentences by a source and a target
     speaker as zero-padded float32 waveforms at 22 050 Hz with their lengths in samples (host integers), and the target speakers'
@@ -357,19 +413,26 @@ def test_conversion_f0(args, vqvae, pair_loader, device, epoch, iters=None, angl
     frame's candidates, which repairs the octave-up picks and dropouts that a per-frame rule makes on a Griffin-Lim waveform and
     that otherwise dominate the figures); tracker_options: audio.f0_track's costs (octave_cost, jump_cost, vuv_cost,
     unvoiced_cost) for "viterbi".  Another tracker, options that do not go with it, a momentum outside [0, 1], or an init that is
-    neither or that comes with angles0 is a ValueError before anything is launched."""
+    neither or that comes with angles0 is a ValueError before anything is launched.
+    A model with an F0 table (VQVAE(n_f0_bins=)): the source's F0 is tracked before the conversion and its first Tc frames become
+    the bins the decoder follows (audio.f0_bins over the model's n_f0_bins and f0_range).  f0_stats (n_speakers, 2): every
+    speaker's mean and standard deviation of log2 F0 (speaker_f0_stats) -- the contour is first moved to the target speaker's
+    statistics, each source clip's own moments (audio.logf0_sums) being the source side (audio.f0_affine); f0_stats=None keeps the
+    source's contour (the identity move).  ValueError before anything is launched: f0_stats for a model without the table or of
+    another shape; before anything of the batch: a target speaker of the batch whose statistics are not finite."""
     from . import audio
     momentum = audio._momentum("test_conversion_f0", momentum)
     audio._init("test_conversion_f0", init, angles0)
-    if tracker not in ("yin", "viterbi"):
-        raise ValueError(f"test_conversion_f0: tracker must be 'yin' or 'viterbi', got {tracker!r}")
-    options = dict(tracker_options or {})
-    if set(options) - (set(audio.F0_TRACK_COSTS) if tracker == "viterbi" else set()):
-        raise ValueError(f"test_conversion_f0: tracker_options {sorted(options)} do not go with tracker {tracker!r} "
-                         f"(viterbi takes {sorted(audio.F0_TRACK_COSTS)})")
-    track = audio.f0 if tracker == "yin" else functools.partial(audio.f0_track, **options)
+    track = _f0_tracker("test_conversion_f0", tracker, tracker_options)
     if getattr(vqvae, "n_speakers", None) is None:
         raise ValueError("test_conversion_f0: the model has no speaker embedding (VQVAE(..., n_speakers=N))")
+    has_f0 = getattr(vqvae, "n_f0_bins", None) is not None
+    if f0_stats is not None:
+        if not has_f0:
+            raise ValueError("test_conversion_f0: f0_stats given to a model without an F0 table (VQVAE(..., n_f0_bins=N))")
+        f0_stats = np.asarray(f0_stats.cpu() if torch.is_tensor(f0_stats) else f0_stats, dtype=np.float64)
+        if f0_stats.shape != (vqvae.n_speakers, 2):
+            raise ValueError(f"test_conversion_f0: f0_stats must be ({vqvae.n_speakers}, 2): mean and std of log2 F0 per speaker")
     hop, fft = 256, 1024
     iters = audio.GRIFFIN_LIM_ITERS if iters is None else int(iters)
     total = torch.zeros(2, 12, dtype=torch.float64, device=device)          # per set: the ten sums, the sums of the clips' MCD and convergence
@@ -385,16 +448,32 @@ def test_conversion_f0(args, vqvae, pair_loader, device, epoch, iters=None, angl
         fc = np.minimum(fs, Tc) // 4 * 4
         if Tc < 4 or fc.min() < 4:
             raise ValueError("test_conversion_f0: every source clip needs at least 4 valid frames (one latent column)")
+        if f0_stats is not None:
+            gt = np.asarray(g_tgt.cpu() if torch.is_tensor(g_tgt) else g_tgt).astype(np.int64)
+            if gt.shape != (len(wav_src),) or gt.min() < 0 or gt.max() >= vqvae.n_speakers:
+                raise ValueError(f"test_conversion_f0: g_tgt must hold {len(wav_src)} speaker ids in [0, {vqvae.n_speakers})")
+            target = f0_stats[gt]                                           # (B, 2)
+            if not np.isfinite(target).all():
+                raise ValueError(f"test_conversion_f0: f0_stats of the target speakers {sorted(set(gt[~np.isfinite(target).all(1)].tolist()))} "
+                                 "are not finite (a speaker without a voiced frame in speaker_f0_stats)")
         wav_src, wav_tgt = wav_src.to(device).contiguous(), wav_tgt.to(device).contiguous()
         mel_s = audio.melspectrogram(wav_src, fft_size=fft, hop_size=hop, lengths=ls)
         mel_t = audio.melspectrogram(wav_tgt, fft_size=fft, hop_size=hop, lengths=lt)
-        _, converted = convert_voice(vqvae, mel_s[:, :, :Tc].contiguous(), g_tgt)
+        f0_s, _ = track(wav_src, hop_size=hop, lengths=ls)
+        bins = None
+        if has_f0:      # the source's contour over the frames that are converted, moved to the target speaker's statistics
+            f0_c_in = f0_s[:, :Tc].contiguous()
+            affine = None
+            if f0_stats is not None:
+                tgt = torch.from_numpy(target).to(device)
+                affine = audio.f0_affine(audio.logf0_sums(f0_c_in, fc), tgt[:, 0], tgt[:, 1])
+            bins = audio.f0_bins(f0_c_in, frames=fc, n_bins=vqvae.n_f0_bins, fmin=vqvae.f0_range[0], fmax=vqvae.f0_range[1], affine=affine)
+        _, converted = convert_voice(vqvae, mel_s[:, :, :Tc].contiguous(), g_tgt, *(() if bins is None else (bins,)))
         a0 = angles0[k] if isinstance(angles0, (list, tuple)) else angles0
         S_c, y_c, wav_c = audio._invert_mel(converted.squeeze(1), 22050, fft, hop, 80, iters, a0, momentum, init)      # inv_mel_spectrogram's steps
         total[0, 11] += audio.spectral_convergence(y_c, S_c, fft, hop).sum()
         f0_c, _ = track(wav_c, hop_size=hop, lengths=hop * (fc - 1))   # hop (Tc - 1) samples: Tc frames, fc of them the clip's
         f0_t, _ = track(wav_tgt, hop_size=hop, lengths=lt)
-        f0_s, _ = track(wav_src, hop_size=hop, lengths=ls)
         cep_t = audio.mel_cepstra(mel_t, ft)
         for row, (mel, frames, f0_x) in enumerate(((converted, fc, f0_c), (mel_s, fs, f0_s))):
             cost, steps, path = ops.dtw(audio.mel_cepstra(mel, frames), cep_t, frames, ft, want_path=True)

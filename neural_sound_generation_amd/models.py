@@ -24,7 +24,7 @@ import torch
 from torch import nn
 
 from . import engine, functional as Fn, ops, vae_engine
-from .vector_quantization import vq, vq_st, codebook_lookup, add_per_clip
+from .vector_quantization import vq, vq_st, codebook_lookup, add_per_clip, add_cond
 
 
 def to_scalar(arr):
@@ -124,12 +124,16 @@ class _Decoder(nn.Sequential):
 
 
 class VQVAE(nn.Module):
-    def __init__(self, input_dim, dim, z_dim=512, ema_decay=None, n_speakers=None, compute_dtype=torch.float32):
+    def __init__(self, input_dim, dim, z_dim=512, ema_decay=None, n_speakers=None, compute_dtype=torch.float32, n_f0_bins=None,
+                 f0_range=(65.0, 500.0)):
         """Reference signature VQVAE(input_dim, dim, z_dim=512) (models.py:162).  Opt-in extensions,
-        neither present in the reference: ema_decay (EMA codebook), n_speakers
+        none present in the reference: ema_decay (EMA codebook), n_speakers
         (speaker embedding added to the decoder input, BASELINE configs[2]) and compute_dtype:
         torch.float32 (default; the parity mode) or torch.bfloat16 (activations and conv operands in
-        bf16, fp32 accumulation / BatchNorm statistics / quantiser / parameters / optimiser)."""
+        bf16, fp32 accumulation / BatchNorm statistics / quantiser / parameters / optimiser).
+        n_f0_bins = N: an F0 table f0_embedding of N + 1 rows, one of which is added to every latent column of the decoder
+        input, chosen by the column's quantised log-F0 (audio.f0_bins over f0_range = (fmin, fmax) Hz; row 0: unvoiced, learned
+        like the others), so the codes need not carry pitch.  Without it nothing changes: keys, RNG draws, outputs."""
         super().__init__()
         if compute_dtype not in (torch.float32, torch.bfloat16):
             raise ValueError("compute_dtype must be torch.float32 or torch.bfloat16")
@@ -169,27 +173,53 @@ class VQVAE(nn.Module):
         if n_speakers is not None:
             self.speaker_embedding = nn.Embedding(n_speakers, dim)
             self.speaker_embedding.weight.data.normal_(0.0, 0.1)
+        self.n_f0_bins = n_f0_bins
+        if n_f0_bins is not None:
+            if isinstance(n_f0_bins, bool) or not isinstance(n_f0_bins, int) or n_f0_bins < 1:
+                raise ValueError(f"n_f0_bins must be a positive integer, got {n_f0_bins!r}")
+            fmin, fmax = (float(v) for v in f0_range)
+            if not 0 < fmin < fmax < float("inf"):
+                raise ValueError(f"f0_range must be 0 < fmin < fmax, got {f0_range!r}")
+            self.f0_range = (fmin, fmax)
+            self.f0_embedding = nn.Embedding(n_f0_bins + 1, dim)
+            self.f0_embedding.weight.data.normal_(0.0, 0.1)
         self.apply(weights_init)
 
-    def _condition(self, z_q_x, g):
-        """Add the speaker embedding of each clip to every latent pixel of that clip (extension)."""
-        if self.n_speakers is None or g is None:
-            return z_q_x
-        rows = codebook_lookup(self.speaker_embedding.weight, g.view(-1).to(torch.int64))
-        return Fn.to_nchw_view(add_per_clip(Fn.to_nhwc(z_q_x), rows))
+    def check_f0_bins(self, f0_bins, B, W, who="VQVAE"):
+        """ValueError unless the model has an F0 table and f0_bins is a (B, W) int64 tensor within [0, n_f0_bins] -- checked on
+        the host (one read-back), as evaluate.convert_voice checks g_target."""
+        if getattr(self, "n_f0_bins", None) is None:
+            raise ValueError(f"{who}: f0_bins given to a model without an F0 table (VQVAE(..., n_f0_bins=N))")
+        if not isinstance(f0_bins, torch.Tensor) or tuple(f0_bins.shape) != (B, W) or f0_bins.dtype != torch.int64:
+            raise ValueError(f"{who}: f0_bins must be an int64 tensor of shape ({B}, {W}): one bin per clip and latent column")
+        if f0_bins.numel():
+            lo, hi = (int(v) for v in torch.stack((f0_bins.min(), f0_bins.max())).tolist())
+            if lo < 0 or hi > self.n_f0_bins:
+                raise ValueError(f"{who}: f0_bins must lie in [0, {self.n_f0_bins}], got {lo} .. {hi}")
+
+    def _condition(self, z_q_x, g, f0_bins=None):
+        """Add the speaker embedding of each clip to every latent pixel of that clip, and the F0 embedding of each latent column
+        to every pixel of that column (extensions)."""
+        rows = None
+        if getattr(self, "n_speakers", None) is not None and g is not None:
+            rows = codebook_lookup(self.speaker_embedding.weight, g.view(-1).to(torch.int64))
+        if f0_bins is None:
+            return z_q_x if rows is None else Fn.to_nchw_view(add_per_clip(Fn.to_nhwc(z_q_x), rows))
+        self.check_f0_bins(f0_bins, z_q_x.shape[0], z_q_x.shape[3])
+        return Fn.to_nchw_view(add_cond(Fn.to_nhwc(z_q_x), rows, self.f0_embedding.weight, f0_bins.to(z_q_x.device)))
 
     def encode(self, x):
         z_e_x = self.encoder(x)
         return self.codebook(z_e_x)
 
-    def decode(self, latents, g=None):
+    def decode(self, latents, g=None, f0_bins=None):
         z_q_x = Fn.to_nchw_view(ops.gather_rows(self.codebook.embedding.weight.detach().contiguous(), latents.contiguous()))
-        return self.decoder(self._condition(z_q_x, g))
+        return self.decoder(self._condition(z_q_x, g, f0_bins))
 
-    def forward(self, x, g=None):
+    def forward(self, x, g=None, f0_bins=None):
         z_e_x = self.encoder(x)
         z_q_x_st, z_q_x = self.codebook.straight_through(z_e_x)
-        x_tilde = self.decoder(self._condition(z_q_x_st, g))
+        x_tilde = self.decoder(self._condition(z_q_x_st, g, f0_bins))
         return x_tilde, z_e_x, z_q_x
 
 

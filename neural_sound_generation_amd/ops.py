@@ -1280,6 +1280,88 @@ def clip_colsum(x, B):
     return out
 
 
+def add_cond(x, table, bins, idx=None, clip_rows=None, relu=False, out=None, out_dtype=torch.float32, grid=None):
+    """The F0- (and speaker-) conditioned decoder input in one pass (include/nsg.h: nsg_add_cond):
+        y[b, h, w] = act((src[b, h, w] + clip_rows[b]) + table[bins[b, w]])
+    x: the fp32 NHWC rows (B, H, W, C) themselves, or -- with idx (B, H, W) int64 -- a (K, C) fp32 table they are gathered from
+    (src = x[idx]); table (n_rows, C) fp32; bins (B, W) int64; clip_rows (B, C) fp32 or None; act = ReLU with relu=True.
+    -> y (B, H, W, C) of out_dtype.  Out-of-range bins / idx values are clamped by the kernel, never read out of a table.
+    grid: (B, H, W) where x's own shape does not say it (rows mode with x given as (N, C))."""
+    _chk(x, "add_cond: x"); _chk(table, "add_cond: table"); _chk(bins, "add_cond: bins", torch.int64)
+    if table.dim() != 2 or bins.dim() != 2 or x.dim() < 2 or x.shape[-1] != table.shape[1]:
+        raise _lib.NsgError(f"add_cond: x {tuple(x.shape)} / table {tuple(table.shape)} / bins {tuple(bins.shape)} are not (.., C) / (n_rows, C) / (B, W)")
+    C = table.shape[1]
+    B, Wd = bins.shape
+    if idx is not None:
+        _chk(idx, "add_cond: idx", torch.int64)
+        if x.dim() != 2:
+            raise _lib.NsgError(f"add_cond: with idx, x {tuple(x.shape)} must be a (K, C) table")
+        shape = tuple(idx.shape) if grid is None else tuple(grid)
+        K = x.shape[0]
+    else:
+        shape = tuple(x.shape[:-1]) if grid is None else tuple(grid)
+        K = 0
+    if len(shape) != 3 or shape[0] != B or shape[2] != Wd or (idx.numel() if idx is not None else x.numel() // C) != B * shape[1] * Wd:
+        raise _lib.NsgError(f"add_cond: the latent grid {shape} does not go with bins {tuple(bins.shape)} (B, H, W) / (B, W)")
+    H = shape[1]
+    if clip_rows is not None and tuple(_chk(clip_rows, "add_cond: clip_rows").shape) != (B, C):
+        raise _lib.NsgError(f"add_cond: clip_rows {tuple(clip_rows.shape)} is not ({B}, {C})")
+    if len({t.device for t in (x, table, bins, idx, clip_rows) if t is not None}) != 1:
+        raise _lib.NsgError("add_cond: the tensors are not on one device")
+    if out is None:
+        out = torch.empty(B, H, Wd, C, dtype=out_dtype, device=x.device)
+    elif _chk(out, "add_cond: out", None).numel() != B * H * Wd * C or out.device != x.device:
+        raise _lib.NsgError(f"add_cond: out {tuple(out.shape)} does not hold {B} x {H} x {Wd} x {C}")
+    nrow = B * H * Wd
+    # (the tables stay in cache: the rows read -- or, gathering, the indices -- and the rows written are what moves)
+    _lib.tag("add_cond (gather)" if idx is not None else "add_cond", 0, float(nrow * C * _es(out) + (8 * nrow if idx is not None else 4 * nrow * C)))
+    _lib.call("nsg_add_cond", _p(x), _p(idx), _p(clip_rows), _p(table), _p(bins), _p(out), B, H, Wd, C, K, table.shape[0], 1 if relu else 0,
+              nsg_dtype(out.dtype), _stream())
+    return out
+
+
+def column_sum(x, out=None):
+    """x NHWC (B, H, W, C) fp32 or bf16 -> (B, W, C) fp32: the sum over h, in ascending h in fp32 (include/nsg.h: nsg_column_sum);
+    two calls give the same bits."""
+    _chk(x, "column_sum: x", None)
+    if x.dim() != 4:
+        raise _lib.NsgError(f"column_sum: x {tuple(x.shape)} is not (B, H, W, C)")
+    B, H, Wd, C = x.shape
+    if out is None:
+        out = torch.empty(B, Wd, C, dtype=torch.float32, device=x.device)
+    elif _chk(out, "column_sum: out").numel() != B * Wd * C or out.device != x.device:
+        raise _lib.NsgError(f"column_sum: out {tuple(out.shape)} does not hold {B} x {Wd} x {C}")
+    _lib.tag("column_sum", 0, x.numel() * _es(x) + 4.0 * B * Wd * C)
+    _lib.call("nsg_column_sum", _p(x), nsg_dtype(x.dtype), B, H, Wd, C, _p(out), _stream())
+    return out
+
+
+def f0_bins(f0, W, n_bins, fmin, fmax, frames=None, affine=None, want_logf=False, out=None):
+    """An F0 track at the mel frame rate -> one bin per latent column (include/nsg.h: nsg_f0_bins).  f0 (B, T) fp32 Hz (+0.0:
+    unvoiced), T >= 4 W; frames: None (all T), or (B,) frame counts in [0, T] (host: checked here and uploaded; int32 on the
+    device: the caller's); affine (B, 3) fp32 rows of (mu_src, ratio, mu_tgt) or None -> bins (B, W) int64: 0 for an unvoiced
+    column, 1 .. n_bins otherwise; with want_logf also logf (B, W) fp32, the column's (moved) mean log2 F0, +0.0 where unvoiced.
+    out: bins, or (bins, logf), to write instead of new tensors."""
+    _chk(f0, "f0_bins: f0")
+    if f0.dim() != 2 or f0.shape[0] < 1 or f0.shape[1] < 1:
+        raise _lib.NsgError(f"f0_bins: f0 {tuple(f0.shape)} is not (B, T) with B, T >= 1")
+    B, T = f0.shape
+    W = int(W)
+    fr = None if frames is None else _lengths_on(frames, "f0_bins: frames", B, 0, T, f0.device)
+    if affine is not None and (tuple(_chk(affine, "f0_bins: affine").shape) != (B, 3) or affine.device != f0.device):
+        raise _lib.NsgError(f"f0_bins: affine {tuple(affine.shape)} is not ({B}, 3) on f0's device")
+    if out is None:
+        bins = torch.empty(B, max(W, 0), dtype=torch.int64, device=f0.device)
+        logf = torch.empty(B, max(W, 0), dtype=torch.float32, device=f0.device) if want_logf else None
+    else:
+        bins, logf = out if want_logf else (out, None)
+        for t, name, dtype in ((bins, "bins", torch.int64), (logf, "logf", torch.float32)):
+            if t is not None and (_chk(t, f"f0_bins: out {name}", dtype).numel() != B * W or t.device != f0.device):
+                raise _lib.NsgError(f"f0_bins: out {name} {tuple(t.shape)} does not hold {B} x {W}")
+    _lib.call("nsg_f0_bins", _p(f0), _p(fr), _p(affine), _p(bins), _p(logf), B, T, W, int(n_bins), float(fmin), float(fmax), _stream())
+    return (bins, logf) if want_logf else bins
+
+
 def mse_padded(a, c, rows, wa, wc, grad_scale=1.0, want_grad=True):
     """mean((pad(a) - c)^2) with a zero-padded from width wa to wc (train.py:118-129)."""
     loss = torch.empty(1, dtype=torch.float32, device=a.device)

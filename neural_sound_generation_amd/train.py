@@ -16,6 +16,7 @@ from __future__ import annotations
 
 import os
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -90,13 +91,16 @@ class FusedTrainStep:
         self.g_code = None if self.ema else self.opt.grads_for([self.codebook])[0]
         self.spk = getattr(model, "speaker_embedding", None)
         self.g_spk = self.opt.grads_for([self.spk.weight])[0] if self.spk is not None else None
-        # Data parallel: the communication buffer is [encoder | codebook | decoder | speaker table | EMA statistics]; everything
+        # the F0 table of an F0-conditioned decoder (VQVAE(n_f0_bins=)): registered after the speaker table, so its slot lies behind it
+        self.f0 = getattr(model, "f0_embedding", None)
+        self.g_f0 = self.opt.grads_for([self.f0.weight])[0] if self.f0 is not None else None
+        # Data parallel: the communication buffer is [encoder | codebook | decoder | speaker table | F0 table | EMA statistics]; everything
         # from the decoder's first gradient on is final when the decoder's backward has been enqueued, BEFORE the encoder's
         # backward starts, so that part is all-reduced on the collective's own stream beside the encoder backward and only the
         # front part waits for the end of the step (two collectives, the first one hidden).
         # (An optimiser with another parameter order: comm_split is 0, one collective at the end.)
         self._comm_split = comm_split(self.opt, front=g_enc + ([] if self.g_code is None else [self.g_code]),
-                                      back=g_dec + ([] if self.g_spk is None else [self.g_spk]))
+                                      back=g_dec + [t for t in (self.g_spk, self.g_f0) if t is not None])
         self._reduce = None               # nsg_dist.TwoPartAllReduce over the communication buffer (made on first use: reserve_tail may still grow it)
         self._stepping = False            # collectives only from step(): forward_backward() alone never communicates
         # test hook: (N,) int64 code indices to use INSTEAD of the search's (the search still runs and is ignored).  Lets a test
@@ -114,19 +118,26 @@ class FusedTrainStep:
         self._kept_rows = None
 
     @torch.no_grad()
-    def forward_backward(self, c: torch.Tensor, g: torch.Tensor | None = None):
+    def forward_backward(self, c: torch.Tensor, g: torch.Tensor | None = None, f0_bins: torch.Tensor | None = None):
         """c: (B,1,80,T) float32 on the GPU; g: optional (B,) int64 speaker ids (speaker-conditioned
-        decoder extension).  Fills the flat gradient bucket; returns the three loss tensors (device
-        scalars; nothing here synchronises with the host)."""
+        decoder extension); f0_bins: optional (B, T // 4) int64 F0 bins in [0, n_f0_bins] on the GPU, one per latent column
+        (F0-conditioned decoder extension, audio.f0_bins; the kernel clamps them, nothing here reads them back).  Fills the flat
+        gradient bucket; returns the three loss tensors (device scalars; nothing here synchronises with the host)."""
         model = self.model
         if not model.training:
             raise RuntimeError("FusedTrainStep needs model.train()")
         x = Fn.to_nhwc(c)
         B, H, T, _ = x.shape
+        if f0_bins is not None:
+            if self.f0 is None:
+                raise ValueError("FusedTrainStep: f0_bins given to a model without an F0 table (VQVAE(..., n_f0_bins=N))")
+            if not isinstance(f0_bins, torch.Tensor) or tuple(f0_bins.shape) != (B, T // 4) or f0_bins.dtype != torch.int64 or f0_bins.device != x.device:
+                raise ValueError(f"FusedTrainStep: f0_bins must be an int64 tensor of shape ({B}, {T // 4}) on the batch's device")
+            f0_bins = f0_bins.contiguous()
         with engine.deferred_batch_counters():
-            return self._forward_backward(x, g, B, H, T)
+            return self._forward_backward(x, g, B, H, T, f0_bins)
 
-    def _forward_backward(self, x, g, B, H, T):
+    def _forward_backward(self, x, g, B, H, T, bins=None):
         enc_packs, dec_packs = engine.pack_all(self.encP, self.decP, B, H, T, self.dtype)
         K, D = self.codebook.shape
         search = getattr(self.model.codebook, "search_impl", "mfma")
@@ -157,9 +168,17 @@ class FusedTrainStep:
                 raise ValueError("force_indices must hold one code index per latent row")
             zq = ops.gather_rows(self.codebook.detach(), idx).view_as(ze)
             zdec = zq
-            if lean:
+            if lean and bins is not None:
+                zdec, zq = ops.add_cond(zq, self.f0.weight.detach(), bins, clip_rows=spk_rows, relu=True, out_dtype=self.dtype), None
+            elif lean:
                 zdec = ops.add_per_clip(zq, spk_rows) if spk_rows is not None else zq
                 zdec, zq = ops.convert(zdec, self.dtype, relu=True), None
+        elif lean and bins is not None:
+            # the search writes the indices alone; the decoder's input is gathered through them with both conditioning rows added
+            idx, _, _ = ops.vq_forward(ze_rows, self.codebook.detach(), want_codes=False, impl=search)
+            zq = None
+            zdec = ops.add_cond(self.codebook.detach(), self.f0.weight.detach(), bins, idx=idx, clip_rows=spk_rows, relu=True,
+                                out_dtype=self.dtype, grid=tuple(ze_shape[:3]))
         elif lean:
             idx, _, _, zdec = ops.vq_forward(ze_rows, self.codebook.detach(), want_codes=False, impl=search, codes_bf16="relu",
                                              clip_rows=spk_rows)
@@ -169,7 +188,9 @@ class FusedTrainStep:
             idx, zq, _ = ops.vq_forward(ze.view(-1, D), self.codebook.detach(), want_codes=True, impl=search)
             zq = zq.view_as(ze)
             zdec = zq
-        if spk_rows is not None and not lean:
+        if bins is not None and not lean:
+            zdec = ops.add_cond(zq, self.f0.weight.detach(), bins, clip_rows=spk_rows, out_dtype=self.dtype)
+        elif spk_rows is not None and not lean:
             zdec = ops.add_per_clip(zq, spk_rows, out_dtype=self.dtype)
         # loss_recons = mse(zero-pad(x_tilde), c) and d/dx_tilde             (train.py:118-129)
         xt, ds = engine.decoder_forward(zdec, self.decP, True, dtype=self.dtype, packs=dec_packs, zq_is_relu=lean, mse_target=x,
@@ -180,9 +201,17 @@ class FusedTrainStep:
         else:
             loss_recons, dxt = ops.mse_padded(xt, x, B * H, xt.shape[2], T)
             dzq, _ = engine.decoder_backward(dxt, ds, self.decP, need_dz=True, gout=self.g_dec)
+        colsum = None
+        if self.f0 is not None:
+            if bins is not None:    # d loss / d F0 rows = per-column sums of dzq over the latent rows, scattered to the bins
+                colsum = ops.column_sum(dzq.view(ze_shape))                 # (B, W, D) fp32: dzq is read once for both tables
+                gf = ops.index_add_rows(bins.view(-1), colsum.view(-1, D), self.f0.weight.shape[0])
+                ops.add(gf, None, out=self.g_f0)
+            else:
+                self.g_f0.zero_()
         if self.spk is not None:
             if g is not None:   # d loss / d speaker rows = per-clip pixel sums of dzq, scattered to the speakers
-                gs = ops.index_add_rows(g, ops.clip_colsum(dzq, B), self.spk.weight.shape[0])
+                gs = ops.index_add_rows(g, ops.clip_colsum(dzq if colsum is None else colsum, B), self.spk.weight.shape[0])
                 ops.add(gs, None, out=self.g_spk)
             else:
                 self.g_spk.zero_()
@@ -237,8 +266,10 @@ class FusedTrainStep:
     # torch.cuda.CUDAGraph: every ctypes launch goes to torch's current stream, which is the capturing stream).  The
     # optimiser step stays outside (its bias-correction scalars change every step), as do the collectives.
     @torch.no_grad()
-    def capture(self, c: torch.Tensor, g: torch.Tensor | None = None, warmup: int = 2):
-        """Capture forward_backward for inputs of c's shape.  The warm-up steps are REAL training steps."""
+    def capture(self, c: torch.Tensor, g: torch.Tensor | None = None, warmup: int = 2, f0_bins: torch.Tensor | None = None):
+        """Capture forward_backward for inputs of c's shape.  The warm-up steps are REAL training steps.  g and f0_bins are kept
+        in static buffers every replay refills; a graph captured with (without) either is replayed only for a step that gives
+        (omits) it too -- any other step runs eagerly."""
         # The captured launches carry the scratch buffer's ADDRESS, and ops.WS keeps one buffer per (device, stream).  So the
         # warm-up steps (first-use work: LDS attributes, workspace growth -- and they are REAL training steps) run on the very
         # stream the capture then uses: the capture finds the warmed-up buffer under its own key and must not outgrow it.  A
@@ -248,9 +279,10 @@ class FusedTrainStep:
         self._graph_stream.wait_stream(torch.cuda.current_stream(c.device))
         with torch.cuda.stream(self._graph_stream):
             for _ in range(warmup):
-                self.step(c, g)
+                self.step(c, g, f0_bins)
             self._static_c = c.clone()
             self._static_g = g.clone() if g is not None else None
+            self._static_bins = f0_bins.clone() if f0_bins is not None else None
             ws = ops.WS.current(c.device)              # (this stream's buffer)
         torch.cuda.current_stream(c.device).wait_stream(self._graph_stream)
         torch.cuda.synchronize()
@@ -258,7 +290,7 @@ class FusedTrainStep:
         self._keep_rows = self.reviver is not None
         try:
             with torch.cuda.graph(self._graph, stream=self._graph_stream):
-                self._graph_losses = self.forward_backward(self._static_c, self._static_g)
+                self._graph_losses = self.forward_backward(self._static_c, self._static_g, self._static_bins)
                 ws_after = ops.WS.current(c.device)
         finally:
             self._keep_rows = False
@@ -269,23 +301,27 @@ class FusedTrainStep:
         self._graph_ws = ws
         return self
 
-    def _replay(self, c, g):
+    def _replay(self, c, g, f0_bins=None):
         self._static_c.copy_(c)
         if g is not None:
             self._static_g.copy_(g)
+        if f0_bins is not None:
+            self._static_bins.copy_(f0_bins)
         self._graph.replay()
         return self._graph_losses
 
     @torch.no_grad()
-    def step(self, c: torch.Tensor, g: torch.Tensor | None = None):
+    def step(self, c: torch.Tensor, g: torch.Tensor | None = None, f0_bins: torch.Tensor | None = None):
         revive = self.reviver is not None and self.reviver.next_step_revives()
-        if getattr(self, "_graph", None) is not None and c.shape == self._static_c.shape and (g is None) == (self._static_g is None):
-            losses = self._replay(c, g)
+        if (getattr(self, "_graph", None) is not None and c.shape == self._static_c.shape and (g is None) == (self._static_g is None)
+                and (f0_bins is None) == (self._static_bins is None)
+                and (f0_bins is None or (f0_bins.shape == self._static_bins.shape and f0_bins.dtype == torch.int64))):
+            losses = self._replay(c, g, f0_bins)
             rows = self._graph_rows if revive else None
         else:
             self._stepping, self._keep_rows = True, revive
             try:
-                losses = self.forward_backward(c, g)
+                losses = self.forward_backward(c, g, f0_bins)
             finally:
                 self._stepping = self._keep_rows = False
             rows, self._kept_rows = self._kept_rows, None
@@ -348,3 +384,41 @@ def train_vqvae(args, model, optimizer, train_loader, device, epoch):
         if batch_idx % args.log_interval == 0:
             print('Train Epoch: {} [{}/{}]\tLoss: {:.6f}'.format(epoch, batch_idx * len(c), len(train_loader.dataset), train_loss))
     return train_loss
+
+
+def train_conditioned(args, model, step, train_loader, device, epoch, tracker="yin", tracker_options=None):
+    """One epoch of a speaker- and / or F0-conditioned VQ-VAE on the fused step (an extension: train_vqvae above stays the
+    reference's, which ignores g).  `train_loader` yields (x, y, c, g, input_lengths) as for train_vqvae; `step` is the model's
+    FusedTrainStep.  Per batch: g goes to the device; for a model with an F0 table (VQVAE(n_f0_bins=)) the F0 of the batch's audio
+    x (B, 1, T * 256) is tracked on the device (tracker, tracker_options: evaluate.test_conversion_f0's; lengths = input_lengths;
+    F0 frame t is mel frame t), its first 4 * (T // 4) frames become the bins of the T // 4 latent columns (audio.f0_bins over the
+    model's n_f0_bins and f0_range, each clip's input_lengths // 256 frames valid) and step.step(c, g, f0_bins=bins) runs.
+    Returns the last batch's loss_recons + loss_vq, as train_vqvae does.  ValueError before anything is launched: a tracker or
+    options that do not exist; a model with an F0 table and a batch without audio (get_data_loaders(with_audio=True))."""
+    from . import audio
+    from .evaluate import _f0_tracker
+    track = _f0_tracker("train_conditioned", tracker, tracker_options)
+    has_f0 = getattr(model, "n_f0_bins", None) is not None
+    hop = 256
+    model.train()
+    train_loss, last = 0, None
+    for batch_idx, (x, y, c, g, input_lengths) in enumerate(train_loader):
+        if has_f0 and x is None:
+            raise ValueError("train_conditioned: the model's decoder is F0-conditioned and the loader yields no audio to track F0 from: "
+                             "get_data_loaders(with_audio=True)")
+        c = c.to(device).unsqueeze(1)
+        g_d = g.to(device) if g is not None and getattr(model, "n_speakers", None) is not None else None
+        bins = None
+        if has_f0:
+            T = c.shape[3]
+            if T < 4:
+                raise ValueError("train_conditioned: a batch of fewer than 4 frames has no latent column")
+            lens = np.asarray(input_lengths.cpu() if torch.is_tensor(input_lengths) else input_lengths).astype(np.int64)
+            f0, _ = track(x.view(x.shape[0], -1).to(device).contiguous(), hop_size=hop, lengths=lens)
+            bins = audio.f0_bins(f0[:, :T // 4 * 4].contiguous(), frames=(lens // hop).clip(0, T // 4 * 4), n_bins=model.n_f0_bins,
+                                 fmin=model.f0_range[0], fmax=model.f0_range[1])
+        loss_recons, loss_vq, _ = step.step(c, g_d, f0_bins=bins) if bins is not None else step.step(c, g_d)
+        last = loss_recons + loss_vq
+        if batch_idx % args.log_interval == 0:      # (the only read-back: the fused step itself never waits for the device)
+            print('Train Epoch: {} [{}/{}]\tLoss: {:.6f}'.format(epoch, batch_idx * len(c), len(train_loader.dataset), float(last)))
+    return float(last) if last is not None else train_loss

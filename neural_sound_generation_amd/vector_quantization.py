@@ -95,6 +95,34 @@ class AddPerClip(Function):
         return gz, gr
 
 
+class AddCond(Function):
+    """z (B,H,W,D) + rows (B,D) per clip (or None) + table[bins] (B,W,D) per latent column -- the F0-conditioned decoder input
+    (extension).  Backward: a copy for z; the column sums of the gradient over h (ops.column_sum), scattered over bins for the
+    table and summed per clip for rows -- the gradient is read once for both."""
+
+    @staticmethod
+    def forward(ctx, z, rows, table, bins):
+        bins = bins.contiguous()
+        ctx.save_for_backward(bins)
+        ctx.table_rows = table.shape[0]
+        return ops.add_cond(z.detach().contiguous(), table.detach().contiguous(), bins,
+                            clip_rows=None if rows is None else rows.detach().contiguous())
+
+    @staticmethod
+    def backward(ctx, g):
+        (bins,) = ctx.saved_tensors
+        g = g.contiguous()
+        gz = ops.add(g, None) if ctx.needs_input_grad[0] else None
+        gr = gt = None
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            cs = ops.column_sum(g)                                           # (B, W, D)
+            if ctx.needs_input_grad[1]:
+                gr = ops.clip_colsum(cs, cs.shape[0])
+            if ctx.needs_input_grad[2]:
+                gt = ops.index_add_rows(bins.view(-1), cs.view(-1, cs.shape[-1]), ctx.table_rows)
+        return gz, gr, gt, None
+
+
 def vq(inputs, codebook, impl="mfma"):
     return VectorQuantization.apply(inputs, codebook, impl)
 
@@ -108,4 +136,5 @@ def codebook_lookup(codebook, indices, impl="f32"):
 
 
 add_per_clip = AddPerClip.apply
+add_cond = AddCond.apply
 __all__ = ["vq", "vq_st", "codebook_lookup"]
