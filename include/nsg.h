@@ -1212,7 +1212,7 @@ NSG_API int nsg_audio_stoi_score(const float *env, const int32_t *kept, double *
  * row of an F0 table per latent COLUMN, chosen by the quantised log-F0 of the four mel frames the column covers, so the codes
  * need not carry pitch.  parity unpinned: the definitions are this project's own, stated here in full and restated in numpy by
  * tests/helpers/f0_cond_ref.py.  models.VQVAE(n_f0_bins=), train.FusedTrainStep, audio.f0_bins (csrc/f0_cond.hip).
- * None of the three entry points takes a workspace; every launcher checks all of its arguments before it launches anything.
+ * None of the four entry points takes a workspace; every launcher checks all of its arguments before it launches anything.
  * ------------------------------------------------------------------------------------------- */
 
 /* The decoder input in one pass, for the latent grid [B][H][W] of C channels:
@@ -1255,6 +1255,26 @@ NSG_API int nsg_column_sum(const void *x, int32_t dtype, int32_t B, int32_t H, i
  * fp32 span is not positive;  a pointer not aligned to its element (4 bytes; bins 8);  B T not below 2^31. */
 NSG_API int nsg_f0_bins(const float *f0, const int32_t *frames, const float *affine, int64_t *bins, float *logf, int32_t B, int32_t T,
                         int32_t W, int32_t n_bins, float fmin, float fmax, void *stream);
+
+/* The same bins for a batch cropped out of a RESIDENT F0 track by nsg_collate_mels' plan -- the rows are never materialised and
+ * nothing is tracked per batch (data.ResidentMelCorpus.track_f0 tracks every clip once; F0 frame t is mel frame t).
+ * f0_corpus [corpus_frames] fp32 Hz, +0.0 where unvoiced: the clips' tracks concatenated exactly as the mel corpus' frames are;
+ * plan [B][3] int64, DEVICE memory: nsg_collate_mels' rows (clip, start, count), clip not read;  affine [B][3] fp32 or NULL, as in
+ * nsg_f0_bins;  bins [B][W] int64;  logf [B][W] fp32 or NULL;  f0_out [B][T] fp32 or NULL.
+ * With  f_b[t] = f0_corpus[start_b + t]  for t < count_b,   +0.0f  for count_b <= t < T,  the outputs are exactly
+ *     nsg_f0_bins(f_b, frames = count_b, affine, ...)   -- bins and logf bit for bit (one column rule serves both kernels) --
+ *     f0_out[b][t] = f_b[t].
+ * Reads and clamps follow nsg_collate_mels: count_b is clamped into [0, T] and a frame outside [0, corpus_frames) reads as +0.0,
+ * so whatever the plan holds no access leaves a buffer.  Every element of bins (and of logf and f0_out where given) is written
+ * exactly once; every corpus offset is 64-bit.  One thread per latent column (per four frames of T where f0_out is given), four
+ * scalar loads each (start_b + 4w has no alignment); one launch, no workspace.
+ * NSG_E_INVALID: a null f0_corpus, plan or bins;  B, T or W not positive;  T < 4 W;  n_bins < 1;  not 0 < fmin < fmax < inf, or a
+ * range whose fp32 span is not positive;  corpus_frames < 0;  a pointer not aligned to its element (4 bytes; plan and bins 8);
+ * B T not below 2^31.
+ * PRECONDITION the entry point cannot check (plan is device memory): nsg_collate_mels'; the caller checks its host copy. */
+NSG_API int nsg_collate_f0_bins(const float *f0_corpus, int64_t corpus_frames, const int64_t *plan, const float *affine,
+                                int64_t *bins, float *logf, float *f0_out, int32_t B, int32_t T, int32_t W, int32_t n_bins,
+                                float fmin, float fmax, void *stream);
 
 #ifdef __cplusplus
 }

@@ -1,12 +1,14 @@
 // The F0-conditioned decoder's kernels (an extension: the reference's VQVAE knows neither the speaker nor the pitch).  include/nsg.h
-// states the definitions (nsg_add_cond, nsg_column_sum, nsg_f0_bins); tests/helpers/f0_cond_ref.py restates them in numpy.
+// states the definitions (nsg_add_cond, nsg_column_sum, nsg_f0_bins, nsg_collate_f0_bins); tests/helpers/f0_cond_ref.py restates them in numpy.
 //   * add_cond_kernel: the decoder input in one pass -- latent rows (given, or gathered from the codebook through the code indices)
 //     + the clip's speaker row + the column's F0 row, ReLU, the store type's rounding.  HBM-bound on the rows and the output; the two
 //     tables and the index vectors stay in L2.  Two 16-byte-vector items per thread and trip: the index loads of both, then the
 //     (up to) six row loads of both, are in flight before the first add.
 //   * column_sum_kernel: out[b][w][:] = sum over h of x[b][h][w][:], one thread per (b, w, 16-byte channel vector), h ascending in
 //     fp32, four rows' loads in flight per trip.  No atomics, no workspace: the order is fixed by construction.
-//   * f0_bins_kernel: one thread per latent column: the voiced frames' mean log2 F0, the affine move, the bin.
+//   * f0_bins_kernel: one thread per latent column: the voiced frames' mean log2 F0, the affine move, the bin (f0_column).
+//   * collate_f0_bins_kernel: the same column rule on frames read straight out of a corpus-wide F0 track through the loader's plan
+//     rows (nsg_collate_f0_bins; data.ResidentMelCorpus.track_f0): a batch's bins without tracking anything in the training loop.
 // None of them takes a workspace.
 #include "nsg_common.h"
 #include <math.h>
@@ -107,8 +109,35 @@ __global__ __launch_bounds__(256) void column_sum_kernel(const T *__restrict__ x
     }
 }
 
-// One thread per latent column (b, w): frames 4w .. 4w + 3 of clip b.  lo = fl(log2 fmin), span = fl(log2 fmax) - lo and
+// The column rule, stated once (include/nsg.h: nsg_f0_bins): fv = the column's four frames, of which frame `first + t` counts when
+// it lies below len and is voiced; row = the clip's affine row or null.  lo = fl(log2 fmin), span = fl(log2 fmax) - lo and
 // nb = (float)n_bins come from the launcher; the expressions are include/nsg.h's, in its order (-ffp-contract=off).
+__device__ __forceinline__ void f0_column(const float (&fv)[4], int first, int len, const float *__restrict__ row, float lo, float span, float nb,
+                                          int64_t &bin, float &lf)
+{
+    int n = 0;
+    float sum = 0.f;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        if (first + t < len && fv[t] > 0.f) {
+            sum += (float)log2((double)fv[t]);
+            ++n;
+        }
+    }
+    bin = 0;
+    lf = 0.f;
+    if (n >= 2) {
+        lf = sum / (float)n;
+        if (row) {
+            const float ms = row[0], ratio = row[1], mt = row[2];
+            lf = mt + (lf - ms) * ratio;
+        }
+        const float u = ((lf - lo) * nb) / span;
+        bin = 1 + (int64_t)fminf(fmaxf(floorf(u), 0.f), nb - 1.f);
+    }
+}
+
+// One thread per latent column (b, w): frames 4w .. 4w + 3 of clip b.
 __global__ __launch_bounds__(256) void f0_bins_kernel(const float *__restrict__ f0, const int32_t *__restrict__ frames, const float *__restrict__ affine,
                                                       int64_t *__restrict__ bins, float *__restrict__ logf, int B, int T, int Wd, float lo, float span,
                                                       float nb)
@@ -122,28 +151,44 @@ __global__ __launch_bounds__(256) void f0_bins_kernel(const float *__restrict__ 
     float fv[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) fv[t] = row[t];
-    int n = 0;
-    float sum = 0.f;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        if (4 * w + t < len && fv[t] > 0.f) {
-            sum += (float)log2((double)fv[t]);
-            ++n;
-        }
-    }
-    int64_t bin = 0;
-    float lf = 0.f;
-    if (n >= 2) {
-        lf = sum / (float)n;
-        if (affine) {
-            const float ms = affine[3 * b], ratio = affine[3 * b + 1], mt = affine[3 * b + 2];
-            lf = mt + (lf - ms) * ratio;
-        }
-        const float u = ((lf - lo) * nb) / span;
-        bin = 1 + (int64_t)fminf(fmaxf(floorf(u), 0.f), nb - 1.f);
-    }
+    int64_t bin;
+    float lf;
+    f0_column(fv, 4 * w, len, affine ? affine + 3 * b : nullptr, lo, span, nb, bin, lf);
     bins[i] = bin;
     if (logf) logf[i] = lf;
+}
+
+// nsg_f0_bins on rows cropped out of a resident track by nsg_collate_mels' plan, without the rows: one thread per frame quad
+// (b, q) -- frames 4q .. 4q + 3 of item b, corpus frames start_b + 4q ..: no alignment, so four scalar loads -- of the Q quads the
+// launcher asks for: W (the latent columns) or, where f0_out is wanted, ceil(T / 4) (then the quads past W only copy).  The clamps
+// are collate_mels_kernel's: count into [0, T], start to where start + t cannot overflow, a frame outside [0, corpus_frames) reads
+// as +0.0 -- whatever the plan holds, no access leaves a buffer.
+__global__ __launch_bounds__(256) void collate_f0_bins_kernel(const float *__restrict__ corpus, int64_t corpus_frames, const int64_t *__restrict__ plan,
+                                                              const float *__restrict__ affine, int64_t *__restrict__ bins, float *__restrict__ logf,
+                                                              float *__restrict__ f0_out, int B, int T, int Wd, int Q, float lo, float span, float nb)
+{
+    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (i >= (int64_t)B * Q) return;
+    const int b = (int)(i / Q), q = (int)(i - (int64_t)b * Q);
+    int64_t start = plan[(int64_t)b * 3 + 1], count = plan[(int64_t)b * 3 + 2];
+    count = count < 0 ? 0 : (count > T ? T : count);
+    start = start < -((int64_t)1 << 31) ? -((int64_t)1 << 31) : (start > corpus_frames ? corpus_frames : start);
+    float fv[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const int64_t f = start + 4 * q + t;                  // |f| <= 2^31 + corpus_frames + T: no overflow
+        fv[t] = (4 * q + t < count && f >= 0 && f < corpus_frames) ? corpus[f] : 0.f;
+    }
+    if (f0_out)
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+            if (4 * q + t < T) f0_out[(int64_t)b * T + 4 * q + t] = fv[t];
+    if (q >= Wd) return;                                      // (T >= 4 Wd: a column's four frames lie below T)
+    int64_t bin;
+    float lf;
+    f0_column(fv, 4 * q, (int)count, affine ? affine + 3 * b : nullptr, lo, span, nb, bin, lf);
+    bins[(int64_t)b * Wd + q] = bin;
+    if (logf) logf[(int64_t)b * Wd + q] = lf;
 }
 
 inline bool aligned_to(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
@@ -216,6 +261,28 @@ int nsg_f0_bins(const float *f0, const int32_t *frames, const float *affine, int
     hipLaunchKernelGGL(f0_bins_kernel, dim3((unsigned)nsg_cdiv((int64_t)B * W, 256)), dim3(256), 0, (hipStream_t)stream, f0, frames, affine, bins, logf,
                        (int)B, (int)T, (int)W, lo, span, (float)n_bins);
     return nsg_check_launch("f0_bins_kernel");
+}
+
+int nsg_collate_f0_bins(const float *f0_corpus, int64_t corpus_frames, const int64_t *plan, const float *affine, int64_t *bins, float *logf,
+                        float *f0_out, int32_t B, int32_t T, int32_t W, int32_t n_bins, float fmin, float fmax, void *stream)
+{
+    NSG_REQUIRE(f0_corpus && plan && bins, NSG_E_INVALID, "nsg_collate_f0_bins: null pointer (f0_corpus, plan and bins are required)");
+    NSG_REQUIRE(B > 0 && T > 0 && W > 0, NSG_E_INVALID, "nsg_collate_f0_bins: B, T and W must be positive");
+    NSG_REQUIRE((int64_t)T >= 4 * (int64_t)W, NSG_E_INVALID, "nsg_collate_f0_bins: T = %d frames do not cover W = %d latent columns (T >= 4 W)", T, W);
+    NSG_REQUIRE(n_bins >= 1, NSG_E_INVALID, "nsg_collate_f0_bins: n_bins = %d < 1", n_bins);
+    NSG_REQUIRE(fmin > 0.f && fmin < fmax && fmax < INFINITY, NSG_E_INVALID, "nsg_collate_f0_bins: the range must be 0 < fmin < fmax (finite)");
+    NSG_REQUIRE(corpus_frames >= 0, NSG_E_INVALID, "nsg_collate_f0_bins: corpus_frames = %lld < 0", (long long)corpus_frames);
+    NSG_REQUIRE(aligned_to(f0_corpus, 4) && aligned_to(plan, 8) && aligned_to(bins, 8) && (!affine || aligned_to(affine, 4)) &&
+                (!logf || aligned_to(logf, 4)) && (!f0_out || aligned_to(f0_out, 4)), NSG_E_INVALID,
+                "nsg_collate_f0_bins: misaligned pointer (4 bytes; plan and bins 8 bytes)");
+    NSG_REQUIRE((int64_t)B * T < (1ll << 31), NSG_E_INVALID, "nsg_collate_f0_bins: B * T must stay below 2^31");
+    const float lo = (float)log2((double)fmin);
+    const float span = (float)log2((double)fmax) - lo;
+    NSG_REQUIRE(span > 0.f, NSG_E_INVALID, "nsg_collate_f0_bins: fmin and fmax are one value in fp32 log2");
+    const int Q = f0_out ? (int)nsg_cdiv((int64_t)T, 4) : (int)W;      // quads per item: the columns, or all of T where the row is copied out
+    hipLaunchKernelGGL(collate_f0_bins_kernel, dim3((unsigned)nsg_cdiv((int64_t)B * Q, 256)), dim3(256), 0, (hipStream_t)stream, f0_corpus,
+                       corpus_frames, plan, affine, bins, logf, f0_out, (int)B, (int)T, (int)W, Q, lo, span, (float)n_bins);
+    return nsg_check_launch("collate_f0_bins_kernel");
 }
 
 }  // extern "C"

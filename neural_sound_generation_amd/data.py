@@ -20,6 +20,8 @@ Pieces (names and behaviour follow src/dataloader.py:97-202,324-434):
   * `ResidentMelCorpus` / `plan_batch` / `ResidentMelLoader` / `get_resident_loaders` -- the same loaders with the whole mel
     corpus in device memory: an epoch's crops are planned here (the sampler and `Collate`'s rule, so equal seeds give the host
     loader's batches bit for bit), uploaded once, and a batch is one launch of csrc/collate.hip (ops.collate_mels).
+    `ResidentMelCorpus.track_f0` keeps every clip's F0 track beside the mels; `ResidentMelLoader(f0=)` /
+    `get_resident_loaders(f0=)` then add the F0-conditioned decoder's bins to each batch (ops.collate_f0_bins, one launch).
 
 parity unpinned: the reference's loader cannot be imported here (ordinary missing dependencies); tests/test_host_logic.py
 checks the format invariants on a synthetic data root.
@@ -281,7 +283,8 @@ class ResidentMelCorpus:
     frames[offsets[i]:offsets[i + 1]]; `n_frames` (n,) int64; `lengths`, the source's `timesteps` column (what the sampler sorts
     by).  `speaker_ids` (n,) int64 on `device` for a multi-speaker root, else None.  The arrays are read into host memory
     first (the corpus' size of it, freed afterwards) and staged through a pinned chunk.  device "cpu" keeps `frames` on the
-    host: enough for planning and for tests, not for `ResidentMelLoader`'s batches (ops.collate_mels has no CPU path)."""
+    host: enough for planning and for tests, not for `ResidentMelLoader`'s batches (ops.collate_mels has no CPU path).
+    `f0`, `f0_sums`, `f0_settings`: None until `track_f0` has put the clips' F0 tracks beside the mels."""
 
     CHUNK_FRAMES = 1 << 16          # the pinned staging buffer: 65 536 frames = 21 MB
 
@@ -302,6 +305,84 @@ class ResidentMelCorpus:
         self._upload(arrays)
         self.speaker_ids = (torch.tensor(mel_source.speaker_ids, dtype=torch.int64, device=self.device)
                             if self.multi_speaker else None)
+        self.f0 = self.f0_sums = self.f0_settings = None
+
+    def track_f0(self, audio_source: RawAudioDataSource, tracker="yin", tracker_options=None, fmin=65.0, fmax=500.0, group_clips=64,
+                 group_samples=1 << 24, hop_size: int = HOP_SIZE):
+        """Track every clip's F0 ONCE and keep it beside the mels: F0 frame t is mel frame t, and a frame's value depends on its
+        own samples alone, so a batch's track is a crop of the clip's by the plan rows collate_mels takes (ops.collate_f0_bins) and
+        no tracker runs in the training loop.  `audio_source`: a `RawAudioDataSource` over the same split as the mels (clip i is
+        its path i; ValueError, `Collate`'s, where len(x) != frames * hop_size).  The clips are tracked whole, in zero-padded
+        groups of at most `group_clips` clips and at most `group_samples` padded samples (a longer clip is a group of its own), by
+        audio.f0 (tracker="yin") or audio.f0_track ("viterbi", tracker_options: its costs) over [fmin, fmax] Hz, as
+        evaluate._f0_tracker names and checks them; of a clip's 1 + len // hop_size frames the first n_frames[i] are kept.  Sets
+          f0          (total_frames,) fp32 on the device, Hz, +0.0 where unvoiced: clip i is f0[offsets[i]:offsets[i + 1]];
+          f0_sums     (n, 3) fp64 numpy: audio.logf0_sums of each clip's kept frames (of the row f0[offsets[i]:offsets[i + 1]]);
+          f0_settings {"tracker", "tracker_options", "fmin", "fmax"}.
+        Both trackers give a clip's track independent of the batch it is tracked in, so none of this depends on the grouping.  The
+        audio is not kept.  AGAINST THE HOST PATH (train.train_conditioned tracking a batch's cropped audio): the crop there is
+        zero outside itself, here the frames at a crop's edges see the clip's real neighbours.  With "yin", crop frame t of count
+        frames is bit for bit the host path's where t * hop - 512 >= 0 and t * hop + 511 + tau_max <= count * hop - 1 (tau_max:
+        audio.f0_lags; at the defaults frames 2 .. count - 4); "viterbi" is a path over the whole clip and promises no such
+        equality."""
+        from . import audio
+        from .evaluate import _f0_tracker
+        track = _f0_tracker("ResidentMelCorpus.track_f0", tracker, tracker_options)
+        audio.f0_lags(22050, fmin, fmax)                                     # (the range, checked before anything is read)
+        if len(audio_source.paths) != len(self):
+            raise ValueError(f"ResidentMelCorpus.track_f0: {len(audio_source.paths)} audio clips for {len(self)} mels: not the same split")
+        if group_clips < 1 or group_samples < 1:
+            raise ValueError("ResidentMelCorpus.track_f0: group_clips and group_samples must be positive")
+        f0_all = torch.empty(int(self.offsets[-1]), dtype=torch.float32, device=self.device)
+        group, first = [], 0                                                 # the waiting clips' audio; the index of the first of them
+
+        def flush():
+            nonlocal group, first
+            lens = np.array([len(x) for x in group], dtype=np.int64)
+            wav = np.zeros((len(group), max(1, int(lens.max()))), dtype=np.float32)
+            for j, x in enumerate(group):
+                wav[j, :len(x)] = x
+            f0, _ = track(torch.from_numpy(wav).to(self.device), hop_size=hop_size, fmin=fmin, fmax=fmax, lengths=lens)
+            keep = torch.from_numpy(self.n_frames[first:first + len(group)]).to(self.device)
+            mask = torch.arange(f0.shape[1], device=self.device).unsqueeze(0) < keep.unsqueeze(1)
+            f0_all[int(self.offsets[first]):int(self.offsets[first + len(group)])] = f0[mask]      # row-major: the clips in order
+            group, first = [], first + len(group)
+
+        for i, path in enumerate(audio_source.paths):
+            x = audio_source.collect_features(path)
+            if x.ndim != 1 or len(x) != int(self.n_frames[i]) * hop_size:
+                raise ValueError("audio and mel lengths disagree: %d samples vs %d frames x hop %d" % (len(x), int(self.n_frames[i]), hop_size))
+            widest = max([len(x)] + [len(v) for v in group])
+            if group and (len(group) + 1 > group_clips or (len(group) + 1) * widest > group_samples):
+                flush()
+            group.append(x.astype(np.float32, copy=False))
+        if group:
+            flush()
+        # (per clip, on its own row: torch's sum over a row may depend on the row's width, and nothing here may depend on the groups)
+        sums = [audio.logf0_sums(f0_all[int(a):int(b)].unsqueeze(0)) if b > a else torch.zeros(1, 3, dtype=torch.float64, device=self.device)
+                for a, b in zip(self.offsets[:-1], self.offsets[1:])]
+        self.f0_sums = (torch.cat(sums).cpu().numpy() if sums else np.zeros((0, 3)))
+        self.f0 = f0_all
+        self.f0_settings = {"tracker": tracker, "tracker_options": dict(tracker_options or {}), "fmin": float(fmin), "fmax": float(fmax)}
+        return self
+
+    def speaker_f0_stats(self, n_speakers: int):
+        """evaluate.speaker_f0_stats from the resident track: `f0_sums` pooled per speaker in fp64 on the host -> (stats
+        (n_speakers, 2) fp64: mean and (population) standard deviation of log2 F0 over the speaker's voiced kept frames, NaN for
+        a speaker without one; counts (n_speakers,) int64), torch tensors on the host.  A root without speaker ids is speaker 0."""
+        if self.f0_sums is None:
+            raise ValueError("ResidentMelCorpus.speaker_f0_stats: the corpus has no F0 track (track_f0)")
+        if isinstance(n_speakers, bool) or not isinstance(n_speakers, (int, np.integer)) or n_speakers < 1:
+            raise ValueError(f"speaker_f0_stats: n_speakers must be a positive integer, got {n_speakers!r}")
+        g = self.speaker_ids.cpu().numpy() if self.speaker_ids is not None else np.zeros(len(self), dtype=np.int64)
+        if len(g) and (g.min() < 0 or g.max() >= n_speakers):
+            raise ValueError(f"speaker_f0_stats: the corpus' speaker ids are not all in [0, {n_speakers})")
+        total = np.zeros((n_speakers, 3), dtype=np.float64)
+        np.add.at(total, g, self.f0_sums)
+        n, s1, s2 = (torch.from_numpy(total[:, k].copy()) for k in range(3))
+        mean = s1 / n                                                           # (0 / 0: NaN for a speaker without a voiced frame)
+        std = torch.sqrt(torch.clamp(s2 / n - mean * mean, min=0.0))
+        return torch.stack((mean, std), dim=1), n.to(torch.int64)
 
     def _upload(self, arrays):
         cuda = self.device.type == "cuda"
@@ -373,12 +454,26 @@ class ResidentMelLoader:
     shard=(rank, world): this rank takes the batches k with k % world == rank among the first (n_batches // world) * world
     batches of the epoch; the remaining n_batches % world batches are DROPPED, so that every rank runs the same number of steps
     (the gradient all-reduce would hang otherwise).  Every rank must seed Python's `random` and `rng` alike: all of them draw
-    the same order and the same plan, then keep their share.  len() is then the rank's number of batches."""
+    the same order and the same plan, then keep their share.  len() is then the rank's number of batches.
+
+    f0=(n_bins, fmin, fmax), over a corpus with an F0 track (`ResidentMelCorpus.track_f0`; ValueError here without one): a batch
+    is the six-tuple (None, None, c, g, input_lengths, f0_bins) with f0_bins (B, T // 4) int64 on the device, the F0-conditioned
+    decoder's bins of the batch's crops (one ops.collate_f0_bins launch on the plan rows already on the device; T < 4: an empty
+    (B, 0) tensor and no launch), which train.train_conditioned, evaluate.test_conditioned and epoch.run_conditioned_epoch take as
+    they come.  The first five elements and the draws from `random` and `rng` are those of the loader without f0.  The bins are
+    crops of the WHOLE clip's track: see track_f0 for where they are, and are not, the host path's."""
 
     def __init__(self, corpus: ResidentMelCorpus, batch_size: int, max_time_steps: Optional[int] = None, frame_multiple: int = 1,
-                 train: bool = True, rng=None, shard=None, hop_size: int = HOP_SIZE):
+                 train: bool = True, rng=None, shard=None, hop_size: int = HOP_SIZE, f0=None):
         if batch_size < 1:
             raise ValueError("ResidentMelLoader: batch_size < 1")
+        if f0 is not None:
+            if len(f0) != 3 or isinstance(f0[0], bool) or not isinstance(f0[0], (int, np.integer)) or f0[0] < 1 or not 0 < f0[1] < f0[2] < float("inf"):
+                raise ValueError(f"ResidentMelLoader: f0 = {f0!r} is not (n_bins, fmin, fmax) with n_bins >= 1 and 0 < fmin < fmax")
+            if getattr(corpus, "f0", None) is None:
+                raise ValueError("ResidentMelLoader: f0 given over a corpus without an F0 track (ResidentMelCorpus.track_f0)")
+            f0 = (int(f0[0]), float(f0[1]), float(f0[2]))
+        self.f0 = f0
         if shard is not None and not (len(shard) == 2 and shard[1] >= 1 and 0 <= shard[0] < shard[1]):
             raise ValueError(f"ResidentMelLoader: shard = {shard} is not (rank, world) with 0 <= rank < world")
         self.dataset = corpus
@@ -422,29 +517,53 @@ class ResidentMelLoader:
             B, rows = int(ep.sizes[k]), plan_dev[k, :int(ep.sizes[k])]
             c = ops.collate_mels(corpus.frames, rows, int(ep.widths[k]))
             g = corpus.speaker_ids[rows[:, 0]] if corpus.speaker_ids is not None else None
-            yield None, None, c, g, torch.from_numpy(ep.plan[k, :B, 2] * self.hop)
+            lengths = torch.from_numpy(ep.plan[k, :B, 2] * self.hop)
+            if self.f0 is None:
+                yield None, None, c, g, lengths
+                continue
+            T = int(ep.widths[k])
+            bins = (ops.collate_f0_bins(corpus.f0, rows, T, *self.f0) if T >= 4 else
+                    torch.empty(B, 0, dtype=torch.int64, device=corpus.device))
+            yield None, None, c, g, lengths, bins
 
 
 def get_resident_loaders(data_root: str, batch_size: int, max_time_steps: Optional[int] = None, speaker_id=None, test_size=0.05,
                          test_num_samples=None, random_state: int = 1234, frame_multiple: int = 1, device="cuda:0", rng=None,
-                         shard=None):
+                         shard=None, f0=None):
     """`get_data_loaders` with the corpus resident on `device`: {"train": ResidentMelLoader, "test": ResidentMelLoader} over the
-    same train / test split (mels only: raw audio stays on the host path).  `shard` applies to the train loader only."""
+    same train / test split (mels only: raw audio stays on the host path).  `shard` applies to the train loader only.
+    f0: None, or a dict {"n_bins", "fmin", "fmax"[, "tracker", "tracker_options"]} for an F0-conditioned model (n_bins and the range
+    are the model's n_f0_bins and f0_range): both corpora read their split's audio once (`RawAudioDataSource`), track it
+    (`ResidentMelCorpus.track_f0` with that tracker over its own default range, the one train.train_conditioned tracks a host
+    batch over) and both loaders yield six-tuples with the bins (`ResidentMelLoader(f0=)`).  The audio is not kept."""
+    if f0 is not None:
+        f0 = dict(f0)
+        if set(f0) - {"n_bins", "fmin", "fmax", "tracker", "tracker_options"} or not {"n_bins", "fmin", "fmax"} <= set(f0):
+            raise ValueError(f"get_resident_loaders: f0 = {sorted(f0)} is not n_bins, fmin, fmax (and tracker, tracker_options)")
     loaders = {}
     for phase in ("train", "test"):
         train = phase == "train"
-        mel = MelSpecDataSource(data_root, speaker_id=speaker_id, train=train, test_size=test_size, test_num_samples=test_num_samples,
-                                random_state=random_state)
-        loaders[phase] = ResidentMelLoader(ResidentMelCorpus(mel, device), batch_size, max_time_steps, frame_multiple, train=train,
-                                           rng=rng, shard=shard if train else None)
+        kw = dict(speaker_id=speaker_id, train=train, test_size=test_size, test_num_samples=test_num_samples, random_state=random_state)
+        corpus = ResidentMelCorpus(MelSpecDataSource(data_root, **kw), device)
+        if f0 is not None:
+            corpus.track_f0(RawAudioDataSource(data_root, **kw), tracker=f0.get("tracker", "yin"), tracker_options=f0.get("tracker_options"))
+        loaders[phase] = ResidentMelLoader(corpus, batch_size, max_time_steps, frame_multiple, train=train, rng=rng,
+                                           shard=shard if train else None,
+                                           f0=None if f0 is None else (f0["n_bins"], f0["fmin"], f0["fmax"]))
     return loaders
 
 
 def write_synthetic_data_root(data_root: str, n_utts: int = 12, min_frames: int = 40, max_frames: int = 200, n_speakers: int = 0,
-                              with_audio: bool = True, seed: int = 0) -> None:
+                              with_audio: bool = True, seed: int = 0, voiced: bool = False) -> None:
     """A data root in the reference's format filled with random mels in [0, 1) (tests, smoke runs: there is no network
-    for LJSpeech / CMU Arctic here)."""
+    for LJSpeech / CMU Arctic here).  The audio is uniform noise, which a pitch tracker calls unvoiced everywhere; voiced=True
+    writes instead, for clip i of n = frames * 256 samples, a gliding harmonic tone with an unvoiced tail,
+        0.3 * sum_{h = 1..6} 0.6^h sin(h phase[m]),   phase = the running sum of 2 pi f[m] / 22050,
+        f[m] = 110 (1 + 0.25 (i mod 4)) (1 + 0.3 m / n),
+    whose last fifth is 0.006 * standard normal noise from a RandomState of its own -- the mels, the speaker ids and train.txt are
+    the same either way (the audio says nothing about the random mels: it gives the F0 paths something to track)."""
     rs = np.random.RandomState(seed)
+    rs_tail = np.random.RandomState([seed, 0xF0]) if voiced else None
     os.makedirs(data_root, exist_ok=True)
     lines = []
     for i in range(n_utts):
@@ -452,7 +571,15 @@ def write_synthetic_data_root(data_root: str, n_utts: int = 12, min_frames: int 
         mel = rs.rand(frames, NUM_MELS).astype(np.float32)
         np.save(join(data_root, "synth-mel-%05d.npy" % i), mel, allow_pickle=False)
         if with_audio:
-            np.save(join(data_root, "synth-audio-%05d.npy" % i), rs.uniform(-1, 1, frames * HOP_SIZE).astype(np.float32), allow_pickle=False)
+            wav = rs.uniform(-1, 1, frames * HOP_SIZE).astype(np.float32)       # (drawn either way: the later clips' mels depend on it)
+            if voiced:
+                n = frames * HOP_SIZE
+                f = 110.0 * (1 + 0.25 * (i % 4)) * (1 + 0.3 * np.arange(n) / n)
+                phase = np.cumsum(2 * np.pi * f / 22050.0)
+                tone = 0.3 * sum(0.6 ** h * np.sin(h * phase) for h in range(1, 7))
+                tone[n - n // 5:] = 0.006 * rs_tail.standard_normal(n // 5)
+                wav = tone.astype(np.float32)
+            np.save(join(data_root, "synth-audio-%05d.npy" % i), wav, allow_pickle=False)
         fields = ["synth-audio-%05d.npy" % i, "synth-mel-%05d.npy" % i, str(frames * HOP_SIZE), "utterance %d" % i]
         if n_speakers > 0:
             fields.append(str(int(rs.randint(0, n_speakers))))

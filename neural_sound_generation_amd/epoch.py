@@ -2,7 +2,8 @@
 package: train_vqvae -> test_vqvae -> reconstruct the first test batch -> np.save it -> invert the last clip's mel to a
 waveform (Griffin-Lim) -> save_wav -> checkpoint.  File names follow the reference's.  The CLI / argument parsing of
 main.py stays out of scope; `args` is any object with the fields used below
-(model, dataset, dim, z_dim, beta, log_interval, sampledir).
+(model, dataset, dim, z_dim, beta, log_interval, sampledir).  run_conditioned_epoch is the same loop for the speaker- and
+F0-conditioned decoder's fused step (an extension).
 """
 from __future__ import annotations
 
@@ -13,9 +14,10 @@ import numpy as np
 import torch
 
 from . import audio as nsg_audio
-from .evaluate import checkpoint_state, sample_mels, save_checkpoint, test_prior, test_vae, test_vqvae
+from .evaluate import (_f0_tracker, batch_conditioning, checkpoint_state, sample_mels, save_checkpoint, test_conditioned, test_prior,
+                       test_vae, test_vqvae)
 from .prior_train import PriorTrainStep, train_prior
-from .train import train_vqvae
+from .train import train_conditioned, train_vqvae
 from .vae_train import VAETrainStep, train_vae
 
 SAMPLING_RATE, FFT_SIZE, HOP_SIZE, N_MELS = 22050, 1024, 256, 80      # src/main.py:167-170
@@ -52,18 +54,21 @@ def _evaluate_and_export(args, model, test_loader, device, epoch, export_audio):
     return _export_first_batch(args, model, test_loader, device, epoch, export_audio, out)
 
 
-def _export_first_batch(args, model, test_loader, device, epoch, export_audio, out):
+def _export_first_batch(args, model, test_loader, device, epoch, export_audio, out, conditioning=None):
     """Reconstruct the loader's first batch in eval mode (model(c)[0]: both autoencoders return the image first), save it as
-    a .npy and, with export_audio, invert the last clip to a wav (main.py:150-187); the files' names go into `out`."""
+    a .npy and, with export_audio, invert the last clip to a wav (main.py:150-187); the files' names go into `out`.
+    conditioning(batch) -> (c on the device, g, f0_bins): the model is then called under them, model(c, g, f0_bins)[0]."""
     sample_dir = os.path.join(args.sampledir, format(args.dataset))
     os.makedirs(sample_dir, exist_ok=True)
     stem = '_' + str(args.model) + '_data_' + str(args.dataset) + '_dim_' + str(args.dim) + '_z_dim_' + str(args.z_dim) + '_epoch_' + str(epoch)
     with torch.no_grad():
-        x, y, c, g, input_lengths = next(iter(test_loader))
-        c = c.to(device).unsqueeze(1)
+        batch = next(iter(test_loader))
         print("Evaluating samples")
         model.eval()
-        reconstruction = model(c)[0]                                      # main.py:150-153
+        if conditioning is None:
+            reconstruction = model(batch[2].to(device).unsqueeze(1))[0]   # main.py:150-153
+        else:
+            reconstruction = model(*conditioning(batch))[0]
         reconstruction = reconstruction.squeeze(1)
         rec_np = reconstruction.float().cpu().numpy()
         out["reconstruction"] = os.path.join(sample_dir, 'reconstruction' + stem + '.npy')
@@ -76,6 +81,26 @@ def _export_first_batch(args, model, test_loader, device, epoch, export_audio, o
             signal = nsg_audio.inv_mel_spectrogram(mel, SAMPLING_RATE, FFT_SIZE, HOP_SIZE, N_MELS)[0].cpu().numpy()
             out["wav"] = os.path.join(sample_dir, 'audio_recon' + stem + '_fftsize_' + str(FFT_SIZE) + '_hopsize_' + str(HOP_SIZE) + '.wav')
             nsg_audio.save_wav(signal, out["wav"], SAMPLING_RATE)
+    return out
+
+
+def run_conditioned_epoch(args, model, step, train_loader, test_loader, device, epoch, checkpoint_path=None, export_audio=True,
+                          eval_with_ema=False, tracker="yin", tracker_options=None):
+    """run_epoch for a speaker- and / or F0-conditioned VQ-VAE on its FusedTrainStep `step` (an extension): train_conditioned ->
+    test_conditioned -> the first test batch reconstructed UNDER ITS OWN CONDITIONING (its g, and its bins: the sixth element of
+    a data.ResidentMelLoader(f0=) batch, or tracked from its audio with tracker / tracker_options) -> the .npy, the wav and the
+    checkpoint (checkpoint_state of the model and step.opt) under run_epoch's file names.  eval_with_ema as in run_epoch.
+    Returns run_epoch's dict."""
+    optimizer = step.opt
+    _require_average(optimizer, eval_with_ema)
+    track = _f0_tracker("run_conditioned_epoch", tracker, tracker_options)
+    train_loss = train_conditioned(args, model, step, train_loader, device, epoch, tracker, tracker_options)
+    with _averaged(optimizer, eval_with_ema):
+        loss_recons, loss_vq = test_conditioned(args, model, test_loader, device, epoch, tracker, tracker_options)
+        out = _export_first_batch(args, model, test_loader, device, epoch, export_audio, {"test_loss_recons": loss_recons, "test_loss_vq": loss_vq},
+                                  conditioning=lambda batch: batch_conditioning("run_conditioned_epoch", model, batch, device, track))
+    out["train_loss"] = train_loss
+    out["checkpoint"] = save_checkpoint(args, checkpoint_state(epoch, args.model, model, optimizer), filename=checkpoint_path)
     return out
 
 

@@ -33,6 +33,9 @@ checkpoint layout, restated from the reference's src/test.py:73-106 and src/main
   * `test_reconstruction_audio(args, vqvae, wav_loader, device, epoch)` -- the reconstruction judged as audio against the
     recording: wav -> mel -> model -> waveform, and the mel inverted without the model beside it, each scored by STOI and ESTOI
     (audio.stoi) against the wav it came from.
+  * `test_conditioned(args, model, test_loader, device, epoch)` -- test_vqvae with the model under each batch's own speaker and F0
+    conditioning (bins from a resident loader's six-tuples, or tracked from the batch's audio); `batch_conditioning` is the rule
+    it shares with train.train_conditioned.
   * `codebook_usage(model, loader, device)` -- how much of the codebook a dataset uses: per-code counts and their perplexity.
 """
 from __future__ import annotations
@@ -349,7 +352,8 @@ def test_conversion(args, vqvae, pair_loader, device, epoch):
 
 
 def _f0_tracker(fn, tracker, tracker_options):
-    """audio.f0 or audio.f0_track with its costs, as test_conversion_f0, speaker_f0_stats and train.train_conditioned name them."""
+    """audio.f0 or audio.f0_track with its costs, as test_conversion_f0, speaker_f0_stats, test_conditioned, train.train_conditioned
+    and data.ResidentMelCorpus.track_f0 name them."""
     from . import audio
     if tracker not in ("yin", "viterbi"):
         raise ValueError(f"{fn}: tracker must be 'yin' or 'viterbi', got {tracker!r}")
@@ -358,6 +362,69 @@ def _f0_tracker(fn, tracker, tracker_options):
         raise ValueError(f"{fn}: tracker_options {sorted(options)} do not go with tracker {tracker!r} "
                          f"(viterbi takes {sorted(audio.F0_TRACK_COSTS)})")
     return audio.f0 if tracker == "yin" else functools.partial(audio.f0_track, **options)
+
+
+def batch_conditioning(fn, model, batch, device, track):
+    """One loader batch as a conditioned model takes it -> (c (B, 1, 80, T) on the device, g on the device or None, f0_bins or
+    None).  batch: (x, y, c, g, input_lengths[, f0_bins]).  g is passed only to a model with a speaker table; bins only to one
+    with an F0 table: the batch's sixth element if it has one (moved to the device), else tracked by `track` (_f0_tracker's) from
+    the audio x (B, 1, T * 256) -- lengths = input_lengths, F0 frame t is mel frame t, the first 4 * (T // 4) frames binned by
+    audio.f0_bins over the model's n_f0_bins and f0_range with input_lengths // 256 frames valid.  ValueError (named `fn`): a
+    model with an F0 table and neither; tracking a batch of fewer than 4 frames.  train.train_conditioned and test_conditioned
+    share it."""
+    from . import audio
+    x, c, g, input_lengths = batch[0], batch[2], batch[3], batch[4]
+    given = batch[5] if len(batch) > 5 else None
+    has_f0 = getattr(model, "n_f0_bins", None) is not None
+    if has_f0 and given is None and x is None:
+        raise ValueError(f"{fn}: the model's decoder is F0-conditioned and the loader yields no audio to track F0 from: "
+                         "get_data_loaders(with_audio=True), or bins from a resident track: get_resident_loaders(f0=...)")
+    c = c.to(device).unsqueeze(1)
+    g_d = g.to(device) if g is not None and getattr(model, "n_speakers", None) is not None else None
+    bins = None
+    if has_f0 and given is not None:
+        bins = given.to(device)
+    elif has_f0:
+        hop, T = 256, c.shape[3]
+        if T < 4:
+            raise ValueError(f"{fn}: a batch of fewer than 4 frames has no latent column")
+        lens = np.asarray(input_lengths.cpu() if torch.is_tensor(input_lengths) else input_lengths).astype(np.int64)
+        f0, _ = track(x.view(x.shape[0], -1).to(device).contiguous(), hop_size=hop, lengths=lens)
+        bins = audio.f0_bins(f0[:, :T // 4 * 4].contiguous(), frames=(lens // hop).clip(0, T // 4 * 4), n_bins=model.n_f0_bins,
+                             fmin=model.f0_range[0], fmax=model.f0_range[1])
+    return c, g_d, bins
+
+
+def test_conditioned(args, model, test_loader, device, epoch, tracker="yin", tracker_options=None):
+    """test_vqvae for a speaker- and / or F0-conditioned VQ-VAE: the same two figures with the model called under each batch's
+    own conditioning, model(c, g, f0_bins) in eval mode (test_vqvae calls model(c): no speaker row, no F0 row).  `test_loader`
+    yields train.train_conditioned's batches: g goes only to a model with a speaker table; the bins of a model with an F0 table
+    are the batch's sixth element (data.ResidentMelLoader(f0=)) or are tracked from its audio x exactly as train_conditioned
+    tracks them (tracker, tracker_options); ValueError for such a model and a batch with neither.  Pools as test_vqvae does (the
+    mean over the batches of mse(padded reconstruction, c) and of mse(z_q, z_e)) and returns (loss_recons, loss_vq) as floats.
+    The model's mode is restored."""
+    track = _f0_tracker("test_conditioned", tracker, tracker_options)
+    was_training = model.training
+    model.eval()
+    loss_recons = torch.zeros((), device=device)
+    loss_vq = torch.zeros((), device=device)
+    n = 0
+    try:
+        with torch.no_grad():
+            for batch in test_loader:
+                c, g_d, bins = batch_conditioning("test_conditioned", model, batch, device, track)
+                x_tilde, z_e_x, z_q_x = model(c, g_d, bins)
+                target = F.pad(x_tilde, (0, c.size(3) - x_tilde.size(3))) if x_tilde.size(3) != c.size(3) else x_tilde
+                loss_recons += F.mse_loss(target, c)
+                loss_vq += F.mse_loss(z_q_x, z_e_x)
+                n += 1
+    finally:
+        model.train(was_training)
+    if n == 0:
+        raise ValueError("test_conditioned: empty loader")
+    loss_recons, loss_vq = float(loss_recons / n), float(loss_vq / n)
+    print('====> Test set loss: {:.4f}'.format(loss_recons + loss_vq))
+    return loss_recons, loss_vq
 
 
 def speaker_f0_stats(wav_loader, n_speakers, device, tracker="yin", tracker_options=None):

@@ -1362,6 +1362,45 @@ def f0_bins(f0, W, n_bins, fmin, fmax, frames=None, affine=None, want_logf=False
     return (bins, logf) if want_logf else bins
 
 
+def collate_f0_bins(f0_corpus, plan, T, n_bins, fmin, fmax, W=None, affine=None, want_logf=False, want_f0=False):
+    """A batch's F0 bins straight from a resident track (include/nsg.h: nsg_collate_f0_bins): f0_corpus (frames,) fp32 Hz (+0.0:
+    unvoiced), laid out as the mel corpus' frames are; plan (B, 3) int64 rows of (clip, start, count), collate_mels' own; T the
+    batch's width; W latent columns (default T // 4; T >= 4 W).  Exactly f0_bins of the rows collate_mels' rule would crop
+    (f0_corpus[start_b : start_b + count_b], +0.0 up to T) with frames = count_b -- one launch, the rows never stored.
+    affine (B, 3) fp32 or None, as in f0_bins.  -> bins (B, W) int64; with want_logf / want_f0 the tuple (bins[, logf (B, W) fp32]
+    [, f0 (B, T) fp32: the cropped rows]).  A plan on the device is the caller's to have checked (check_collate_plan on its host
+    copy); a plan on the host is checked here and uploaded."""
+    for t, name, dtype in ((f0_corpus, "f0_corpus", torch.float32), (plan, "plan", torch.int64)):
+        if t.dtype != dtype:
+            raise _lib.NsgError(f"collate_f0_bins: {name}: expected {dtype}, got {t.dtype}")
+        if not t.is_contiguous():
+            raise _lib.NsgError(f"collate_f0_bins: {name}: expected a contiguous tensor")
+    if f0_corpus.dim() != 1:
+        raise _lib.NsgError(f"collate_f0_bins: f0_corpus {tuple(f0_corpus.shape)} is not (frames,)")
+    if plan.dim() != 2 or plan.shape[1] != 3 or plan.shape[0] < 1:
+        raise _lib.NsgError(f"collate_f0_bins: plan {tuple(plan.shape)} is not (B, 3) with B >= 1")
+    T = int(T)
+    W = T // 4 if W is None else int(W)
+    frames, B = f0_corpus.shape[0], plan.shape[0]
+    if not plan.is_cuda:
+        check_collate_plan(plan, T, frames)
+    _chk(f0_corpus, "collate_f0_bins: f0_corpus")
+    if not plan.is_cuda:
+        plan = plan.to(f0_corpus.device)
+    dev = f0_corpus.device
+    if affine is not None and (tuple(_chk(affine, "collate_f0_bins: affine").shape) != (B, 3) or affine.device != dev):
+        raise _lib.NsgError(f"collate_f0_bins: affine {tuple(affine.shape)} is not ({B}, 3) on f0_corpus' device")
+    if plan.device != dev:
+        raise _lib.NsgError("collate_f0_bins: plan and f0_corpus are not on one device")
+    bins = torch.empty(B, max(W, 0), dtype=torch.int64, device=dev)
+    logf = torch.empty(B, max(W, 0), dtype=torch.float32, device=dev) if want_logf else None
+    f0 = torch.empty(B, max(T, 0), dtype=torch.float32, device=dev) if want_f0 else None
+    _lib.call("nsg_collate_f0_bins", _p(f0_corpus), frames, _p(plan), _p(affine), _p(bins), _p(logf), _p(f0), B, T, W, int(n_bins),
+              float(fmin), float(fmax), _stream())
+    out = (bins,) + ((logf,) if want_logf else ()) + ((f0,) if want_f0 else ())
+    return out if len(out) > 1 else bins
+
+
 def mse_padded(a, c, rows, wa, wc, grad_scale=1.0, want_grad=True):
     """mean((pad(a) - c)^2) with a zero-padded from width wa to wc (train.py:118-129)."""
     loss = torch.empty(1, dtype=torch.float32, device=a.device)

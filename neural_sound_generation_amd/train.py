@@ -16,7 +16,6 @@ from __future__ import annotations
 
 import os
 
-import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -388,35 +387,22 @@ def train_vqvae(args, model, optimizer, train_loader, device, epoch):
 
 def train_conditioned(args, model, step, train_loader, device, epoch, tracker="yin", tracker_options=None):
     """One epoch of a speaker- and / or F0-conditioned VQ-VAE on the fused step (an extension: train_vqvae above stays the
-    reference's, which ignores g).  `train_loader` yields (x, y, c, g, input_lengths) as for train_vqvae; `step` is the model's
-    FusedTrainStep.  Per batch: g goes to the device; for a model with an F0 table (VQVAE(n_f0_bins=)) the F0 of the batch's audio
-    x (B, 1, T * 256) is tracked on the device (tracker, tracker_options: evaluate.test_conversion_f0's; lengths = input_lengths;
+    reference's, which ignores g).  `train_loader` yields (x, y, c, g, input_lengths) as for train_vqvae, or the six-tuple
+    (x, y, c, g, input_lengths, f0_bins) of a resident loader with an F0 track (data.ResidentMelLoader(f0=)); `step` is the model's
+    FusedTrainStep.  Per batch: g goes to the device; for a model with an F0 table (VQVAE(n_f0_bins=)) a sixth element is the bins
+    and goes straight to the step (moved to the device if it is not there; x is not needed and the tracker arguments are unused);
+    otherwise the F0 of the batch's audio x (B, 1, T * 256) is tracked on the device (tracker, tracker_options: evaluate.test_conversion_f0's; lengths = input_lengths;
     F0 frame t is mel frame t), its first 4 * (T // 4) frames become the bins of the T // 4 latent columns (audio.f0_bins over the
     model's n_f0_bins and f0_range, each clip's input_lengths // 256 frames valid) and step.step(c, g, f0_bins=bins) runs.
+    (The two sources differ at a crop's edge frames: data.ResidentMelCorpus.track_f0.)
     Returns the last batch's loss_recons + loss_vq, as train_vqvae does.  ValueError before anything is launched: a tracker or
-    options that do not exist; a model with an F0 table and a batch without audio (get_data_loaders(with_audio=True))."""
-    from . import audio
-    from .evaluate import _f0_tracker
+    options that do not exist; a model with an F0 table and a batch with neither bins nor audio (get_data_loaders(with_audio=True))."""
+    from .evaluate import _f0_tracker, batch_conditioning
     track = _f0_tracker("train_conditioned", tracker, tracker_options)
-    has_f0 = getattr(model, "n_f0_bins", None) is not None
-    hop = 256
     model.train()
     train_loss, last = 0, None
-    for batch_idx, (x, y, c, g, input_lengths) in enumerate(train_loader):
-        if has_f0 and x is None:
-            raise ValueError("train_conditioned: the model's decoder is F0-conditioned and the loader yields no audio to track F0 from: "
-                             "get_data_loaders(with_audio=True)")
-        c = c.to(device).unsqueeze(1)
-        g_d = g.to(device) if g is not None and getattr(model, "n_speakers", None) is not None else None
-        bins = None
-        if has_f0:
-            T = c.shape[3]
-            if T < 4:
-                raise ValueError("train_conditioned: a batch of fewer than 4 frames has no latent column")
-            lens = np.asarray(input_lengths.cpu() if torch.is_tensor(input_lengths) else input_lengths).astype(np.int64)
-            f0, _ = track(x.view(x.shape[0], -1).to(device).contiguous(), hop_size=hop, lengths=lens)
-            bins = audio.f0_bins(f0[:, :T // 4 * 4].contiguous(), frames=(lens // hop).clip(0, T // 4 * 4), n_bins=model.n_f0_bins,
-                                 fmin=model.f0_range[0], fmax=model.f0_range[1])
+    for batch_idx, batch in enumerate(train_loader):
+        c, g_d, bins = batch_conditioning("train_conditioned", model, batch, device, track)
         loss_recons, loss_vq, _ = step.step(c, g_d, f0_bins=bins) if bins is not None else step.step(c, g_d)
         last = loss_recons + loss_vq
         if batch_idx % args.log_interval == 0:      # (the only read-back: the fused step itself never waits for the device)
