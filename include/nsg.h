@@ -1276,6 +1276,86 @@ NSG_API int nsg_collate_f0_bins(const float *f0_corpus, int64_t corpus_frames, c
                                 int64_t *bins, float *logf, float *f0_out, int32_t B, int32_t T, int32_t W, int32_t n_bins,
                                 float fmin, float fmax, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Pitch change that keeps the spectral envelope and the duration: time-domain pitch-synchronous overlap-add, TD-PSOLA (Moulines &
+ * Charpentier 1990), driven by an F0 track (extension; not in the reference).  parity unpinned: the definition is this project's
+ * own, stated here in full and restated in fp32 and fp64 by tests/helpers/psola_ref.py.  audio.pitch_marks,
+ * audio.pitch_shift_psola, audio.perturb_pitch (csrc/psola.hip).  Neither entry point takes a workspace: every intermediate is
+ * an output of the caller's; both check all of their arguments before they launch anything.
+ * ------------------------------------------------------------------------------------------- */
+
+/* What the two entry points share.  wav [B][L] fp32; clip b has len = lengths[b] samples (lengths int32 DEVICE memory, clamped
+ * into [0, L]; NULL: L).  f0_in [B][T] fp32 Hz under nsg_audio_f0's conventions: frame t sits at sample t hop, and a value that
+ * is not > 0 (+0.0, a negative number, NaN) means unvoiced.  Sample n belongs to frame  t(n) = min(T - 1, (n + hop / 2) / hop)
+ * (integer divisions).  With the launch constants P_min <= P_max, P_u and alpha = alpha_num / alpha_den:
+ *     clamp(p)  = P_min where not p >= P_min, P_max where p > P_max, else p
+ *     P(n)      = clamp((int) floor((double)sample_rate / (double)f0_in[b][t(n)] + 0.5))   on a voiced frame (the clamp is applied
+ *                 to the fp64 value before the conversion, so +inf, 1e30 and 1e-30 Hz give P_min, P_min and P_max)
+ *               = clamp(P_u)                                                               on an unvoiced one
+ *     G         = P_min - (alpha_num P_min) / alpha_den       the least distance of two marks (P - (alpha_num P) / alpha_den does
+ *                                                             not fall as P grows)
+ *     K_max     = ceil(L / G)                                 marks a clip can have:  m_k >= k G  and  m_k <= len - 1
+ *     H_max     = P_max + (alpha_num P_max) / alpha_den       the greatest distance of two marks
+ *     G_s       = max(1, (int) floor((double)G / 4.0 + 0.5))  the least distance of two synthesis marks
+ *     J_max     = ceil(L / G_s)                               synthesis marks a clip can have
+ * The maximum of x over a range [lo, hi] is the sample with the greatest KEY, an integer comparison with nothing left to a
+ * float's corner cases:  key(i) = o(bits(x[i])) << 32 | (0xffffffff - (i - lo)),  o(u) = u ^ 0x80000000 for u < 2^31 (a cleared sign)
+ * and ~u otherwise -- the order of the reals on numbers (-0.0 below +0.0), NaNs at the two ends -- so among equal samples the
+ * SMALLEST index wins.
+ * Shared refusals, before any launch, the message starting with the entry point's name.  NSG_E_INVALID: a null pointer other than
+ * lengths;  B, L, T or hop < 1;  sample_rate not finite or not > 0;  P_u < 1;  alpha_num < 0 or alpha_den < 1;  K_max (J_max) below
+ * the figure above.  NSG_E_UNSUPPORTED: hop outside [16, 2^20];  P_min < 2, P_min > P_max or P_max > 1024 (nsg_audio_f0's longest
+ * lag);  2 alpha_num > alpha_den or alpha_den > 2^20;  B * L, B * K_max or B * J_max >= 2^31, or L > 2^31 - 2^21. */
+
+/* Analysis marks: one per pitch period on voiced stretches, on the waveform's local maxima; every clamp(P_u) samples on unvoiced
+ * ones.  Per clip, in order:
+ *     len = 0:   no mark.
+ *     m_0        = the maximum of x over [0, min(P(0), len) - 1]
+ *     from m_k on a voiced frame t(m_k), with P = P(m_k) and d = (alpha_num P) / alpha_den:
+ *                  lo = m_k + P - d,  hi = min(m_k + P + d, len - 1);   lo > len - 1: the chain ends;
+ *                  m_{k+1} = the maximum of x over [lo, hi]
+ *     from m_k on an unvoiced frame:   m_{k+1} = m_k + clamp(P_u);   m_{k+1} > len - 1: the chain ends.
+ * No float arithmetic enters a mark beyond P(n).  marks [B][K_max] int32: marks[b][k] = m_k for k < n_marks[b], -1 beyond;
+ * n_marks [B] int32.  Every element of both is written exactly once; a clip's marks depend on its own samples, length and track
+ * alone: bit for bit independent of B, L, K_max and its row.  One launch, one wave per clip: the clip's neighbourhood (two halves
+ * of 4096 samples) and its frames' periods live in LDS, the search is a wave maximum of the keys with lane l owning the samples
+ * lo + l, lo + l + 64, ..., and the next half is loaded from global memory while the current range is searched (csrc/psola.hip). */
+NSG_API int nsg_audio_pitch_marks(const float *wav, const int32_t *lengths, const float *f0_in, int32_t *marks, int32_t *n_marks,
+                                  int32_t B, int32_t L, int32_t T, int32_t hop, float sample_rate, int32_t P_u, int32_t P_min,
+                                  int32_t P_max, int32_t alpha_num, int32_t alpha_den, int32_t K_max, void *stream);
+
+/* Synthesis marks and the overlap-add, from the marks above (marks, n_marks: nsg_audio_pitch_marks' outputs for the same wav,
+ * lengths, f0_in and constants; K = n_marks[b] clamped into [0, K_max], every mark clamped into [0, len - 1]).  f0_out [B][T] fp32:
+ * the track the output is to have.  Per clip:
+ *     D_a   = m_{a+1} - m_a for a < K - 1,   D_{K-1} = m_{K-1} - m_{K-2},   D_0 = clamp(P_u) when K = 1      (the LOCAL spacing)
+ *     s_0 = m_0,  a(0) = 0;   K = 0: no synthesis mark
+ *     r_j   = (double)f0_out[t(s_j)] / (double)f0_in[t(s_j)] when both are > 0, taken into [0.25, 4] (below: 0.25, above: 4, NaN: 1);
+ *             otherwise 1
+ *     s_{j+1} = s_j + max(1, (int) floor((double)D_{a(j)} / r_j + 0.5));    s_{j+1} > m_{K-1}: the chain ends
+ *     a(j+1)  = the a >= a(j) that minimises |m_a - s_{j+1}|, the smaller a on a tie  (the time map is the identity: duration is kept)
+ * syn [B][J_max] int32 = s_j, map [B][J_max] int32 = a(j), both -1 for j >= n_syn[b];  n_syn [B] int32.
+ * Grain j is x around m_a, a = a(j), under an asymmetric window of left half-length  hl = m_a - m_{a-1}  (0 for a = 0) and right
+ * half-length  hr = m_{a+1} - m_a  (0 for a = K - 1): at output sample n, with dist = n - s_j,
+ *     dist = 0:            w = 1
+ *     -hl < dist < 0:      u = fl((float)(-dist) / (float)hl)
+ *     0 < dist < hr:       u = fl((float)dist / (float)hr)         (elsewhere the grain does not reach n)
+ *     w = fl(1 - fl(fl(u u) * fl(3 - fl(2 u))))                    (w(u) + w(1 - u) = 1, as for a Hann window; no cosine)
+ * and over the grains that reach n, j ascending, both sums fp32 from +0.0, every operation rounded and never contracted:
+ *     num = sum fl(w_j * x[m_{a(j)} + dist]),   den = sum w_j
+ *     out[n] = fl(num / den)  where den >= 2^-NSG_PSOLA_MIN_WEIGHT_LOG2 = 2^-10,   x[n] elsewhere (so before s_0 and after the last s_j)
+ * for n < len, and +0.0 for len <= n < L.  (m_{a-1} < m_a + dist < m_{a+1}: a grain never reads outside the clip.)  With
+ * f0_out = f0_in, or with no voiced frame, s = m and a(j) = j: the output is x exactly outside [m_0, m_{K-1}] and at the marks, and
+ * x to within the roundings of w, num, den and the quotient between them.  out [B][L] fp32 may not alias wav; every element of
+ * syn, map, n_syn and out is written exactly once; a clip's results are bit for bit independent of B, L, K_max, J_max, its row and
+ * any tiling.  Two launches: the chain over j, one thread per clip; then a thread per output sample, which finds the first grain
+ * that can reach it by a binary search in s (s_j > n - H_max) and walks on while s_j < n + H_max.
+ * Refusals: the shared ones, for marks, n_marks, f0_out, syn, map, n_syn and out too. */
+#define NSG_PSOLA_MIN_WEIGHT_LOG2 10
+NSG_API int nsg_audio_psola(const float *wav, const int32_t *lengths, const float *f0_in, const float *f0_out, const int32_t *marks,
+                            const int32_t *n_marks, int32_t *syn, int32_t *map, int32_t *n_syn, float *out, int32_t B, int32_t L,
+                            int32_t T, int32_t hop, float sample_rate, int32_t P_u, int32_t P_min, int32_t P_max, int32_t alpha_num,
+                            int32_t alpha_den, int32_t K_max, int32_t J_max, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

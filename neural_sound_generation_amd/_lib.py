@@ -98,6 +98,7 @@ NSG_RELU_IN, NSG_TANH_OUT, NSG_OUT_F32, NSG_RELU_OUT, NSG_F32, NSG_BF16, NSG_C1_
     "NSG_RELU_IN", "NSG_TANH_OUT", "NSG_OUT_F32", "NSG_RELU_OUT", "NSG_F32", "NSG_BF16", "NSG_C1_MOMENTS"))
 NSG_DTW_MAX_FRAMES, NSG_DTW_BLOCK_COLS = _CONSTS["NSG_DTW_MAX_FRAMES"], _CONSTS["NSG_DTW_BLOCK_COLS"]
 NSG_F0_MAX_CANDIDATES, NSG_F0_VITERBI_LDS_FRAMES = _CONSTS["NSG_F0_MAX_CANDIDATES"], _CONSTS["NSG_F0_VITERBI_LDS_FRAMES"]
+NSG_PSOLA_MIN_WEIGHT_LOG2 = _CONSTS["NSG_PSOLA_MIN_WEIGHT_LOG2"]
 
 _lib = None
 

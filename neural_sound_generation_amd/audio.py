@@ -810,6 +810,167 @@ def pitch_shift(wav, num, den, sample_rate=22050, lengths=None, device="cuda:0")
     return out[0, :int(out_lens[0])].cpu().numpy() if as_numpy else (out, out_lens)
 
 
+PSOLA_UNVOICED_S = 0.005             # the spacing of the marks on unvoiced stretches, in seconds
+PSOLA_ALPHA = (1, 4)                 # a mark is looked for within a quarter period of where the period puts it
+PSOLA_MIN_RATIO, PSOLA_MAX_RATIO = 0.5, 2.0
+
+
+def psola_periods(sample_rate, fmin=65.0, fmax=500.0):
+    """(P_u, P_min, P_max) in samples, as the PSOLA kernels take them: round(0.005 sample_rate), and f0_lags(sample_rate, fmin,
+    fmax), the periods of [fmin, fmax]; (110, 45, 339) at 22 050 Hz.  ValueError unless 2 <= P_min <= P_max <= F0_MAX_LAG."""
+    if isinstance(sample_rate, bool) or not isinstance(sample_rate, (int, float, np.integer, np.floating)) or not 0 < sample_rate < float("inf"):
+        raise ValueError(f"psola: sample_rate must be a positive finite number, got {sample_rate!r}")
+    P_min, P_max = f0_lags(sample_rate, fmin, fmax)
+    if P_min < 2:
+        raise ValueError(f"psola: fmax = {fmax} Hz at {sample_rate} Hz is a period of {P_min} sample(s); need at least 2")
+    return max(1, int(round(PSOLA_UNVOICED_S * float(sample_rate)))), P_min, P_max
+
+
+def _psola_args(fn, wav, f0, sample_rate, hop_size, fmin, fmax, lengths, device):
+    """The checks pitch_marks and pitch_shift_psola share, before anything is launched -> (as_numpy, B, the track as given, int32 host
+    lengths or None, (P_u, P_min, P_max)); nothing is uploaded."""
+    if isinstance(hop_size, bool) or not isinstance(hop_size, (int, np.integer)) or not ops.PSOLA_MIN_HOP <= hop_size <= ops.PSOLA_MAX_HOP:
+        raise ValueError(f"{fn}: hop_size must be an integer in [{ops.PSOLA_MIN_HOP}, {ops.PSOLA_MAX_HOP}], got {hop_size!r}")
+    periods = psola_periods(sample_rate, fmin, fmax)
+    as_numpy, B, L, lens = _clip_batch(fn, wav, lengths, 0)
+    if L < 1:
+        raise ValueError(f"{fn}: an empty waveform")
+    if B * L >= 2 ** 31 - 1:
+        raise ValueError(f"{fn}: {B} clips of {L} samples are 2^31 samples or more")
+    f = _psola_track(fn, "f0", f0, as_numpy, B, None)
+    return as_numpy, B, f, lens, periods
+
+
+def _psola_track(fn, name, f0, as_numpy, B, T):
+    """An F0 track that goes with the waveform: (T,) floating-point numpy for a numpy waveform, a float32 tensor (B, T) for a batch."""
+    if as_numpy:
+        if not isinstance(f0, np.ndarray) or f0.ndim != 1 or len(f0) < 1 or not np.issubdtype(f0.dtype, np.floating):
+            raise TypeError(f"{fn}: with a numpy waveform {name} must be a 1-D floating-point numpy track, not empty")
+        if T is not None and len(f0) != T:
+            raise ValueError(f"{fn}: {name} has {len(f0)} frames, f0 has {T}")
+        return f0
+    if not torch.is_tensor(f0) or f0.dim() != 2 or f0.dtype != torch.float32 or f0.shape[0] != B or f0.shape[1] < 1:
+        raise TypeError(f"{fn}: with a batch {name} must be a float32 tensor ({B}, T) with T >= 1")
+    if T is not None and f0.shape[1] != T:
+        raise ValueError(f"{fn}: {name} has {f0.shape[1]} frames, f0 has {T}")
+    return f0
+
+
+def _track_on(f0, as_numpy, device):
+    return torch.from_numpy(np.ascontiguousarray(f0, dtype=np.float32)[None]).to(device) if as_numpy else f0
+
+
+def pitch_marks(wav, f0, sample_rate=22050, hop_size=256, lengths=None, device="cuda:0", fmin=65.0, fmax=500.0):
+    """Pitch marks for PSOLA (include/nsg.h: nsg_audio_pitch_marks states the chain, csrc/psola.hip runs it): one mark per period
+    on the waveform's local maxima where the track `f0` (Hz, frame t at sample t * hop_size, a value not > 0: unvoiced, as f0 /
+    f0_track return it) is voiced -- each looked for within a quarter period of where the period at the mark before it puts it,
+    the earliest of equal maxima -- and one every 5 ms where it is not.  Periods are clamped into f0_lags(sample_rate, fmin, fmax).
+    wav: a 1-D numpy waveform with a 1-D numpy track (returns (marks (K,) int32 numpy, K)), or a float32 GPU tensor (B, L) of
+    zero-padded clips with a float32 track (B, T) and optional lengths (returns (marks (B, K_max) int32 with -1 past a clip's
+    marks, n_marks (B,) int32) on the device).  A clip's marks are bit for bit what they are alone.  Every argument is checked
+    before anything is launched."""
+    as_numpy, B, f, lens, (P_u, P_min, P_max) = _psola_args("pitch_marks", wav, f0, sample_rate, hop_size, fmin, fmax, lengths, device)
+    y = _on_device(wav, as_numpy, device)
+    if not as_numpy and f.device != y.device:
+        raise ValueError(f"pitch_marks: f0 on {f.device}, the batch on {y.device}")
+    marks, n = ops.pitch_marks(y, _track_on(f, as_numpy, y.device), int(hop_size), float(sample_rate), P_u, P_min, P_max, PSOLA_ALPHA, lens)
+    if not as_numpy:
+        return marks, n
+    k = int(n[0])
+    return marks[0, :k].cpu().numpy(), k
+
+
+def pitch_shift_psola(wav, f0, ratio=None, target_f0=None, sample_rate=22050, hop_size=256, lengths=None, device="cuda:0", detail=False,
+                      fmin=65.0, fmax=500.0):
+    """Pitch change with the spectral envelope and the duration kept, by time-domain pitch-synchronous overlap-add (Moulines &
+    Charpentier 1990; include/nsg.h: nsg_audio_pitch_marks and nsg_audio_psola state the arithmetic, csrc/psola.hip runs it).
+    Two-sided windowed grains are cut around pitch_marks(wav, f0) and laid down again at marks whose spacing is the local spacing
+    divided by the pitch ratio, each taking the grain of the nearest analysis mark: the pulses come more or less often, each
+    pulse's shape -- the formants -- stays, and the length is the input's, sample for sample.  (pitch_shift, tempo then resample,
+    moves the formants with the pitch.)  Exactly one of
+        ratio      a number or one per clip in [0.5, 2]: the output's track is f0 * ratio (an fp32 product);
+        target_f0  the track the output is to have, in f0's form; only frames both tracks voice are moved
+    f0: the clip's own track (Hz, frame t at sample t * hop_size, not > 0: unvoiced).  wav: a 1-D numpy waveform with 1-D numpy
+    tracks (returns a float32 numpy waveform), or a float32 GPU tensor (B, L) with float32 tracks (B, T) and optional lengths
+    (returns a tensor (B, L), zeros past each length).  ratio = 1 returns the input, exactly outside the marks and within a few
+    roundings between them.  detail=True also returns (marks, n_marks, syn, map, n_syn) as ops.pitch_marks and ops.psola return
+    them (numpy, cut to their counts, for a numpy waveform).  Every argument is checked before anything is launched."""
+    if (ratio is None) == (target_f0 is None):
+        raise ValueError("pitch_shift_psola: give exactly one of ratio and target_f0")
+    as_numpy, B, f, lens, (P_u, P_min, P_max) = _psola_args("pitch_shift_psola", wav, f0, sample_rate, hop_size, fmin, fmax, lengths, device)
+    if ratio is not None:
+        r = _per_clip("pitch_shift_psola", "ratio", ratio, B, PSOLA_MIN_RATIO, PSOLA_MAX_RATIO)
+    else:
+        tgt = _psola_track("pitch_shift_psola", "target_f0", target_f0, as_numpy, B, f.shape[-1])
+    if not as_numpy and (f.device != wav.device or (ratio is None and tgt.device != wav.device)):
+        raise ValueError(f"pitch_shift_psola: the tracks are not on the batch's device {wav.device}")
+    y = _on_device(wav, as_numpy, device)
+    f_d = _track_on(f, as_numpy, y.device)
+    f_out = f_d * torch.from_numpy(r.astype(np.float32)).to(y.device)[:, None] if ratio is not None else _track_on(tgt, as_numpy, y.device)
+    P = (int(hop_size), float(sample_rate), P_u, P_min, P_max, PSOLA_ALPHA, lens)
+    marks, n_marks = ops.pitch_marks(y, f_d, *P)
+    out, syn, mp, n_syn = ops.psola(y, f_d, f_out.contiguous(), marks, n_marks, *P)
+    if not as_numpy:
+        return (out, marks, n_marks, syn, mp, n_syn) if detail else out
+    res = out[0].cpu().numpy()
+    if not detail:
+        return res
+    k, j = int(n_marks[0]), int(n_syn[0])
+    return res, marks[0, :k].cpu().numpy(), k, syn[0, :j].cpu().numpy(), mp[0, :j].cpu().numpy(), j
+
+
+PITCH_PERTURB_SEMITONES = (-4.0, 4.0)
+
+
+def pitch_draws(n, generator, semitones=PITCH_PERTURB_SEMITONES):
+    """The pitch perturbation's parameters for n clips from a CPU torch.Generator: per clip, in clip order, one fp64 u in [0, 1)
+    (torch.rand(1, dtype=float64, generator=generator)), semitones = low + (high - low) u, ratio = 2^(semitones / 12) -> dict of
+    (n,) fp64 arrays semitones, ratio.  Equal generator states give equal draws.  The range must lie inside [-12, 12]."""
+    if not isinstance(generator, torch.Generator) or generator.device.type != "cpu":
+        raise TypeError("perturb_pitch: generator must be a CPU torch.Generator")
+    lo, hi = _range("perturb_pitch", "semitones", semitones)
+    if lo < -12.0 or hi > 12.0:
+        raise ValueError(f"perturb_pitch: semitones {semitones!r} outside [-12, 12] (a pitch ratio in [0.5, 2])")
+    st = np.empty(n)
+    for i in range(n):
+        st[i] = lo + (hi - lo) * float(torch.rand(1, dtype=torch.float64, generator=generator))
+    return dict(semitones=st, ratio=np.clip(2.0 ** (st / 12.0), PSOLA_MIN_RATIO, PSOLA_MAX_RATIO))
+
+
+def perturb_pitch(wav, lengths, generator, semitones=PITCH_PERTURB_SEMITONES, tracker="yin", tracker_options=None, sample_rate=22050):
+    """Information perturbation for an F0-conditioned model: each clip's pitch moved by a random number of semitones with its
+    formants and its length kept, so that what an encoder sees no longer tells the pitch the decoder must produce.  wav (B, L)
+    float32 GPU tensor, lengths (B,) integers on the host or None.  The clips' F0 is tracked with f0 (tracker="yin") or f0_track
+    ("viterbi") under tracker_options (their keyword arguments: hop_size, frame_length, fmin, fmax, ...); the shifts are
+    pitch_draws(B, generator, semitones): a CPU torch.Generator, one draw per clip in clip order, so equal seeds give equal batches;
+    then pitch_shift_psola(wav, f0, ratio) -> (out (B, L), params: semitones, ratio (B,) fp64 numpy and f0, the tracked (B, T)
+    tensor).  Every argument is checked before anything is launched; pitch_shift, random_augment and augment_draws are untouched."""
+    as_numpy, B, L, lens = _clip_batch("perturb_pitch", wav, lengths, 0)
+    if as_numpy:
+        raise TypeError("perturb_pitch: expected a float32 tensor (B, L)")
+    if tracker not in ("yin", "viterbi"):
+        raise ValueError(f"perturb_pitch: tracker must be 'yin' or 'viterbi', got {tracker!r}")
+    opts = dict(tracker_options or {})
+    if not set(opts) <= {"hop_size", "frame_length", "fmin", "fmax", "threshold", "octave_cost", "jump_cost", "vuv_cost", "unvoiced_cost"}:
+        raise ValueError(f"perturb_pitch: tracker_options {sorted(opts)} has a key the trackers do not take")
+    hop, fmin, fmax = opts.get("hop_size", 256), opts.get("fmin", 65.0), opts.get("fmax", 500.0)
+    if isinstance(hop, bool) or not isinstance(hop, (int, np.integer)) or not ops.PSOLA_MIN_HOP <= hop <= ops.PSOLA_MAX_HOP:
+        raise ValueError(f"perturb_pitch: hop_size must be an integer in [{ops.PSOLA_MIN_HOP}, {ops.PSOLA_MAX_HOP}], got {hop!r}")
+    psola_periods(sample_rate, fmin, fmax)
+    if L < 1:
+        raise ValueError("perturb_pitch: an empty waveform")
+    state = generator.get_state() if isinstance(generator, torch.Generator) else None
+    params = pitch_draws(B, generator, semitones)
+    try:
+        track = (f0 if tracker == "yin" else f0_track)(wav, sample_rate=sample_rate, lengths=lens, **opts)[0]
+    except Exception:
+        generator.set_state(state)                     # a refused call draws nothing
+        raise
+    out = pitch_shift_psola(wav, track, ratio=params["ratio"], sample_rate=sample_rate, hop_size=int(hop), lengths=lens, fmin=fmin, fmax=fmax)
+    params["f0"] = track
+    return out, params
+
+
 def mix_noise(wav, noise, level, offset, gain_db=0.0, lengths=None, device="cuda:0"):
     """Gain, then a noise recording added at `level` relative to the clip's RMS: util.py:185-196 (NoiseInjection.inject_noise_sample)
     with sox's `gain` (util.py:112-113) applied in front (include/nsg.h: nsg_audio_mix_noise):

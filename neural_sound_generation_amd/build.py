@@ -24,7 +24,7 @@ LIB = os.path.join(PKG, "libnsg.so")
 # libnsg.so: the product library exports exactly what include/nsg.h declares.
 OBJ_DIAG = os.path.join(CSRC, "_obj_diag")
 LIB_DIAG = os.path.join(PKG, "libnsg_diag.so")
-SOURCES = ["api_common.hip", "gemm_gather.hip", "gemm_patch.hip", "gemm_wgrad.hip", "gemm_wgrad_strip.hip", "gemm_flat.hip", "vq.hip", "segsum.hip", "vq_revive.hip", "vq_bf16.hip", "bn.hip", "elementwise.hip", "optim.hip", "conv_api.hip", "vae_latent.hip", "stencil_c1.hip", "c1_mfma.hip", "prior_ops.hip", "prior_sample.hip", "audio.hip", "resample.hip", "collate.hip", "dtw.hip", "f0.hip", "f0_track.hip", "tsm.hip", "stoi.hip", "f0_cond.hip"]
+SOURCES = ["api_common.hip", "gemm_gather.hip", "gemm_patch.hip", "gemm_wgrad.hip", "gemm_wgrad_strip.hip", "gemm_flat.hip", "vq.hip", "segsum.hip", "vq_revive.hip", "vq_bf16.hip", "bn.hip", "elementwise.hip", "optim.hip", "conv_api.hip", "vae_latent.hip", "stencil_c1.hip", "c1_mfma.hip", "prior_ops.hip", "prior_sample.hip", "audio.hip", "resample.hip", "collate.hip", "dtw.hip", "f0.hip", "f0_track.hip", "tsm.hip", "stoi.hip", "f0_cond.hip", "psola.hip"]
 DIAG_SOURCES = SOURCES + ["diag.hip"]
 # f0.hip's loop is scalar subtract / multiply / add triples on adjacent registers; packed into v_pk_* by the SLP vectoriser it
 # pays for the shuffles and runs slower

@@ -457,7 +457,7 @@ def speaker_f0_stats(wav_loader, n_speakers, device, tracker="yin", tracker_opti
 
 
 def test_conversion_f0(args, vqvae, pair_loader, device, epoch, iters=None, angles0=None, *, tracker="yin", tracker_options=None, momentum=0.0, init="random",
-                       f0_stats=None):
+                       f0_stats=None, psola_baseline=False):
     """The pitch figures of a speaker-conditioned VQ-VAE over parallel utterances, from waveforms: `pair_loader` yields
     (wav_src (B, Ls), len_src (B,), wav_tgt (B, Lt), len_tgt (B,), g_tgt (B,) int64) -- the same sentences by a source and a target
     speaker as zero-padded float32 waveforms at 22 050 Hz with their lengths in samples (host integers), and the target speakers'
@@ -486,7 +486,12 @@ def test_conversion_f0(args, vqvae, pair_loader, device, epoch, iters=None, angl
     speaker's mean and standard deviation of log2 F0 (speaker_f0_stats) -- the contour is first moved to the target speaker's
     statistics, each source clip's own moments (audio.logf0_sums) being the source side (audio.f0_affine); f0_stats=None keeps the
     source's contour (the identity move).  ValueError before anything is launched: f0_stats for a model without the table or of
-    another shape; before anything of the batch: a target speaker of the batch whose statistics are not finite."""
+    another shape; before anything of the batch: a target speaker of the batch whose statistics are not finite.
+    psola_baseline=True adds a third set, "psola_source", with the same five figures: the source waveform moved by signal
+    processing alone -- audio.pitch_shift_psola to the contour the decoder would be given (the source's track under audio.f0_affine
+    of the target speaker's f0_stats, over all of its frames; without f0_stats the source's own) -- then audio.melspectrogram and
+    the tracker, scored against the target exactly as "source" is.  It is the row a conversion has to beat on pitch without the
+    help of a model.  With the flag off nothing of it runs and the dict is what it was."""
     from . import audio
     momentum = audio._momentum("test_conversion_f0", momentum)
     audio._init("test_conversion_f0", init, angles0)
@@ -502,7 +507,7 @@ def test_conversion_f0(args, vqvae, pair_loader, device, epoch, iters=None, angl
             raise ValueError(f"test_conversion_f0: f0_stats must be ({vqvae.n_speakers}, 2): mean and std of log2 F0 per speaker")
     hop, fft = 256, 1024
     iters = audio.GRIFFIN_LIM_ITERS if iters is None else int(iters)
-    total = torch.zeros(2, 12, dtype=torch.float64, device=device)          # per set: the ten sums, the sums of the clips' MCD and convergence
+    total = torch.zeros(3 if psola_baseline else 2, 12, dtype=torch.float64, device=device)          # per set: the ten sums, the sums of the clips' MCD and convergence
     n = 0
     for k, (wav_src, len_src, wav_tgt, len_tgt, g_tgt) in enumerate(pair_loader):
         ls = np.asarray(len_src.cpu() if torch.is_tensor(len_src) else len_src).astype(np.int64)
@@ -535,6 +540,16 @@ def test_conversion_f0(args, vqvae, pair_loader, device, epoch, iters=None, angl
                 tgt = torch.from_numpy(target).to(device)
                 affine = audio.f0_affine(audio.logf0_sums(f0_c_in, fc), tgt[:, 0], tgt[:, 1])
             bins = audio.f0_bins(f0_c_in, frames=fc, n_bins=vqvae.n_f0_bins, fmin=vqvae.f0_range[0], fmax=vqvae.f0_range[1], affine=affine)
+        sets = []
+        if psola_baseline:
+            f0_goal = f0_s
+            if f0_stats is not None:
+                tgt = torch.from_numpy(target).to(device)
+                aff = audio.f0_affine(audio.logf0_sums(f0_s, fs), tgt[:, 0], tgt[:, 1])
+                moved = torch.exp2(aff[:, 2:3] + (torch.log2(f0_s.clamp_min(1e-30)) - aff[:, 0:1]) * aff[:, 1:2])
+                f0_goal = torch.where(f0_s > 0, moved, torch.zeros_like(f0_s)).contiguous()
+            wav_p = audio.pitch_shift_psola(wav_src, f0_s, target_f0=f0_goal, hop_size=hop, lengths=ls)
+            sets.append((audio.melspectrogram(wav_p, fft_size=fft, hop_size=hop, lengths=ls), fs, track(wav_p, hop_size=hop, lengths=ls)[0]))
         _, converted = convert_voice(vqvae, mel_s[:, :, :Tc].contiguous(), g_tgt, *(() if bins is None else (bins,)))
         a0 = angles0[k] if isinstance(angles0, (list, tuple)) else angles0
         S_c, y_c, wav_c = audio._invert_mel(converted.squeeze(1), 22050, fft, hop, 80, iters, a0, momentum, init)      # inv_mel_spectrogram's steps
@@ -542,7 +557,7 @@ def test_conversion_f0(args, vqvae, pair_loader, device, epoch, iters=None, angl
         f0_c, _ = track(wav_c, hop_size=hop, lengths=hop * (fc - 1))   # hop (Tc - 1) samples: Tc frames, fc of them the clip's
         f0_t, _ = track(wav_tgt, hop_size=hop, lengths=lt)
         cep_t = audio.mel_cepstra(mel_t, ft)
-        for row, (mel, frames, f0_x) in enumerate(((converted, fc, f0_c), (mel_s, fs, f0_s))):
+        for row, (mel, frames, f0_x) in enumerate([(converted, fc, f0_c), (mel_s, fs, f0_s)] + sets):
             cost, steps, path = ops.dtw(audio.mel_cepstra(mel, frames), cep_t, frames, ft, want_path=True)
             stats = ops.f0_path_stats(f0_x, f0_t, path, steps)
             mcd = (cost / steps.to(torch.float32)) * audio.MCD_DB
@@ -553,7 +568,7 @@ def test_conversion_f0(args, vqvae, pair_loader, device, epoch, iters=None, angl
         raise ValueError("test_conversion_f0: empty loader")
     sums = torch.cat((total, torch.stack(audio.f0_figures(total[:, :10]), dim=1)), dim=1).tolist()      # the one read-back
     out = {"clips": n}
-    for row, name in enumerate(("converted", "source")):
+    for row, name in enumerate(("converted", "source") + (("psola_source",) if psola_baseline else ())):
         rmse, vuv, corr = sums[row][12:]
         out[name] = {"f0_rmse_cents": rmse, "vuv_error": vuv, "f0_corr": corr, "mcd": sums[row][10] / n, "stats": sums[row][:10]}
     out["converted"]["spectral_convergence"] = sums[0][11] / n
@@ -561,6 +576,9 @@ def test_conversion_f0(args, vqvae, pair_loader, device, epoch, iters=None, angl
           '{:.2f} cents, {:.4f}, {:.4f}, {:.4f} dB source against target ({} clips)'.format(
               *(out["converted"][k] for k in ("f0_rmse_cents", "vuv_error", "f0_corr", "mcd")),
               *(out["source"][k] for k in ("f0_rmse_cents", "vuv_error", "f0_corr", "mcd")), n))
+    if psola_baseline:
+        print('====> Conversion test set: {:.2f} cents, {:.4f}, {:.4f}, {:.4f} dB source moved by PSOLA against target'.format(
+            *(out["psola_source"][k] for k in ("f0_rmse_cents", "vuv_error", "f0_corr", "mcd"))))
     print('====> Conversion test set: spectral convergence of the inversion {:.4f} ({} Griffin-Lim iterations, momentum {:g}, init {})'.format(
         out["converted"]["spectral_convergence"], iters, momentum, init))
     return out

@@ -694,6 +694,64 @@ def tempo(wav, factor, S, O, W, lengths=None, want_positions=False, out=None):
     return res + (pos,) if want_positions else res
 
 
+PSOLA_MAX_PERIOD, PSOLA_MIN_HOP, PSOLA_MAX_HOP = 1024, 16, 2 ** 20      # include/nsg.h: nsg_audio_pitch_marks' envelope
+PSOLA_MIN_WEIGHT = 2.0 ** -_lib.NSG_PSOLA_MIN_WEIGHT_LOG2               # below it the overlap-add passes the input through
+
+
+def psola_sizes(L, P_min, P_max, alpha):
+    """(G, K_max, H_max, G_s, J_max) of include/nsg.h for rows of L samples, periods [P_min, P_max] and alpha = (num, den): the
+    least and (H_max) greatest distance of two marks, the marks a row can have, and the same for the synthesis marks."""
+    import math
+    an, ad = alpha
+    G = P_min - an * P_min // ad
+    Gs = max(1, int(math.floor(G / 4.0 + 0.5)))
+    return G, -(-L // G), P_max + an * P_max // ad, Gs, -(-L // Gs)
+
+
+def _psola_args(fn, wav, f0, lengths, hop, P):
+    _chk(wav, f"{fn}: wav"); _chk(f0, f"{fn}: f0")
+    if wav.dim() != 2 or wav.shape[0] < 1 or wav.shape[1] < 1:
+        raise _lib.NsgError(f"{fn}: wav {tuple(wav.shape)} is not (B, L) with B, L >= 1")
+    B, L = wav.shape
+    if f0.dim() != 2 or f0.shape[0] != B or f0.shape[1] < 1 or f0.device != wav.device:
+        raise _lib.NsgError(f"{fn}: f0 {tuple(f0.shape)} on {f0.device} is not ({B}, T >= 1) on {wav.device}")
+    P_u, P_min, P_max, alpha = P
+    if not (2 <= P_min <= P_max and 0 <= alpha[0] and 1 <= alpha[1] and 2 * alpha[0] <= alpha[1]):
+        raise _lib.NsgError(f"{fn}: need 2 <= P_min <= P_max and 0 <= alpha <= 1 / 2, got [{P_min}, {P_max}], {alpha[0]} / {alpha[1]}")
+    lens = None if lengths is None else _lengths_on(lengths, f"{fn}: lengths", B, 0, L, wav.device)
+    return B, L, f0.shape[1], lens, psola_sizes(L, P_min, P_max, alpha)
+
+
+def pitch_marks(wav, f0, hop, sample_rate, P_u, P_min, P_max, alpha=(1, 4), lengths=None):
+    """Pitch marks (include/nsg.h: nsg_audio_pitch_marks).  wav (B, L) fp32 zero-padded clips, f0 (B, T) fp32 Hz (not > 0:
+    unvoiced; frame t at sample t hop); lengths as ops.f0 takes them; alpha = (num, den) -> (marks (B, K_max) int32, -1 past a
+    clip's marks; n_marks (B,) int32), K_max = psola_sizes(...)[1].  The envelope is the entry point's to state and refuse."""
+    B, L, T, lens, (_, K_max, _, _, _) = _psola_args("pitch_marks", wav, f0, lengths, hop, (P_u, P_min, P_max, alpha))
+    marks = torch.empty(B, K_max, dtype=torch.int32, device=wav.device)
+    n_marks = torch.empty(B, dtype=torch.int32, device=wav.device)
+    _lib.call("nsg_audio_pitch_marks", _p(wav), _p(lens), _p(f0), _p(marks), _p(n_marks), B, L, T, int(hop), float(sample_rate), int(P_u), int(P_min),
+              int(P_max), int(alpha[0]), int(alpha[1]), K_max, _stream())
+    return marks, n_marks
+
+
+def psola(wav, f0, f0_out, marks, n_marks, hop, sample_rate, P_u, P_min, P_max, alpha=(1, 4), lengths=None):
+    """Pitch-synchronous overlap-add (include/nsg.h: nsg_audio_psola).  wav, f0, lengths and the constants as ops.pitch_marks took
+    them, marks and n_marks as it returned them, f0_out (B, T) fp32 Hz: the track the output is to have -> (out (B, L) fp32, zeros
+    past each clip; syn (B, J_max) int32: the synthesis marks, map (B, J_max) int32: the mark each takes its grain from, both -1
+    past a clip's n_syn (B,) int32), J_max = psola_sizes(...)[4]."""
+    B, L, T, lens, (_, K_max, _, _, J_max) = _psola_args("psola", wav, f0, lengths, hop, (P_u, P_min, P_max, alpha))
+    _chk(f0_out, "psola: f0_out"); _chk(marks, "psola: marks", torch.int32); _chk(n_marks, "psola: n_marks", torch.int32)
+    if f0_out.shape != f0.shape or tuple(marks.shape) != (B, K_max) or tuple(n_marks.shape) != (B,) or len({t.device for t in (wav, f0_out, marks, n_marks)}) != 1:
+        raise _lib.NsgError(f"psola: f0_out {tuple(f0_out.shape)} / marks {tuple(marks.shape)} / n_marks {tuple(n_marks.shape)} do not go with f0 "
+                            f"{tuple(f0.shape)} and K_max = {K_max} on {wav.device}")
+    out = torch.empty(B, L, dtype=torch.float32, device=wav.device)
+    syn, mp = (torch.empty(B, J_max, dtype=torch.int32, device=wav.device) for _ in range(2))
+    n_syn = torch.empty(B, dtype=torch.int32, device=wav.device)
+    _lib.call("nsg_audio_psola", _p(wav), _p(lens), _p(f0), _p(f0_out), _p(marks), _p(n_marks), _p(syn), _p(mp), _p(n_syn), _p(out), B, L, T, int(hop),
+              float(sample_rate), int(P_u), int(P_min), int(P_max), int(alpha[0]), int(alpha[1]), K_max, J_max, _stream())
+    return out, syn, mp, n_syn
+
+
 def mix_noise(wav, noise, gain, level, offset, lengths=None, out=None, want_energy=False):
     """Gain and noise at a level relative to each clip's RMS (include/nsg.h: nsg_audio_mix_noise).  wav (B, L) fp32 zero-padded
     clips, noise (Ln,) fp32 on the same device (one recording, read cyclically from offset[b]); gain, level: B numbers on the

@@ -16,6 +16,8 @@ from __future__ import annotations
 
 import os
 
+import numpy as np
+
 import torch
 import torch.nn.functional as F
 
@@ -117,10 +119,14 @@ class FusedTrainStep:
         self._kept_rows = None
 
     @torch.no_grad()
-    def forward_backward(self, c: torch.Tensor, g: torch.Tensor | None = None, f0_bins: torch.Tensor | None = None):
+    def forward_backward(self, c: torch.Tensor, g: torch.Tensor | None = None, f0_bins: torch.Tensor | None = None,
+                         target: torch.Tensor | None = None):
         """c: (B,1,80,T) float32 on the GPU; g: optional (B,) int64 speaker ids (speaker-conditioned
         decoder extension); f0_bins: optional (B, T // 4) int64 F0 bins in [0, n_f0_bins] on the GPU, one per latent column
-        (F0-conditioned decoder extension, audio.f0_bins; the kernel clamps them, nothing here reads them back).  Fills the flat
+        (F0-conditioned decoder extension, audio.f0_bins; the kernel clamps them, nothing here reads them back); target: optional
+        (B,1,80,T) float32 on c's device, what the reconstruction loss compares the decoder's output against in place of c (the
+        encoder still sees c: a perturbed input with the clean mel as the target, audio.perturb_pitch).  It takes c's place as the
+        output layer's mse_target: no launch is added, and None is the step as it was, bit for bit.  Fills the flat
         gradient bucket; returns the three loss tensors (device scalars; nothing here synchronises with the host)."""
         model = self.model
         if not model.training:
@@ -133,10 +139,15 @@ class FusedTrainStep:
             if not isinstance(f0_bins, torch.Tensor) or tuple(f0_bins.shape) != (B, T // 4) or f0_bins.dtype != torch.int64 or f0_bins.device != x.device:
                 raise ValueError(f"FusedTrainStep: f0_bins must be an int64 tensor of shape ({B}, {T // 4}) on the batch's device")
             f0_bins = f0_bins.contiguous()
+        if target is not None:
+            if (not isinstance(target, torch.Tensor) or target.shape != c.shape or target.dtype != torch.float32 or target.device != c.device):
+                raise ValueError(f"FusedTrainStep: target must be a float32 tensor of c's shape {tuple(c.shape)} on the batch's device")
+            target = Fn.to_nhwc(target)
         with engine.deferred_batch_counters():
-            return self._forward_backward(x, g, B, H, T, f0_bins)
+            return self._forward_backward(x, g, B, H, T, f0_bins, target)
 
-    def _forward_backward(self, x, g, B, H, T, bins=None):
+    def _forward_backward(self, x, g, B, H, T, bins=None, target=None):
+        tgt = x if target is None else target          # what the reconstruction loss compares against
         enc_packs, dec_packs = engine.pack_all(self.encP, self.decP, B, H, T, self.dtype)
         K, D = self.codebook.shape
         search = getattr(self.model.codebook, "search_impl", "mfma")
@@ -192,13 +203,13 @@ class FusedTrainStep:
         elif spk_rows is not None and not lean:
             zdec = ops.add_per_clip(zq, spk_rows, out_dtype=self.dtype)
         # loss_recons = mse(zero-pad(x_tilde), c) and d/dx_tilde             (train.py:118-129)
-        xt, ds = engine.decoder_forward(zdec, self.decP, True, dtype=self.dtype, packs=dec_packs, zq_is_relu=lean, mse_target=x,
+        xt, ds = engine.decoder_forward(zdec, self.decP, True, dtype=self.dtype, packs=dec_packs, zq_is_relu=lean, mse_target=tgt,
                                         mse_dbias=self.g_dec.convt6.bias)
         if isinstance(xt, engine.FusedLoss):    # the fused output layer formed the loss and the gradient at the Tanh's input with the image
             loss_recons = xt.loss
             dzq, _ = engine.decoder_backward(xt.dpre, ds, self.decP, need_dz=True, dxt_is_pre_tanh=True, gout=self.g_dec)
         else:
-            loss_recons, dxt = ops.mse_padded(xt, x, B * H, xt.shape[2], T)
+            loss_recons, dxt = ops.mse_padded(xt, tgt, B * H, xt.shape[2], T)
             dzq, _ = engine.decoder_backward(dxt, ds, self.decP, need_dz=True, gout=self.g_dec)
         colsum = None
         if self.f0 is not None:
@@ -265,10 +276,12 @@ class FusedTrainStep:
     # torch.cuda.CUDAGraph: every ctypes launch goes to torch's current stream, which is the capturing stream).  The
     # optimiser step stays outside (its bias-correction scalars change every step), as do the collectives.
     @torch.no_grad()
-    def capture(self, c: torch.Tensor, g: torch.Tensor | None = None, warmup: int = 2, f0_bins: torch.Tensor | None = None):
-        """Capture forward_backward for inputs of c's shape.  The warm-up steps are REAL training steps.  g and f0_bins are kept
-        in static buffers every replay refills; a graph captured with (without) either is replayed only for a step that gives
-        (omits) it too -- any other step runs eagerly."""
+    def capture(self, c: torch.Tensor, g: torch.Tensor | None = None, warmup: int = 2, f0_bins: torch.Tensor | None = None,
+                target: torch.Tensor | None = None):
+        """Capture forward_backward for inputs of c's shape.  The warm-up steps are REAL training steps.  g, f0_bins and target are
+        kept in static buffers every replay refills; a graph captured with (without) any of them is replayed only for a step that
+        gives (omits) it too -- any other step runs eagerly.  So a graph captured without a target is never replayed for a step
+        that has one: its launches carry c's buffer as the loss target."""
         # The captured launches carry the scratch buffer's ADDRESS, and ops.WS keeps one buffer per (device, stream).  So the
         # warm-up steps (first-use work: LDS attributes, workspace growth -- and they are REAL training steps) run on the very
         # stream the capture then uses: the capture finds the warmed-up buffer under its own key and must not outgrow it.  A
@@ -278,10 +291,11 @@ class FusedTrainStep:
         self._graph_stream.wait_stream(torch.cuda.current_stream(c.device))
         with torch.cuda.stream(self._graph_stream):
             for _ in range(warmup):
-                self.step(c, g, f0_bins)
+                self.step(c, g, f0_bins, target)
             self._static_c = c.clone()
             self._static_g = g.clone() if g is not None else None
             self._static_bins = f0_bins.clone() if f0_bins is not None else None
+            self._static_target = target.clone() if target is not None else None
             ws = ops.WS.current(c.device)              # (this stream's buffer)
         torch.cuda.current_stream(c.device).wait_stream(self._graph_stream)
         torch.cuda.synchronize()
@@ -289,7 +303,7 @@ class FusedTrainStep:
         self._keep_rows = self.reviver is not None
         try:
             with torch.cuda.graph(self._graph, stream=self._graph_stream):
-                self._graph_losses = self.forward_backward(self._static_c, self._static_g, self._static_bins)
+                self._graph_losses = self.forward_backward(self._static_c, self._static_g, self._static_bins, self._static_target)
                 ws_after = ops.WS.current(c.device)
         finally:
             self._keep_rows = False
@@ -300,27 +314,31 @@ class FusedTrainStep:
         self._graph_ws = ws
         return self
 
-    def _replay(self, c, g, f0_bins=None):
+    def _replay(self, c, g, f0_bins=None, target=None):
         self._static_c.copy_(c)
         if g is not None:
             self._static_g.copy_(g)
         if f0_bins is not None:
             self._static_bins.copy_(f0_bins)
+        if target is not None:
+            self._static_target.copy_(target)
         self._graph.replay()
         return self._graph_losses
 
     @torch.no_grad()
-    def step(self, c: torch.Tensor, g: torch.Tensor | None = None, f0_bins: torch.Tensor | None = None):
+    def step(self, c: torch.Tensor, g: torch.Tensor | None = None, f0_bins: torch.Tensor | None = None, target: torch.Tensor | None = None):
         revive = self.reviver is not None and self.reviver.next_step_revives()
         if (getattr(self, "_graph", None) is not None and c.shape == self._static_c.shape and (g is None) == (self._static_g is None)
                 and (f0_bins is None) == (self._static_bins is None)
-                and (f0_bins is None or (f0_bins.shape == self._static_bins.shape and f0_bins.dtype == torch.int64))):
-            losses = self._replay(c, g, f0_bins)
+                and (f0_bins is None or (f0_bins.shape == self._static_bins.shape and f0_bins.dtype == torch.int64))
+                and (target is None) == (getattr(self, "_static_target", None) is None)
+                and (target is None or (target.shape == self._static_target.shape and target.dtype == torch.float32))):
+            losses = self._replay(c, g, f0_bins, target)
             rows = self._graph_rows if revive else None
         else:
             self._stepping, self._keep_rows = True, revive
             try:
-                losses = self.forward_backward(c, g, f0_bins)
+                losses = self.forward_backward(c, g, f0_bins, target)
             finally:
                 self._stepping = self._keep_rows = False
             rows, self._kept_rows = self._kept_rows, None
@@ -385,7 +403,7 @@ def train_vqvae(args, model, optimizer, train_loader, device, epoch):
     return train_loss
 
 
-def train_conditioned(args, model, step, train_loader, device, epoch, tracker="yin", tracker_options=None):
+def train_conditioned(args, model, step, train_loader, device, epoch, tracker="yin", tracker_options=None, pitch_perturb=None, generator=None):
     """One epoch of a speaker- and / or F0-conditioned VQ-VAE on the fused step (an extension: train_vqvae above stays the
     reference's, which ignores g).  `train_loader` yields (x, y, c, g, input_lengths) as for train_vqvae, or the six-tuple
     (x, y, c, g, input_lengths, f0_bins) of a resident loader with an F0 track (data.ResidentMelLoader(f0=)); `step` is the model's
@@ -396,14 +414,45 @@ def train_conditioned(args, model, step, train_loader, device, epoch, tracker="y
     model's n_f0_bins and f0_range, each clip's input_lengths // 256 frames valid) and step.step(c, g, f0_bins=bins) runs.
     (The two sources differ at a crop's edge frames: data.ResidentMelCorpus.track_f0.)
     Returns the last batch's loss_recons + loss_vq, as train_vqvae does.  ValueError before anything is launched: a tracker or
-    options that do not exist; a model with an F0 table and a batch with neither bins nor audio (get_data_loaders(with_audio=True))."""
+    options that do not exist; a model with an F0 table and a batch with neither bins nor audio (get_data_loaders(with_audio=True)).
+    pitch_perturb=(low, high) in semitones (None, the default: the loop as it was): information perturbation.  The bins still
+    come from the batch as given; then the encoder's input is replaced by c' = the first T frames of audio.melspectrogram of
+    audio.perturb_pitch(x, input_lengths, generator, pitch_perturb, tracker, tracker_options) -- each clip's pitch moved by a
+    random shift with its formants and length kept -- while the loss target stays c: step.step(c', g, f0_bins=bins, target=c).
+    The codes then no longer tell the pitch of the mel to be reproduced, and an F0-conditioned decoder has to take it from the
+    bins.  generator: the CPU torch.Generator of the shifts (None: a new one seeded with `epoch`).  It needs the batch's audio:
+    a batch without x (a resident loader, which keeps no audio; a host loader built without with_audio=True) is a ValueError
+    before anything of that batch is launched, as are a range outside [-12, 12] and a generator that is not a CPU one."""
+    from . import audio
     from .evaluate import _f0_tracker, batch_conditioning
     track = _f0_tracker("train_conditioned", tracker, tracker_options)
+    if pitch_perturb is not None:
+        lo, hi = audio._range("train_conditioned", "pitch_perturb", pitch_perturb)
+        if lo < -12.0 or hi > 12.0:
+            raise ValueError(f"train_conditioned: pitch_perturb {pitch_perturb!r} outside [-12, 12] semitones")
+        if generator is None:
+            generator = torch.Generator().manual_seed(int(epoch))
+        elif not isinstance(generator, torch.Generator) or generator.device.type != "cpu":
+            raise ValueError("train_conditioned: generator must be a CPU torch.Generator")
     model.train()
     train_loss, last = 0, None
     for batch_idx, batch in enumerate(train_loader):
+        if pitch_perturb is not None and batch[0] is None:
+            raise ValueError("train_conditioned: pitch_perturb needs the batch's audio and the loader yields none: "
+                             "get_data_loaders(with_audio=True) (a resident loader keeps no audio)")
         c, g_d, bins = batch_conditioning("train_conditioned", model, batch, device, track)
-        loss_recons, loss_vq, _ = step.step(c, g_d, f0_bins=bins) if bins is not None else step.step(c, g_d)
+        if pitch_perturb is not None:
+            T = c.shape[3]
+            lens = np.asarray(batch[4].cpu() if torch.is_tensor(batch[4]) else batch[4]).astype(np.int64)
+            wav = batch[0].view(batch[0].shape[0], -1).to(device).contiguous()
+            moved, _ = audio.perturb_pitch(wav, lens, generator, (lo, hi), tracker, tracker_options)
+            mel = audio.melspectrogram(moved, lengths=lens)
+            if mel.shape[2] < T:
+                raise ValueError(f"train_conditioned: the batch's audio gives {mel.shape[2]} mel frames, its mel has {T}")
+            c_in = mel[:, None, :, :T].contiguous()
+            loss_recons, loss_vq, _ = step.step(c_in, g_d, f0_bins=bins, target=c)
+        else:
+            loss_recons, loss_vq, _ = step.step(c, g_d, f0_bins=bins) if bins is not None else step.step(c, g_d)
         last = loss_recons + loss_vq
         if batch_idx % args.log_interval == 0:      # (the only read-back: the fused step itself never waits for the device)
             print('Train Epoch: {} [{}/{}]\tLoss: {:.6f}'.format(epoch, batch_idx * len(c), len(train_loader.dataset), float(last)))
