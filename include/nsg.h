@@ -931,6 +931,25 @@ NSG_API int nsg_audio_trim_bounds(const float *wav, const int32_t *lengths, int3
 NSG_API int nsg_collate_mels(const float *corpus, int64_t corpus_frames, int32_t n_mels, const int64_t *plan, int32_t B, int32_t T,
                              float *out, void *stream);
 
+/* The same batch's waveform (collate_fn's audio: x[s hop : (s + count) hop], zero-padded to the batch's longest) from the clips'
+ * samples kept beside the mels.  corpus [corpus_samples] fp32: the clips' on-disk audio arrays concatenated in the mel corpus'
+ * clip order; every clip has frames * hop samples, so the clip whose mels start at corpus frame f starts at sample f * hop and
+ * corpus_samples = corpus_frames * hop.  plan [B][3] int64, DEVICE memory: nsg_collate_mels' own rows (clip, start, count) in
+ * FRAMES, clip not read.  out [B][T * hop] fp32, the memory of the loader's x (B, 1, T hop) and y (B, T hop, 1):
+ *     out[b][i] = corpus[start_b * hop + i]   for i < count_b * hop,        +0.0f   for count_b * hop <= i < T * hop
+ * A copy, bit for bit; every element of out is written exactly once (out need not be initialised).  One launch, no workspace,
+ * no LDS; a lane has four independent accesses in flight; neither B nor a row's length is bound by a grid dimension; every
+ * corpus and out offset is 64-bit (both may pass 2^31 elements).  16-byte accesses are used only where every such access is
+ * aligned (loads: hop % 4 == 0 and corpus 16-byte aligned; stores: (T * hop) % 4 == 0 and out 16-byte aligned); any hop >= 1, any
+ * T and any alignment of 4 is served.
+ * NSG_E_INVALID: a null pointer, B < 1, T < 1, hop < 1, corpus_samples < 0, T * hop not below 2^31, a pointer not aligned to its
+ * element (4 bytes; plan 8).
+ * PRECONDITION the entry point cannot check (plan is device memory): nsg_collate_mels', with corpus_frames = corpus_samples / hop;
+ * the caller checks its host copy.  (The kernel clamps count_b into [0, T] and reads a sample outside [0, corpus_samples) as
+ * +0.0, so whatever the plan holds no access leaves either buffer.) */
+NSG_API int nsg_collate_audio(const float *corpus, int64_t corpus_samples, int32_t hop, const int64_t *plan, int32_t B, int32_t T,
+                              float *out, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Judging a converted utterance: mel cepstra and dynamic time warping (extension; the reference has no objective figure
  * for the speaker-conditioned decoder).  evaluate.test_conversion reports the mel-cepstral distortion of parallel pairs.

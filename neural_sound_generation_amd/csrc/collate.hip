@@ -74,7 +74,126 @@ __global__ __launch_bounds__(CT_THREADS) void collate_mels_kernel(const float *_
     }
 }
 
+// The same batch's waveform from the clips' samples resident beside the mels (data.py: ResidentMelCorpus.keep_audio): row b of
+// out is the run corpus[start_b hop : (start_b + count_b) hop] followed by zeros up to T hop -- no transpose, so no LDS: a
+// streaming copy, 2 x B x T x hop x 4 bytes of compulsory traffic.  A row is cut into units of W floats (W = 4 where either side
+// moves 16 bytes a lane, else 1) and into chunks of CA_THREADS * CA_UNROLL units; a workgroup owns a chunk, and a lane owns
+// CA_UNROLL units CA_THREADS apart, so each wave instruction covers one contiguous run.  A chunk that lies wholly inside the
+// row's samples (and the corpus), or wholly inside its padding, is straight-line code: CA_UNROLL independent loads in flight,
+// then the stores, no predicate and no wait between them (behind per-unit predicates the compiler waits for every earlier
+// access, stores included, before each store).  Only the chunk that holds the samples' end or the row's end takes the
+// predicated path: a unit past the samples is stored as zeros without a load, one past the row's end is skipped.  No loop's
+// trip count depends on the lane.
+constexpr int CA_THREADS = 256;
+constexpr int CA_UNROLL = 4;
+constexpr int CA_MAX_BLOCKS = 1 << 16;   // the workgroups stride over the chunks: neither B nor a row's length is bound by a grid dimension
+
+template <bool V, int W> __device__ __forceinline__ void ca_load(const float *p, float *v)
+{
+    if (V) Elem<float>::load16(p, v);
+    else
+#pragma unroll
+        for (int e = 0; e < W; ++e) v[e] = p[e];
+}
+template <bool V, int W> __device__ __forceinline__ void ca_store(float *p, const float *v)
+{
+    if (V) Elem<float>::store16(p, v);
+    else
+#pragma unroll
+        for (int e = 0; e < W; ++e) p[e] = v[e];
+}
+
+template <bool VL, bool VS>
+__global__ __launch_bounds__(CA_THREADS) void collate_audio_kernel(const float *__restrict__ corpus, int64_t corpus_samples, int64_t corpus_frames,
+                                                                    int hop, const int64_t *__restrict__ plan, int64_t n_chunks, int chunks_row,
+                                                                    int T, int64_t L, float *__restrict__ out)
+{
+    constexpr int W = (VL || VS) ? 4 : 1, STEP = CA_THREADS * W, CHUNK = STEP * CA_UNROLL;
+    for (int64_t w = blockIdx.x; w < n_chunks; w += gridDim.x) {
+        const int64_t b = w / chunks_row;
+        // collate_mels_kernel's clamps: whatever the plan holds, no access leaves either buffer
+        int64_t start = plan[b * 3 + 1], count = plan[b * 3 + 2];
+        count = count < 0 ? 0 : (count > T ? T : count);
+        start = start < -((int64_t)1 << 31) ? -((int64_t)1 << 31) : (start > corpus_frames ? corpus_frames : start);
+        const int64_t n = count * hop;                                   // the row's samples, <= L < 2^31
+        const int64_t s0 = start * hop;                                  // |start| <= 2^31 + corpus_frames and hop < 2^31: no overflow
+        const int64_t c0 = (w - b * chunks_row) * CHUNK, c1 = c0 + CHUNK; // the chunk: elements [c0, c1) of the row
+        const int64_t i0 = c0 + threadIdx.x * W;
+        float *__restrict__ dst = out + b * L;
+        float v[CA_UNROLL][W];
+        if (c1 <= n && s0 + c0 >= 0 && s0 + c1 <= corpus_samples) {      // n <= L.  (hop % 4 == 0 where VL: s0 + i is a multiple of 4)
+#pragma unroll
+            for (int u = 0; u < CA_UNROLL; ++u) ca_load<VL, W>(corpus + s0 + i0 + u * STEP, v[u]);
+#pragma unroll
+            for (int u = 0; u < CA_UNROLL; ++u) ca_store<VS, W>(dst + i0 + u * STEP, v[u]);
+        } else if (c0 >= n && c1 <= L) {
+#pragma unroll
+            for (int e = 0; e < W; ++e) v[0][e] = 0.f;
+#pragma unroll
+            for (int u = 0; u < CA_UNROLL; ++u) ca_store<VS, W>(dst + i0 + u * STEP, v[0]);
+        } else {
+#pragma unroll
+            for (int u = 0; u < CA_UNROLL; ++u) {
+                const int64_t i = i0 + u * STEP, s = s0 + i;
+#pragma unroll
+                for (int e = 0; e < W; ++e) v[u][e] = 0.f;
+                if (i < n) {
+                    // where VL, i + 4 <= n and s is a multiple of 4; only a corpus whose end is not can cut a unit
+                    if (VL && s >= 0 && s + W <= corpus_samples) {
+                        Elem<float>::load16(corpus + s, v[u]);
+                    } else {
+#pragma unroll
+                        for (int e = 0; e < W; ++e)
+                            if (i + e < n && s + e >= 0 && s + e < corpus_samples) v[u][e] = corpus[s + e];
+                    }
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < CA_UNROLL; ++u) {
+                const int64_t i = i0 + u * STEP;
+                if (VS) {                                                // L % 4 == 0: a unit that starts inside the row ends inside it
+                    if (i < L) Elem<float>::store16(dst + i, v[u]);
+                } else {
+#pragma unroll
+                    for (int e = 0; e < W; ++e)
+                        if (i + e < L) dst[i + e] = v[u][e];
+                }
+            }
+        }
+    }
+}
+
 }  // namespace
+
+int nsg_collate_audio(const float *corpus, int64_t corpus_samples, int32_t hop, const int64_t *plan, int32_t B, int32_t T, float *out,
+                      void *stream)
+{
+    NSG_REQUIRE(corpus && plan && out, NSG_E_INVALID, "nsg_collate_audio: null pointer");
+    NSG_REQUIRE(B >= 1 && T >= 1 && hop >= 1 && corpus_samples >= 0, NSG_E_INVALID,
+                "nsg_collate_audio: bad size (B = %d, T = %d, hop = %d, corpus_samples = %lld)", B, T, hop, (long long)corpus_samples);
+    const int64_t L = (int64_t)T * hop;
+    NSG_REQUIRE(L < ((int64_t)1 << 31), NSG_E_INVALID, "nsg_collate_audio: T * hop = %lld is not below 2^31", (long long)L);
+    NSG_REQUIRE((reinterpret_cast<uintptr_t>(corpus) & 3u) == 0 && (reinterpret_cast<uintptr_t>(out) & 3u) == 0 &&
+                    (reinterpret_cast<uintptr_t>(plan) & 7u) == 0,
+                NSG_E_INVALID, "nsg_collate_audio: a pointer is not aligned to its element (4 bytes; plan 8)");
+    // 16 bytes a lane only where every such access is aligned: a row's first sample start_b * hop is a multiple of 4 floats and
+    // the corpus starts on 16 bytes; a row of out is a multiple of 16 bytes and out starts on one
+    const bool vl = hop % 4 == 0 && nsg_aligned16(corpus), vs = L % 4 == 0 && nsg_aligned16(out);
+    const int W = (vl || vs) ? 4 : 1;
+    const int chunks_row = (int)nsg_cdiv(nsg_cdiv(L, W), CA_THREADS * CA_UNROLL);
+    const int64_t n_chunks = (int64_t)B * chunks_row;
+    const dim3 grid((unsigned)(n_chunks < CA_MAX_BLOCKS ? n_chunks : CA_MAX_BLOCKS)), block(CA_THREADS);
+    const hipStream_t s = (hipStream_t)stream;
+    const int64_t corpus_frames = corpus_samples / hop;
+#define NSG_CA_LAUNCH(VL, VS) \
+    hipLaunchKernelGGL((collate_audio_kernel<VL, VS>), grid, block, 0, s, corpus, corpus_samples, corpus_frames, hop, plan, n_chunks, chunks_row, T, L, out)
+    if (vl && vs) NSG_CA_LAUNCH(true, true);
+    else if (vl) NSG_CA_LAUNCH(true, false);
+    else if (vs) NSG_CA_LAUNCH(false, true);
+    else NSG_CA_LAUNCH(false, false);
+#undef NSG_CA_LAUNCH
+    return nsg_check_launch("collate_audio_kernel");
+}
 
 int nsg_collate_mels(const float *corpus, int64_t corpus_frames, int32_t n_mels, const int64_t *plan, int32_t B, int32_t T, float *out,
                      void *stream)

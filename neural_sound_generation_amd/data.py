@@ -22,6 +22,8 @@ Pieces (names and behaviour follow src/dataloader.py:97-202,324-434):
     loader's batches bit for bit), uploaded once, and a batch is one launch of csrc/collate.hip (ops.collate_mels).
     `ResidentMelCorpus.track_f0` keeps every clip's F0 track beside the mels; `ResidentMelLoader(f0=)` /
     `get_resident_loaders(f0=)` then add the F0-conditioned decoder's bins to each batch (ops.collate_f0_bins, one launch).
+    `ResidentMelCorpus.keep_audio` keeps the clips' samples as well; `ResidentMelLoader(audio=True)` / `get_resident_loaders(
+    audio=True)` then yield the host loader's x and y too (ops.collate_audio, one launch), which pitch-perturbed training needs.
 
 parity unpinned: the reference's loader cannot be imported here (ordinary missing dependencies); tests/test_host_logic.py
 checks the format invariants on a synthetic data root.
@@ -284,7 +286,8 @@ class ResidentMelCorpus:
     by).  `speaker_ids` (n,) int64 on `device` for a multi-speaker root, else None.  The arrays are read into host memory
     first (the corpus' size of it, freed afterwards) and staged through a pinned chunk.  device "cpu" keeps `frames` on the
     host: enough for planning and for tests, not for `ResidentMelLoader`'s batches (ops.collate_mels has no CPU path).
-    `f0`, `f0_sums`, `f0_settings`: None until `track_f0` has put the clips' F0 tracks beside the mels."""
+    `f0`, `f0_sums`, `f0_settings`: None until `track_f0` has put the clips' F0 tracks beside the mels.
+    `audio`, `audio_hop`: None until `keep_audio` has put the clips' samples there too."""
 
     CHUNK_FRAMES = 1 << 16          # the pinned staging buffer: 65 536 frames = 21 MB
 
@@ -302,12 +305,39 @@ class ResidentMelCorpus:
         self.offsets = np.concatenate([np.zeros(1, np.int64), np.cumsum(self.n_frames, dtype=np.int64)])
         total = int(self.offsets[-1])
         self.frames = torch.empty(total, NUM_MELS, dtype=torch.float32, device=self.device)
-        self._upload(arrays)
+        self._upload(arrays, self.frames, self.CHUNK_FRAMES)
         self.speaker_ids = (torch.tensor(mel_source.speaker_ids, dtype=torch.int64, device=self.device)
                             if self.multi_speaker else None)
         self.f0 = self.f0_sums = self.f0_settings = None
+        self.audio = self.audio_hop = None
 
-    def track_f0(self, audio_source: RawAudioDataSource, tracker="yin", tracker_options=None, fmin=65.0, fmax=500.0, group_clips=64,
+    def keep_audio(self, audio_source: RawAudioDataSource, hop_size: int = HOP_SIZE):
+        """Keep every clip's waveform beside the mels: `audio` (total_frames * hop_size,) fp32 on the corpus' device, the clips'
+        on-disk audio arrays concatenated in the mels' order, so that clip i is audio[offsets[i] * hop_size : offsets[i + 1] *
+        hop_size] and a batch's x is a crop by the plan rows collate_mels takes (ops.collate_audio, `ResidentMelLoader(audio=True)`);
+        `audio_hop` = hop_size.  `audio_source`: a `RawAudioDataSource` over the same split as the mels (clip i is its path i;
+        ValueError, `Collate`'s, where len(x) != frames * hop_size).  Each clip is read once and staged through a pinned chunk, one
+        clip in host memory at a time; device "cpu" keeps the array on the host (planning, host tests).  The samples stay fp32 --
+        the host loader's x is the file's fp32 and the batches are to equal it bit for bit --, 1 024 bytes a frame beside the mels'
+        320: LJSpeech is about 7.6 GB of samples beside 2.4 GB of mels."""
+        if isinstance(hop_size, bool) or not isinstance(hop_size, (int, np.integer)) or hop_size < 1:
+            raise ValueError(f"ResidentMelCorpus.keep_audio: hop_size must be a positive integer, got {hop_size!r}")
+        if len(audio_source.paths) != len(self):
+            raise ValueError(f"ResidentMelCorpus.keep_audio: {len(audio_source.paths)} audio clips for {len(self)} mels: not the same split")
+        hop_size = int(hop_size)
+
+        def clips():
+            for i, path in enumerate(audio_source.paths):
+                x = audio_source.collect_features(path)
+                if x.ndim != 1 or len(x) != int(self.n_frames[i]) * hop_size:
+                    raise ValueError("audio and mel lengths disagree: %d samples vs %d frames x hop %d" % (len(x), int(self.n_frames[i]), hop_size))
+                yield x
+        samples = torch.empty(int(self.offsets[-1]) * hop_size, dtype=torch.float32, device=self.device)
+        self._upload(clips(), samples, self.CHUNK_FRAMES * NUM_MELS)           # (the mels' staging size)
+        self.audio, self.audio_hop = samples, hop_size
+        return self
+
+    def track_f0(self, audio_source: Optional[RawAudioDataSource] = None, tracker="yin", tracker_options=None, fmin=65.0, fmax=500.0, group_clips=64,
                  group_samples=1 << 24, hop_size: int = HOP_SIZE):
         """Track every clip's F0 ONCE and keep it beside the mels: F0 frame t is mel frame t, and a frame's value depends on its
         own samples alone, so a batch's track is a crop of the clip's by the plan rows collate_mels takes (ops.collate_f0_bins) and
@@ -324,12 +354,21 @@ class ResidentMelCorpus:
         zero outside itself, here the frames at a crop's edges see the clip's real neighbours.  With "yin", crop frame t of count
         frames is bit for bit the host path's where t * hop - 512 >= 0 and t * hop + 511 + tau_max <= count * hop - 1 (tau_max:
         audio.f0_lags; at the defaults frames 2 .. count - 4); "viterbi" is a path over the whole clip and promises no such
-        equality."""
-        from . import audio
+        equality.
+        audio_source=None over a corpus with resident audio (`keep_audio`; ValueError without it, or where hop_size is not its
+        audio_hop): nothing is read from disk -- a group's zero-padded rows are one ops.collate_audio launch on whole-clip plan
+        rows (i, offsets[i], n_frames[i]), the groups follow the same rule, and f0, f0_sums and f0_settings are bit for bit those
+        of track_f0(audio_source)."""
+        from . import audio, ops
         from .evaluate import _f0_tracker
         track = _f0_tracker("ResidentMelCorpus.track_f0", tracker, tracker_options)
         audio.f0_lags(22050, fmin, fmax)                                     # (the range, checked before anything is read)
-        if len(audio_source.paths) != len(self):
+        if audio_source is None:
+            if self.audio is None:
+                raise ValueError("ResidentMelCorpus.track_f0: no audio_source and the corpus keeps no audio (keep_audio)")
+            if hop_size != self.audio_hop:
+                raise ValueError(f"ResidentMelCorpus.track_f0: hop_size = {hop_size}, the resident audio's is {self.audio_hop}")
+        elif len(audio_source.paths) != len(self):
             raise ValueError(f"ResidentMelCorpus.track_f0: {len(audio_source.paths)} audio clips for {len(self)} mels: not the same split")
         if group_clips < 1 or group_samples < 1:
             raise ValueError("ResidentMelCorpus.track_f0: group_clips and group_samples must be positive")
@@ -339,23 +378,32 @@ class ResidentMelCorpus:
         def flush():
             nonlocal group, first
             lens = np.array([len(x) for x in group], dtype=np.int64)
-            wav = np.zeros((len(group), max(1, int(lens.max()))), dtype=np.float32)
-            for j, x in enumerate(group):
-                wav[j, :len(x)] = x
-            f0, _ = track(torch.from_numpy(wav).to(self.device), hop_size=hop_size, fmin=fmin, fmax=fmax, lengths=lens)
+            if audio_source is None:                                         # (a group of empty clips: one frame of zeros, none kept)
+                clips = np.arange(first, first + len(group), dtype=np.int64)
+                rows = np.stack((clips, self.offsets[clips], self.n_frames[clips]), axis=1)
+                wav = ops.collate_audio(self.audio, torch.from_numpy(rows), max(1, int(self.n_frames[clips].max())), hop_size)
+            else:
+                wav = np.zeros((len(group), max(1, int(lens.max()))), dtype=np.float32)
+                for j, x in enumerate(group):
+                    wav[j, :len(x)] = x
+                wav = torch.from_numpy(wav).to(self.device)
+            f0, _ = track(wav, hop_size=hop_size, fmin=fmin, fmax=fmax, lengths=lens)
             keep = torch.from_numpy(self.n_frames[first:first + len(group)]).to(self.device)
             mask = torch.arange(f0.shape[1], device=self.device).unsqueeze(0) < keep.unsqueeze(1)
             f0_all[int(self.offsets[first]):int(self.offsets[first + len(group)])] = f0[mask]      # row-major: the clips in order
             group, first = [], first + len(group)
 
-        for i, path in enumerate(audio_source.paths):
-            x = audio_source.collect_features(path)
-            if x.ndim != 1 or len(x) != int(self.n_frames[i]) * hop_size:
-                raise ValueError("audio and mel lengths disagree: %d samples vs %d frames x hop %d" % (len(x), int(self.n_frames[i]), hop_size))
+        for i in range(len(self)):
+            if audio_source is None:
+                x = range(int(self.n_frames[i]) * hop_size)                  # (its length is all the grouping rule and flush need)
+            else:
+                x = audio_source.collect_features(audio_source.paths[i])
+                if x.ndim != 1 or len(x) != int(self.n_frames[i]) * hop_size:
+                    raise ValueError("audio and mel lengths disagree: %d samples vs %d frames x hop %d" % (len(x), int(self.n_frames[i]), hop_size))
             widest = max([len(x)] + [len(v) for v in group])
             if group and (len(group) + 1 > group_clips or (len(group) + 1) * widest > group_samples):
                 flush()
-            group.append(x.astype(np.float32, copy=False))
+            group.append(x if audio_source is None else x.astype(np.float32, copy=False))
         if group:
             flush()
         # (per clip, on its own row: torch's sum over a row may depend on the row's width, and nothing here may depend on the groups)
@@ -384,24 +432,25 @@ class ResidentMelCorpus:
         std = torch.sqrt(torch.clamp(s2 / n - mean * mean, min=0.0))
         return torch.stack((mean, std), dim=1), n.to(torch.int64)
 
-    def _upload(self, arrays):
+    def _upload(self, arrays, dst, chunk_rows):
+        """The rows of `arrays` (an iterable, read one at a time), in order, into `dst` through a pinned chunk of `chunk_rows` rows."""
         cuda = self.device.type == "cuda"
-        stage = torch.empty(self.CHUNK_FRAMES, NUM_MELS, dtype=torch.float32, pin_memory=cuda)
+        stage = torch.empty(chunk_rows, *dst.shape[1:], dtype=torch.float32, pin_memory=cuda)
         stage_np = stage.numpy()
-        done = fill = 0                                      # frames already on the device / waiting in the chunk
+        done = fill = 0                                      # rows already on the device / waiting in the chunk
 
         def flush():
             nonlocal done, fill
-            self.frames[done:done + fill].copy_(stage[:fill])    # blocking: the chunk is free again when it returns
+            dst[done:done + fill].copy_(stage[:fill])            # blocking: the chunk is free again when it returns
             done, fill = done + fill, 0
 
         for c in arrays:
             at = 0
             while at < len(c):
-                n = min(len(c) - at, self.CHUNK_FRAMES - fill)
+                n = min(len(c) - at, chunk_rows - fill)
                 stage_np[fill:fill + n] = c[at:at + n]
                 at, fill = at + n, fill + n
-                if fill == self.CHUNK_FRAMES:
+                if fill == chunk_rows:
                     flush()
         if fill:
             flush()
@@ -461,12 +510,25 @@ class ResidentMelLoader:
     decoder's bins of the batch's crops (one ops.collate_f0_bins launch on the plan rows already on the device; T < 4: an empty
     (B, 0) tensor and no launch), which train.train_conditioned, evaluate.test_conditioned and epoch.run_conditioned_epoch take as
     they come.  The first five elements and the draws from `random` and `rng` are those of the loader without f0.  The bins are
-    crops of the WHOLE clip's track: see track_f0 for where they are, and are not, the host path's."""
+    crops of the WHOLE clip's track: see track_f0 for where they are, and are not, the host path's.
+
+    audio=True, over a corpus with resident audio (`ResidentMelCorpus.keep_audio`; ValueError here without it, or where hop_size
+    is not its audio_hop): the first two elements are x (B, 1, T * hop) and y (B, T * hop, 1) fp32 on the device, two views of one
+    fresh tensor -- one ops.collate_audio launch on the plan rows already on the device.  With equal seeds they are
+    get_data_loaders(with_audio=True)'s x and y bit for bit; c, g, input_lengths, the optional f0_bins and the draws from
+    `random` and `rng` are exactly those of the loader without audio.  train.train_conditioned(pitch_perturb=) runs on such
+    batches."""
 
     def __init__(self, corpus: ResidentMelCorpus, batch_size: int, max_time_steps: Optional[int] = None, frame_multiple: int = 1,
-                 train: bool = True, rng=None, shard=None, hop_size: int = HOP_SIZE, f0=None):
+                 train: bool = True, rng=None, shard=None, hop_size: int = HOP_SIZE, f0=None, audio: bool = False):
         if batch_size < 1:
             raise ValueError("ResidentMelLoader: batch_size < 1")
+        if audio:
+            if getattr(corpus, "audio", None) is None:
+                raise ValueError("ResidentMelLoader: audio=True over a corpus without resident audio (ResidentMelCorpus.keep_audio)")
+            if hop_size != corpus.audio_hop:
+                raise ValueError(f"ResidentMelLoader: hop_size = {hop_size}, the corpus' resident audio has hop {corpus.audio_hop}")
+        self.audio = bool(audio)
         if f0 is not None:
             if len(f0) != 3 or isinstance(f0[0], bool) or not isinstance(f0[0], (int, np.integer)) or f0[0] < 1 or not 0 < f0[1] < f0[2] < float("inf"):
                 raise ValueError(f"ResidentMelLoader: f0 = {f0!r} is not (n_bins, fmin, fmax) with n_bins >= 1 and 0 < fmin < fmax")
@@ -518,24 +580,31 @@ class ResidentMelLoader:
             c = ops.collate_mels(corpus.frames, rows, int(ep.widths[k]))
             g = corpus.speaker_ids[rows[:, 0]] if corpus.speaker_ids is not None else None
             lengths = torch.from_numpy(ep.plan[k, :B, 2] * self.hop)
-            if self.f0 is None:
-                yield None, None, c, g, lengths
-                continue
             T = int(ep.widths[k])
+            x = y = None
+            if self.audio:
+                wav = ops.collate_audio(corpus.audio, rows, T, self.hop)
+                x, y = wav.unsqueeze(1), wav.unsqueeze(2)
+            if self.f0 is None:
+                yield x, y, c, g, lengths
+                continue
             bins = (ops.collate_f0_bins(corpus.f0, rows, T, *self.f0) if T >= 4 else
                     torch.empty(B, 0, dtype=torch.int64, device=corpus.device))
-            yield None, None, c, g, lengths, bins
+            yield x, y, c, g, lengths, bins
 
 
 def get_resident_loaders(data_root: str, batch_size: int, max_time_steps: Optional[int] = None, speaker_id=None, test_size=0.05,
                          test_num_samples=None, random_state: int = 1234, frame_multiple: int = 1, device="cuda:0", rng=None,
-                         shard=None, f0=None):
+                         shard=None, f0=None, audio: bool = False):
     """`get_data_loaders` with the corpus resident on `device`: {"train": ResidentMelLoader, "test": ResidentMelLoader} over the
-    same train / test split (mels only: raw audio stays on the host path).  `shard` applies to the train loader only.
+    same train / test split.  `shard` applies to the train loader only.
     f0: None, or a dict {"n_bins", "fmin", "fmax"[, "tracker", "tracker_options"]} for an F0-conditioned model (n_bins and the range
     are the model's n_f0_bins and f0_range): both corpora read their split's audio once (`RawAudioDataSource`), track it
     (`ResidentMelCorpus.track_f0` with that tracker over its own default range, the one train.train_conditioned tracks a host
-    batch over) and both loaders yield six-tuples with the bins (`ResidentMelLoader(f0=)`).  The audio is not kept."""
+    batch over) and both loaders yield six-tuples with the bins (`ResidentMelLoader(f0=)`).  The audio is not kept.
+    audio=True: both corpora read their split's audio once and KEEP it (`ResidentMelCorpus.keep_audio`), both loaders yield x
+    and y (`ResidentMelLoader(audio=True)`: get_data_loaders(with_audio=True)'s batches), and with f0 as well the tracks come from
+    the resident samples (`track_f0()` without a source), not from a second read."""
     if f0 is not None:
         f0 = dict(f0)
         if set(f0) - {"n_bins", "fmin", "fmax", "tracker", "tracker_options"} or not {"n_bins", "fmin", "fmax"} <= set(f0):
@@ -545,11 +614,13 @@ def get_resident_loaders(data_root: str, batch_size: int, max_time_steps: Option
         train = phase == "train"
         kw = dict(speaker_id=speaker_id, train=train, test_size=test_size, test_num_samples=test_num_samples, random_state=random_state)
         corpus = ResidentMelCorpus(MelSpecDataSource(data_root, **kw), device)
+        if audio:
+            corpus.keep_audio(RawAudioDataSource(data_root, **kw))
         if f0 is not None:
-            corpus.track_f0(RawAudioDataSource(data_root, **kw), tracker=f0.get("tracker", "yin"), tracker_options=f0.get("tracker_options"))
+            corpus.track_f0(None if audio else RawAudioDataSource(data_root, **kw), tracker=f0.get("tracker", "yin"), tracker_options=f0.get("tracker_options"))
         loaders[phase] = ResidentMelLoader(corpus, batch_size, max_time_steps, frame_multiple, train=train, rng=rng,
                                            shard=shard if train else None,
-                                           f0=None if f0 is None else (f0["n_bins"], f0["fmin"], f0["fmax"]))
+                                           f0=None if f0 is None else (f0["n_bins"], f0["fmin"], f0["fmax"]), audio=audio)
     return loaders
 
 

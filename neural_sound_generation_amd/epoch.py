@@ -85,16 +85,18 @@ def _export_first_batch(args, model, test_loader, device, epoch, export_audio, o
 
 
 def run_conditioned_epoch(args, model, step, train_loader, test_loader, device, epoch, checkpoint_path=None, export_audio=True,
-                          eval_with_ema=False, tracker="yin", tracker_options=None):
+                          eval_with_ema=False, tracker="yin", tracker_options=None, pitch_perturb=None, generator=None):
     """run_epoch for a speaker- and / or F0-conditioned VQ-VAE on its FusedTrainStep `step` (an extension): train_conditioned ->
     test_conditioned -> the first test batch reconstructed UNDER ITS OWN CONDITIONING (its g, and its bins: the sixth element of
     a data.ResidentMelLoader(f0=) batch, or tracked from its audio with tracker / tracker_options) -> the .npy, the wav and the
     checkpoint (checkpoint_state of the model and step.opt) under run_epoch's file names.  eval_with_ema as in run_epoch.
+    pitch_perturb, generator: train_conditioned's (the training half only; the loaders must yield audio:
+    get_data_loaders(with_audio=True) or get_resident_loaders(audio=True)); the defaults leave the loop as it was.
     Returns run_epoch's dict."""
     optimizer = step.opt
     _require_average(optimizer, eval_with_ema)
     track = _f0_tracker("run_conditioned_epoch", tracker, tracker_options)
-    train_loss = train_conditioned(args, model, step, train_loader, device, epoch, tracker, tracker_options)
+    train_loss = train_conditioned(args, model, step, train_loader, device, epoch, tracker, tracker_options, pitch_perturb, generator)
     with _averaged(optimizer, eval_with_ema):
         loss_recons, loss_vq = test_conditioned(args, model, test_loader, device, epoch, tracker, tracker_options)
         out = _export_first_batch(args, model, test_loader, device, epoch, export_audio, {"test_loss_recons": loss_recons, "test_loss_vq": loss_vq},

@@ -445,7 +445,39 @@ def collate_mels(corpus, plan, T, out=None):
     return out
 
 
-DTW_MAX_FRAMES, DTW_BLOCK_COLS = _lib.NSG_DTW_MAX_FRAMES, _lib.NSG_DTW_BLOCK_COLS     # include/nsg.h: longest sequence; columns of one sweep
+def collate_audio(corpus, plan, T, hop=256, out=None):
+    """corpus (samples,) fp32: the clips' audio concatenated in the mel corpus' clip order, frames * hop samples a clip; plan (B, 3)
+    int64, collate_mels' own rows (clip, start, count) in FRAMES; T -> (B, T * hop) fp32:
+    out[b, i] = corpus[start_b * hop + i] for i < count_b * hop, +0.0 up to T * hop (data.Collate's audio crop and padding; one
+    launch, a copy bit for bit).  The plan is checked as collate_mels checks it, against corpus.numel() // hop frames: on the host
+    here, on the device by the caller on its host copy."""
+    for t, name, dtype in ((corpus, "corpus", torch.float32), (plan, "plan", torch.int64)):
+        if t.dtype != dtype:
+            raise _lib.NsgError(f"collate_audio: {name}: expected {dtype}, got {t.dtype}")
+        if not t.is_contiguous():
+            raise _lib.NsgError(f"collate_audio: {name}: expected a contiguous tensor")
+    if corpus.dim() != 1:
+        raise _lib.NsgError(f"collate_audio: corpus {tuple(corpus.shape)} is not (samples,)")
+    if plan.dim() != 2 or plan.shape[1] != 3 or plan.shape[0] < 1:
+        raise _lib.NsgError(f"collate_audio: plan {tuple(plan.shape)} is not (B, 3) with B >= 1")
+    T, hop = int(T), int(hop)
+    if T < 1 or hop < 1 or T * hop >= 1 << 31:
+        raise _lib.NsgError(f"collate_audio: T = {T}, hop = {hop}: both must be positive and T * hop below 2^31")
+    B = plan.shape[0]
+    if not plan.is_cuda:
+        check_collate_plan(plan, T, corpus.numel() // hop)
+    _chk(corpus, "collate_audio: corpus")
+    if not plan.is_cuda:
+        plan = plan.to(corpus.device)
+    if out is None:
+        out = torch.empty(B, T * hop, dtype=torch.float32, device=corpus.device)
+    elif _chk(out, "collate_audio: out").numel() != B * T * hop:
+        raise _lib.NsgError(f"collate_audio: out {tuple(out.shape)} does not hold {B} x {T * hop}")
+    _lib.call("nsg_collate_audio", _p(corpus), corpus.numel(), hop, _p(plan), B, T, _p(out), _stream())
+    return out
+
+
+DTW_MAX_FRAMES, DTW_BLOCK_COLS =_lib.NSG_DTW_MAX_FRAMES, _lib.NSG_DTW_BLOCK_COLS     # include/nsg.h: longest sequence; columns of one sweep
 
 
 def _lengths_on(lengths, name, B, lo, hi, device):

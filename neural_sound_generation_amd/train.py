@@ -421,7 +421,7 @@ def train_conditioned(args, model, step, train_loader, device, epoch, tracker="y
     random shift with its formants and length kept -- while the loss target stays c: step.step(c', g, f0_bins=bins, target=c).
     The codes then no longer tell the pitch of the mel to be reproduced, and an F0-conditioned decoder has to take it from the
     bins.  generator: the CPU torch.Generator of the shifts (None: a new one seeded with `epoch`).  It needs the batch's audio:
-    a batch without x (a resident loader, which keeps no audio; a host loader built without with_audio=True) is a ValueError
+    a batch without x (a resident loader built without audio=True; a host loader built without with_audio=True) is a ValueError
     before anything of that batch is launched, as are a range outside [-12, 12] and a generator that is not a CPU one."""
     from . import audio
     from .evaluate import _f0_tracker, batch_conditioning
@@ -439,7 +439,8 @@ def train_conditioned(args, model, step, train_loader, device, epoch, tracker="y
     for batch_idx, batch in enumerate(train_loader):
         if pitch_perturb is not None and batch[0] is None:
             raise ValueError("train_conditioned: pitch_perturb needs the batch's audio and the loader yields none: "
-                             "get_data_loaders(with_audio=True) (a resident loader keeps no audio)")
+                             "get_data_loaders(with_audio=True) or get_resident_loaders(audio=True) (a resident loader without "
+                             "audio=True keeps no audio)")
         c, g_d, bins = batch_conditioning("train_conditioned", model, batch, device, track)
         if pitch_perturb is not None:
             T = c.shape[3]
