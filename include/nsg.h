@@ -1368,6 +1368,10 @@ NSG_API int nsg_audio_pitch_marks(const float *wav, const int32_t *lengths, cons
  * syn, map, n_syn and out is written exactly once; a clip's results are bit for bit independent of B, L, K_max, J_max, its row and
  * any tiling.  Two launches: the chain over j, one thread per clip; then a thread per output sample, which finds the first grain
  * that can reach it by a binary search in s (s_j > n - H_max) and walks on while s_j < n + H_max.
+ * With marks and counts that are not nsg_audio_pitch_marks' own, the clamps above keep every access inside its buffer and two more
+ * rules apply, neither of which binds otherwise:  the chain over j also ends once it holds J_max synthesis marks (n_syn <= J_max);
+ * and a grain reaches only |dist| < H_max, so a half-length above H_max (marks further apart than any the analysis makes) is cut
+ * there, its window still taken over the full half-length.
  * Refusals: the shared ones, for marks, n_marks, f0_out, syn, map, n_syn and out too. */
 #define NSG_PSOLA_MIN_WEIGHT_LOG2 10
 NSG_API int nsg_audio_psola(const float *wav, const int32_t *lengths, const float *f0_in, const float *f0_out, const int32_t *marks,

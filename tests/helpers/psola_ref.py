@@ -51,15 +51,17 @@ def argmax_key(x, lo, hi):
     return lo + int(np.argmax(key))
 
 
-def marks_ref(x, n, f0, hop, sr, P_u, P_min, P_max, alpha=ALPHA):
-    """nsg_audio_pitch_marks for one clip x[:n] with the track f0 (T,) -> the marks, a list of ints."""
+def marks_trace(x, n, f0, hop, sr, P_u, P_min, P_max, alpha=ALPHA):
+    """marks_ref, and every search after the first one as the chain made it -> (marks, [(lo, hi, P)]): the range of search k + 1
+    and the signed period it was derived from (lo = hi and P < 0 from an unvoiced frame), the search that ended the chain with
+    lo > n - 1 left out, as the kernel leaves it before it touches its ring."""
     n = max(0, min(int(n), len(x)))
     if n == 0:
-        return []
+        return [], []
     T, (an, ad) = len(f0), alpha
     per = lambda s: period(f0[frame(s, hop, T)], sr, P_u, P_min, P_max)
     m = argmax_key(x, 0, min(abs(per(0)), n) - 1)
-    marks = [m]
+    marks, searches = [m], []
     while True:
         pp = per(m)
         if pp > 0:
@@ -68,13 +70,30 @@ def marks_ref(x, n, f0, hop, sr, P_u, P_min, P_max, alpha=ALPHA):
         else:
             lo = hi = m - pp
         if lo > n - 1:
-            return marks
+            return marks, searches
+        searches.append((lo, hi, pp))
         m = argmax_key(x, lo, hi) if pp > 0 else lo
         marks.append(m)
 
 
-def syn_ref(marks, f0_in, f0_out, hop, P_u, P_min, P_max):
-    """The synthesis marks and the mapping of nsg_audio_psola for one clip -> (syn, map), lists of ints."""
+def marks_ref(x, n, f0, hop, sr, P_u, P_min, P_max, alpha=ALPHA):
+    """nsg_audio_pitch_marks for one clip x[:n] with the track f0 (T,) -> the marks, a list of ints."""
+    return marks_trace(x, n, f0, hop, sr, P_u, P_min, P_max, alpha)[0]
+
+
+def clamped_marks(marks, n_marks, K_max, n):
+    """The marks as nsg_audio_psola reads a row `marks` (at least min(n_marks, K_max) long) and a count it did not make itself:
+    K = n_marks clamped into [0, K_max] (0 for an empty clip), every mark clamped into [0, n - 1] -> a list of K ints."""
+    K = clamp(int(n_marks), 0, K_max) if n > 0 else 0
+    return [clamp(int(m), 0, n - 1) for m in list(marks)[:K]]
+
+
+def syn_ref(marks, f0_in, f0_out, hop, P_u, P_min, P_max, J_max=None, clamps=None):
+    """The synthesis marks and the mapping of nsg_audio_psola for one clip -> (syn, map), lists of ints.  J_max: the chain also
+    ends when it holds J_max marks (never reached with nsg_audio_pitch_marks' marks and J_max >= ceil(L / G_s)).  clamps =
+    (n_marks, K_max, n): `marks` is a row as handed to the entry point, read through clamped_marks."""
+    if clamps is not None:
+        marks = clamped_marks(marks, *clamps)
     K = len(marks)
     if K == 0:
         return [], []
@@ -91,18 +110,22 @@ def syn_ref(marks, f0_in, f0_out, hop, P_u, P_min, P_max):
             r = 0.25 if r < 0.25 else (4.0 if r > 4.0 else (r if r == r else 1.0))
         q = math.floor(D / r + 0.5)
         s2 = s + (int(q) if q >= 1.0 else 1)
-        if s2 > marks[-1]:
+        if s2 > marks[-1] or (J_max is not None and len(syn) >= J_max):
             return syn, mp
         s = s2
         while a + 1 < K and abs(marks[a + 1] - s) < abs(marks[a] - s):
             a += 1
 
 
-def ola_ref(x, n, marks, syn, mp, dtype=np.float32, L=None):
+def ola_ref(x, n, marks, syn, mp, dtype=np.float32, L=None, H_max=None, clamps=None):
     """The overlap-add of nsg_audio_psola for one clip in `dtype` arithmetic, grains added in ascending j, every operation rounded
-    -> (out (L,), den (L,), grains (L,) int: how many grains reach each sample)."""
+    -> (out (L,), den (L,), grains (L,) int: how many grains reach each sample).  clamps = (n_marks, K_max, n): `marks` is a row
+    as handed to the entry point, read through clamped_marks.  H_max: a grain reaches only |dist| < H_max, the header's walk over
+    s_j -- no restriction on nsg_audio_pitch_marks' marks, which are at most H_max apart; it cuts the halves of foreign ones."""
     L = len(x) if L is None else L
     n = max(0, min(int(n), len(x)))
+    if clamps is not None:
+        marks = clamped_marks(marks, *clamps)
     F = dtype
     xs = np.asarray(x[:n], dtype=np.float32).astype(F)
     num, den, cnt = np.zeros(n, dtype=F), np.zeros(n, dtype=F), np.zeros(n, dtype=np.int64)
@@ -123,6 +146,8 @@ def ola_ref(x, n, marks, syn, mp, dtype=np.float32, L=None):
                 w = F(1) - (u * u) * (F(3) - F(2) * u)
             at = s + dist
             ok = (at >= 0) & (at < n)
+            if H_max is not None:
+                ok &= np.abs(dist) < H_max
             at, src, w = at[ok], ma + dist[ok], w[ok]
             num[at] = num[at] + w * xs[src]
             den[at] = den[at] + w
